@@ -376,20 +376,8 @@ static std::atomic<int> g_engines_on_device[MAX_COUNTED_DEVICES];      // engine
 int Engine::init(const mm2gb_config_t *c, const mm2gb_misc_t *m, int dev)
 {
 	// An engine has up to four HIP streams (H2D, two compute, D2H) whose whole point is to run at the same time.  The HIP runtime
-	// multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by default, and streams that share a queue run one after the
-	// other: next to a framework's own streams the engine's copies and kernels then serialise (200 M anchors through
-	// mm2gb_score_host: 146 ms instead of 92 ms, profiles/README.md).  Only effective before the runtime starts, so hosts
-	// export it themselves before their first HIP call; bench.py and tests/conftest.py do.
-	// The library does not touch the environment here (setenv races with getenv in threaded hosts, and is too late once the runtime
-	// runs): it says so once when the variable is missing.  INTEGRATION.md documents it; init_stream_gpu, the one entry point that IS
-	// the process's first HIP call and runs before the host starts threads, still exports it for the C host.
-	{
-		static std::once_flag warned;
-		const char *q = getenv("GPU_MAX_HW_QUEUES");
-		if (!q || atoi(q) < 8)
-			std::call_once(warned, [] { fprintf(stderr, "[mm2gb] GPU_MAX_HW_QUEUES is unset or below 8: the engine's copy and compute streams may share a hardware queue and "
-			                                            "serialise (export GPU_MAX_HW_QUEUES=8 before the process starts HIP)\n"); });
-	}
+	// multiplexes streams onto a fixed number of hardware queues, and streams that share a queue run one after the other.  How many queues
+	// a process opens is the host's (and the machine's) choice, made before the runtime starts: the library neither sets nor asks for it.
 	int n_dev = 0;
 	MM2GB_HIP(hipGetDeviceCount(&n_dev));
 	if (dev < 0 || dev >= n_dev) return fail("mm2gb: device " + std::to_string(dev) + " not present (" + std::to_string(n_dev) + " visible)");

@@ -6,7 +6,6 @@ map.c:887-920 and go to the engines' workers, every read's chains come back thro
 import argparse, json, os, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import bench, mm2gb_amd as mm
 

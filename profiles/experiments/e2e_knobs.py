@@ -4,7 +4,6 @@ usage: python profiles/experiments/e2e_knobs.py [copies [ENGINESxCHUNK_MBP,...]]
 import os, sys, time, json, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "profiles"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 import bench, mm2gb_amd as mm, sim_reads
 from test_seeding_cpu import read_fasta
 

@@ -4,7 +4,6 @@ python profiles/experiments/gang_trace.py [gang_max] [anchors] [xwin]"""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ.setdefault("MM2GB_LIB_PATH", os.path.join(ROOT, "mm2-gb_amd", "ab", "libchain.so"))
 os.environ["MM2GB_GANG_MAX"] = sys.argv[1] if len(sys.argv) > 1 else "8"
 import numpy as np

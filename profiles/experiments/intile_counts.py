@@ -3,7 +3,6 @@
 import ctypes as C, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["MM2GB_LIB_PATH"] = os.path.join(ROOT, "mm2-gb_amd", "ab", "libintile.so")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, ROOT)
 import mm2gb_amd as mm
 names = ["in_tile_phases", "plain_steps_calls", "sources_needed", "rows_computed", "calls_free", "calls_checked", "calls_clamped", "fast_path_undone", "entry_or_full_steps",

@@ -4,7 +4,6 @@ what the reads that end k_post_chains spend where.  usage: MM2GB_DEBUG_PHASES=1 
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ["MM2GB_DEBUG_PHASES"] = "1"
 import numpy as np
 import bench, mm2gb_amd as mm

@@ -4,7 +4,6 @@ copy is exposed: that slice's kernels and its D2H).   python profiles/experiment
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 import bench, mm2gb_amd as mm
 

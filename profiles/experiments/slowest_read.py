@@ -4,7 +4,6 @@ usage: python profiles/experiments/slowest_read.py [anchors]"""
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import bench, mm2gb_amd as mm
 

@@ -4,7 +4,6 @@ prints the call's seconds (three calls: the first makes arenas and result blocks
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 import mm2gb_amd as mm

@@ -4,7 +4,6 @@ mm2gb_post_device a few times; per-run milliseconds, totals and a digest of the 
 full size).  MM2GB_DEBUG_PHASES=1 in the environment adds the library's per-phase sums and the schedule of the reads that end last (stderr).
     python3 profiles/post_only.py [--anchors 500000000] [--runs 3] [--lo 100000 --hi 300000] [--out file.json]"""
 import argparse, ctypes as C, json, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

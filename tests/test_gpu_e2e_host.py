@@ -244,6 +244,8 @@ def test_rechaining_ahead_at_a_finite_max_chain_skip(tmp_path):
     import re
     import sim_reads
     host_rmq = HOST + "_rmq"
+    if not os.path.exists(host_rmq):
+        pytest.fail("oracle/_ref/minimap2_gpuhost_rmq is missing (make -C oracle gpuhost_rmq where the reference checkout exists)")
     meta = json.load(open(os.path.join(GOLD, "sim160.json")))
     ref, reads = str(tmp_path / "ref.fa"), str(tmp_path / "reads.fa")
     sim_reads.simulate(ref, reads, seed=meta["seed"], n_reads=48, len_lo=meta["len_lo"], len_hi=meta["len_hi"], tandem=meta["tandem"])
