@@ -84,6 +84,18 @@ int  mm2gb_numa_cpus_for_bdf(const char *bdf, const char *sysfs_root_dir, int32_
 mm2gb_engine_t *mm2gb_engine_create(const mm2gb_config_t *cfg, const mm2gb_misc_t *misc, int device);
 void mm2gb_engine_destroy(mm2gb_engine_t *eng);
 int  mm2gb_engine_set_misc(mm2gb_engine_t *eng, const mm2gb_misc_t *misc);
+/* The chaining DP's skip limit (misc.max_skip, lchain.c:183-187).  keep = 0 (the default): the DP is exhaustive whatever max_skip says,
+ * i.e. results are those of max_skip = INT32_MAX.  keep = 1: every later call on this engine (score, chain, sliced, host-buffer and stream
+ * paths, mm2gb_lchain_dp) gives mg_lchain_dp's results at misc.max_skip: a skip-limited walk, one wave per planner chunk, runs in place
+ * of the exhaustive kernel unless the limit cannot be reached (max_skip >= max_iter).  MM2GB_CHAIN_SKIP=keep|ignore sets the mode an
+ * engine starts with (read when it is created).  mm2gb_engine_last_score_form: the form the engine's last call ran, 0 exhaustive,
+ * 1 the skip-limited walk.  Stats keep their meaning (n_pairs: the sum of window sizes, not the candidates met). */
+int  mm2gb_engine_set_chain_skip(mm2gb_engine_t *eng, int keep);
+int  mm2gb_engine_last_score_form(const mm2gb_engine_t *eng);
+/* measurement aid: with MM2GB_SKIP_STATS=1 set when the engine was made, the skip-limited walk of its last micro-batch counts, and this waits for
+ * the engine and gives: [0] walk rounds of 64 candidates, [1] rounds of the max_ii search, [2] targets, [3] the slowest chunk's time and [4] its
+ * anchors, [5] the walk's span from the first chunk's start to the last chunk's end; times in ticks of the 100 MHz s_memrealtime clock */
+int  mm2gb_engine_skip_stats(mm2gb_engine_t *eng, int64_t *out6);
 int  mm2gb_engine_device(const mm2gb_engine_t *eng);
 /* of the engine's last completed call: heavy chunks that were scored strip by strip with the help of idle workgroups (micro-batches of
  * up to MM2GB_SPLIT_MAX_ANCHORS anchors; 0 = never, the default: the build is exact but measured slower), and the items
@@ -261,8 +273,9 @@ void mm2gb_matches_free(mm2gb_matches_t *m);
 /* ---- reads in, PAF out (csrc/mapper.cpp): seeding on host threads, anchors / chaining / re-chaining / hit records on the
  *      device, primary-secondary decisions, divergence, mapping quality and the PAF line on the host, written from scratch after
  *      mm_map_frag (map.c:630-790) for single-segment reads without base-level alignment.  Options: the fields of mm_mapopt_t this
- *      path looks at, mm2gb_map_opt_init sets the defaults of mm_mapopt_init (options.c:15-75); chaining runs at max-chain-skip =
- *      infinity (the GPU path's contract).  paf: malloc'd text, one line per hit in read order (free with mm2gb_free). ---- */
+ *      path looks at, mm2gb_map_opt_init sets the defaults of mm_mapopt_init (options.c:15-75) except max_chain_skip: chaining runs at
+ *      max-chain-skip = infinity (the GPU path's contract) unless max_chain_skip is set below INT32_MAX.  paf: malloc'd text, one line per
+ *      hit in read order (free with mm2gb_free). ---- */
 typedef struct {
 	int64_t flag;              /* MM_F_FOR_ONLY | MM_F_REV_ONLY only */
 	int32_t seed, mid_occ, min_mid_occ, max_mid_occ, max_max_occ, occ_dist;
@@ -274,6 +287,7 @@ typedef struct {
 	int32_t host_threads;      /* 0: every CPU the process may use, at most 32 */
 	int32_t seeds_on_device;   /* matches -> sorted anchors: 1 on the device, -1 on host threads, 0 by batch size */
 	int32_t rechain_on_device; /* mg_lchain_rmq's fill: 0 (default) mm2gb_rmq_chain -- device and host threads at the same time, reads dealt by cost, ties redone on the host; 1 every read on the device first (ties redone on host threads); -1 host threads only */
+	int32_t max_chain_skip;    /* mm_mapopt_t::max_chain_skip; INT32_MAX (the default here): chaining and re-chaining exhaustive.  Below it both keep the limit */
 } mm2gb_map_opt_t;
 typedef struct { int64_t n_reads, n_mapped, n_anchors, n_chains, n_rechained, n_rmq_tied; double s_seed, s_anchors, s_chain, s_rechain, s_regs, s_post; } mm2gb_map_stats_t;   /* s_*: seconds per stage */
 void mm2gb_map_opt_init(mm2gb_map_opt_t *opt);
@@ -355,7 +369,8 @@ void mm2gb_free(void *ptr);
 
 /* ---- synchronous single-read entry with the signature of mg_lchain_dp (mmpriv.h:84-85, lchain.c:148-149):
  *      consumes a[] (freed with the host's kfree when linked into minimap2, free() otherwise), returns the compacted
- *      anchors and *_u allocated the same way.  max_skip is ignored: the GPU path is exhaustive (== INT32_MAX). ---- */
+ *      anchors and *_u allocated the same way.  max_skip is ignored (the DP is exhaustive, == INT32_MAX) unless the engines were
+ *      created with MM2GB_CHAIN_SKIP=keep: then it is kept as mg_lchain_dp keeps it. ---- */
 mm2gb_anchor_t *mm2gb_lchain_dp(int max_dist_x, int max_dist_y, int bw, int max_skip, int max_iter, int min_cnt, int min_sc,
                                 float chn_pen_gap, float chn_pen_skip, int is_cdna, int n_seg, int64_t n, mm2gb_anchor_t *a,
                                 int *n_u_, uint64_t **_u, void *km);

@@ -85,7 +85,7 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_batcher_create", "mm2gb_batcher_add", "mm2gb_batcher_feed", "mm2gb_batcher_flush", "mm2gb_batcher_stats", "mm2gb_batcher_destroy",
                 "mm2gb_plan_batches", "mm2gb_rmq_chain_gpu", "mm2gb_lchain_rmq", "mm2gb_lchain_rmq_counts",
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
-                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_has_split_build", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream"]
+                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_has_split_build", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -110,6 +110,8 @@ def lib():
         L.mm2gb_engine_set_misc.argtypes = [C.c_void_p, C.POINTER(Misc)]
         L.mm2gb_engine_device.argtypes = [C.c_void_p]
         L.mm2gb_engine_reserve.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
+        L.mm2gb_engine_set_chain_skip.argtypes = [C.c_void_p, C.c_int]
+        L.mm2gb_engine_last_score_form.argtypes = [C.c_void_p]
         L.mm2gb_score_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.mm2gb_score_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mm2gb_engine_sync.argtypes = [C.c_void_p]
@@ -239,7 +241,9 @@ def numa_cpus_for_bdf(bdf, sysfs_root=""):
 class Engine:
     """One chaining engine on one GPU (mm2gb_engine_t)."""
 
-    def __init__(self, misc=None, config=None, device=0):
+    def __init__(self, misc=None, config=None, device=0, chain_skip=None):
+        """chain_skip: True keeps misc.max_skip in the chaining DP (mg_lchain_dp's results at that limit), False ignores it (exhaustive,
+        the default); None leaves the mode the engine starts with (MM2GB_CHAIN_SKIP=keep|ignore, else exhaustive)."""
         L = lib()
         self.misc = misc if misc is not None else default_misc()
         self.config = config if config is not None else default_config()
@@ -247,6 +251,8 @@ class Engine:
         self._h = L.mm2gb_engine_create(C.byref(self.config), C.byref(self.misc), device)
         if not self._h:
             raise Mm2gbError(L.mm2gb_last_error().decode())
+        if chain_skip is not None:
+            self.set_chain_skip(chain_skip)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -264,6 +270,24 @@ class Engine:
     def set_misc(self, misc):
         _check(lib().mm2gb_engine_set_misc(self._h, C.byref(misc)))
         self.misc = misc
+
+    def set_chain_skip(self, keep):
+        """keep=True: later calls keep misc.max_skip in the chaining DP (the skip-limited walk); False: exhaustive whatever max_skip is."""
+        _check(lib().mm2gb_engine_set_chain_skip(self._h, 1 if keep else 0))
+
+    def last_score_form(self):
+        """Form of the DP the last call ran: 0 exhaustive (k_score), 1 the skip-limited walk (k_skip_fill)."""
+        return int(lib().mm2gb_engine_last_score_form(self._h))
+
+    def skip_stats(self):
+        """Counters of the skip-limited walk's last micro-batch (engine made with MM2GB_SKIP_STATS=1): rounds of 64 candidates, max_ii search
+        rounds, targets, the slowest chunk's ticks and anchors, the walk's span in ticks (100 MHz clock)."""
+        L = lib()
+        L.mm2gb_engine_skip_stats.argtypes = [C.c_void_p, C.c_void_p]
+        out = np.zeros(6, dtype=np.int64)
+        _check(L.mm2gb_engine_skip_stats(self._h, out.ctypes.data))
+        keys = ("rounds", "rescan_rounds", "targets", "slowest_chunk_ticks", "slowest_chunk_anchors", "span_ticks")
+        return {k: int(v) for k, v in zip(keys, out)}
 
     def split_counts(self):
         """Of the last completed call: (chunks scored strip by strip with other workgroups' help, items those others took)."""
@@ -738,7 +762,8 @@ class MapOpt(C.Structure):
                 ("min_cnt", C.c_int32), ("min_chain_score", C.c_int32), ("bw", C.c_int32), ("bw_long", C.c_int32), ("max_gap", C.c_int32),
                 ("max_gap_ref", C.c_int32), ("max_chain_iter", C.c_int32), ("rmq_inner_dist", C.c_int32), ("rmq_size_cap", C.c_int32),
                 ("rmq_rescue_size", C.c_int32), ("rmq_rescue_ratio", C.c_float), ("chain_gap_scale", C.c_float), ("chain_skip_scale", C.c_float),
-                ("mask_level", C.c_float), ("mask_len", C.c_int32), ("pri_ratio", C.c_float), ("best_n", C.c_int32), ("host_threads", C.c_int32), ("seeds_on_device", C.c_int32), ("rechain_on_device", C.c_int32)]
+                ("mask_level", C.c_float), ("mask_len", C.c_int32), ("pri_ratio", C.c_float), ("best_n", C.c_int32), ("host_threads", C.c_int32), ("seeds_on_device", C.c_int32), ("rechain_on_device", C.c_int32),
+                ("max_chain_skip", C.c_int32)]
 
 
 class MapStats(C.Structure):

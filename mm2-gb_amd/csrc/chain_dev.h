@@ -150,6 +150,10 @@ struct LaunchCfg {
 void launch_window(const DevBatch &b, const DevParams &P, hipStream_t s);
 void launch_plan(const DevBatch &b, const LaunchCfg &cfg, hipStream_t s);
 void launch_score(const DevBatch &b, const DevParams &P, const LaunchCfg &cfg, hipStream_t s);
+// the DP with mg_lchain_dp's skip limit kept (k_skip_fill; after launch_window + launch_plan, in place of launch_score): mark = n ints of scratch;
+// stats (optional, SKIP_STAT_WORDS words): walk rounds, max_ii search rounds, targets, slowest chunk (ticks << 24 | anchors), ~first start, last end
+constexpr int SKIP_STAT_WORDS = 6;
+void launch_skip_fill(const DevBatch &b, const DevParams &P, int max_skip, int32_t *mark, unsigned long long *stats, int n_cu, hipStream_t s);
 void launch_build_lut(int *d_lut, const DevParams &P, hipStream_t s);
 size_t score_lds_bytes(const DevParams &P, int host_mode, int ring_slots);
 int  score_set_lds_limit(size_t bytes);     // hipFuncSetAttribute on every k_score instance

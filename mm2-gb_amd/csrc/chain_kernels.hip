@@ -19,6 +19,7 @@
 #include <limits.h>
 #include <algorithm>
 #include "chain_dev.h"
+#include "wave_scan.h"
 
 namespace mm2gb {
 
@@ -2501,6 +2502,174 @@ void launch_score(const DevBatch &b, const DevParams &P, const LaunchCfg &cfg, h
 	}
 	if (cfg.host_mode == MODE_FAST || cfg.host_mode == MODE_LUT) hipLaunchKernelGGL((k_score<MODE_FAST, false, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
 	hipLaunchKernelGGL((k_score<MODE_GENERAL, false, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds_general, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
+}
+
+
+// --------------------------------------------------------------------------------------------------------------
+// k_skip_fill: the DP with the skip limit kept (lchain.c:169-207 with lines 183-187), the engine's opt-in form (mm2gb_engine_set_chain_skip).
+// A target's walk depends on where the walks of earlier targets put their f/p, and target i + 1 meets i first: inside a planner chunk
+// the targets are walked one after another by one wave; chunks are independent (a limit only shortens walks, so the cuts hold) and are
+// taken from the planner's lists, heavy lists first.  A walk meets 64 candidates per round in the reference's order (lane 0 = i - 1):
+//   * valid[l]   pair_score (comput_sc exactly); an invalid candidate is skipped and marks nothing
+//   * better[l]  its score beats q_span(i) and every valid score of the lanes before it (wave_max_below): the running best of line 181
+//   * again[l]   not better, and some candidate met earlier has it as predecessor (t[j] == i, line 184): marks from this round are one
+//                64-bit mask (wave_or_u64), marks for later rounds go to mark[] (4 B per anchor, the value is the target's index)
+//   * counter    better: x -> max(x - 1, 0), again: x -> x + 1, else x -> x (wave_skip_counts); the walk ends at the first lane whose
+//                count passes max_skip (line 185)
+// A mark does not depend on where the walk ends: it comes from a candidate met before the one it marks.  The previous 64 anchors of the
+// chunk (position, query position, tag, f, predecessor) stay in registers, lane k = anchor i - 1 - k, so a walk that ends in its first
+// round reads nothing from memory but the target's own record.  The max_ii rescue (lines 189-201) keeps the reference's state: the
+// anchor of best f within max_dist_x, looked for again when it falls out of reach, and tried when it lies below where the walk ended.
+// Rounds after the first are software pipelined: round k + 1's loads are issued before round k is scored (marks round k puts on round k + 1
+// travel in a mask).  Loops are bounded by the chunk and the window; f/p/marks written by the wave are read back past the CU's cache.
+// --------------------------------------------------------------------------------------------------------------
+constexpr int SKIP_THREADS = 256;
+constexpr int SKIP_WAVES_PER_CU = 32;
+
+__device__ __forceinline__ int load_past_cache(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// every lane takes the previous lane's value, lane 0 takes `first` (wave-uniform).  Written as a DPP shift of the whole wave and a lane write:
+// `l == 0 ? first : prev_lane(v)` let the compiler move the shift under a branch without lane 0, whose value lane 1 then never received
+__device__ __forceinline__ int shift_in(int v, int first)
+{
+	int r = prev_lane(v);
+	asm volatile("v_writelane_b32 %0, %1, 0" : "+v"(r) : "s"(first_lane(first)));
+	return r;
+}
+
+// One round's candidates (lane l: anchor top - l), as the round after next needs them.  A wave's own earlier stores are seen by its later
+// loads (one wavefront: its memory operations are performed in order); f / p / marks are read past the CU's cache.
+struct SkipCand { int x, y, t, f, p, mk; };
+__device__ __forceinline__ SkipCand skip_round_load(const DevBatch &b, const int32_t *mark, int top, int st_i, int l)
+{
+	SkipCand c = { 0, 0, 0, 0, -1, -1 };
+	const int j = top - l;
+	if (j >= st_i) {
+		const uint4 e = b.raw[j];
+		c.x = (int)e.x; c.y = (int)e.z; c.t = tag_of(e.w);
+		c.f = load_past_cache(b.f + j);
+		const int pr = load_past_cache(b.p + j);
+		c.p = pr ? j - pr : -1;
+		c.mk = load_past_cache(mark + j);
+	}
+	return c;
+}
+
+__global__ __launch_bounds__(SKIP_THREADS) void k_skip_fill(DevBatch b, DevParams P, int max_skip, int32_t *mark, unsigned long long *stats)
+{
+	const int l = lane_id();
+	const int n_chunks = b.counters[CNT_NCHUNK], n_long = b.counters[CNT_NLONG], n_mid = b.counters[CNT_NMID];
+	const unsigned long long reach = (unsigned long long)P.max_dist_x;
+	for (;;) {
+		int item = 0;
+		if (l == 0) item = atomicAdd(&b.counters[CNT_CURSOR], 1);
+		item = bcast(item, 0);
+		if (item >= n_chunks) break;
+		const int c = item < n_long ? b.long_list[item] : item < n_long + n_mid ? b.mid_list[item - n_long] : b.order[item - n_long - n_mid];
+		const int cs = b.chunk_start[c], ce = b.chunk_end[c];
+		const unsigned long long t_start = stats ? __builtin_amdgcn_s_memrealtime() : 0;
+		unsigned long long n_rounds = 0, n_rescan = 0;
+		// the read that owns the chunk's first anchor, and where the next read starts (max_ii is per call of mg_lchain_dp, i.e. per read)
+		int64_t r = b.blk_read[cs / PLAN_BLOCK];
+		while (r + 1 < b.n_reads && b.offsets[r + 1] <= cs) ++r;
+		int64_t next_read = r + 1 <= b.n_reads ? b.offsets[r + 1] : INT64_MAX;
+		int rx = 0, ry = 0, rt = 0, rf = 0, rp = -1;               // anchor i - 1 - l: x.lo, y.lo, tag, f, predecessor (-1 none)
+		int max_ii = -1, mi_x = 0, mi_y = 0, mi_tag = 0, mi_f = 0;
+		unsigned long long mi_x64 = 0;
+		uint4 nxt = b.raw[cs];
+		int nxt_st = b.st[cs];
+		for (int i = cs; i < ce; ++i) {
+			const uint4 ai = nxt;
+			const int st_i = min(max(nxt_st, cs), i);
+			if (i + 1 < ce) { nxt = b.raw[i + 1]; nxt_st = b.st[i + 1]; }
+			if (i >= next_read) {
+				while (r + 1 < b.n_reads && b.offsets[r + 1] <= i) ++r;
+				next_read = r + 1 <= b.n_reads ? b.offsets[r + 1] : INT64_MAX;
+				max_ii = -1;
+			}
+			const int xi = (int)ai.x, yi = (int)ai.z, ti = tag_of(ai.w), segi = ti >> 8;
+			const unsigned long long xi64 = (unsigned long long)ai.y << 32 | ai.x;
+			int max_f = ti & 0xff, max_j = -1, n_skip = 0, end_j = st_i - 1;
+			// Software pipelined: the loads of round k + 1 are in flight while round k is scored.  A mark that round k puts on a candidate of
+			// round k + 1 cannot be in those loads: it travels in `carry` (a 64-bit mask); marks on later rounds go to mark[], stored before
+			// their round's loads are issued.  Round 0 (the previous 64 anchors) is in registers.
+			SkipCand nx = { 0, 0, 0, 0, -1, -1 };
+			if (i - 1 - WAVE >= st_i) nx = skip_round_load(b, mark, i - 1 - WAVE, st_i, l);
+			unsigned long long carry = 0;
+			for (int top = i - 1; top >= st_i; top -= WAVE) {
+				++n_rounds;
+				const bool have = top - l >= st_i;
+				SkipCand cu = { rx, ry, rt, rf, rp, -1 };
+				if (top != i - 1) {
+					cu = nx;
+					if (top - WAVE >= st_i) nx = skip_round_load(b, mark, top - WAVE, st_i, l);
+				}
+				int sc = 0;
+				const bool ok = have && pair_score<MODE_GENERAL>(xi, yi, segi, cu.x, cu.y, cu.t, P, nullptr, sc);
+				const int val = sc + cu.f;
+				const int pj = cu.p;
+				const int below = wave_max_below(ok ? val : INT_MIN);
+				const bool better = ok && val > max(max_f, below);
+				const int to = top - pj;                                           // lane of this round holding the predecessor (> l)
+				const unsigned long long offered = wave_or_u64(ok && pj >= 0 && to < WAVE ? 1ull << to : 0ull);
+				const bool again = ok && !better && (cu.mk == i || (((offered | carry) >> l) & 1));
+				const int count = wave_skip_counts(better ? -1 : again ? 1 : 0, better ? 0 : SKIP_NONE, n_skip);
+				const unsigned long long ends = __ballot(again && count > max_skip);
+				const int upto = ends ? __builtin_ctzll(ends) : WAVE;                // lanes below `upto` were met
+				const unsigned long long got = __ballot(better) & (upto < WAVE ? (1ull << upto) - 1 : ~0ull);
+				if (got) {
+					const int last = 63 - __builtin_clzll(got);                    // every better one replaced the one before
+					max_f = bcast(val, last); max_j = top - last;
+				}
+				if (ends) { end_j = top - upto; break; }
+				n_skip = bcast(count, WAVE - 1);
+				carry = wave_or_u64(ok && pj >= 0 && to >= WAVE && to < 2 * WAVE ? 1ull << (to - WAVE) : 0ull);
+				if (ok && pj >= 0 && to >= 2 * WAVE) __hip_atomic_store(mark + pj, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+			// lchain.c:189-195: the best f of the window (the highest j among equal ones) when the remembered anchor is out of reach
+			if (max_ii < 0 || xi64 - mi_x64 > reach) {
+				int best = INT_MIN, who = -1;
+				for (int top = i - 1; top >= st_i; top -= WAVE) {
+					++n_rescan;
+					const int j = top - l;
+					int fj = rf;
+					if (top != i - 1) fj = j >= st_i ? load_past_cache(b.f + j) : INT_MIN;
+					else if (j < st_i) fj = INT_MIN;
+					const int m = wave_max_i32_dpp(fj);
+					if (m > best) { best = m; who = top - (int)__builtin_ctzll(__ballot(fj == m)); }
+				}
+				max_ii = who;
+				if (who >= 0) {
+					const uint4 e = b.raw[who];
+					mi_x = (int)e.x; mi_y = (int)e.z; mi_tag = tag_of(e.w); mi_f = best;
+					mi_x64 = (unsigned long long)e.y << 32 | e.x;
+				}
+			}
+			// lchain.c:196-201: one more candidate if the walk stopped above it
+			if (max_ii >= 0 && max_ii < end_j) {
+				int tmp = 0;
+				if (pair_score<MODE_GENERAL>(xi, yi, segi, mi_x, mi_y, mi_tag, P, nullptr, tmp) && max_f < tmp + mi_f) { max_f = tmp + mi_f; max_j = max_ii; }
+			}
+			if (l == 0) { b.f[i] = max_f; b.p[i] = max_j >= 0 ? i - max_j : 0; }
+			// lchain.c:204-205
+			if (max_ii < 0 || (xi64 - mi_x64 <= reach && mi_f < max_f)) { max_ii = i; mi_x = xi; mi_y = yi; mi_tag = ti; mi_f = max_f; mi_x64 = xi64; }
+			rx = shift_in(rx, xi); ry = shift_in(ry, yi); rt = shift_in(rt, ti); rf = shift_in(rf, max_f); rp = shift_in(rp, max_j);
+		}
+		if (stats && l == 0) {
+			// SKIP_STAT_*: walk rounds, max_ii search rounds, targets, the slowest chunk's ticks and length, first start (as its complement), last end
+			const unsigned long long t_end = __builtin_amdgcn_s_memrealtime(), ticks = t_end - t_start;
+			atomicAdd(&stats[0], n_rounds); atomicAdd(&stats[1], n_rescan); atomicAdd(&stats[2], (unsigned long long)(ce - cs));
+			atomicMax(&stats[3], ticks << 24 | (unsigned long long)min(ce - cs, (1 << 24) - 1));
+			atomicMax(&stats[4], ~t_start); atomicMax(&stats[5], t_end);
+		}
+	}
+}
+
+void launch_skip_fill(const DevBatch &b, const DevParams &P, int max_skip, int32_t *mark, unsigned long long *stats, int n_cu, hipStream_t s)
+{
+	if (b.n <= 0) return;
+	(void)hipMemsetAsync(mark, 0xff, (size_t)b.n * sizeof(int32_t), s);     // -1: no anchor has been offered to any target
+	if (stats) (void)hipMemsetAsync(stats, 0, SKIP_STAT_WORDS * sizeof(unsigned long long), s);
+	hipLaunchKernelGGL(k_skip_fill, dim3((unsigned)(n_cu * SKIP_WAVES_PER_CU / (SKIP_THREADS / WAVE))), dim3(SKIP_THREADS), 0, s, b, P, max_skip, mark, stats);
 }
 
 } // namespace mm2gb

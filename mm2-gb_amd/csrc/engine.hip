@@ -410,6 +410,10 @@ int Engine::init(const mm2gb_config_t *c, const mm2gb_misc_t *m, int dev)
 	if (const char *v = getenv("MM2GB_DEBUG_PHASES")) debug_phases = *v && *v != '0';
 	if (const char *v = getenv("MM2GB_POST_FORM")) post_split = strcmp(v, "fused") != 0;
 	if (const char *v = getenv("MM2GB_POST_SORT")) post_levels = strcmp(v, "reads") != 0;
+	// the DP's skip limit (mg_lchain_dp's max_skip): kept only on request, so that hosts that cannot call mm2gb_engine_set_chain_skip (the
+	// reference's own host, the engines of pools and batchers) can opt in; read here once, never per call
+	if (const char *v = getenv("MM2GB_CHAIN_SKIP")) chain_skip = strcmp(v, "keep") == 0;
+	{ const char *v = getenv("MM2GB_SKIP_STATS"); skip_stats = v && *v && *v != '0'; }
 	// Gangs: a chunk whose share of the batch's pairs is worth two workgroups or more is scored by several (chain_kernels.hip, plan_gangs):
 	// batches that cannot fill the machine end with their largest chunks.  MM2GB_GANG_MAX=0 turns them off.
 	// Large micro-batches keep the kernel without the gang code (MM2GB_GANG_MAX_ANCHORS: the largest batch that gets gangs).
@@ -595,7 +599,16 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 		launch_plan(b, cfg_now, stream);
 	}
 	if (want_stats) MM2GB_HIP(hipEventRecord(bs.prep1, stream));
-	if (n > 0) launch_score(b, params, cfg_now, stream);
+	// with the skip limit kept, the walk runs unless the limit cannot be reached: the counter rises at most once per candidate and a
+	// window holds at most max_iter of them, so at max_skip >= max_iter the exhaustive kernel gives the same f/p
+	const bool walk = chain_skip && misc.max_skip < misc.max_iter;
+	last_score_form = walk ? 1 : 0;
+	if (n > 0 && walk) {
+		if (w.skip_mark.ensure((size_t)n * sizeof(int32_t))) return -1;
+		if (skip_stats && w.skip_stats.ensure(SKIP_STAT_WORDS * sizeof(unsigned long long))) return -1;
+		last_skip_set = set;
+		launch_skip_fill(b, params, misc.max_skip, (int32_t*)w.skip_mark.ptr, skip_stats ? (unsigned long long*)w.skip_stats.ptr : nullptr, n_cu, stream);
+	} else if (n > 0) launch_score(b, params, cfg_now, stream);
 	if (want_stats) {
 		MM2GB_HIP(hipEventRecord(bs.score1, stream));
 		MM2GB_HIP(hipMemcpyAsync(h_counters + (size_t)slot * CNT_WORDS, counters.ptr, CNT_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -1345,6 +1358,20 @@ void mm2gb_engine_destroy(mm2gb_engine_t *eng)
 int mm2gb_engine_set_misc(mm2gb_engine_t *eng, const mm2gb_misc_t *misc) { return eng ? eng->e.set_misc(misc) : fail("mm2gb: null engine"); }
 int mm2gb_engine_device(const mm2gb_engine_t *eng) { return eng ? eng->e.device : -1; }
 int mm2gb_engine_set_rmq_team_reads(mm2gb_engine_t *eng, int n) { if (!eng || n < 0) return fail("mm2gb_engine_set_rmq_team_reads: bad argument"); eng->e.rmq_team_reads = n; return 0; }
+int mm2gb_engine_set_chain_skip(mm2gb_engine_t *eng, int keep) { if (!eng || keep < 0 || keep > 1) return fail("mm2gb_engine_set_chain_skip: bad argument"); eng->e.chain_skip = keep == 1; return 0; }
+int mm2gb_engine_last_score_form(const mm2gb_engine_t *eng) { return eng ? eng->e.last_score_form : -1; }
+int mm2gb_engine_skip_stats(mm2gb_engine_t *eng, int64_t *out)
+{
+	if (!eng || !out) return fail("mm2gb_engine_skip_stats: null argument");
+	Engine &e = eng->e;
+	if (!e.skip_stats || !e.work[e.last_skip_set].skip_stats.ptr) return fail("mm2gb_engine_skip_stats: no counters (MM2GB_SKIP_STATS=1 when the engine is made, then a call that ran the walk)");
+	if (e.sync()) return -1;
+	unsigned long long v[SKIP_STAT_WORDS];
+	MM2GB_HIP(hipMemcpy(v, e.work[e.last_skip_set].skip_stats.ptr, sizeof v, hipMemcpyDeviceToHost));
+	out[0] = (int64_t)v[0]; out[1] = (int64_t)v[1]; out[2] = (int64_t)v[2];
+	out[3] = (int64_t)(v[3] >> 24); out[4] = (int64_t)(v[3] & ((1u << 24) - 1)); out[5] = (int64_t)(v[5] - ~v[4]);
+	return 0;
+}
 int mm2gb_engine_set_rmq_kernel(mm2gb_engine_t *eng, int kind) { if (!eng || kind < 0 || kind > 1) return fail("mm2gb_engine_set_rmq_kernel: bad argument"); eng->e.rmq_kernel = kind; return 0; }
 int mm2gb_engine_reserve(mm2gb_engine_t *eng, int64_t n_anchors, int64_t n_reads) { return eng ? eng->e.reserve(n_anchors, n_reads) : fail("mm2gb: null engine"); }
 void *mm2gb_engine_stream(mm2gb_engine_t *eng) { return eng ? (void*)eng->e.stream : nullptr; }

@@ -247,6 +247,7 @@ void mm2gb_map_opt_init(mm2gb_map_opt_t *o)       // mm_mapopt_init (options.c:1
 	o->chain_gap_scale = 0.8f; o->chain_skip_scale = 0.0f; o->max_max_occ = 4095; o->occ_dist = 500;
 	o->mask_level = 0.5f; o->mask_len = INT32_MAX; o->pri_ratio = 0.8f; o->best_n = 5;
 	o->host_threads = 0;           // 0: as many as the process may use, at most 32
+	o->max_chain_skip = INT32_MAX; // (mm_mapopt_init: 25) the GPU path's contract is max-chain-skip = infinity; a finite value is kept on request
 }
 
 int mm2gb_engine_release_host_scratch(mm2gb_engine_t *eng)
@@ -368,18 +369,30 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 	lap(st_local.s_anchors);
 	tr.reset(); tr.reset(new TraceRange("mm2gb:map_chain"));
 
-	// 3. chains on the device; map.c:393-426 for the parameters (the GPU path chains with max-chain-skip = infinity)
+	// 3. chains on the device; map.c:393-426 for the parameters (the GPU path chains with max-chain-skip = infinity unless the options set
+	//    a finite one: then the engine keeps it for this call, and the re-chaining call below gets it too)
 	mm2gb_misc_t misc;
+	const bool skip_limit = opt.max_chain_skip != INT32_MAX;
 	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = opt.max_gap; misc.max_dist_x = opt.max_gap_ref > 0 ? opt.max_gap_ref : opt.max_gap;
-	misc.max_skip = INT32_MAX; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
+	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
 	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * k);
 	if (mm2gb_engine_set_misc(eng, &misc)) { free_matches(); return -1; }
 	ChainsOwner ch_own;                                  // (freed on every way out)
 	mm2gb_chains_t &ch = ch_own.c;
 	// backtrack + compaction as kernels for large batches; below that on host threads, overlapped with the device: a single huge read (a
 	// tandem array) keeps one wave busy for hundreds of milliseconds where a core needs tens
-	if (a_off[R] >= 200000000 ? mm2gb_chain_gpu(eng, n_reads, a_off.data(), anchors.data(), &ch, nullptr)
-	                          : mm2gb_chain_host(eng, n_reads, a_off.data(), anchors.data(), std::max(1, opt.host_threads), &ch, nullptr)) { free_matches(); return -1; }
+	struct ChainSkipMode {                               // the engine's own mode comes back on every way out of the chaining call
+		bool &mode; const bool before;
+		ChainSkipMode(bool &m, bool keep) : mode(m), before(m) { mode = keep; }
+		~ChainSkipMode() { mode = before; }
+	};
+	int chained;
+	{
+		ChainSkipMode guard(eng->e.chain_skip, skip_limit);
+		chained = a_off[R] >= 200000000 ? mm2gb_chain_gpu(eng, n_reads, a_off.data(), anchors.data(), &ch, nullptr)
+		                                : mm2gb_chain_host(eng, n_reads, a_off.data(), anchors.data(), std::max(1, opt.host_threads), &ch, nullptr);
+	}
+	if (chained) { free_matches(); return -1; }
 
 	// 4. re-chaining of long reads whose best chain leaves much of the read uncovered (map.c:697-708): the chained anchors, sorted
 	//    again, through mg_lchain_rmq's fill
@@ -435,7 +448,7 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 			}
 		}
 		const auto t_sorted = std::chrono::steady_clock::now();
-		const mm2gb_rmq_param_t rp = { opt.max_gap, opt.rmq_inner_dist, opt.bw_long, INT32_MAX, opt.rmq_size_cap, opt.min_cnt, opt.min_chain_score, misc.chn_pen_gap, misc.chn_pen_skip };
+		const mm2gb_rmq_param_t rp = { opt.max_gap, opt.rmq_inner_dist, opt.bw_long, opt.max_chain_skip, opt.rmq_size_cap, opt.min_cnt, opt.min_chain_score, misc.chn_pen_gap, misc.chn_pen_skip };
 		ChainsOwner rc_own, rc_tie_own;
 		mm2gb_chains_t &rc = rc_own.c, &rc_tie = rc_tie_own.c;
 		std::vector<int32_t> tied(redo.size(), 0);
