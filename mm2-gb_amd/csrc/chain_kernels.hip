@@ -55,22 +55,25 @@ __device__ __forceinline__ int a_tag(const DevBatch &b, int i) { return tag_of((
 // --------------------------------------------------------------------------------------------------------------
 // predecessor window start (lchain.c:172-173), input flags, planner reductions
 //   the block's own anchors are read once as mm128_t (16 B, coalesced); nothing but st[] and the flags is written (the score kernel
-//   reads the same records in place: no SoA copy, role of plmem.cu:154-198 not needed); look-back probes read the raw anchors too
+//   reads the same records in place: no SoA copy, role of plmem.cu:154-198 not needed)
 //   st[i] = max( first j <= i in the same read with xhi[j]==xhi[i] and x[i] <= x[j]+max_dist_x ,  i - max_iter )
 // The CPU carries st across iterations; because validity is monotone in both i and j (anchors sorted by x) the
 // carried value equals this closed form ("window start").
 // --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool in_reach(const DevBatch &b, int j, int hi_i, unsigned x_i, unsigned dist)
+__device__ __forceinline__ bool in_reach(int2 v, int hi_i, unsigned x_i, unsigned dist)
 {
-	const uint2 v = *(const uint2*)&b.raw[j];                    // x.lo = reference position, x.hi = strand | rid
-	return (int)v.y == hi_i && x_i <= v.x + dist;                // positions < 2^31, dist < 2^31: no wrap
+	return v.y == hi_i && x_i <= (unsigned)v.x + dist;           // x.lo = reference position, x.hi = strand | rid; positions < 2^31, dist < 2^31: no wrap
 }
 
-constexpr int WIN_SAMPLE = 32;                         // anchors per sample = ints per 128-byte line
-constexpr int WIN_MAX_SAMPLES = 512;                   // look-back of 16 K anchors; a larger max_iter probes memory beyond it
-// (Tried, round 6: the 1 024 anchors right before the block in LDS as well, so that the probes between two samples are LDS reads instead of
-// dependent trips to L2 -- 24 KB of LDS per workgroup instead of 16, 8 KB more to load per block: the step went from 48.8 to 49.3 ms at
-// 500 M anchors and from 3.33 to 3.44 ms on 10-30 kb reads.  The kernel is not waiting for those probes.)
+constexpr int WIN_SAMPLE = 32;                         // anchors per look-back sample
+#ifndef MM2GB_WIN_LOOKBACK
+#define MM2GB_WIN_LOOKBACK 1024
+#endif
+constexpr int WIN_LOOKBACK = MM2GB_WIN_LOOKBACK;       // anchors before its block that a k_window workgroup may hold in LDS
+constexpr int WIN_SAMPLES = WIN_LOOKBACK / WIN_SAMPLE; // samples that place the block's first window start, one per lane of a wave
+constexpr int WIN_PER = PLAN_BLOCK / PLAN_THREADS;     // consecutive anchors per k_window thread
+static_assert(WIN_LOOKBACK % WIN_SAMPLE == 0 && WIN_SAMPLES <= WAVE, "the samples are one wave's lanes");
+static_assert(WIN_LOOKBACK % PLAN_THREADS == 0 && 32 % WIN_PER == 0, "staging rounds; a thread's anchors share one word of read starts");
 
 // Read that owns the first anchor of every planning block: one bisection of the read offsets per block, all blocks at once
 // (done by the first thread of each k_window workgroup it put ~13 dependent loads in front of every workgroup).
@@ -87,153 +90,194 @@ __global__ __launch_bounds__(256) void k_block_reads(DevBatch b)
 	b.blk_read[blk] = (int32_t)lo;
 }
 
-// A block of PLAN_BLOCK anchors first puts into LDS (a) its own anchors' reference position and strand|rid (a.x) and (b) one sample per 32 anchors (one per
-// 128-byte line of x) of the max_iter anchors before it.  A window start is then found with LDS probes only -- bisection
-// over the block's own anchors, or over the samples followed by at most five probes inside the one line the answer lies in,
-// a line the block has just touched -- instead of ~25 dependent trips to L2/HBM per search.
-
+// Window starts of a block come from LDS, with no chain of dependent global loads behind any lane.  Until round 7 a thread bisected one
+// sample per 32 anchors in LDS and then probed global memory: up to 5 probes inside a line, a gallop from its neighbour's start, a
+// max_iter-clamp probe and a search of offsets[] at read boundaries, ~12 dependent trips to L2 in a row, 3.9 ms per 500 M anchors.
+// Now a workgroup makes three rounds of independent loads and then works in LDS alone:
+//   1. its own 1 024 records, the first one's x word, WIN_SAMPLES samples of x words before the block (every wave loads them: no barrier)
+//      and the read starts that fall inside the block (offsets[] after the block's first read, PLAN_THREADS at a time);
+//   2. the first anchor's window start is bounded by the samples (validity is monotone, so the samples in reach are a prefix: one ballot),
+//      and every later window of the block starts at or after that bound; the x words from it up to the block, at most WIN_LOOKBACK,
+//      are staged in LDS next to the block's own ones -- lines the same XCD read a moment ago;
+//   3. a thread's read start is the last bit set at or before its anchor in a 1 024-bit map of read starts (no search of offsets[]).
+// A window wider than WIN_LOOKBACK (every sample in reach) probes global memory below the staged stretch; only such blocks do.
+// The clamp bit (lchain.c:173) needs no probe: the search begins one anchor below i - max_iter, so "the window was cut" is "the first
+// anchor in reach lies below the cut".
 __global__ __launch_bounds__(PLAN_THREADS) void k_window(DevBatch b, DevParams P)
 {
-	__shared__ int s_cut[PLAN_THREADS / WAVE];
-	__shared__ unsigned long long s_pairs[PLAN_THREADS / WAVE];
-	__shared__ int s_clamp[PLAN_THREADS / WAVE];
-	__shared__ int s_wmax[2 * PLAN_THREADS / WAVE];
-	__shared__ int own_x[PLAN_BLOCK], own_hi[PLAN_BLOCK];
-	__shared__ int smp_x[WIN_MAX_SAMPLES], smp_hi[WIN_MAX_SAMPLES];      // sample k-1 = anchor base - 32 k
-	__shared__ int s_st[PLAN_BLOCK];                                    // results, written out coalesced at the end
+	constexpr int NW = PLAN_THREADS / WAVE;
+	__shared__ int s_cut[NW];
+	__shared__ unsigned long long s_pairs[NW];
+	__shared__ int s_clamp[NW];
+	__shared__ int s_wmax[2 * NW];
+	__shared__ int2 win[WIN_LOOKBACK + PLAN_BLOCK];       // x word (x.lo, x.hi) of anchor base - WIN_LOOKBACK + slot
+	__shared__ unsigned s_starts[PLAN_BLOCK / 32];        // bit q: a read starts at anchor base + q
+	__shared__ unsigned s_disorder[PLAN_BLOCK / 32];      // bit q: anchor base + q lies before its read's previous anchor in x
 	// Workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8 share an XCD and its L2, MI355X_MICROARCH.md): planning block =
-	// f(blockIdx) is chosen so that every XCD works through ONE contiguous eighth of the batch, in order.  The max_iter anchors a
-	// block looks back at were then read moments earlier by workgroups of the same XCD and are still in that L2; with the
+	// f(blockIdx) is chosen so that every XCD works through ONE contiguous eighth of the batch, in order.  The anchors a block
+	// looks back at were then read moments earlier by workgroups of the same XCD and are still in that L2; with the
 	// identity mapping they had been read by the other seven XCDs and every look-back line came from HBM again.  Speed only.
 	const unsigned nb = gridDim.x, per = nb / 8, rem = nb % 8, xcd = blockIdx.x % 8, kth = blockIdx.x / 8;
 	const unsigned blk = nb < 64 ? blockIdx.x : xcd * per + (xcd < rem ? xcd : rem) + kth;
 	const int64_t base = (int64_t)blk * PLAN_BLOCK;
+	const int base32 = (int)base, lds0 = base32 - WIN_LOOKBACK;
 	const unsigned dist = (unsigned)P.max_dist_x;
-	const int n_samples = (int)min((int64_t)WIN_MAX_SAMPLES, min(base, (int64_t)P.max_iter + WIN_SAMPLE - 1) / WIN_SAMPLE);
-	// (the block's first read and its bounds are asked for before the anchors: two dependent loads that every thread's first search waited for)
+	if (threadIdx.x < PLAN_BLOCK / 32) s_starts[threadIdx.x] = s_disorder[threadIdx.x] = 0;
+	__syncthreads();
+
+	// round 1: nothing here waits for anything but the block's first read
 	const int64_t rd_first = b.blk_read[blk];
-	const int64_t rd_first_s = b.offsets[rd_first], rd_first_e = b.offsets[rd_first + 1];
+	uint4 own[WIN_PER];
+#pragma unroll
+	for (int m = 0; m < WIN_PER; ++m) {
+		const int64_t g = base + threadIdx.x + m * PLAN_THREADS;
+		own[m] = g < b.n ? b.raw[g] : make_uint4(0, 0, 0, 0);      // x.lo x.hi y.lo y.hi
+	}
+	const uint2 x0 = *(const uint2*)&b.raw[base];
+	uint2 own_prev[WIN_PER];                          // x word of the anchor before each own one, for lane 0 (the others take their neighbour's)
+#pragma unroll
+	for (int m = 0; m < WIN_PER; ++m) {
+		const int64_t g = base + threadIdx.x + m * PLAN_THREADS;
+		own_prev[m] = make_uint2(0, 0);
+		if (lane_id() == 0 && g > 0 && g <= b.n) own_prev[m] = *(const uint2*)&b.raw[g - 1];
+	}
+	const int64_t smp_pos = base - (int64_t)(lane_id() + 1) * WIN_SAMPLE;
+	uint2 smp = make_uint2(0, 0);
+	if (lane_id() < WIN_SAMPLES && smp_pos >= 0) smp = *(const uint2*)&b.raw[smp_pos];
+	const int rs_first = (int)b.offsets[rd_first];
+	for (int64_t r0 = rd_first + 1; r0 <= b.n_reads; r0 += PLAN_THREADS) {        // read starts after the first read's (all > base)
+		const int64_t r = r0 + threadIdx.x;
+		if (r <= b.n_reads) {
+			const int64_t v = b.offsets[r] - base;
+			if (v >= 0 && v < PLAN_BLOCK) atomicOr(&s_starts[v >> 5], 1u << (v & 31));
+		}
+		if (b.offsets[min(r0 + PLAN_THREADS - 1, b.n_reads)] >= base + PLAN_BLOCK) break;
+	}
 	bool any_seg = false, big_y = false;
-	for (int k = threadIdx.x; k < PLAN_BLOCK; k += PLAN_THREADS) {
-		const int64_t g = base + k;
-		uint4 v = make_uint4(0, 0, 0, 0);                 // x.lo x.hi y.lo y.hi
-		if (g < b.n) {
-			v = b.raw[g];
+#pragma unroll
+	for (int m = 0; m < WIN_PER; ++m) {
+		const int k = threadIdx.x + m * PLAN_THREADS;
+		const uint4 v = own[m];
+		if (base + k < b.n) {
 			const unsigned span = v.w & 0xffu;            // y>>32 & 0xff      (lchain.c:125)
 			const unsigned seg = (v.w >> 16) & 0xffu;     // (y & MM_SEED_SEG_MASK) >> 48 (lchain.c:116)
 			any_seg |= seg != 0;
 			big_y |= v.z >= (1u << 22) || span == 0;
 		}
-		own_x[k] = (int)v.x; own_hi[k] = (int)v.y;
-	}
-	for (int k = threadIdx.x; k < n_samples; k += PLAN_THREADS) {
-		const uint2 v = *(const uint2*)&b.raw[base - (int64_t)(k + 1) * WIN_SAMPLE];
-		smp_x[k] = (int)v.x; smp_hi[k] = (int)v.y;
+		win[WIN_LOOKBACK + k] = make_int2((int)v.x, (int)v.y);
+		// x below the previous anchor's (read starts are sorted out after the barrier)
+		const unsigned nx = (unsigned)prev_lane((int)v.x), nh = (unsigned)prev_lane((int)v.y);
+		const unsigned px = lane_id() == 0 ? own_prev[m].x : nx, ph = lane_id() == 0 ? own_prev[m].y : nh;
+		if (k > 0 && base + k < b.n && (ph > v.y || (ph == v.y && px > v.x))) atomicOr(&s_disorder[k >> 5], 1u << (k & 31));
 	}
 	if (__ballot(any_seg) != 0 && lane_id() == 0) atomicOr(b.flags, FLAG_ANY_SEGID);
 	if (__ballot(big_y) != 0 && lane_id() == 0) atomicOr(b.flags, FLAG_NO_LUT);
+
+	// round 2: every window start of the block is >= floor: anchors below it are out of reach of the first anchor, hence of all
+	// (anchors of the first read share its strand | rid or come later in x; those of later reads start at their read)
+	const int lo = (int)max((int64_t)rs_first, base - (int64_t)P.max_iter - 1);
+	const bool smp_in = lane_id() < WIN_SAMPLES && smp_pos >= lo && in_reach(make_int2((int)smp.x, (int)smp.y), (int)x0.y, x0.x, dist);
+	const unsigned long long smp_mask = ~__ballot(smp_in);
+	const int n_in = smp_mask == 0 ? WAVE : __builtin_ctzll(smp_mask);                    // leading samples in reach
+	const int floor_ = n_in < WIN_SAMPLES ? max(lo, base32 - (n_in + 1) * WIN_SAMPLE) : lo;
+	const int ls = max(floor_, lds0);                                                     // first anchor staged in LDS
+#pragma unroll
+	for (int m = 0; m < WIN_LOOKBACK / PLAN_THREADS; ++m) {
+		const int j = base32 - WIN_LOOKBACK + (int)threadIdx.x + m * PLAN_THREADS;
+		if (j >= ls) win[j - lds0] = *(const int2*)&b.raw[j];
+	}
 	__syncthreads();
+
+	// round 3, LDS only (but for windows wider than WIN_LOOKBACK): each thread owns WIN_PER CONSECUTIVE anchors
+	const int q0 = (int)threadIdx.x * WIN_PER;
+	const int w0 = q0 >> 5;
+	int start_before = -1;                             // last read start in the words before w0
+	for (int u = 0; u < w0; ++u) {
+		const unsigned word = s_starts[u];
+		if (word != 0) start_before = u * 32 + 31 - __clz(word);
+	}
+	const unsigned my_word = s_starts[w0];
+	// Anchors of a read out of x order break the caller's contract (map.c:329) and the monotone searches below; every anchor of a read
+	// found out of order in the block gets an empty window (a cut), so that the score kernel, whose tiles also take sorted positions
+	// for granted, finds no predecessor there rather than one outside the window (the values are unspecified).
+	const bool sorted = __ballot(lane_id() < PLAN_BLOCK / 32 && (s_disorder[lane_id()] & ~s_starts[lane_id()]) != 0) == 0;
+	auto read_in_order = [&](int q, int rq) {           // no anchor of q's read inside the block is out of order
+		const int lo = max(rq, 0);
+		int hi = PLAN_BLOCK;                             // the next read start after q
+		for (int u = q >> 5; u < PLAN_BLOCK / 32; ++u) {
+			const unsigned m = s_starts[u] & (u > q >> 5 ? 0xffffffffu : (q & 31) == 31 ? 0u : 0xffffffffu << ((q & 31) + 1));
+			if (m != 0) { hi = u * 32 + __ffs(m) - 1; break; }
+		}
+		for (int u = lo >> 5; u <= (hi - 1) >> 5; ++u) {
+			const unsigned from = u == lo >> 5 ? 0xffffffffu << (lo & 31) : 0xffffffffu;
+			const unsigned to = u == (hi - 1) >> 5 ? 0xffffffffu >> (31 - ((hi - 1) & 31)) : 0xffffffffu;
+			if (s_disorder[u] & ~s_starts[u] & from & to) return false;
+		}
+		return true;
+	};
+	auto in_reach_at = [&](int j, int hi_i, unsigned x_i) {
+		const int2 v = j >= ls ? win[j - lds0] : *(const int2*)&b.raw[j];
+		return in_reach(v, hi_i, x_i, dist);
+	};
 	int my_cut = INT_MAX, my_clamp = 0;
 	unsigned long long my_pairs = 0;
-
-	// Each thread owns PLAN_BLOCK / PLAN_THREADS CONSECUTIVE anchors: the first gets a full search, and because window starts
-	// are monotone (st[i+1] >= st[i]) the others continue forward from their neighbour's start, usually one or two probes.
-	constexpr int PER = PLAN_BLOCK / PLAN_THREADS;
-	const int64_t i_first = base + (int64_t)threadIdx.x * PER;
-	const int base32 = (int)base;
-	int64_t rd = rd_first;                            // read of the current anchor
-	int rs = 0, re = 0, st_prev = 0;
-	int win[PER];
+	int st_out[WIN_PER], wsz[WIN_PER];
+	int rs_prev = -1, first_prev = 0;                 // read start and first anchor in reach of the thread's previous searched anchor
 #pragma unroll
-	for (int k = 0; k < PER; ++k) win[k] = -1;
-#pragma unroll
-	for (int k = 0; k < PER; ++k) {
-		const int64_t i64 = i_first + k;
-		if (i64 >= b.n) break;
-		const int i = (int)i64;
-		bool fresh = k == 0;
-		if (k == 0 || i >= re) {
-			// read that owns anchor i: last r with offsets[r] <= i (gallop forward from the last known read, then bisect)
-			int64_t lo = rd, hi = b.n_reads;
-			if (k == 0 && rd_first_e > i64) { rs = (int)rd_first_s; re = (int)rd_first_e; fresh = true; }
-			else {
-			if (b.offsets[lo + 1] > i64) hi = lo + 1;
-			else {
-				int64_t step = 1;
-				while (lo + step < b.n_reads && b.offsets[lo + step] <= i64) { lo += step; step <<= 1; }
-				hi = min(lo + step, b.n_reads);
-			}
-			while (hi - lo > 1) {
-				const int64_t mid = (lo + hi) >> 1;
-				if (b.offsets[mid] <= i64) lo = mid; else hi = mid;
-			}
-			rd = lo; rs = (int)b.offsets[lo]; re = (int)b.offsets[lo + 1];
-			fresh = true;
-			}
-		}
+	for (int k = 0; k < WIN_PER; ++k) {
+		const int q = q0 + k;
+		const int i = base32 + q;
+		st_out[k] = i; wsz[k] = -1;
+		if (base + q >= b.n) continue;
+		const unsigned upto = my_word & (0xffffffffu >> (31 - (q & 31)));
+		const int rq = upto != 0 ? (w0 << 5) + 31 - __clz(upto) : start_before;
+		const int rs = rq >= 0 ? base32 + rq : rs_first;
 		int lb = i - P.max_iter;                      // may be negative
 		if (lb < rs) lb = rs;
-		const int hi_i = own_hi[i - base32];
-		const unsigned x_i = (unsigned)own_x[i - base32];
-		auto reach_own = [&](int j) { return own_hi[j - base32] == hi_i && x_i <= (unsigned)own_x[j - base32] + dist; };
-		auto reach_smp = [&](int s) { return smp_hi[s] == hi_i && x_i <= (unsigned)smp_x[s] + dist; };   // anchor base - 32 (s + 1)
-		// validity is monotone over [lb, i): false ... false true ... true.  st = first valid index, i if none.
-		auto reach_at = [&](int j) { return j >= base32 ? reach_own(j) : in_reach(b, j, hi_i, x_i, dist); };
 		int st = i;
-		if (i > lb && !fresh) {
-			// first valid index >= max(neighbour's start, lb); validity is monotone, so gallop forward and bisect
-			int l = st_prev > lb ? st_prev : lb, h = i;
-			if (reach_at(l)) h = l;
+		if (i > lb && (sorted || read_in_order(q, rq))) {
+			const int2 me = win[WIN_LOOKBACK + q];
+			const int hi_i = me.y;
+			const unsigned x_i = (unsigned)me.x;
+			// first anchor in reach in [s, i), i if none: from one below the max_iter cut (or the read start), the floor, and -- the starts
+			// being monotone within a read -- the previous anchor's answer
+			const bool cont = rs == rs_prev;
+			int s = max(max(rs, i - P.max_iter - 1), floor_);
+			if (cont) s = max(s, first_prev);
+			int first;
+			if (s >= i) first = i;
+			else if (in_reach_at(s, hi_i, x_i)) first = s;
 			else {
-				for (int step = 1; l + step < h; step <<= 1) {
-					if (reach_at(l + step)) { h = l + step; break; }
-					l += step;
+				int l = s, h = i;                         // invariant: l is out of reach, h is in reach (or i)
+				if (cont) {
+					for (int step = 1; l + step < h; step <<= 1) {
+						if (in_reach_at(l + step, hi_i, x_i)) { h = l + step; break; }
+						l += step;
+					}
+				} else if (l < ls && ls < h) {
+					if (in_reach_at(ls, hi_i, x_i)) h = ls; else l = ls;
 				}
 				while (h - l > 1) {
 					const int mid = (l + h) >> 1;
-					if (in_reach(b, mid, hi_i, x_i, dist)) h = mid; else l = mid;
+					if (in_reach_at(mid, hi_i, x_i)) h = mid; else l = mid;
 				}
+				first = h;
 			}
-			st = h;
-			if (st == lb && lb > rs && lb == i - P.max_iter && in_reach(b, lb - 1, hi_i, x_i, dist)) my_clamp = 1;
-		} else if (i > lb) {
-			int l, h;                                   // invariant: l is out of reach (or lb - 1), h is in reach (or i)
-			bool in_block = true;
-			if (lb >= base32) { l = lb - 1; h = i; }
-			else if (i > base32 && !reach_own(base32)) { l = base32; h = i; }
-			else {
-				// the window starts at or before the block's first anchor: bisect the samples (closest first: in reach ...
-				// in reach, out of reach ...), then the <= 32 anchors between two samples, which share one line of x
-				in_block = false;
-				const int s_cnt = min(n_samples, (base32 - lb) / WIN_SAMPLE);          // samples at positions >= lb
-				int sl = -1, sh = s_cnt;
-				while (sh - sl > 1) {
-					const int mid = (sl + sh) >> 1;
-					if (reach_smp(mid)) sl = mid; else sh = mid;
-				}
-				h = sl >= 0 ? base32 - (sl + 1) * WIN_SAMPLE : (i > base32 ? base32 : i);
-				l = sh < s_cnt ? base32 - (sh + 1) * WIN_SAMPLE : lb - 1;
-			}
-			if (in_block) {
-				while (h - l > 1) {
-					const int mid = (l + h) >> 1;
-					if (reach_own(mid)) h = mid; else l = mid;
-				}
-			} else {
-				while (h - l > 1) {
-					const int mid = (l + h) >> 1;
-					if (in_reach(b, mid, hi_i, x_i, dist)) h = mid; else l = mid;
-				}
-			}
-			st = h;
-			// the max_iter clamp bit (lchain.c:173): window would have reached further back
-			if (st == lb && lb > rs && lb == i - P.max_iter && in_reach(b, lb - 1, hi_i, x_i, dist)) my_clamp = 1;
+			st = max(first, lb);
+			// the max_iter clamp bit (lchain.c:173): the window would have reached further back
+			if (lb == i - P.max_iter && lb > rs && first < lb) my_clamp = 1;
+			rs_prev = rs; first_prev = first;
 		}
-		s_st[i - base32] = st;
-		st_prev = st;
+		st_out[k] = st;
 		my_pairs += (unsigned)(i - st);
-		win[k] = i - st;
+		wsz[k] = i - st;
 		if (st == i && i < my_cut) my_cut = i;
+	}
+	if (WIN_PER == 4 && base + q0 + 4 <= b.n)          // one 16-byte store per lane
+		*(int4*)&b.st[base + q0] = make_int4(st_out[0], st_out[1 % WIN_PER], st_out[2 % WIN_PER], st_out[3 % WIN_PER]);
+	else {
+#pragma unroll
+		for (int k = 0; k < WIN_PER; ++k) if (base + q0 + k < b.n) b.st[base + q0 + k] = st_out[k];
 	}
 	// wave then block reductions
 	for (int off = WAVE / 2; off > 0; off >>= 1) {
@@ -244,24 +288,23 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_window(DevBatch b, DevParams P
 	const int w = threadIdx.x / WAVE;
 	if (lane_id() == 0) { s_cut[w] = my_cut; s_pairs[w] = my_pairs; s_clamp[w] = my_clamp; }
 	__syncthreads();
-	for (int k = threadIdx.x; k < PLAN_BLOCK && base + k < b.n; k += PLAN_THREADS) b.st[base + k] = s_st[k];
 	int blk_cut = s_cut[0];
-	for (int k = 1; k < PLAN_THREADS / WAVE; ++k) blk_cut = min(blk_cut, s_cut[k]);
+	for (int k = 1; k < NW; ++k) blk_cut = min(blk_cut, s_cut[k]);
 	// widest window before the block's first cut (belongs to the chunk that started earlier) and from it on (belongs to
 	// the chunk that starts here)
 	int head = 0, tail = 0;
 #pragma unroll
-	for (int k = 0; k < PER; ++k) {
-		if (win[k] < 0) continue;
-		if (i_first + k < blk_cut) head = max(head, win[k]); else tail = max(tail, win[k]);
+	for (int k = 0; k < WIN_PER; ++k) {
+		if (wsz[k] < 0) continue;
+		if (base32 + q0 + k < blk_cut) head = max(head, wsz[k]); else tail = max(tail, wsz[k]);
 	}
 	for (int off = WAVE / 2; off > 0; off >>= 1) { head = max(head, __shfl_xor(head, off)); tail = max(tail, __shfl_xor(tail, off)); }
-	if (lane_id() == 0) { s_wmax[w] = head; s_wmax[PLAN_THREADS / WAVE + w] = tail; }
+	if (lane_id() == 0) { s_wmax[w] = head; s_wmax[NW + w] = tail; }
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		for (int k = 1; k < PLAN_THREADS / WAVE; ++k) { my_pairs += s_pairs[k]; my_clamp |= s_clamp[k]; }
+		for (int k = 1; k < NW; ++k) { my_pairs += s_pairs[k]; my_clamp |= s_clamp[k]; }
 		head = tail = 0;
-		for (int k = 0; k < PLAN_THREADS / WAVE; ++k) { head = max(head, s_wmax[k]); tail = max(tail, s_wmax[PLAN_THREADS / WAVE + k]); }
+		for (int k = 0; k < NW; ++k) { head = max(head, s_wmax[k]); tail = max(tail, s_wmax[NW + k]); }
 		b.blk_wmax[2 * blk] = head;
 		b.blk_wmax[2 * blk + 1] = tail;
 		b.blk_firstcut[blk] = blk_cut;
