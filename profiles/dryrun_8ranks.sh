@@ -1,5 +1,5 @@
 #!/bin/bash
-# The 8-GPU command at its REAL per-rank load, on the one GPU there is: MM2GB_DEVICES=0,0,0,0,0,0,0,0 python3 bench.py --gpus 8 (500 M anchors
+# The 8-GPU command at its REAL per-rank load, on the one GPU there is: MM2GB_DEVICES=0,0,0,0,0,0,0,0 python3 bench.py --gpus 8 --full (500 M anchors
 # per rank, every leg), with the host's memory and the device's memory sampled every 2 s.  No curve is claimed from it: it shows that the
 # command the driver will run on an 8-GPU node completes, how long it takes and what it needs.   bash profiles/dryrun_8ranks.sh r05
 TAG=${1:-r05}
@@ -11,7 +11,7 @@ O=gpurun_out
   done ) > $O/${TAG}_dryrun8_mem.log 2>&1 &
 SAMPLER=$!
 t0=$(date +%s)
-MM2GB_DEVICES=0,0,0,0,0,0,0,0 python3 bench.py --gpus 8 > $O/${TAG}_bench_8ranks_full_size_one_gpu.json 2> $O/${TAG}_bench_8ranks_full_size_one_gpu.err
+MM2GB_DEVICES=0,0,0,0,0,0,0,0 python3 bench.py --gpus 8 --full > $O/${TAG}_bench_8ranks_full_size_one_gpu.json 2> $O/${TAG}_bench_8ranks_full_size_one_gpu.err
 rc=$?
 t1=$(date +%s)
 kill $SAMPLER

@@ -12,7 +12,7 @@ bash profiles/collect_pmc_post.sh $GRAFT_REPO_ROOT/gpurun_out/pmc_post_$TAG > $O
 python profiles/summarize_post.py $TAG > $O/${TAG}_post_summary.log 2>&1; tail -12 $O/${TAG}_post_summary.log
 bash profiles/profile_config2.sh $TAG > $O/${TAG}_config2.log 2>&1; tail -5 $O/${TAG}_config2.log
 cp profiles/${TAG}_*.csv profiles/${TAG}_*.json profiles/traffic_latest.json profiles/post_traffic_latest.json profiles/config2_counters_latest.json $O/ 2>/dev/null
-python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; echo "bench rc=$?"; cut -c1-300 $O/${TAG}_bench_default.json
+python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; echo "bench rc=$?"; cut -c1-300 $O/${TAG}_bench_default.json
 bash profiles/dryrun_8ranks.sh $TAG
 python profiles/mapper_rate.py 3000 > $O/${TAG}_mapper_rate_3000.json 2> $O/${TAG}_mapper_rate_3000.err; echo "mapper rc=$?"; tail -c 600 $O/${TAG}_mapper_rate_3000.json
 python profiles/rmq_rate.py > $O/${TAG}_rmq_rate.json 2> $O/${TAG}_rmq_rate.err; echo "rmq rc=$?"; tail -c 400 $O/${TAG}_rmq_rate.json
