@@ -92,6 +92,9 @@ int  mm2gb_engine_set_misc(mm2gb_engine_t *eng, const mm2gb_misc_t *misc);
  * 1 the skip-limited walk.  Stats keep their meaning (n_pairs: the sum of window sizes, not the candidates met). */
 int  mm2gb_engine_set_chain_skip(mm2gb_engine_t *eng, int keep);
 int  mm2gb_engine_last_score_form(const mm2gb_engine_t *eng);
+/* measurement aid: groups of 64 targets that k_score's band pass (far predecessors by diagonal band; MM2GB_BAND, MM2GB_BAND_SLAB,
+ * MM2GB_BAND_LAG when the engine is made) swept in the engine's calls since its stats were last reset: out[0] the wave path, out[1] the teams */
+int  mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out);
 /* measurement aid: with MM2GB_SKIP_STATS=1 set when the engine was made, the skip-limited walk of its last micro-batch counts, and this waits for
  * the engine and gives: [0] walk rounds of 64 candidates, [1] rounds of the max_ii search, [2] targets, [3] the slowest chunk's time and [4] its
  * anchors, [5] the walk's span from the first chunk's start to the last chunk's end; times in ticks of the 100 MHz s_memrealtime clock */

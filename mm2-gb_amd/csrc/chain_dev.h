@@ -14,6 +14,8 @@ struct DevParams {
 	int   lut_clamp;         // 1: the sweeps clamp the table index to lut_last; 0: an index beyond it reads beyond LDS, i.e. 0 = reject
 	int   free_sweep;        // 1 (only without lut_clamp): source blocks whose every pair has bw < dr <= dq_lim - bw are swept without range test
 	int   edge_prefix;       // 1: edge blocks of tiles whose window starts rise from lane to lane take their window test from a scalar prefix mask (sweep_block_lut_edge_sorted); only with MM2GB_EDGE=new
+	int   band_slab;         // MODE_LUT without lut_clamp: predecessors older than band_lag anchors before a target's slab of band_slab anchors are swept by
+	int   band_lag;          // diagonal band (chain_kernels.hip, band_slab_part); 0 = off.  band_slab in {128, 256, 512}, band_lag a multiple of 64 <= band_slab
 	float gap, skip;
 };
 
@@ -89,6 +91,8 @@ struct DevBatch {
 	// outputs
 	int32_t  *f;               // score                                                4 B
 	int32_t  *p;               // i - predecessor, 0 = none                            4 B
+	int32_t  *diag;            // x - y of each anchor, written by k_score when P.band_slab > 0 (the band pass reads 4 B per source)
+	int32_t  *band_res;        // two per anchor: the band pass's best score and predecessor (-1: none) for the target's later sweep
 	// planner (per PLAN_BLOCK anchors)
 	int32_t  *blk_firstcut;    // smallest i in block with st[i] == i, INT32_MAX if none
 	int64_t  *blk_pairs;       // sum of window sizes in block
@@ -127,7 +131,9 @@ enum { CNT_NCHUNK = 0, CNT_CURSOR = 1, CNT_NLONG = 2, CNT_LCURSOR = 3, CNT_NTRAC
        CNT_NGANG = 12,          // chunks scored by a gang of workgroups
        CNT_GANG_STRIPS = 13,    // strips of such chunks
        CNT_GANG_WGS = 14,       // workgroups that started in a gang
-       CNT_WORDS = 16 };
+       CNT_BAND_WAVE = 16,      // groups of targets the band pass swept (k_score, band_group) in the wave path ...
+       CNT_BAND_TEAM = 17,      // ... and in the team paths
+       CNT_WORDS = 18 };
 
 struct LaunchCfg {
 	int score_grid;          // persistent 1024-thread workgroups of k_score

@@ -1708,15 +1708,249 @@ __device__ __forceinline__ void sweep_a_into_b(const DevBatch &b, TilePair &t, i
 	__builtin_amdgcn_wave_barrier();
 }
 
+// ---- band pass: predecessors far behind a target by diagonal (MODE_LUT without lut_clamp; P.band_slab > 0) -------------------
+// A pair scores only if |dr - dq| <= bw, and dr - dq = d_i - d_j with d = x - y, the anchor's diagonal.  A tile of 64 consecutive
+// targets of a repeat block covers every diagonal, so the dense sweep cannot use that; a group of targets with similar diagonals can.
+// A chunk is cut into slabs of band_slab anchors.  For the targets of slab [s0, s0 + S) the sources older than jl = s0 - band_lag go
+// through this pass; those from jl on keep the dense sweep (sweep_pair_block, then the in-tile phase), started from jl.  The slab's
+// targets are dealt into groups of 64 by diagonal (band_slab_part); a group scans its sources [smallest window start, jl) in index
+// order, 64 at a time, reading 4 B per source (diag[], written as tiles are loaded), and stages those whose diagonal lies within
+// [d_min - bw, d_max + bw] of the group -- every source that can score against one of its targets -- compacted IN INDEX ORDER
+// (band_group); each full stage is swept with the forms the dense sweep uses, chosen from the staged block's own x extent.  A
+// target's best over these sources and its predecessor go to band_res; the dense sweep's result is merged with it before the in-tile
+// phase (band_merge).  Any grouping gives the same result: the best is the largest score with the largest source index among
+// equals, and all band sources are older than all dense ones.
+__device__ __forceinline__ int wave_min_i32(int v) { return -wave_max_i32_dpp(-v); }   // (v > INT_MIN)
+
+// A staged block whose sources are not consecutive, some target's window starting inside it: sweep_block_lut_edge with the source's
+// index taken from lane k of `idx`.
+__device__ __forceinline__ void sweep_block_lut_band(int t_st, int tx4, int ty4, int idx, const int4 *stage, const DevParams &P, int &bestv)
+{
+	constexpr int G = 4;
+	const unsigned base = (unsigned)P.lut_base, lim4 = (unsigned)P.dq_lim << 2;
+	int pos = 0x7fffffff;
+	asm volatile("" : "+v"(pos));
+	for (int kg = 0; kg < WAVE; kg += G) {
+		int4 s4[G];
+		int dqm[G], drm[G], pen[G];
+#pragma unroll
+		for (int u = 0; u < G; ++u) s4[u] = stage[kg + u];
+#pragma unroll
+		for (int u = 0; u < G; ++u) {
+			dqm[u] = ty4 - s4[u].w; drm[u] = tx4 - s4[u].z;
+			pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(drm[u], dqm[u] & pos, base);
+		}
+#pragma unroll
+		for (int u = 0; u < G; ++u) {
+			const int dg = drm[u] < dqm[u] ? drm[u] : dqm[u];
+			int v = ((s4[u].y < dg ? s4[u].y : dg) << 5) + s4[u].x;
+			asm("" : "+v"(v));
+			v += pen[u];
+			const int j = __builtin_amdgcn_readlane(idx, kg + u);
+			unsigned long long saved;                               // (the mask on entry is saved and put back inside the statement: sweep_block_lut)
+			asm volatile("s_mov_b64 %[sv], exec\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[dq]\n\tv_cmpx_ge_i32_e32 vcc, %[j], %[st]\n\tv_max_i32_e32 %[b], %[v], %[b]\n\ts_mov_b64 exec, %[sv]"
+			             : [b] "+v"(bestv), [sv] "=&s"(saved) : [lim] "s"(lim4), [dq] "v"(dqm[u]), [st] "v"(t_st), [j] "s"(j), [v] "v"(v) : "vcc");
+		}
+	}
+}
+
+// One group of targets (lane: target index, -1 = none; at least one lane holds one) against the sources [smallest window start, jl).
+__device__ __forceinline__ int band_group(const DevBatch &b, const DevParams &P, int4 *stage, const int tgt, const int jl)
+{
+	const int lane = lane_id();
+	const int l0 = __builtin_ctzll(__ballot(tgt >= 0));
+	const int t = tgt >= 0 ? tgt : bcast(tgt, l0);                 // empty lanes repeat a target of the group
+	const int x = a_x(b, t), y = a_y(b, t), st = b.st[t];
+	int best = a_span(b, t) + 1, arg = -1;                         // threshold form, as the dense sweep
+	const int lo = wave_min_i32(st), hi_st = wave_max_i32_dpp(st);
+	if (lo < jl) {
+		const int d = x - y;
+		const int dmin = wave_min_i32(d), dmax = wave_max_i32_dpp(d);
+		const int gx_min = wave_min_i32(x), gx_max = wave_max_i32_dpp(x);
+		// |d_i - d_j| <= bw for some target i  =>  d_j - (dmin - bw) in [0, width]; the unsigned difference wraps only for sources
+		// that cannot score, which then pass or not -- a superset is all the test has to give
+		const int band_lo = dmin - P.bw;
+		const unsigned width = (unsigned)(dmax - dmin) + 2u * (unsigned)P.bw;
+		const int tx4 = (int)(((unsigned)x - 1u) << 2), ty4 = (int)(((unsigned)y - 1u) << 2);
+		const unsigned free_span = (unsigned)(P.dq_lim - P.bw);
+		auto sweep = [&](const int idx) __attribute__((always_inline)) {
+			// lane k: the k-th staged source, indices ascending (the tie rule: a later source wins an equal score)
+			const int xs = a_x(b, idx), ys = a_y(b, idx), sq = a_span(b, idx), sf = b.f[idx];
+			const int sx_min = wave_min_i32(xs), sx_max = wave_max_i32_dpp(xs);
+			// every source inside every target's window (hence of its read) and left of every target: no test; then the dense
+			// sweep's free and FAR forms on the block's own extent (sweep_block_lut2_free)
+			const bool no_check = first_lane(idx) >= hi_st && gx_min > sx_max;
+			const bool free_block = no_check && P.free_sweep && (unsigned)(gx_max - sx_min) <= free_span;
+			const bool far_block = free_block && __ballot(sq + P.bw > gx_min - xs) == 0;
+			const int d0 = (first_lane(xs) - first_lane(ys)) * 4;
+			stage_block_lut(xs, ys, sf, sq, stage, far_block, d0);
+			int bestv = best << 7;
+			if (far_block) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
+			else if (free_block) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
+			else if (no_check) sweep_block_lut<false, false>(st, tx4, ty4, 0, 0, stage, P, bestv);
+			else sweep_block_lut_band(st, tx4, ty4, idx, stage, P, bestv);
+			const int won = bestv & 127;                            // k+1 of the staged source that holds the best
+			const int wj = __shfl(idx, (won - 1) & (WAVE - 1));
+			arg = (unsigned)(won - 1) < (unsigned)WAVE ? wj : arg;
+			best = bestv >> 7;
+			__builtin_amdgcn_wave_barrier();
+		};
+		// scan: the hits of 64 sources go, in index order, to the lanes after those already staged (ds_permute pushes each hit to its
+		// lane; what does not fit goes round to the first lanes and waits for the next stage); diagonals are read one step ahead,
+		// past the CU's cache (written by other waves of the workgroup, or by this one from other lanes)
+		int sidx = 0, n_st = 0;
+		int jb = lo;
+		int dn = jb + lane < jl ? __hip_atomic_load(b.diag + jb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+		for (; jb < jl; jb += WAVE) {
+			const int j = jb + lane;
+			const int dj = dn;
+			dn = j + WAVE < jl ? __hip_atomic_load(b.diag + j + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+			const bool hit = j < jl && (unsigned)(dj - band_lo) <= width;
+			const unsigned long long m = __ballot(hit);
+			if (m == 0) continue;
+			const int c = __popcll(m);
+			const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+			// (a lane without a hit writes to the first lane that takes none, so no hit is overwritten)
+			const int dst = (hit ? n_st + rank : n_st + c) & (WAVE - 1);
+			const int recv = __builtin_amdgcn_ds_permute(dst << 2, j);
+			if (n_st + c < WAVE) {
+				sidx = lane >= n_st && lane < n_st + c ? recv : sidx;
+				n_st += c;
+			} else {
+				sweep(lane >= n_st ? recv : sidx);
+				n_st += c - WAVE;
+				sidx = recv;                                        // lanes below n_st: the hits that did not fit
+			}
+		}
+		// the last stage, filled up with copies of its last source (same score, same index: nothing changes)
+		if (n_st > 0) sweep(lane < n_st ? sidx : bcast(sidx, n_st - 1));
+	}
+	if (tgt >= 0) { b.band_res[2 * tgt] = best; b.band_res[2 * tgt + 1] = arg; }
+	return lo < jl;
+}
+
+// Groups [g_from, g_to) of the slab [s0, s0 + n) (n <= 512): the targets sorted by (diagonal, index) -- a bitonic sort of one key per
+// target, eight per lane, element r * 64 + lane in register r --, group g = register g.  A slab whose diagonals all lie within 2 bw is
+// left in index order (a stretch of one chain: nothing to gain from the sort).
+__device__ __forceinline__ int band_slab_part(const DevBatch &b, const DevParams &P, int4 *stage, const int s0, const int n, const int jl,
+                                              const int g_from, const int g_to)
+{
+	constexpr int R = 8;
+	const int lane = lane_id();
+	unsigned key[R];
+	int lo = INT_MAX, hi = INT_MIN, st_lo = INT_MAX;
+#pragma unroll
+	for (int r = 0; r < R; ++r) {
+		const int e = r * WAVE + lane;
+		const int d = e < n ? a_x(b, s0 + e) - a_y(b, s0 + e) : 0;
+		if (e < n) { lo = min(lo, d); hi = max(hi, d); st_lo = min(st_lo, b.st[s0 + e]); }
+	}
+	// no window of the slab reaches before jl: nothing to do (band_merge is skipped for tiles whose windows all start at jl or later)
+	if (wave_min_i32(st_lo) >= jl) return 0;
+	const int dmin = wave_min_i32(lo), dmax = wave_max_i32_dpp(hi);
+	const unsigned range = (unsigned)(dmax - dmin);
+	if (range <= 2u * (unsigned)P.bw) {
+#pragma unroll
+		for (int r = 0; r < R; ++r) key[r] = r * WAVE + lane < n ? (unsigned)(r * WAVE + lane) : ~0u;
+	} else {
+		const int sh = (range >> 22) ? 32 - __clz((int)(range >> 22)) : 0;     // (diagonal - dmin) >> sh < 2^22: keys below 2^31
+#pragma unroll
+		for (int r = 0; r < R; ++r) {
+			const int e = r * WAVE + lane;
+			key[r] = e < n ? (((unsigned)(a_x(b, s0 + e) - a_y(b, s0 + e) - dmin) >> sh) << 9) | (unsigned)e : ~0u;
+		}
+#pragma unroll
+		for (int k = 2; k <= R * WAVE; k <<= 1) {
+#pragma unroll
+			for (int j = k >> 1; j > 0; j >>= 1) {
+				if (j >= WAVE) {
+					const int jr = j / WAVE;
+#pragma unroll
+					for (int r = 0; r < R; ++r) {
+						if (r & jr) continue;
+						const bool up = ((r * WAVE) & k) == 0;              // (k > 64 here: the direction is the register's)
+						const unsigned a = key[r], c = key[r | jr];
+						key[r] = up ? min(a, c) : max(a, c);
+						key[r | jr] = up ? max(a, c) : min(a, c);
+					}
+				} else {
+#pragma unroll
+					for (int r = 0; r < R; ++r) {
+						const unsigned o = (unsigned)__shfl_xor((int)key[r], j);
+						const bool up = ((r * WAVE + lane) & k) == 0, lower = (lane & j) == 0;
+						key[r] = up == lower ? min(key[r], o) : max(key[r], o);
+					}
+				}
+			}
+		}
+	}
+	int swept = 0;                                                  // groups that had sources before jl (MM2GB counters CNT_BAND_*)
+	for (int g = g_from; g < g_to; ++g) {
+		unsigned kg = key[0];
+#pragma unroll
+		for (int r = 1; r < R; ++r) kg = g == r ? key[r] : kg;
+		const int tgt = kg == ~0u ? -1 : s0 + (int)(kg & 511u);
+		if (__ballot(tgt >= 0) == 0) break;                         // (empty keys sort last)
+		swept += band_group(b, P, stage, tgt, jl);
+	}
+	return swept;
+}
+// A team's wave waits, before a tile's in-tile phase, for every band part of the tile's slab, and a slab's parts are taken by the
+// waves that own its tiles (or pairs).  That is deadlock-free only while those are distinct waves of the team: parts per slab <= team size.
+// The engine allows slabs of 128, 256 and 512 anchors (2, 4, 8 parts in whole-workgroup teams; 1, 2, 4 in pair teams of 4 or 8 waves);
+// a team that is too small for its slab's parts scores its chunk without the band pass.
+__device__ __forceinline__ bool band_fits_team(const DevParams &P, const int anchors_per_part, const int n_waves)
+{
+	return P.band_slab > 0 && P.band_slab / anchors_per_part <= n_waves;
+}
+// Whether a chunk takes the band pass at all: only if its mean window (planner cost = sum of windows + 16 per anchor) is wider than half
+// the lag.  Chunks of narrow windows -- short reads, chain-only stretches -- would pay the diagonals' stores and a look at every slab
+// for sources that are almost never older than the lag.  (Speed only: the results are the same either way.)
+__device__ __forceinline__ bool band_chunk(const DevBatch &b, const DevParams &P, const int ci, const int cs, const int ce)
+{
+	const long long len = ce - cs;
+	return P.band_slab > 0 && b.band_res && 2 * (b.chunk_cost[ci] - 16 * len) > (long long)P.band_lag * len;
+}
+
+// The band pass's result for the 64 targets from i0 merged into the dense sweep's (threshold form, both): the band's sources are all
+// older, so it wins only with a strictly larger score.
+__device__ __forceinline__ void band_merge(const DevBatch &b, const int i0, const int n_here, int &best, int &arg)
+{
+	const int i = i0 + min(lane_id(), n_here - 1);
+	const int bb = __hip_atomic_load(b.band_res + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	const int ba = __hip_atomic_load(b.band_res + 2 * i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	const bool take = ba >= 0 && (arg < 0 || bb > best);
+	best = take ? bb : best;
+	arg = take ? ba : arg;
+}
+
+// this pair's anchors' diagonals, for the band passes of later slabs
+__device__ __forceinline__ void band_store_diag(const DevBatch &b, const TilePair &t, const int i0)
+{
+	if (lane_id() < t.n_a) b.diag[i0 + lane_id()] = t.A.x - t.A.y;
+	if (lane_id() < t.n_b) b.diag[i0 + WAVE + lane_id()] = t.B.x - t.B.y;
+}
+
 template <bool TRACK>
-__device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevParams &P, const int *lut, int4 *stage, const int cs, const int ce)
+__device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevParams &P, const int *lut, int4 *stage, const int cs, const int ce, const bool band_on)
 {
 	const int lane = lane_id();
 	Keep keep; keep.idx = -1; keep.x = keep.hi = keep.y = keep.tag = keep.f = 0;
 	auto f_old = [&](int jj) { return b.f[jj]; };
+	const bool band = band_on;
+	int band_groups = 0;
 	for (int i0 = cs; i0 < ce; i0 += 2 * WAVE) {
 		TilePair t = load_pair(b, i0, ce);
 		int jb = cs + ((t.lo_a - cs) & ~(WAVE - 1));
+		// band pass (band_slab_part): the whole slab at its first pair; the dense sweep starts at jl
+		const int s0 = band ? i0 - (i0 - cs) % P.band_slab : cs, jl = s0 - P.band_lag;
+		const bool in_band = band && jl > cs;
+		if (band) band_store_diag(b, t, i0);
+		if (in_band && i0 == s0) {
+			band_groups += band_slab_part(b, P, stage, s0, min(P.band_slab, ce - s0), jl, 0, P.band_slab / WAVE);
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (band_merge reads the results past the CU's cache)
+		}
+		if (in_band && jb < jl) jb = jl;
 		if (jb < i0) {
 			const int eq_lo = equal_x_run_start(b, cs, i0, first_lane(t.A.x));
 			int sf = b.f[jb + lane], sq = a_span(b, jb + lane);
@@ -1729,6 +1963,7 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 			}
 		}
 		const Target TA = load_target(b, i0, ce, TRACK);
+		if (in_band && t.lo_a < jl) band_merge(b, i0, t.n_a, t.best_a, t.arg_a);
 		in_tile<MODE_LUT, TRACK>(b, TA, i0, t.n_a, P, lut, stage, t.best_a, t.arg_a, keep, f_old);
 		const int f_a = t.arg_a < 0 ? TA.q : t.best_a;
 		if (TA.live) {
@@ -1739,6 +1974,7 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 		if (t.n_b == 0) break;
 		sweep_a_into_b(b, t, cs, i0, f_a, TA.q, stage, P);
 		const Target TB = load_target(b, i0 + WAVE, ce, TRACK);
+		if (in_band && t.lo_b < jl) band_merge(b, i0 + WAVE, t.n_b, t.best_b, t.arg_b);
 		in_tile<MODE_LUT, TRACK>(b, TB, i0 + WAVE, t.n_b, P, lut, stage, t.best_b, t.arg_b, keep, f_old);
 		if (TB.live) {
 			const int i = i0 + WAVE + lane;
@@ -1746,6 +1982,7 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 			b.p[i] = t.arg_b < 0 ? 0 : i - t.arg_b;
 		}
 	}
+	if (band_groups > 0 && lane == 0) atomicAdd(&b.counters[CNT_BAND_WAVE], band_groups);
 }
 
 // ---- team mode: the waves of a team (4, 8 or 16) pipeline the tiles of ONE heavy chunk ------------------------
@@ -1754,7 +1991,7 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 // (a tile needs ~(window/64 + 2) block sweeps, its critical dependency is 2 of them).  Final scores travel between
 // waves through an LDS ring indexed by anchor number (the sliding predecessor window, max_iter + slack entries);
 // "tiles done" is a release/acquire counter in LDS.  No block barrier inside a chunk.
-struct CoopShared { int done; int keep[6]; int chunk; int bar_count; int bar_gen; int part; };   // one per team (part: Progress)
+struct CoopShared { int done; int keep[6]; int chunk; int bar_count; int bar_gen; int part; int band; };   // one per team (part: Progress; in coop_chunk_pairs part / band count the band parts of even / odd slabs)
 // Gangs (several workgroups on one chunk, gang_chunk_pairs) are an instantiation of their own, k_score<MODE_LUT, false, true>: the gang code
 // costs the plain kernel registers (250 -> 283 spilled scalars) and 1-3 % at 500 M anchors, where no chunk gets a gang anyway; the host
 // launches it for the micro-batches small enough to end with their largest chunks (Engine: gang_max_n).
@@ -1810,7 +2047,7 @@ __device__ __forceinline__ void sweep_block_by_quarters(const DevBatch &b, const
 
 template <int MODE, bool TRACK>
 __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P, const int *lut, int4 *stage, int *ring, const int n_slots, CoopShared *sh,
-                           const int cs, const int ce, const int wave, const int n_waves)
+                           const int cs, const int ce, const int wave, const int n_waves, const bool band_on)
 {
 	const int lane = lane_id();
 	const int n_tiles = (ce - cs + WAVE - 1) / WAVE;
@@ -1819,6 +2056,10 @@ __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P
 		// a few percent of the shortest tile)
 		while (first_lane(__hip_atomic_load(&sh->done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) __builtin_amdgcn_s_sleep(MM2GB_POLL_SLEEP);
 	};
+	// band pass (MODE_LUT; band_slab_part, coop_chunk_pairs): the tiles of a slab take one group each
+	const bool band = MODE == MODE_LUT && band_on && band_fits_team(P, WAVE, n_waves);
+	const int tps = band ? P.band_slab / WAVE : 1, s_first = band ? P.band_lag / P.band_slab + 1 : 0;
+	int band_groups = 0;
 	for (int t = wave; t < n_tiles; t += n_waves) {
 		const int i0 = cs + t * WAVE;
 		const Target T = load_target(b, i0, ce, TRACK);
@@ -1827,6 +2068,17 @@ __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P
 		const int tile_lo = first_lane(T.st);
 		const int st_hi = bcast(T.st, n_here - 1);
 		int jb = cs + ((tile_lo - cs) & ~(WAVE - 1));
+		const int sl = t / tps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
+		const bool in_band = band && jl > cs;
+		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
+		if (band && T.live) b.diag[i0 + lane] = T.x - T.y;
+		if (in_band) {
+			const int part = t - sl * tps;
+			wait_done((jl - cs) / WAVE);                               // the band's sources are final
+			band_groups += band_slab_part(b, P, stage, s0, min(P.band_slab, ce - s0), jl, part, part + 1);
+			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+			if (jb < jl) jb = jl;
+		}
 		const int eq_lo = MODE == MODE_LUT && jb < i0 ? equal_x_run_start(b, cs, i0, first_lane(T.x)) : i0;
 		// tile k of the chunk lives in ring slot k mod n_slots (64 scores per slot; the planner made sure the slots cover
 		// this chunk's widest window plus the tile being written)
@@ -1841,6 +2093,13 @@ __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P
 		}
 		const int my_slot = (int)((unsigned)t % (unsigned)n_slots);
 		wait_done(t);                                                    // every earlier tile is final
+		if (in_band && tile_lo < jl) {
+			// every part of this slab, and of the earlier slabs of its parity (all full), is out
+			const int s_min = s_first + ((sl - s_first) & 1);
+			const int need = tps * ((sl - s_min) / 2) + min(tps, n_tiles - sl * tps);
+			while (first_lane(__hip_atomic_load(band_cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) __builtin_amdgcn_s_sleep(MM2GB_POLL_SLEEP);
+			band_merge(b, i0, n_here, best, arg);
+		}
 		Keep keep;
 		if (TRACK) { keep.idx = first_lane(sh->keep[0]); keep.x = first_lane(sh->keep[1]); keep.hi = first_lane(sh->keep[2]); keep.y = first_lane(sh->keep[3]); keep.tag = first_lane(sh->keep[4]); keep.f = first_lane(sh->keep[5]); }
 		else { keep.idx = -1; keep.x = keep.hi = keep.y = keep.tag = keep.f = 0; }
@@ -1859,13 +2118,14 @@ __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P
 		// publish: ring + keep writes above are ordered before the counter by the release
 		if (lane == 0) __hip_atomic_store(&sh->done, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 	}
+	if (band_groups > 0 && lane == 0) atomicAdd(&b.counters[CNT_BAND_TEAM], band_groups);
 }
 
 // Team mode of the table build: waves take PAIRS of tiles round-robin (run_chunk_pairs explains the pair).  Tile A is published as
 // soon as it is final, so the chain through the tiles of the chunk is as long as with single tiles.
 template <bool TRACK>
 __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevParams &P, const int *lut, int4 *stage, int *ring, const int n_slots, CoopShared *sh,
-                                 const int cs, const int ce, const int wave, const int n_waves)
+                                 const int cs, const int ce, const int wave, const int n_waves, const bool band_on)
 {
 	const int lane = lane_id();
 	const int n_tiles = (ce - cs + WAVE - 1) / WAVE;
@@ -1885,10 +2145,27 @@ __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevPar
 		const int k = (int)(d / WAVE);
 		return k >= cur - n_slots ? ring_l[(unsigned)k % (unsigned)n_slots * WAVE + d % WAVE] : b.f[jj];
 	};
+	// band pass (band_slab_part): the pairs of a slab share its groups out, two per pair; a pair's targets are merged with the band's
+	// result once every part of its slab has been published.  Parts of slab s may be in flight with those of slab s + 1 (a band pass
+	// waits only for the slabs before jl), never with those of s + 2: they are counted per parity of the slab (sh->part, sh->band)
+	const bool band = band_on && band_fits_team(P, 2 * WAVE, n_waves);
+	const int pps = band ? P.band_slab / (2 * WAVE) : 1, n_pairs = (n_tiles + 1) / 2, s_first = band ? P.band_lag / P.band_slab + 1 : 0;
+	int band_groups = 0;
 	for (int pr = wave; 2 * pr < n_tiles; pr += n_waves) {
 		const int ta = 2 * pr, i0 = cs + ta * WAVE;              // tile A = tile ta of the chunk, tile B = ta + 1
 		TilePair t = load_pair(b, i0, ce);
 		int jb = cs + ((t.lo_a - cs) & ~(WAVE - 1));
+		const int sl = pr / pps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
+		const bool in_band = band && jl > cs;
+		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
+		if (band) band_store_diag(b, t, i0);
+		if (in_band) {
+			const int part = pr - sl * pps;
+			wait_done((jl - cs) / WAVE);                               // the band's sources are final
+			band_groups += band_slab_part(b, P, stage, s0, min(P.band_slab, ce - s0), jl, 2 * part, 2 * part + 2);
+			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+			if (jb < jl) jb = jl;
+		}
 		const int eq_lo = jb < i0 ? equal_x_run_start(b, cs, i0, first_lane(t.A.x)) : i0;
 		int slot = (int)((unsigned)((jb - cs) / WAVE) % (unsigned)n_slots);
 		const int first_in_ring = ta - n_slots;                      // tiles from this one on are in the ring
@@ -1912,6 +2189,13 @@ __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevPar
 		if (TRACK) { keep.idx = first_lane(sh->keep[0]); keep.x = first_lane(sh->keep[1]); keep.hi = first_lane(sh->keep[2]); keep.y = first_lane(sh->keep[3]); keep.tag = first_lane(sh->keep[4]); keep.f = first_lane(sh->keep[5]); }
 		else { keep.idx = -1; keep.x = keep.hi = keep.y = keep.tag = keep.f = 0; }
 		const Target TA = load_target(b, i0, ce, TRACK);
+		if (in_band && t.lo_a < jl) {
+			// every part of this slab, and of the earlier slabs of its parity (all full), is out
+			const int s_min = s_first + ((sl - s_first) & 1);
+			const int need = pps * ((sl - s_min) / 2) + min(pps, n_pairs - sl * pps);
+			while (first_lane(__hip_atomic_load(band_cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) __builtin_amdgcn_s_sleep(MM2GB_POLL_SLEEP);
+			band_merge(b, i0, t.n_a, t.best_a, t.arg_a);
+		}
 		cur = ta;
 		in_tile<MODE_LUT, TRACK>(b, TA, i0, t.n_a, P, lut, stage, t.best_a, t.arg_a, keep, f_old);
 		__builtin_amdgcn_s_setprio(MM2GB_INTILE_PRIO);                 // still on the team's critical path: publish A, A into B, B, publish B
@@ -1927,6 +2211,13 @@ __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevPar
 			if (lane == 0) __hip_atomic_store(&sh->done, ta + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 			sweep_a_into_b(b, t, cs, i0, f_a, TA.q, stage, P);
 			const Target TB = load_target(b, i0 + WAVE, ce, TRACK);
+			if (in_band && t.lo_b < jl) {
+				// (tile A may not have needed the band: wait here then)
+				const int s_min = s_first + ((sl - s_first) & 1);
+				const int need = pps * ((sl - s_min) / 2) + min(pps, n_pairs - sl * pps);
+				while (first_lane(__hip_atomic_load(band_cnt, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) __builtin_amdgcn_s_sleep(MM2GB_POLL_SLEEP);
+				band_merge(b, i0 + WAVE, t.n_b, t.best_b, t.arg_b);
+			}
 			cur = ta + 1;
 			in_tile<MODE_LUT, TRACK>(b, TB, i0 + WAVE, t.n_b, P, lut, stage, t.best_b, t.arg_b, keep, f_old);
 			__builtin_amdgcn_s_setprio(MM2GB_INTILE_PRIO);
@@ -1943,6 +2234,7 @@ __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevPar
 		if (lane == 0) __hip_atomic_store(&sh->done, ta + (t.n_b > 0 ? 2 : 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 		__builtin_amdgcn_s_setprio(0);
 	}
+	if (band_groups > 0 && lane == 0) atomicAdd(&b.counters[CNT_BAND_TEAM], band_groups);
 }
 
 
@@ -2330,7 +2622,7 @@ __device__ __forceinline__ int team_phase(const DevBatch &b, const DevParams &P,
 	CoopShared *sh = &teams[team];
 	while (true) {
 		const bool given = first >= 0 && team == 0;
-		if (team_wave == 0 && lane_id() == 0) { sh->chunk = given ? first : atomicAdd(&b.counters[cursor], 1); sh->done = 0; sh->part = 0; sh->keep[0] = -1; }
+		if (team_wave == 0 && lane_id() == 0) { sh->chunk = given ? first : atomicAdd(&b.counters[cursor], 1); sh->done = 0; sh->part = 0; sh->band = 0; sh->keep[0] = -1; }
 		first = -1;
 		team_barrier(sh, team_size);
 		const int c = first_lane(sh->chunk);
@@ -2339,17 +2631,18 @@ __device__ __forceinline__ int team_phase(const DevBatch &b, const DevParams &P,
 		if (min_cost > 0 && b.chunk_cost[ci] < min_cost) return c;
 		if (GANG && (b.chunk_track[ci] & 8)) { team_barrier(sh, team_size); continue; }   // a gang's chunk (phase 0 of k_score)
 		const int cs = first_lane(b.chunk_start[ci]), ce = first_lane(b.chunk_end[ci]);
+		const bool band_on = MODE == MODE_LUT && band_chunk(b, P, ci, cs, ce);
 		// whole-workgroup teams keep one tile per wave: with two, 32 tiles of one chunk would be in flight and the largest
 		// chunks -- the ones that decide when a small batch ends -- ran 6 % slower
 		if (SPLIT && MODE == MODE_LUT && team_size == SCORE_THREADS / WAVE) {
 			if (b.chunk_track[ci] & 1) split_chunk<true>(b, P, lut, stage, my_ring, sh, split_tab, cs, ce, team_wave);
 			else split_chunk<false>(b, P, lut, stage, my_ring, sh, split_tab, cs, ce, team_wave);
 		} else if (MODE == MODE_LUT && team_size < SCORE_THREADS / WAVE) {
-			if (b.chunk_track[ci] & 1) coop_chunk_pairs<true>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size);
-			else coop_chunk_pairs<false>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size);
+			if (b.chunk_track[ci] & 1) coop_chunk_pairs<true>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size, band_on);
+			else coop_chunk_pairs<false>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size, band_on);
 		} else {
-			if (b.chunk_track[ci] & 1) coop_chunk<MODE, true>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size);
-			else coop_chunk<MODE, false>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size);
+			if (b.chunk_track[ci] & 1) coop_chunk<MODE, true>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size, band_on);
+			else coop_chunk<MODE, false>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size, band_on);
 		}
 		team_barrier(sh, team_size);
 	}
@@ -2414,7 +2707,7 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 				const int st_tiles = (gload(&gs->tiles_per_wave) == 2 ? 2 : 1) * GANG_STRIP_PAIRS;
 				go = next * st_tiles < n_tiles && next * st_tiles - done < 4 * st_tiles;
 			}
-			sh->chunk = go; sh->done = 0; sh->part = 0; sh->keep[0] = -1;
+			sh->chunk = go; sh->done = 0; sh->part = 0; sh->band = 0; sh->keep[0] = -1;
 		}
 		team_barrier(sh, SCORE_THREADS / WAVE);
 		const int go = first_lane(sh->chunk);
@@ -2465,8 +2758,9 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 		const int ci = first_lane(b.order[c]);
 		const int cs = first_lane(b.chunk_start[ci]), ce = first_lane(b.chunk_end[ci]);
 		if (MODE == MODE_LUT) {
-			if (b.chunk_track[ci] & 1) run_chunk_pairs<true>(b, P, lut, stage, cs, ce);
-			else run_chunk_pairs<false>(b, P, lut, stage, cs, ce);
+			const bool band_on = band_chunk(b, P, ci, cs, ce);
+			if (b.chunk_track[ci] & 1) run_chunk_pairs<true>(b, P, lut, stage, cs, ce, band_on);
+			else run_chunk_pairs<false>(b, P, lut, stage, cs, ce, band_on);
 		} else {
 			if (b.chunk_track[ci] & 1) run_chunk<MODE, true>(b, P, lut, stage, cs, ce);
 			else run_chunk<MODE, false>(b, P, lut, stage, cs, ce);

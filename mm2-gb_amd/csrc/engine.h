@@ -80,8 +80,9 @@ struct Engine {
 		DevBuf gang_slots;                    // one chunk on several workgroups (gangs, k_score's phase 0): GANG_MAX_CHUNKS slots
 		DevBuf skip_mark;                     // k_skip_fill's marks (lchain.c:175 t[]): 4 B per anchor, allocated when first used
 		DevBuf skip_stats;                    // k_skip_fill's counters (SKIP_STAT_WORDS), only with MM2GB_SKIP_STATS=1
+		DevBuf band_diag, band_res;           // k_score's band pass (params.band_slab > 0): x - y per anchor 4 B, its result 8 B, allocated when first used
 		std::vector<DevBuf*> all() { return { &st, &blk_firstcut, &blk_pairs, &blk_clamped, &blk_wmax, &blk_read, &chunk_start, &chunk_end, &chunk_cost,
-		                                      &chunk_track, &order, &long_list, &mid_list, &chunk_pp, &chunk_kk, &chunk_blk, &tile_sums, &tile_base, &bins, &counters, &totals, &flags, &split_slots, &split_part, &gang_slots, &skip_mark, &skip_stats }; }
+		                                      &chunk_track, &order, &long_list, &mid_list, &chunk_pp, &chunk_kk, &chunk_blk, &tile_sums, &tile_base, &bins, &counters, &totals, &flags, &split_slots, &split_part, &gang_slots, &skip_mark, &skip_stats, &band_diag, &band_res }; }
 	};
 	WorkSet work[2];
 	DevBuf lut, dbg;
@@ -131,6 +132,7 @@ struct Engine {
 	bool lds_contract_ok = false;   // this device reads 0 beyond a workgroup's LDS and saturates v_sad_u32 ... clamp (probed in init)
 	int64_t dual_stream_max_n = 16 * 1000 * 1000;   // micro-batches up to this many anchors alternate between the two compute streams
 	bool chain_skip = false;        // the DP keeps misc.max_skip (k_skip_fill) where the limit can be reached; false: exhaustive (k_score), the default.  MM2GB_CHAIN_SKIP=keep at creation
+	int64_t last_band_groups[2] = { 0, 0 };   // groups of targets k_score's band pass swept in the wave path / the team paths, since the last reset of the stats
 	int  last_score_form = 0;       // form of the DP the last enqueued micro-batch ran: 0 exhaustive (k_score), 1 the skip-limited walk (k_skip_fill)
 	bool skip_stats = false;        // MM2GB_SKIP_STATS=1: k_skip_fill counts rounds, targets and its slowest chunk (mm2gb_engine_skip_stats; profiles/skip_rate.py)
 	int  last_skip_set = 0;         // work set of the last micro-batch the walk ran on

@@ -261,6 +261,7 @@ static DevParams make_params(const mm2gb_misc_t &m)
 	P.max_iter = m.max_iter; P.n_seg = m.n_seg; P.is_cdna = m.is_cdna;
 	P.dq_lim = std::min(P.max_dist_x, P.max_dist_y);
 	P.lut_last = P.bw + 1; P.lut_base = LUT_LDS_TOTAL - 4 * (P.lut_last + 1); P.lut_clamp = 1; P.free_sweep = 0; P.edge_prefix = 0;
+	P.band_slab = 0; P.band_lag = 0;
 	P.gap = m.chn_pen_gap; P.skip = m.chn_pen_skip;
 	return P;
 }
@@ -345,11 +346,23 @@ int Engine::configure_score()
 	// beyond a workgroup's LDS (probed in init) the index is not clamped -- a distance beyond bw is an address beyond LDS -- and source
 	// blocks far enough inside a window are swept without any range test (MM2GB_FREE_SWEEP=0 turns that off, for A/B runs).
 	params.lut_last = params.bw + 1; params.lut_base = LUT_LDS_TOTAL - 4 * (params.lut_last + 1); params.lut_clamp = 1; params.free_sweep = 0; params.edge_prefix = 0;
+	params.band_slab = 0; params.band_lag = 0;
 	if (launch.host_mode == SCORE_MODE_LUT && lds_contract_ok && !getenv("MM2GB_LUT_CLAMP")) {
 		params.lut_clamp = 0;
 		{ const char *e = getenv("MM2GB_EDGE"); params.edge_prefix = e && !strcmp(e, "new"); }   // MM2GB_EDGE=new: the window test of edge blocks from a scalar prefix mask (measured: +1 % on 10-30 kb reads, -1 % on 30-100 kb: profiles/r06_narrow_ab.txt; off)
 		const char *v = getenv("MM2GB_FREE_SWEEP");
 		params.free_sweep = !(v && atoi(v) == 0) && params.dq_lim > 2 * params.bw;
+		// sources older than a lag before the target's slab by diagonal band (chain_kernels.hip, band_slab_part): MM2GB_BAND=0 gives the
+		// dense sweep of every window (same results), MM2GB_BAND_SLAB (128, 256, 512) and MM2GB_BAND_LAG (a multiple of 64, at most the slab) the shape
+		const char *bv = getenv("MM2GB_BAND");
+		if (!(bv && atoi(bv) == 0)) {
+			int slab = 512, lag = 512;
+			if (const char *e = getenv("MM2GB_BAND_SLAB")) slab = atoi(e);
+			if (slab != 128 && slab != 256 && slab != 512) slab = 512;
+			if (const char *e = getenv("MM2GB_BAND_LAG")) lag = atoi(e);
+			lag = std::min(std::max(lag, 0) & ~63, slab);
+			params.band_slab = slab; params.band_lag = lag;
+		}
 	}
 	(void)n_big;
 	int64_t slots = fit_slots(params);
@@ -541,6 +554,7 @@ int Engine::begin_call()
 	n_slots = 0;
 	last = mm2gb_stats_t();
 	last_split_chunks = last_helped_items = 0; last_gang_chunks = last_gang_wgs = 0;
+	last_band_groups[0] = last_band_groups[1] = 0;
 	return 0;
 }
 
@@ -562,6 +576,7 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 	b.raw = (const uint4*)d_anchors; b.offsets = d_offsets; b.n = n; b.n_reads = n_reads;
 	b.st = (int32_t*)st.ptr;
 	b.f = d_f; b.p = d_p;
+	b.diag = nullptr; b.band_res = nullptr;
 	b.blk_firstcut = (int32_t*)blk_firstcut.ptr; b.blk_pairs = (int64_t*)blk_pairs.ptr; b.blk_clamped = (int32_t*)blk_clamped.ptr; b.blk_wmax = (int32_t*)blk_wmax.ptr; b.blk_read = (int32_t*)blk_read.ptr;
 	b.n_blocks = (n + PLAN_BLOCK - 1) / PLAN_BLOCK;
 	b.chunk_start = (int32_t*)chunk_start.ptr; b.chunk_end = (int32_t*)chunk_end.ptr; b.chunk_cost = (int64_t*)chunk_cost.ptr;
@@ -608,7 +623,14 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 		if (skip_stats && w.skip_stats.ensure(SKIP_STAT_WORDS * sizeof(unsigned long long))) return -1;
 		last_skip_set = set;
 		launch_skip_fill(b, params, misc.max_skip, (int32_t*)w.skip_mark.ptr, skip_stats ? (unsigned long long*)w.skip_stats.ptr : nullptr, n_cu, stream);
-	} else if (n > 0) launch_score(b, params, cfg_now, stream);
+	} else if (n > 0) {
+		// the band pass's arrays (k_score only): diagonals 4 B and results 8 B per anchor
+		if (params.band_slab > 0 && launch.host_mode == SCORE_MODE_LUT) {
+			if (w.band_diag.ensure((size_t)n * sizeof(int32_t)) || w.band_res.ensure((size_t)n * 2 * sizeof(int32_t))) return -1;
+			b.diag = (int32_t*)w.band_diag.ptr; b.band_res = (int32_t*)w.band_res.ptr;
+		}
+		launch_score(b, params, cfg_now, stream);
+	}
 	if (want_stats) {
 		MM2GB_HIP(hipEventRecord(bs.score1, stream));
 		MM2GB_HIP(hipMemcpyAsync(h_counters + (size_t)slot * CNT_WORDS, counters.ptr, CNT_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -1226,6 +1248,7 @@ int Engine::collect_stats()
 		last.n_clamped_blocks += c[CNT_NCLAMP];
 		last_split_chunks += c[CNT_NSPLIT]; last_helped_items += c[CNT_HELPED];
 		last_gang_chunks += c[CNT_NGANG]; last_gang_wgs += c[CNT_GANG_WGS];
+		last_band_groups[0] += c[CNT_BAND_WAVE]; last_band_groups[1] += c[CNT_BAND_TEAM];
 		float ms = 0;
 		if (hipEventElapsedTime(&ms, slots[k].prep0, slots[k].prep1) == hipSuccess) last.ms_prep += ms;
 		if (hipEventElapsedTime(&ms, slots[k].prep1, slots[k].score1) == hipSuccess) last.ms_score += ms;
@@ -1360,6 +1383,12 @@ int mm2gb_engine_device(const mm2gb_engine_t *eng) { return eng ? eng->e.device 
 int mm2gb_engine_set_rmq_team_reads(mm2gb_engine_t *eng, int n) { if (!eng || n < 0) return fail("mm2gb_engine_set_rmq_team_reads: bad argument"); eng->e.rmq_team_reads = n; return 0; }
 int mm2gb_engine_set_chain_skip(mm2gb_engine_t *eng, int keep) { if (!eng || keep < 0 || keep > 1) return fail("mm2gb_engine_set_chain_skip: bad argument"); eng->e.chain_skip = keep == 1; return 0; }
 int mm2gb_engine_last_score_form(const mm2gb_engine_t *eng) { return eng ? eng->e.last_score_form : -1; }
+int mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out)
+{
+	if (!eng || !out) return fail("mm2gb_engine_band_groups: null argument");
+	out[0] = eng->e.last_band_groups[0]; out[1] = eng->e.last_band_groups[1];
+	return 0;
+}
 int mm2gb_engine_skip_stats(mm2gb_engine_t *eng, int64_t *out)
 {
 	if (!eng || !out) return fail("mm2gb_engine_skip_stats: null argument");
