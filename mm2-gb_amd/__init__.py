@@ -76,7 +76,7 @@ _lib = None
 
 # every symbol include/mm2gb_chain.h and include/mm2gb_plutils.h declare
 CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "mm2gb_config_parse", "mm2gb_config_load",
-                "mm2gb_device_count", "mm2gb_device_numa_node", "mm2gb_pin_thread_to_device", "mm2gb_numa_cpus_for_bdf", "mm2gb_engine_create", "mm2gb_engine_destroy", "mm2gb_engine_set_misc", "mm2gb_engine_device", "mm2gb_engine_split_counts", "mm2gb_engine_gang_counts", "mm2gb_has_gang_build",
+                "mm2gb_device_count", "mm2gb_device_numa_node", "mm2gb_pin_thread_to_device", "mm2gb_numa_cpus_for_bdf", "mm2gb_engine_create", "mm2gb_engine_destroy", "mm2gb_engine_set_misc", "mm2gb_engine_device", "mm2gb_engine_gang_counts", "mm2gb_has_gang_build",
                 "mm2gb_engine_reserve", "mm2gb_score_host", "mm2gb_score_device", "mm2gb_engine_sync", "mm2gb_engine_stats",
                 "mm2gb_engine_stream", "mm2gb_engine_last_kernel_ms", "mm2gb_chain_host", "mm2gb_chain_gpu", "mm2gb_post_device", "mm2gb_post_device_enqueue", "mm2gb_post_device_totals", "mm2gb_post_device_digest", "mm2gb_chains_free", "mm2gb_backtrack_host",
                 "mm2gb_free", "mm2gb_lchain_dp", "mm2gb_synth_count", "mm2gb_synth_fill",
@@ -85,7 +85,7 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_batcher_create", "mm2gb_batcher_add", "mm2gb_batcher_feed", "mm2gb_batcher_flush", "mm2gb_batcher_stats", "mm2gb_batcher_destroy",
                 "mm2gb_plan_batches", "mm2gb_rmq_chain_gpu", "mm2gb_lchain_rmq", "mm2gb_lchain_rmq_counts",
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
-                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_has_split_build", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream"]
+                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -295,14 +295,6 @@ class Engine:
         _check(L.mm2gb_engine_skip_stats(self._h, out.ctypes.data))
         keys = ("rounds", "rescan_rounds", "targets", "slowest_chunk_ticks", "slowest_chunk_anchors", "span_ticks")
         return {k: int(v) for k, v in zip(keys, out)}
-
-    def split_counts(self):
-        """Of the last completed call: (chunks scored strip by strip with other workgroups' help, items those others took)."""
-        c, h = C.c_int64(), C.c_int64()
-        lib().mm2gb_engine_split_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        lib().mm2gb_engine_split_counts.restype = None
-        lib().mm2gb_engine_split_counts(self._h, C.byref(c), C.byref(h))
-        return c.value, h.value
 
     def gang_counts(self):
         """Of the last completed call: (chunks scored by a gang of workgroups, workgroups that started in a gang)."""

@@ -13,7 +13,6 @@ struct DevParams {
 	int   lut_base;          // LDS byte address of the table's entry 0: LUT_LDS_TOTAL - 4 * (lut_last + 1), so that it ends where LDS ends
 	int   lut_clamp;         // 1: the sweeps clamp the table index to lut_last; 0: an index beyond it reads beyond LDS, i.e. 0 = reject
 	int   free_sweep;        // 1 (only without lut_clamp): source blocks whose every pair has bw < dr <= dq_lim - bw are swept without range test
-	int   edge_prefix;       // 1: edge blocks of tiles whose window starts rise from lane to lane take their window test from a scalar prefix mask (sweep_block_lut_edge_sorted); only with MM2GB_EDGE=new
 	int   band_slab;         // MODE_LUT without lut_clamp: predecessors older than band_lag anchors before a target's slab of band_slab anchors are swept by
 	int   band_lag;          // diagonal band (chain_kernels.hip, band_slab_part); 0 = off.  band_slab in {128, 256, 512}, band_lag a multiple of 64 <= band_slab
 	float gap, skip;
@@ -43,21 +42,6 @@ constexpr int PLAN_THREADS = MM2GB_PLAN_THREADS;   // k_window: each thread owns
 constexpr int COST_PER_ANCHOR = 16;
 // cost bins per work list of the planner (chain_kernels.hip: 16 per power of two; the engine sizes DevBatch::bins by it)
 constexpr int PLAN_COST_BINS = 1024;
-
-// A heavy chunk scored by its owner workgroup strip by strip (16 tiles = 1 024 anchors), the sweeps over the sources BEFORE the strip
-// cut into items that any idle workgroup may take (chain_kernels.hip, split_chunk).  Every word is accessed with agent-scope atomics.
-struct SplitSlot {
-	unsigned long long word;   // total items of the open strip << 32 | next item to hand out (0: nothing open)
-	int done;                  // items of the open strip that are finished
-	int cs, ce, i_s;           // the chunk, the strip's first anchor
-	int blocks_per_item;
-	int jbs[8];                // per tile pair of the strip: first source block of its window
-	int base[9];               // per tile pair: its first item; base[8] = total
-	int pad_[8];
-};
-static_assert(sizeof(SplitSlot) == 128, "one slot per 128-byte line");
-constexpr int SPLIT_MAX_ITEMS = 128;                   // per strip: 8 tile pairs x at most 16 items
-constexpr int SPLIT_STRIP_TILES = 16;                  // = waves of a score workgroup
 
 // A GANG: several workgroups on ONE chunk (k_score's first phase; chain_kernels.hip, gang_chunk_pairs).  A batch that cannot fill
 // the machine ends with its largest chunks, and a team is bounded by one CU.  The chunk is cut into strips of GANG_STRIP_PAIRS tile pairs
@@ -117,17 +101,9 @@ struct DevBatch {
 	unsigned *flags;           // FLAG_*
 	const int32_t *lut;        // penalty table by dd, LUT_ENTRIES entries (MODE_LUT only)
 	int64_t  *dbg;             // optional: 4 time stamps per score workgroup (MM2GB_DEBUG_PHASES), else null
-	// one chunk on several workgroups (k_score's SPLIT build): a slot per score workgroup, zeroed before every launch, and room
-	// for the partial results of one strip's items per workgroup; null when the build is not used
-	SplitSlot          *split_slots;
-	unsigned long long *split_part;
-	GangSlot           *gang_slots;   // GANG_MAX_CHUNKS of them, set up by plan_gangs; null: no gangs
+	GangSlot *gang_slots;      // GANG_MAX_CHUNKS of them, set up by plan_gangs; null: no gangs
 };
 enum { CNT_NCHUNK = 0, CNT_CURSOR = 1, CNT_NLONG = 2, CNT_LCURSOR = 3, CNT_NTRACK = 4, CNT_NCLAMP = 5, CNT_NMID = 6, CNT_MCURSOR = 7,
-       CNT_SPLIT_OPEN = 8,      // score workgroups that have started and not yet left the whole-workgroup phase
-       CNT_NSPLIT = 9,          // chunks scored strip by strip with other workgroups' help
-       CNT_HELPED = 10,         // items of such chunks that a workgroup other than the chunk's owner took
-       CNT_SPLIT_ANY = 11,      // strips that are open for items right now (what idle waves poll)
        CNT_NGANG = 12,          // chunks scored by a gang of workgroups
        CNT_GANG_STRIPS = 13,    // strips of such chunks
        CNT_GANG_WGS = 14,       // workgroups that started in a gang
@@ -147,7 +123,6 @@ struct LaunchCfg {
 	int gang_max;            // most workgroups the planner gives one chunk (0: no gangs)
 	int gang_pct;            // a chunk gets gang_pct % of the workgroups its share of the batch's pairs would give it, if that is at least two
 	int gang_pairs;          // 1: a gang's waves take pairs of tiles (as 4- and 8-wave teams do); 0: single tiles, the shorter chain per tile
-	int split;               // 1: launch the SPLIT build (such chunks strip by strip, idle workgroups help); the host's choice by batch size
 	int64_t long_min_cost;   // chunks at least this expensive ...
 	int     long_min_window; // ... whose mean window is at least this are candidates for the cooperative mode
 	int     wide_window;     // mean window from which a big team pays; narrower heavy chunks get 4-wave teams
@@ -163,7 +138,6 @@ void launch_skip_fill(const DevBatch &b, const DevParams &P, int max_skip, int32
 void launch_build_lut(int *d_lut, const DevParams &P, hipStream_t s);
 size_t score_lds_bytes(const DevParams &P, int host_mode, int ring_slots);
 int  score_set_lds_limit(size_t bytes);     // hipFuncSetAttribute on every k_score instance
-bool score_has_split_build();               // compiled with -DMM2GB_WITH_SPLIT (make SPLIT=1)
 enum { SCORE_MODE_LUT = 0, SCORE_MODE_FAST = 1, SCORE_MODE_GENERAL = 2 };
 
 } // namespace mm2gb

@@ -894,68 +894,6 @@ __device__ __forceinline__ void sweep_block_lut_edge(int t_st, int tx4, int ty4,
 		}
 	}
 }
-// The same block where the targets' window starts do not fall from lane to lane -- every tile of a chunk (anchors come sorted by position, a
-// window start never moves back; dead lanes sit at the end with INT_MAX) --: the lanes whose window holds source k are then a PREFIX of the
-// wave, so "source inside this target's window" needs no vector compare per source: how many lanes hold source k is found for all 64 sources
-// at once (lane k bisects the lanes' starts, six LDS permutes), four counts are packed per register, and the execution mask of a source is
-// made from its count by scalar instructions, which issue beside another wave's vector ones.  What is left per source: the two distances,
-// the table address, min3, shift-add, add, the query distance's range straight into the mask, max -- 8 vector instructions (11 above; the
-// narrow-window regime, 10-30 kb reads, is made of these blocks).  The caller checks the order of the starts (edge_starts_sorted).
-__device__ __forceinline__ bool edge_starts_sorted(int t_st)
-{
-	const int before = __shfl_up(t_st, 1);
-	return __ballot(lane_id() > 0 && t_st < before) == 0;
-}
-__device__ __forceinline__ void sweep_block_lut_edge_sorted(int t_st, int tx4, int ty4, int jb, int k_from, const int4 *stage, const DevParams &P, int &bestv, const int k_to = WAVE)
-{
-	constexpr int G = 4;
-	const unsigned base = (unsigned)P.lut_base, lim4 = (unsigned)P.dq_lim << 2;
-	// lane k: how many lanes' windows hold source jb + k
-	int c = 0;
-	{
-		const int j = jb + lane_id();
-#pragma unroll
-		for (int step = WAVE / 2; step > 0; step >>= 1) c += __shfl(t_st, c + step - 1) <= j ? step : 0;
-		c += __shfl(t_st, c) <= j ? 1 : 0;                        // (c <= 63 here)
-	}
-	// four counts per register: lane 4 m holds those of sources 4 m .. 4 m + 3
-	unsigned packed = (unsigned)c;
-	packed |= (unsigned)__builtin_amdgcn_update_dpp(0, c, 0x101, 0xf, 0xf, true) << 8;     // row_shl:1: lane i takes lane i + 1's
-	packed |= (unsigned)__builtin_amdgcn_update_dpp(0, c, 0x102, 0xf, 0xf, true) << 16;
-	packed |= (unsigned)__builtin_amdgcn_update_dpp(0, c, 0x103, 0xf, 0xf, true) << 24;
-	for (int kg = k_from & ~(G - 1); kg < k_to; kg += G) {
-		int4 s4[G];
-		int dqm[G], drm[G], pen[G], v[G];
-		unsigned long long m[G];
-		const unsigned c4 = (unsigned)__builtin_amdgcn_readlane((int)packed, kg);
-#pragma unroll
-		for (int u = 0; u < G; ++u) s4[u] = stage[kg + u];
-#pragma unroll
-		for (int u = 0; u < G; ++u) {
-			dqm[u] = ty4 - s4[u].w; drm[u] = tx4 - s4[u].z;
-			pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(drm[u], dqm[u], base);     // (a query distance <= 0 may read anything: its lane is masked below)
-			const unsigned cu = (c4 >> (8 * u)) & 0xffu;
-			m[u] = cu ? ~0ull >> (64u - cu) : 0ull;                 // the first cu lanes
-		}
-#pragma unroll
-		for (int u = 0; u < G; ++u) {
-			const int dg = drm[u] < dqm[u] ? drm[u] : dqm[u];
-			v[u] = ((s4[u].y < dg ? s4[u].y : dg) << 5) + s4[u].x;
-			asm("" : "+v"(v[u]));
-			v[u] += pen[u];
-		}
-		unsigned long long saved;
-		asm volatile("s_mov_b64 %[sv], exec\n\t"
-		             "s_mov_b64 exec, %[m0]\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[q0]\n\tv_max_i32_e32 %[b], %[v0], %[b]\n\t"
-		             "s_mov_b64 exec, %[m1]\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[q1]\n\tv_max_i32_e32 %[b], %[v1], %[b]\n\t"
-		             "s_mov_b64 exec, %[m2]\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[q2]\n\tv_max_i32_e32 %[b], %[v2], %[b]\n\t"
-		             "s_mov_b64 exec, %[m3]\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[q3]\n\tv_max_i32_e32 %[b], %[v3], %[b]\n\t"
-		             "s_mov_b64 exec, %[sv]"
-		             : [b] "+v"(bestv), [sv] "=&s"(saved)
-		             : [lim] "s"(lim4), [q0] "v"(dqm[0]), [q1] "v"(dqm[1]), [q2] "v"(dqm[2]), [q3] "v"(dqm[3]), [v0] "v"(v[0]), [v1] "v"(v[1]), [v2] "v"(v[2]), [v3] "v"(v[3]),
-		               [m0] "s"(m[0]), [m1] "s"(m[1]), [m2] "s"(m[2]), [m3] "s"(m[3]) : "vcc");
-	}
-}
 __device__ __forceinline__ void sweep_staged_lut(const TileXY &T, int jb, int k_from, bool no_check, bool free_block, const int4 *stage, const DevParams &P,
                                                  int &best, int &arg, bool far_block = false, int d0 = 0)
 {
@@ -963,10 +901,7 @@ __device__ __forceinline__ void sweep_staged_lut(const TileXY &T, int jb, int k_
 	int bestv = best << 7;
 	if (far_block) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
 	else if (free_block) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
-	else if (!no_check && !P.lut_clamp) {
-		if (P.edge_prefix && edge_starts_sorted(T.st)) sweep_block_lut_edge_sorted(T.st, tx4, ty4, jb, k_from, stage, P, bestv);
-		else sweep_block_lut_edge(T.st, tx4, ty4, jb, k_from, stage, P, bestv);
-	}
+	else if (!no_check && !P.lut_clamp) sweep_block_lut_edge(T.st, tx4, ty4, jb, k_from, stage, P, bestv);
 	else if (P.lut_clamp) {
 		if (no_check) sweep_block_lut<false, true>(T.st, tx4, ty4, jb, k_from, stage, P, bestv);
 		else sweep_block_lut<true, true>(T.st, tx4, ty4, jb, k_from, stage, P, bestv);
@@ -1992,17 +1927,17 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 // waves through an LDS ring indexed by anchor number (the sliding predecessor window, max_iter + slack entries);
 // "tiles done" is a release/acquire counter in LDS.  No block barrier inside a chunk.
 struct CoopShared { int done; int keep[6]; int chunk; int bar_count; int bar_gen; int part; int band; };   // one per team (part: Progress; in coop_chunk_pairs part / band count the band parts of even / odd slabs)
-// Gangs (several workgroups on one chunk, gang_chunk_pairs) are an instantiation of their own, k_score<MODE_LUT, false, true>: the gang code
+// Gangs (several workgroups on one chunk, gang_chunk_pairs) are an instantiation of their own, k_score<MODE_LUT, true>: the gang code
 // costs the plain kernel registers (250 -> 283 spilled scalars) and 1-3 % at 500 M anchors, where no chunk gets a gang anyway; the host
 // launches it for the micro-batches small enough to end with their largest chunks (Engine: gang_max_n).
-// what crosses workgroups (gangs, the SPLIT build): agent-scope accesses -- they go past the caches that are not coherent between CUs / XCDs
+// what crosses workgroups (gangs): agent-scope accesses -- they go past the caches that are not coherent between CUs / XCDs
 #define MM2GB_AGENT __HIP_MEMORY_SCOPE_AGENT
 __device__ __forceinline__ int  gload(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, MM2GB_AGENT); }
 __device__ __forceinline__ void gstore(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, MM2GB_AGENT); }
 __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 constexpr int SMALL_TEAM = 4, N_SMALL_TEAMS = SCORE_THREADS / WAVE / SMALL_TEAM;
 constexpr int N_TEAM_RECORDS = N_SMALL_TEAMS + 3;      // four small teams, two big ones, the whole workgroup
-constexpr int TAB_INTS = 36;                           // behind the team records: 24 ints of the SPLIT build's strip table, 9 of a gang's turns
+constexpr int TAB_INTS = 12;                           // behind the team records: the 9 ints of a gang's turns (gang_chunk_pairs' tab), kept a multiple of 16 B
 
 // Barrier among the waves of one small team (a workgroup barrier would stall the other teams): sense-reversing counter
 // in LDS, one lane per wave takes part.
@@ -2036,8 +1971,7 @@ __device__ __forceinline__ void sweep_block_by_quarters(const DevBatch &b, const
 		if (lo >= hi) continue;
 		stage_block_lut(xs, ys, sf_of(), sq, stage);          // (the quarters that are not out yet hold stale scores: nobody reads them)
 		int bestv = best << 7;
-		if (P.edge_prefix && edge_starts_sorted(T.st)) sweep_block_lut_edge_sorted(T.st, tx4, ty4, jb, lo, stage, P, bestv, hi);
-		else sweep_block_lut_edge(T.st, tx4, ty4, jb, lo, stage, P, bestv, hi);
+		sweep_block_lut_edge(T.st, tx4, ty4, jb, lo, stage, P, bestv, hi);
 		const int won = bestv & 127;
 		arg = (unsigned)(won - 1) < (unsigned)WAVE ? jb + won - 1 : arg;
 		best = bestv >> 7;
@@ -2388,232 +2322,14 @@ __device__ __forceinline__ void gang_chunk_pairs(const DevBatch &b, const DevPar
 }
 
 
-// ---- one chunk on several workgroups (SPLIT build) ------------------------------------------------------------------------
-// A team is bounded by one CU; the largest chunks of a batch that cannot fill the machine decide when it ends.  Such a chunk (one that
-// the planner gives a whole workgroup, its OWNER) is scored strip by strip, a strip being 16 tiles, one per wave.  For every strip:
-//   phase A  the sweeps over the sources BEFORE the strip -- all final -- are cut into items (a tile pair x some source blocks) in a
-//            slot in global memory; the owner's waves take items, and so does every wave of the launch that has nothing else left to
-//            do (help_split_chunks, at the end of the kernel).  An item leaves per target the best score and its source;
-//   phase B  wave w combines tile w's items in source order (a later source wins ties, as everywhere), then goes through the tiles
-//            of its own strip that precede it -- scores through the LDS ring -- and the in-tile phase, as a team does (coop_chunk).
-// Nothing waits for a workgroup that may not be running: the owner takes items itself and only waits for items somebody HAS taken,
-// i.e. for waves that are executing them; helpers leave when no workgroup is in the whole-workgroup phase any more.
-// What crosses workgroups: the chunk's scores (owner -> whoever takes an item) and the items' partial results (-> owner).  Both are
-// PLAIN stores, drained by every storing wave, then ONE agent-scope release by the lane that signals (owner: before it opens a strip;
-// item: before it counts itself done) and an agent-scope acquire on the reading side before its plain loads -- the form
-// cdna_hip_programming.md Guideline 16 gives as always valid.  (A cheaper form, write-through sc1 stores and sc1 loads with no
-// fences, was what the first build used; it was replaced while chasing wrong results that turned out to be the compiler problem noted at
-// split_do_item_owner, and has not been tried again since.)  The slot's words are agent-scope atomics.  x, y, tag, st are not written
-// in this launch.
-__device__ __forceinline__ unsigned long long uni64(unsigned long long v)
-{
-	return (unsigned long long)(unsigned)first_lane((int)(v >> 32)) << 32 | (unsigned)first_lane((int)v);
-}
-
-// Item `it` of workgroup `wg`'s open strip.  Any wave of the launch, whole-wave (uniform) control flow only.
-__device__ __forceinline__ void split_do_item(const DevBatch &b, const DevParams &P, int4 *stage, const int wg, const int it)
-{
-	SplitSlot *slot = b.split_slots + wg;
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");            // the scores the owner released when it opened this strip
-	// the slot's fields belong to this strip until every item that was handed out is done
-	// (plain loads behind the acquire, like the scores: the owner wrote them with plain stores before its release)
-	const volatile SplitSlot *vs = slot;
-	const int cs = first_lane(vs->cs), ce = first_lane(vs->ce), i_s = first_lane(vs->i_s), per = first_lane(vs->blocks_per_item);
-	int p = 0;
-	for (int q = 1; q < 8; ++q) if (it >= first_lane(vs->base[q])) p = q;
-	const int k = it - first_lane(vs->base[p]);
-	const int jb0 = first_lane(vs->jbs[p]) + k * per * WAVE, jb1 = min(i_s, jb0 + per * WAVE);
-	const int i0 = i_s + p * 2 * WAVE;
-	TilePair t = load_pair(b, i0, ce);
-	const int eq_lo = equal_x_run_start(b, cs, i0, first_lane(t.A.x));
-	for (int jb = jb0; jb < jb1; jb += WAVE) {
-		const int sf = b.f[jb + lane_id()], sq = a_span(b, jb + lane_id());
-		sweep_pair_block(b, t, jb, eq_lo, sf, sq, stage, P);
-	}
-	unsigned long long *part = b.split_part + ((size_t)wg * SPLIT_MAX_ITEMS + it) * 2 * WAVE;
-	part[lane_id()] = (unsigned long long)(unsigned)t.best_a << 32 | (unsigned)t.arg_a;
-	part[WAVE + lane_id()] = (unsigned long long)(unsigned)t.best_b << 32 | (unsigned)t.arg_b;
-	drain_stores();
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-	drain_stores();
-	if (lane_id() == 0) {
-		__hip_atomic_fetch_add(&slot->done, 1, __ATOMIC_RELAXED, MM2GB_AGENT);
-		if (wg != (int)blockIdx.x) atomicAdd(&b.counters[CNT_HELPED], 1);
-	}
-}
-// The same for the owner's own waves, as a function of its own.  Inlined into split_chunk the item code was miscompiled (ROCm 7.2): items
-// that contain a range-tested block came out with lanes missing -- every run of profiles/split_soak.py with a build without helpers
-// wrong from the first such strip on, whatever the memory protocol -- while the copy inlined into help_split_chunks and this
-// out-of-line copy give the oracle's results.  The call costs the owner little: with helpers around it takes few items itself.
-__device__ __attribute__((noinline)) void split_do_item_owner(const DevBatch &b, const DevParams &P, int4 *stage, const int it)
-{
-	split_do_item(b, P, stage, (int)blockIdx.x, it);
-}
-// Take the next item of workgroup `wg`'s open strip: its number, or -1 when none is left.  (The same shape as the work cursors of
-// k_score: one lane adds, the value is made wave-uniform.)
-__device__ __forceinline__ int split_claim(const DevBatch &b, const int wg)
-{
-	unsigned long long w = 0;
-	if (lane_id() == 0) w = __hip_atomic_fetch_add(&b.split_slots[wg].word, 1ull, __ATOMIC_RELAXED, MM2GB_AGENT);
-	w = uni64(w);
-	const int it = (int)(unsigned)w, total = (int)(w >> 32);
-	return it < total ? it : -1;
-}
-
-// A wave with nothing else to do: items of any workgroup's open strip, until no workgroup is in the whole-workgroup phase any more.
-__device__ __forceinline__ void help_split_chunks(const DevBatch &b, const DevParams &P, int4 *stage)
-{
-	unsigned idle = 0;
-	for (;;) {
-		const int open = first_lane(gload(&b.counters[CNT_SPLIT_OPEN]));       // read BEFORE the look at the slots
-		bool any = false;
-		// one word says whether any strip is open at all: that is all an idle wave reads, every few microseconds
-		if (first_lane(gload(&b.counters[CNT_SPLIT_ANY])) > 0)
-		for (int base = 0; base < (int)gridDim.x; base += WAVE) {
-			const int wg = base + lane_id();
-			unsigned long long w = 0;
-			if (wg < (int)gridDim.x) w = __hip_atomic_load(&b.split_slots[wg].word, __ATOMIC_RELAXED, MM2GB_AGENT);
-			unsigned long long has = __ballot((unsigned)w < (unsigned)(w >> 32));
-			while (has) {
-				const int sel = base + __builtin_ctzll(has);
-				const int it = split_claim(b, sel);
-				if (it >= 0) { split_do_item(b, P, stage, sel, it); any = true; }
-				else has &= has - 1;
-			}
-		}
-		if (!any) {
-			if (open <= 0 || ++idle > (1u << 22)) return;             // (the bound: seconds; helping is optional, hanging is not)
-			__builtin_amdgcn_s_sleep(64);
-		}
-	}
-}
-
-// The owner: all 16 waves of the workgroup, chunk [cs, ce).  tab: 24 ints of LDS.
-template <bool TRACK>
-__device__ __forceinline__ void split_chunk(const DevBatch &b, const DevParams &P, const int *lut, int4 *stage, int *ring, CoopShared *sh, int *tab,
-                                            const int cs, const int ce, const int wave)
-{
-	constexpr int S = SPLIT_STRIP_TILES;
-	const int lane = lane_id();
-	SplitSlot *slot = b.split_slots + blockIdx.x;
-	const unsigned long long *part = b.split_part + (size_t)blockIdx.x * SPLIT_MAX_ITEMS * 2 * WAVE;
-	const int n_tiles = (ce - cs + WAVE - 1) / WAVE;
-	auto wait_done = [&](int need) {
-		while (first_lane(__hip_atomic_load(&sh->done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) __builtin_amdgcn_s_sleep(MM2GB_POLL_SLEEP);
-	};
-	if (wave == 0 && lane == 0) atomicAdd(&b.counters[CNT_NSPLIT], 1);
-	for (int s0 = 0; s0 < n_tiles; s0 += S) {
-		const int i_s = cs + s0 * WAVE;
-		// ---- phase A: the sources before the strip ----
-		if (wave < 8 && lane == 0) {
-			const int i0 = i_s + wave * 2 * WAVE;
-			int jbs = i_s, nblk = 0;
-			if (s0 > 0 && i0 < ce) {
-				const int lo = b.st[i0];                           // window starts are monotone: the pair's first anchor has the smallest
-				jbs = cs + ((lo - cs) & ~(WAVE - 1));
-				nblk = jbs < i_s ? (i_s - jbs) / WAVE : 0;
-			}
-			tab[wave] = jbs; tab[8 + wave] = nblk;
-		}
-		if (wave == 0 && lane == 0) __hip_atomic_store(&sh->done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-		team_barrier(sh, S);
-		int total = 0, per = 8;
-		{
-			int widest = 0;
-			for (int q = 0; q < 8; ++q) widest = max(widest, first_lane(tab[8 + q]));
-			per = max(8, (widest + 15) / 16);                       // at most 16 items per pair
-			for (int q = 0; q < 8; ++q) total += (first_lane(tab[8 + q]) + per - 1) / per;
-		}
-		if (total > 0) {
-			if (wave == 0 && lane == 0) {
-				volatile SplitSlot *vs = slot;
-				vs->cs = cs; vs->ce = ce; vs->i_s = i_s; vs->blocks_per_item = per; gstore(&slot->done, 0);
-				int acc = 0;
-				for (int q = 0; q < 8; ++q) { vs->jbs[q] = tab[q]; vs->base[q] = acc; acc += (tab[8 + q] + per - 1) / per; }
-				vs->base[8] = acc;
-				drain_stores();
-				// the scores of the strips before this one: every wave drained its stores before the barrier above
-				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-				drain_stores();
-				__hip_atomic_store(&slot->word, (unsigned long long)total << 32, __ATOMIC_RELAXED, MM2GB_AGENT);    // open
-				atomicAdd(&b.counters[CNT_SPLIT_ANY], 1);
-			}
-			team_barrier(sh, S);
-			for (;;) {
-				const int it = split_claim(b, (int)blockIdx.x);
-				if (it < 0) break;
-				split_do_item_owner(b, P, stage, it);
-			}
-			// every item is handed out; wait for the ones still being worked on (by waves that are running: no wait for anybody's turn)
-			if (lane == 0) {
-				unsigned spins = 0;
-				while (__hip_atomic_load(&slot->done, __ATOMIC_RELAXED, MM2GB_AGENT) < total) {
-					__builtin_amdgcn_s_sleep(8);
-					if (++spins > (1u << 26)) __builtin_trap();       // minutes: something is broken; fail loudly rather than hang
-				}
-			}
-			team_barrier(sh, S);
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the partial results (every wave reads some)
-			if (wave == 0 && lane == 0) { __hip_atomic_store(&slot->word, 0ull, __ATOMIC_RELAXED, MM2GB_AGENT); atomicAdd(&b.counters[CNT_SPLIT_ANY], -1); }   // closed
-		}
-		// ---- phase B: the strip itself, wave w its tile w ----
-		const int tix = s0 + wave;
-		if (tix < n_tiles) {
-			const int i0 = cs + tix * WAVE;
-			const Target T = load_target(b, i0, ce, TRACK);
-			const int n_here = min(WAVE, ce - i0);
-			int best = T.q + 1, arg = -1;
-			if (total > 0) {
-				const int q = wave >> 1, side = wave & 1;
-				int first = 0;
-				for (int r = 0; r < q; ++r) first += (first_lane(tab[8 + r]) + per - 1) / per;
-				const int n_it = (first_lane(tab[8 + q]) + per - 1) / per;
-				for (int k = 0; k < n_it; ++k) {                     // ascending sources: a later one wins ties
-					const unsigned long long v = part[((size_t)(first + k) * 2 + side) * WAVE + lane];
-					const int pb = (int)(unsigned)(v >> 32), pa = (int)(unsigned)v;
-					if (pa >= 0 && pb >= best) { best = pb; arg = pa; }
-				}
-			}
-			const int tile_lo = first_lane(T.st), st_hi = bcast(T.st, n_here - 1);
-			int jb = cs + ((tile_lo - cs) & ~(WAVE - 1));
-			if (jb < i_s) jb = i_s;
-			const int eq_lo = jb < i0 ? equal_x_run_start(b, cs, i0, first_lane(T.x)) : i0;
-			for (; jb < i0; jb += WAVE) {
-				const int src = (jb - i_s) / WAVE;                  // tile of this strip, one of the waves before this one
-				const int sq = a_span(b, jb + lane);
-				wait_done(src + 1);
-				const int sf = ring[src * WAVE + lane];
-				const int k_from = tile_lo > jb ? tile_lo - jb : 0;
-				sweep_any<MODE_LUT>(b, T, jb, k_from, sf, sq, jb >= st_hi && jb + WAVE <= eq_lo, stage, P, lut, best, arg);
-			}
-			wait_done(wave);                                         // every earlier tile of the strip is final (earlier strips: the barrier)
-			Keep keep;
-			if (TRACK) { keep.idx = first_lane(sh->keep[0]); keep.x = first_lane(sh->keep[1]); keep.hi = first_lane(sh->keep[2]); keep.y = first_lane(sh->keep[3]); keep.tag = first_lane(sh->keep[4]); keep.f = first_lane(sh->keep[5]); }
-			else { keep.idx = -1; keep.x = keep.hi = keep.y = keep.tag = keep.f = 0; }
-			in_tile<MODE_LUT, TRACK>(b, T, i0, n_here, P, lut, stage, best, arg, keep, [&](int jj) { return b.f[jj]; });
-			const int i = i0 + lane;
-			const int fi = arg < 0 ? T.q : best;
-			if (T.live) {
-				ring[wave * WAVE + lane] = fi;
-				b.f[i] = fi;                                          // other workgroups read it in later strips' items (released when a strip opens)
-				b.p[i] = arg < 0 ? 0 : i - arg;
-			}
-			if (TRACK && lane == 0) { sh->keep[0] = keep.idx; sh->keep[1] = keep.x; sh->keep[2] = keep.hi; sh->keep[3] = keep.y; sh->keep[4] = keep.tag; sh->keep[5] = keep.f; }
-			drain_stores();
-			if (lane == 0) __hip_atomic_store(&sh->done, wave + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-		}
-		team_barrier(sh, S);
-	}
-}
-
 // One phase of team work: the workgroup's waves form teams of team_size (4, 8 or 16) that pull chunks from `list`.
 // first: a chunk (position in the list) already pulled for team 0 by the previous phase, or -1.
 // min_cost: a chunk cheaper than this ends the phase for the team that pulled it; its position is returned (else -1) so
 // that the next phase can start with it.  Only meaningful for a one-team phase (whole workgroup).
-template <int MODE, bool SPLIT, bool GANG>
+template <int MODE, bool GANG>
 __device__ __forceinline__ int team_phase(const DevBatch &b, const DevParams &P, const int *lut, int4 *stage, int *ring, const int ring_slots, CoopShared *teams,
                           const int32_t *list, const int n_list, const int cursor, const int wave, const int team_size,
-                          int first = -1, const long long min_cost = 0, int *split_tab = nullptr)
+                          int first = -1, const long long min_cost = 0)
 {
 	const int n_teams = SCORE_THREADS / WAVE / team_size;
 	const int team = wave / team_size, team_wave = wave - team * team_size;
@@ -2634,10 +2350,7 @@ __device__ __forceinline__ int team_phase(const DevBatch &b, const DevParams &P,
 		const bool band_on = MODE == MODE_LUT && band_chunk(b, P, ci, cs, ce);
 		// whole-workgroup teams keep one tile per wave: with two, 32 tiles of one chunk would be in flight and the largest
 		// chunks -- the ones that decide when a small batch ends -- ran 6 % slower
-		if (SPLIT && MODE == MODE_LUT && team_size == SCORE_THREADS / WAVE) {
-			if (b.chunk_track[ci] & 1) split_chunk<true>(b, P, lut, stage, my_ring, sh, split_tab, cs, ce, team_wave);
-			else split_chunk<false>(b, P, lut, stage, my_ring, sh, split_tab, cs, ce, team_wave);
-		} else if (MODE == MODE_LUT && team_size < SCORE_THREADS / WAVE) {
+		if (MODE == MODE_LUT && team_size < SCORE_THREADS / WAVE) {
 			if (b.chunk_track[ci] & 1) coop_chunk_pairs<true>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size, band_on);
 			else coop_chunk_pairs<false>(b, P, lut, stage, my_ring, slots, sh, cs, ce, team_wave, team_size, band_on);
 		} else {
@@ -2659,7 +2372,7 @@ __device__ __forceinline__ int team_phase(const DevBatch &b, const DevParams &P,
 // table (bw + 2 entries) from P.lut_base to the end of the allocation, LUT_LDS_TOTAL (chain_dev.h)
 // --------------------------------------------------------------------------------------------------------------
 
-template <int MODE, bool SPLIT, bool GANG>
+template <int MODE, bool GANG>
 __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParams P, int host_mode, int ring_slots, int big_team, int whole_wg_pct)
 {
 	extern __shared__ __attribute__((aligned(16))) int smem[];
@@ -2677,9 +2390,8 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 	CoopShared *teams = (CoopShared*)((int4*)(ring + ring_slots * WAVE) + SCORE_THREADS);   // N_SMALL_TEAMS of them
 	if (MODE == MODE_LUT) for (int k = threadIdx.x; k <= P.lut_last; k += SCORE_THREADS) lut[k] = b.lut[k];    // entry lut_last = bw + 1 is 0: reject
 	if (threadIdx.x < N_TEAM_RECORDS) { teams[threadIdx.x].bar_count = 0; teams[threadIdx.x].bar_gen = 0; }
-	int *split_tab = (int*)(teams + N_TEAM_RECORDS);           // TAB_INTS ints between the team records and the table
-	if (threadIdx.x == 0) split_tab[24 + 8] = 0;               // a gang's turns announced so far
-	if (SPLIT && threadIdx.x == 0) atomicAdd(&b.counters[CNT_SPLIT_OPEN], 1);   // this workgroup is in the whole-workgroup phase
+	int *gang_tab = (int*)(teams + N_TEAM_RECORDS);            // TAB_INTS ints between the team records and the table
+	if (threadIdx.x == 0) gang_tab[8] = 0;                     // a gang's turns announced so far
 	__syncthreads();
 
 	const int n_long = first_lane(b.counters[CNT_NLONG]), n_mid = first_lane(b.counters[CNT_NMID]);
@@ -2691,9 +2403,8 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 	// phase 0: gangs -- the chunks that would outlast the batch on one workgroup are scored by several (gang_chunk_pairs); this workgroup
 	// starts on the chunk the planner gave it, if any.
 	int gang_seq = 0;
-	int *gang_tab = split_tab + 24;
-	const int n_gang = (GANG && MODE == MODE_LUT && !SPLIT && b.gang_slots && ring_slots > 0) ? first_lane(b.counters[CNT_NGANG]) : 0;
-	if constexpr (GANG && MODE == MODE_LUT && !SPLIT) {
+	const int n_gang = (GANG && MODE == MODE_LUT && b.gang_slots && ring_slots > 0) ? first_lane(b.counters[CNT_NGANG]) : 0;
+	if constexpr (GANG && MODE == MODE_LUT) {
 	auto gang_run = [&](int e, bool late) __attribute__((always_inline)) {
 		CoopShared *sh = teams + N_SMALL_TEAMS + 2;
 		GangSlot *gs = b.gang_slots + e;
@@ -2735,18 +2446,16 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 		int first = -1;
 		for (int phase = 0; phase < 3; ++phase) {
 			const bool whole = phase == 0, small = phase == 2;
-			if (whole && !(big_team < SCORE_THREADS / WAVE && whole_wg_pct > 0)) { if (SPLIT && threadIdx.x == 0) atomicAdd(&b.counters[CNT_SPLIT_OPEN], -1); continue; }
+			if (whole && !(big_team < SCORE_THREADS / WAVE && whole_wg_pct > 0)) continue;
 			const long long share = whole ? max(1ll, (long long)(b.totals[2] / gridDim.x * whole_wg_pct / 100)) : 0;
 			CoopShared *records = small ? teams : whole ? teams + N_SMALL_TEAMS + 2 : teams + N_SMALL_TEAMS;
-			const int got = team_phase<MODE, SPLIT, GANG>(b, P, lut, stage, ring, ring_slots, records, small ? b.mid_list : b.long_list, small ? n_mid : n_long,
-			                                        small ? CNT_MCURSOR : CNT_LCURSOR, wave, small ? SMALL_TEAM : whole ? SCORE_THREADS / WAVE : big_team,
-			                                        whole || small ? -1 : first, share, split_tab);
+			const int got = team_phase<MODE, GANG>(b, P, lut, stage, ring, ring_slots, records, small ? b.mid_list : b.long_list, small ? n_mid : n_long,
+			                                 small ? CNT_MCURSOR : CNT_LCURSOR, wave, small ? SMALL_TEAM : whole ? SCORE_THREADS / WAVE : big_team,
+			                                 whole || small ? -1 : first, share);
 			if (whole) first = got;
-			if (SPLIT && whole && threadIdx.x == 0) atomicAdd(&b.counters[CNT_SPLIT_OPEN], -1);   // (all 16 waves return together: the team's barrier)
 			if (phase == 1 && b.dbg && lane_id() == 0) atomicMax((unsigned long long*)&b.dbg[blockIdx.x * 4 + 1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 		}
 	}
-	else if (SPLIT && threadIdx.x == 0) atomicAdd(&b.counters[CNT_SPLIT_OPEN], -1);
 	if (b.dbg && lane_id() == 0) atomicMax((unsigned long long*)&b.dbg[blockIdx.x * 4 + 2], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 	// phase 2: one wave per chunk
 	const int n_chunks = b.counters[CNT_NCHUNK] - n_long - n_mid;
@@ -2766,8 +2475,6 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 			else run_chunk<MODE, false>(b, P, lut, stage, cs, ce);
 		}
 	}
-	// nothing left of its own: items of chunks that other workgroups score strip by strip
-	if (SPLIT && MODE == MODE_LUT) help_split_chunks(b, P, stage);
 	if (b.dbg && lane_id() == 0) atomicMax((unsigned long long*)&b.dbg[blockIdx.x * 4 + 3], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 
@@ -2807,23 +2514,12 @@ size_t score_lds_bytes(const DevParams &P, int host_mode, int ring_slots)
 	return front <= (size_t)LUT_LDS_BASE ? (size_t)LUT_LDS_TOTAL : (size_t)1 << 30;     // the table's place is fixed: what does not fit before it does not fit
 }
 
-// The SPLIT instantiation of k_score (one chunk on several workgroups: exact, and measured slower at every batch size)
-// is only compiled into builds that ask for it (make SPLIT=1): it is the heaviest instantiation of the kernel (hundreds of spilled
-// registers) and nothing selects it by default.
-#ifdef MM2GB_WITH_SPLIT
-constexpr bool HAVE_SPLIT = true;
-#else
-constexpr bool HAVE_SPLIT = false;
-#endif
-bool score_has_split_build() { return HAVE_SPLIT; }
-
 int score_set_lds_limit(size_t bytes)
 {
-	hipError_t e = hipFuncSetAttribute((const void*)k_score<MODE_LUT, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-	if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_LUT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-	if constexpr (HAVE_SPLIT) if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_LUT, HAVE_SPLIT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-	if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_FAST, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-	if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_GENERAL, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+	hipError_t e = hipFuncSetAttribute((const void*)k_score<MODE_LUT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+	if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_LUT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+	if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_FAST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+	if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_score<MODE_GENERAL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 	return e == hipSuccess ? 0 : -1;
 }
 
@@ -2833,12 +2529,11 @@ void launch_score(const DevBatch &b, const DevParams &P, const LaunchCfg &cfg, h
 	const size_t lds = score_lds_bytes(P, cfg.host_mode, cfg.ring_slots);
 	const size_t lds_general = score_lds_bytes(P, MODE_GENERAL, cfg.ring_slots);
 	if (cfg.host_mode == MODE_LUT) {
-		if (HAVE_SPLIT && cfg.split && b.split_slots) hipLaunchKernelGGL((k_score<MODE_LUT, HAVE_SPLIT, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
-		else if (b.gang_slots) hipLaunchKernelGGL((k_score<MODE_LUT, false, true>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
-		else hipLaunchKernelGGL((k_score<MODE_LUT, false, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
+		if (b.gang_slots) hipLaunchKernelGGL((k_score<MODE_LUT, true>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
+		else hipLaunchKernelGGL((k_score<MODE_LUT, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
 	}
-	if (cfg.host_mode == MODE_FAST || cfg.host_mode == MODE_LUT) hipLaunchKernelGGL((k_score<MODE_FAST, false, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
-	hipLaunchKernelGGL((k_score<MODE_GENERAL, false, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds_general, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
+	if (cfg.host_mode == MODE_FAST || cfg.host_mode == MODE_LUT) hipLaunchKernelGGL((k_score<MODE_FAST, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
+	hipLaunchKernelGGL((k_score<MODE_GENERAL, false>), dim3(cfg.score_grid), dim3(SCORE_THREADS), lds_general, s, b, P, cfg.host_mode, cfg.ring_slots, cfg.big_team, cfg.whole_wg_pct);
 }
 
 

@@ -76,19 +76,18 @@ struct Engine {
 		DevBuf chunk_start, chunk_end, chunk_cost, chunk_track, order, long_list, mid_list;
 		DevBuf chunk_pp, chunk_kk, chunk_blk, tile_sums, tile_base, bins;
 		DevBuf counters, totals, flags;
-		DevBuf split_slots, split_part;       // one chunk on several workgroups (k_score's SPLIT build): allocated when first used
 		DevBuf gang_slots;                    // one chunk on several workgroups (gangs, k_score's phase 0): GANG_MAX_CHUNKS slots
 		DevBuf skip_mark;                     // k_skip_fill's marks (lchain.c:175 t[]): 4 B per anchor, allocated when first used
 		DevBuf skip_stats;                    // k_skip_fill's counters (SKIP_STAT_WORDS), only with MM2GB_SKIP_STATS=1
 		DevBuf band_diag, band_res;           // k_score's band pass (params.band_slab > 0): x - y per anchor 4 B, its result 8 B, allocated when first used
 		std::vector<DevBuf*> all() { return { &st, &blk_firstcut, &blk_pairs, &blk_clamped, &blk_wmax, &blk_read, &chunk_start, &chunk_end, &chunk_cost,
-		                                      &chunk_track, &order, &long_list, &mid_list, &chunk_pp, &chunk_kk, &chunk_blk, &tile_sums, &tile_base, &bins, &counters, &totals, &flags, &split_slots, &split_part, &gang_slots, &skip_mark, &skip_stats, &band_diag, &band_res }; }
+		                                      &chunk_track, &order, &long_list, &mid_list, &chunk_pp, &chunk_kk, &chunk_blk, &tile_sums, &tile_base, &bins, &counters, &totals, &flags, &gang_slots, &skip_mark, &skip_stats, &band_diag, &band_res }; }
 	};
 	WorkSet work[2];
 	DevBuf lut, dbg;
 	// device post-pass (post_kernels.hip), allocated on first use: 41 B/anchor of work arrays (candidates 8, walk records 8, picked 4, two lifting tables 8, the sort's bytes / permutation / way station 13), + chains' arrays, + outputs
 	int64_t cap_post_n = 0, cap_post_reads = 0;
-	DevBuf post_dbg_reads, post_dbg_tasks, post_dbg_stasks, rmq_dbg_reads, rmq_skey_in, rmq_skey, rmq_sa, rmq_srange, rmq_sort_tmp, post_z, post_fp, post_picked, post_utmp, post_heads, post_nu, post_nkept, post_misc, post_bins, post_order, post_up4, post_up16, post_sort_s, post_sort_perm, post_sort_tmp, post_cls, post_cls_cnt, post_cls_nz, post_read_nz, post_uloc, post_wtask, post_stask, rmq_tied, rmq_sum, rmq_by_y, rmq_ord, rmq_meta, rmq_win, rmq_tree, reg_out;
+	DevBuf post_dbg_tasks, post_dbg_stasks, rmq_dbg_reads, rmq_skey_in, rmq_skey, rmq_sa, rmq_srange, rmq_sort_tmp, post_z, post_fp, post_picked, post_utmp, post_heads, post_nu, post_nkept, post_misc, post_bins, post_order, post_up4, post_up16, post_sort_s, post_sort_perm, post_sort_tmp, post_cls, post_cls_cnt, post_cls_nz, post_read_nz, post_uloc, post_wtask, post_stask, rmq_tied, rmq_sum, rmq_by_y, rmq_ord, rmq_meta, rmq_win, rmq_tree, reg_out;
 	DevBuf sd_seeds, sd_seed_off, sd_hit_off, sd_hits, sd_qlen, sd_q_rank, sd_ref_len, sd_ref_rank, sd_seed_read, sd_tmp, sd_n_kept, sd_a_off, sd_out;   // mm2gb_collect_seeds_gpu
 	// what the post-pass leaves for the host, two sets: the boundary keeps two batches in flight (the results of batch k are
 	// fetched after batch k+1 has been launched)
@@ -115,13 +114,9 @@ struct Engine {
 
 	mm2gb_stats_t last = {};
 	bool misc_valid = false, coop_disabled = false, debug_phases = false, one_compute_stream = false;
-	bool post_levels = true;        // the split form's sort level by level over the whole batch, a task per run (MM2GB_POST_SORT=reads: one wave sorts a read from top to bottom)
-	bool post_split = true;         // device post-pass: a read's walks shared out by tree over several waves (MM2GB_POST_FORM=fused: one wave sorts and walks a read)
 	int64_t team4_min_n = 0;        // micro-batches from this many anchors on send wide-window heavy chunks to 4-wave teams (launch.team4_share_pct)
-	int64_t split_max_n = 0;        // micro-batches up to this many anchors run the SPLIT build of k_score (0: never)
 	int64_t gang_max_n = 0;         // micro-batches up to this many anchors run the instantiation of k_score with the gang phase
 	int64_t last_gang_chunks = 0, last_gang_wgs = 0;        // of the last call: chunks scored by a gang of workgroups, workgroups that started in one
-	int64_t last_split_chunks = 0, last_helped_items = 0;   // of the last call: chunks scored strip by strip, items other workgroups took
 	bool rmq_tiles_last = false;    // which form the last RMQ call ran (for the debug print)
 	std::function<void(const int32_t*)> rmq_tied_ready;   // the NEXT device re-chaining call only: called on the calling thread as soon as the fill's tie counts are on the host, while the call's post-pass and copies still run
 	hipEvent_t rmq_fill_done = nullptr;
@@ -155,7 +150,7 @@ struct Engine {
 	// h_post_totals once the stream has been synchronised.
 	int  reserve_post(int64_t n_anchors, int64_t n_reads);                 // work arrays of the post kernels (shared by both result sets)
 	int  reserve_post_out(int set, int64_t n_anchors, int64_t n_reads);    // result buffers of one set; never touches the other
-	void print_post_debug(int64_t n_reads, const int64_t *d_offsets);   // MM2GB_DEBUG_PHASES: the last post-pass kernel's records, to stderr
+	void print_post_debug(int64_t n_reads);   // MM2GB_DEBUG_PHASES: the last post-pass kernel's records, to stderr
 	int  enqueue_post(int64_t n_reads, const int64_t *d_offsets, const mm2gb_anchor_t *d_anchors, int64_t n, const int32_t *d_f, const int32_t *d_p,
 	                  const mm2gb_rmq_param_t *rmq = nullptr, int out_set = 0);   // rmq given: thresholds of the re-chaining call (lchain.c:355) instead of misc's
 	// the boundary's device post-pass: host anchors in (page-locked), H2D + score kernels + post kernels enqueued, nothing waited

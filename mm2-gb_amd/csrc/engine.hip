@@ -260,7 +260,7 @@ static DevParams make_params(const mm2gb_misc_t &m)
 	if (P.max_dist_y < P.bw && !m.is_cdna) P.max_dist_y = P.bw;        // lchain.c:161
 	P.max_iter = m.max_iter; P.n_seg = m.n_seg; P.is_cdna = m.is_cdna;
 	P.dq_lim = std::min(P.max_dist_x, P.max_dist_y);
-	P.lut_last = P.bw + 1; P.lut_base = LUT_LDS_TOTAL - 4 * (P.lut_last + 1); P.lut_clamp = 1; P.free_sweep = 0; P.edge_prefix = 0;
+	P.lut_last = P.bw + 1; P.lut_base = LUT_LDS_TOTAL - 4 * (P.lut_last + 1); P.lut_clamp = 1; P.free_sweep = 0;
 	P.band_slab = 0; P.band_lag = 0;
 	P.gap = m.chn_pen_gap; P.skip = m.chn_pen_skip;
 	return P;
@@ -345,11 +345,10 @@ int Engine::configure_score()
 	// Penalty table: bw + 1 entries and a rejecting one, ending where the workgroup's LDS ends (chain_dev.h).  On a device that reads 0
 	// beyond a workgroup's LDS (probed in init) the index is not clamped -- a distance beyond bw is an address beyond LDS -- and source
 	// blocks far enough inside a window are swept without any range test (MM2GB_FREE_SWEEP=0 turns that off, for A/B runs).
-	params.lut_last = params.bw + 1; params.lut_base = LUT_LDS_TOTAL - 4 * (params.lut_last + 1); params.lut_clamp = 1; params.free_sweep = 0; params.edge_prefix = 0;
+	params.lut_last = params.bw + 1; params.lut_base = LUT_LDS_TOTAL - 4 * (params.lut_last + 1); params.lut_clamp = 1; params.free_sweep = 0;
 	params.band_slab = 0; params.band_lag = 0;
 	if (launch.host_mode == SCORE_MODE_LUT && lds_contract_ok && !getenv("MM2GB_LUT_CLAMP")) {
 		params.lut_clamp = 0;
-		{ const char *e = getenv("MM2GB_EDGE"); params.edge_prefix = e && !strcmp(e, "new"); }   // MM2GB_EDGE=new: the window test of edge blocks from a scalar prefix mask (measured: +1 % on 10-30 kb reads, -1 % on 30-100 kb: profiles/r06_narrow_ab.txt; off)
 		const char *v = getenv("MM2GB_FREE_SWEEP");
 		params.free_sweep = !(v && atoi(v) == 0) && params.dq_lim > 2 * params.bw;
 		// sources older than a lag before the target's slab by diagonal band (chain_kernels.hip, band_slab_part): MM2GB_BAND=0 gives the
@@ -421,8 +420,6 @@ int Engine::init(const mm2gb_config_t *c, const mm2gb_misc_t *m, int dev)
 	if (const char *v = getenv("MM2GB_TEAM4_SHARE_PCT")) launch.team4_share_pct = std::max(0, atoi(v));
 	if (const char *v = getenv("MM2GB_TEAM4_MIN_ANCHORS")) team4_min_n = std::max<int64_t>(0, atoll(v));
 	if (const char *v = getenv("MM2GB_DEBUG_PHASES")) debug_phases = *v && *v != '0';
-	if (const char *v = getenv("MM2GB_POST_FORM")) post_split = strcmp(v, "fused") != 0;
-	if (const char *v = getenv("MM2GB_POST_SORT")) post_levels = strcmp(v, "reads") != 0;
 	// the DP's skip limit (mg_lchain_dp's max_skip): kept only on request, so that hosts that cannot call mm2gb_engine_set_chain_skip (the
 	// reference's own host, the engines of pools and batchers) can opt in; read here once, never per call
 	if (const char *v = getenv("MM2GB_CHAIN_SKIP")) chain_skip = strcmp(v, "keep") == 0;
@@ -436,8 +433,6 @@ int Engine::init(const mm2gb_config_t *c, const mm2gb_misc_t *m, int dev)
 	launch.gang_pairs = 0;
 	if (const char *v = getenv("MM2GB_GANG_PAIRS")) launch.gang_pairs = *v && *v != '0';
 	if (const char *v = getenv("MM2GB_GANG_MAX_ANCHORS")) gang_max_n = std::max<int64_t>(0, atoll(v));
-	split_max_n = 0;                                           // off: measured slower at every batch size (profiles/earlier/r02y_split_rate.json)
-	if (const char *v = getenv("MM2GB_SPLIT_MAX_ANCHORS")) split_max_n = std::max<int64_t>(0, atoll(v));
 	if (debug_phases && dbg.ensure((size_t)launch.score_grid * 32)) return -1;
 	const char *env = getenv("MM2GB_NO_COOP");
 	coop_disabled = env && *env && *env != '0';
@@ -505,7 +500,7 @@ void Engine::shutdown()
 	h_slice_off.release(); h_res_f.release(); h_res_p.release();
 	for (hipEvent_t &e : slice_in) if (e) (void)hipEventDestroy(e);
 	slice_in.clear();
-	for (DevBuf *b : { &post_dbg_reads, &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
+	for (DevBuf *b : { &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
 	                   &post_out[0].u_off, &post_out[0].a_off, &post_out[0].u_out, &post_out[0].a_out, &post_out[1].u_off, &post_out[1].a_off, &post_out[1].u_out, &post_out[1].a_out })
 		b->release();
@@ -553,7 +548,7 @@ int Engine::begin_call()
 	if (n_slots > 0 && sync()) return -1;     // a previous call was never collected
 	n_slots = 0;
 	last = mm2gb_stats_t();
-	last_split_chunks = last_helped_items = 0; last_gang_chunks = last_gang_wgs = 0;
+	last_gang_chunks = last_gang_wgs = 0;
 	last_band_groups[0] = last_band_groups[1] = 0;
 	return 0;
 }
@@ -587,20 +582,10 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 	b.lut = (const int32_t*)lut.ptr;
 	b.dbg = debug_phases ? (int64_t*)dbg.ptr : nullptr;
 	if (debug_phases) MM2GB_HIP(hipMemsetAsync(dbg.ptr, 0, (size_t)launch.score_grid * 32, stream));
-	// A batch that cannot fill the machine ends with its largest chunks: the SPLIT build scores those strip by strip with the help of
-	// the workgroups that have run out of work (chain_kernels.hip, split_chunk).  Large batches keep the plain build.
 	LaunchCfg cfg_now = launch;
 	if (n < team4_min_n) cfg_now.team4_share_pct = 0;
-	cfg_now.split = score_has_split_build() && launch.host_mode == SCORE_MODE_LUT && launch.ring_slots > 0 && n > 0 && n <= split_max_n;
-	b.split_slots = nullptr; b.split_part = nullptr;
-	if (cfg_now.split) {
-		if (w.split_slots.ensure((size_t)launch.score_grid * sizeof(SplitSlot)) || w.split_part.ensure((size_t)launch.score_grid * SPLIT_MAX_ITEMS * 2 * 64 * 8)) return -1;
-		b.split_slots = (SplitSlot*)w.split_slots.ptr; b.split_part = (unsigned long long*)w.split_part.ptr;
-		MM2GB_HIP(hipMemsetAsync(w.split_slots.ptr, 0, (size_t)launch.score_grid * sizeof(SplitSlot), stream));
-	}
-
 	b.gang_slots = nullptr;
-	if (launch.gang_max >= 2 && launch.host_mode == SCORE_MODE_LUT && launch.ring_slots > 0 && !cfg_now.split && n > 0 && n <= gang_max_n) {
+	if (launch.gang_max >= 2 && launch.host_mode == SCORE_MODE_LUT && launch.ring_slots > 0 && n > 0 && n <= gang_max_n) {
 		if (w.gang_slots.ensure((size_t)GANG_MAX_CHUNKS * sizeof(GangSlot))) return -1;
 		b.gang_slots = (GangSlot*)w.gang_slots.ptr;                  // (filled by plan_gangs; CNT_NGANG says how many)
 	}
@@ -664,7 +649,7 @@ int Engine::reserve_post(int64_t n, int64_t n_reads)
 	if (post_z.ensure((size_t)nn * 8) || post_fp.ensure((size_t)nn * 8) || post_picked.ensure((size_t)nn * 4) || post_utmp.ensure(chains * 8) ||
 	    post_heads.ensure(chains * 16) || post_nu.ensure((size_t)nr * 4) || post_nkept.ensure((size_t)nr * 4) || post_misc.ensure(2048) || post_bins.ensure(2 * N_SIZE_CLASSES * 4) || post_order.ensure((size_t)nr * 4) ||
 	    post_up4.ensure((size_t)nn * 4) || post_up16.ensure((size_t)nn * 4)) return -1;
-	// split form: a class per anchor, per read and class the anchors / candidates, per chain slot where its anchors are, the walk tasks and their order
+	// a class per anchor, per read and class the anchors / candidates, per chain slot where its anchors are, the walk tasks and their order
 	if (post_cls.ensure((size_t)nn) || post_cls_cnt.ensure((size_t)nr * N_TREE_CLASSES * 4) || post_cls_nz.ensure((size_t)nr * N_TREE_CLASSES * 4) || post_read_nz.ensure((size_t)nr * 4) ||
 	    post_uloc.ensure(chains * 4) || post_wtask.ensure((size_t)nr * N_TREE_CLASSES * 4 * 2)) return -1;
 	// the sort's tasks: runs of more than 64 candidates, at most n / 65 of them at a level (+ a read's first): two lists and an order
@@ -705,14 +690,14 @@ int Engine::enqueue_post(int64_t n_reads, const int64_t *d_offsets, const mm2gb_
 	b.u_out = (unsigned long long*)po.u_out.ptr; b.a_out = (uint4*)po.a_out.ptr;
 	b.totals = (int64_t*)post_misc.ptr; b.cursor = (int32_t*)((char*)post_misc.ptr + 16);
 	b.order = (int32_t*)post_order.ptr; b.size_bins = (int32_t*)post_bins.ptr;
-	b.cls = post_split ? (unsigned char*)post_cls.ptr : nullptr;
+	b.cls = (unsigned char*)post_cls.ptr;
 	b.cls_cnt = (int32_t*)post_cls_cnt.ptr; b.cls_nz = (int32_t*)post_cls_nz.ptr; b.read_nz = (int32_t*)post_read_nz.ptr;
 	b.zc = (unsigned long long*)post_sort_tmp.ptr; b.kpos = (int32_t*)post_sort_perm.ptr; b.u_loc = (int32_t*)post_uloc.ptr;
 	b.wtask = (int32_t*)post_wtask.ptr; b.wtask_order = b.wtask + (size_t)std::max<int64_t>(cap_post_reads, 16) * N_TREE_CLASSES;
 	{
 		const size_t cap = (size_t)cap_post_n / 64 + (size_t)cap_post_reads + 64;
-		b.stask[0] = post_levels ? (int4*)post_stask.ptr : nullptr; b.stask[1] = b.stask[0] ? b.stask[0] + cap : nullptr;
-		b.stask_order = b.stask[0] ? (int32_t*)(b.stask[0] + 2 * cap) : nullptr;
+		b.stask[0] = (int4*)post_stask.ptr; b.stask[1] = b.stask[0] + cap;
+		b.stask_order = (int32_t*)(b.stask[0] + 2 * cap);
 	}
 	b.walk_grid_waves = n_cu * 4 * 8;
 	if (const char *v = getenv("MM2GB_WALK_WAVES")) b.walk_grid_waves = std::max(4, atoi(v));
@@ -720,11 +705,7 @@ int Engine::enqueue_post(int64_t n_reads, const int64_t *d_offsets, const mm2gb_
 	if (const char *v = getenv("MM2GB_SORT_PAIRS")) b.sort_pairs = atoi(v) != 0;
 	b.dbg = debug_phases ? (long long*)((char*)post_misc.ptr + 1024) : nullptr;
 	if (debug_phases) { MM2GB_HIP(hipMemsetAsync((char*)post_misc.ptr + 1024, 0, 512, stream)); MM2GB_HIP(hipMemsetAsync((char*)post_misc.ptr + 1024 + 22 * 8, 0xff, 8, stream)); }   // ([22]: a minimum)
-	b.dbg_reads = nullptr;
 	if (debug_phases) {
-		if (post_dbg_reads.ensure((size_t)std::max<int64_t>(n_reads, 1) * 32)) return -1;
-		MM2GB_HIP(hipMemsetAsync(post_dbg_reads.ptr, 0, (size_t)std::max<int64_t>(n_reads, 1) * 32, stream));
-		b.dbg_reads = (long long*)post_dbg_reads.ptr;
 		if (post_dbg_tasks.ensure((size_t)std::max<int64_t>(n_reads, 1) * N_TREE_CLASSES * 64)) return -1;
 		MM2GB_HIP(hipMemsetAsync(post_dbg_tasks.ptr, 0, (size_t)std::max<int64_t>(n_reads, 1) * N_TREE_CLASSES * 64, stream));
 	}
@@ -737,16 +718,8 @@ int Engine::enqueue_post(int64_t n_reads, const int64_t *d_offsets, const mm2gb_
 	// one read per wave at a time: as many waves as the chip holds (latency-bound pointer chases; parallelism is across reads)
 	b.grid_waves = n_cu * 32;
 	if (const char *v = getenv("MM2GB_POST_WAVES")) b.grid_waves = std::max(4, atoi(v));
-	// Whole workgroups start on the largest reads together (k_post_chains: collection and the buckets of the sort's top pass shared by the
-	// four waves): every read of a batch that leaves the chip idle anyway (at most one read per workgroup the chip holds at a time, 3 per CU by
-	// the kernel's LDS), the 64 largest of any other.  The kernel ends with its largest reads (sort + walks of the largest: 49 ms on one wave, 45
-	// with a workgroup's start), and since it runs three waves per SIMD the helpers' wait for the serial top pass no longer costs what it saves:
-	// k_post_chains + lift + emit at 500 M anchors / 9 016 reads 54.1-54.3 ms with no teams, 51.5-52.4 with 16 ... 128, 52.9 with 256, 55.1-55.7
-	// with 640 or 1 500 (profiles/r03_post_teams.txt; at two waves per SIMD every setting lost).
-	b.team_reads = n_reads <= (int64_t)n_cu * 3 ? (int)n_reads : 64;
-	if (const char *v = getenv("MM2GB_POST_TEAM_READS")) b.team_reads = std::max(0, atoi(v));
 	MM2GB_HIP(hipEventRecord(post0, stream));
-	launch_post(b, stream, !lean_streams && work[1].stream && work[1].stream != stream ? work[1].stream : nullptr, post_fork, post_join);
+	launch_post(b, n_cu, stream, !lean_streams && work[1].stream && work[1].stream != stream ? work[1].stream : nullptr, post_fork, post_join);
 	MM2GB_HIP(hipEventRecord(post1, stream));
 	MM2GB_HIP(hipMemcpyAsync(po.h_totals, post_misc.ptr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
 	MM2GB_HIP(hipEventRecord(po.done, stream));
@@ -806,7 +779,7 @@ int Engine::fetch_chains(int out_set, int64_t n_reads, mm2gb_chains_t *out)
 
 // The same for a LARGE batch: the anchors go in in slices of reads, each slice's score kernels running under the next slice's H2D (the
 // link is never idle; round 4 copied everything in, then ran the kernels, then copied the chains into fresh pageable memory: 170 ms for 200 M
-// anchors against 55.6 ms of H2D alone).  The post-pass runs ONCE, over the whole batch, when the last slice is scored: k_post_chains is as
+// anchors against 55.6 ms of H2D alone).  The post-pass runs ONCE, over the whole batch, when the last slice is scored: the post-pass is as
 // long as its largest read takes (28 ms for a 64 M-anchor slice, 30 ms for the whole 200 M: four slices' post-passes one after the other were
 // no faster than the round-4 call, profiles/r05_host_path_timeline.md), so it is paid once and only the chains' D2H follows it.
 // Results land in page-locked blocks of the result cache (exact sizes: the totals are known before the copies start).
@@ -1052,7 +1025,7 @@ int Engine::chain_gpu(int64_t n_reads, const int64_t *offsets, const mm2gb_ancho
 	float ms = 0;
 	if (n_reads > 0 && hipEventElapsedTime(&ms, post0, post1) == hipSuccess) last.ms_post = ms;
 	last.ms_total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-	if (debug_phases && n > 0) print_post_debug(n_reads, (const int64_t*)s.offsets.ptr);
+	if (debug_phases && n > 0) print_post_debug(n_reads);
 	if (debug_phases && n > 0)
 		fprintf(stderr, "[mm2gb chain_gpu%s] %lld anchors in, %lld kept: enqueued at %.1f ms, device done at %.1f ms (post-pass %.1f ms), results copied at %.1f ms\n", rmq ? ", rmq" : "",
 		        (long long)n, (long long)n_a, s_enqueued * 1e3, s_synced * 1e3, ms, last.ms_total);
@@ -1246,7 +1219,6 @@ int Engine::collect_stats()
 		last.n_mid_chunks += c[CNT_NMID];
 		last.n_tracked_chunks += c[CNT_NTRACK];
 		last.n_clamped_blocks += c[CNT_NCLAMP];
-		last_split_chunks += c[CNT_NSPLIT]; last_helped_items += c[CNT_HELPED];
 		last_gang_chunks += c[CNT_NGANG]; last_gang_wgs += c[CNT_GANG_WGS];
 		last_band_groups[0] += c[CNT_BAND_WAVE]; last_band_groups[1] += c[CNT_BAND_TEAM];
 		float ms = 0;
@@ -1336,13 +1308,6 @@ using namespace mm2gb;
 extern "C" {
 
 const char *mm2gb_last_error(void) { return last_error_cstr(); }
-// of the engine's last completed call: chunks scored strip by strip (k_score's SPLIT build) and the items of such chunks that
-// workgroups other than the owner took
-void mm2gb_engine_split_counts(const mm2gb_engine_t *eng, int64_t *chunks, int64_t *helped_items)
-{
-	if (chunks) *chunks = eng ? eng->e.last_split_chunks : 0;
-	if (helped_items) *helped_items = eng ? eng->e.last_helped_items : 0;
-}
 // of the engine's last completed call: chunks that a gang of workgroups scored (k_score's phase 0) and the workgroups that started in one
 void mm2gb_engine_gang_counts(const mm2gb_engine_t *eng, int64_t *chunks, int64_t *workgroups)
 {
@@ -1350,7 +1315,6 @@ void mm2gb_engine_gang_counts(const mm2gb_engine_t *eng, int64_t *chunks, int64_
 	if (workgroups) *workgroups = eng ? eng->e.last_gang_wgs : 0;
 }
 const char *mm2gb_version(void) { return MM2GB_VERSION; }
-int mm2gb_has_split_build(void) { return score_has_split_build() ? 1 : 0; }
 int mm2gb_has_gang_build(void) { return 1; }
 
 int mm2gb_device_count(void)
@@ -1427,7 +1391,7 @@ int mm2gb_chain_gpu(mm2gb_engine_t *eng, int64_t n_reads, const int64_t *offsets
 }
 
 // MM2GB_DEBUG_PHASES: what the last post-pass kernel recorded (to stderr)
-void Engine::print_post_debug(int64_t n_reads, const int64_t *d_offsets)
+void Engine::print_post_debug(int64_t n_reads)
 {
 	long long t[64] = { 0 };
 	if (hipMemcpy(t, (char*)post_misc.ptr + 1024, sizeof(t), hipMemcpyDeviceToHost) == hipSuccess)
@@ -1435,40 +1399,11 @@ void Engine::print_post_debug(int64_t n_reads, const int64_t *d_offsets)
 			fprintf(stderr, "[mm2gb post-pass] sort level %d: %.1f ms; %lld radix passes over %lld elements: %lld cycles, %lld steps, refills of one line %lld, of all lines %lld\n",
 			        lv, t[13 + lv] / 1e5, t[24 + 6 * lv + 5], t[24 + 6 * lv + 4], t[24 + 6 * lv + 3], t[24 + 6 * lv], t[24 + 6 * lv + 1], t[24 + 6 * lv + 2]);
 	if (t[21])
-		fprintf(stderr, "[mm2gb post-pass] split form: %lld walk tasks, first starts at 0, last ends at %.2f ms; summed %.1f ms, longest task %.2f ms; spec loads %.1f ms, long walks %.1f ms; groups %lld, open %lld, long %lld (%lld rounds)\n",
+		fprintf(stderr, "[mm2gb post-pass] walks: %lld tasks, first starts at 0, last ends at %.2f ms; summed %.1f ms, longest task %.2f ms; spec loads %.1f ms, long walks %.1f ms; groups %lld, open %lld, long %lld (%lld rounds)\n",
 		        t[21], (t[23] - t[22]) / 1e5, t[2] / 1e5, t[5] / 1e5, t[7] / 1e5, t[8] / 1e5, t[9], t[10], t[11], t[20]);
-	if (t[6])
-		fprintf(stderr, "[mm2gb post-pass] walks: spec loads %.1f ms, long walks %.1f ms; groups %lld, open %lld, long %lld (%lld rounds of 64 anchors), candidates %lld\n", t[7] / 1e5, t[8] / 1e5, t[9], t[10], t[11], t[20], t[12]);
-	if (t[6] || t[21])
-		fprintf(stderr, "[mm2gb post-pass] wave-time summed over reads: collect %.1f ms | sort %.1f ms | chain walks %.1f ms | emit %.1f ms  (%lld reads) | slowest read: sort %.2f ms, walks %.2f ms, whole %.2f ms\n",
-		        t[0] / 1e5, t[1] / 1e5, t[2] / 1e5, t[3] / 1e5, (long long)n_reads, t[4] / 1e5, t[5] / 1e5, t[6] / 1e5);
-	// the schedule: when the reads that finish last were started, and how long their parts took
-	if (n_reads > 0 && post_dbg_reads.ptr) {
-		std::vector<long long> tr((size_t)n_reads * 4);
-		std::vector<int64_t> off((size_t)n_reads + 1);
-		if (hipMemcpy(tr.data(), post_dbg_reads.ptr, tr.size() * 8, hipMemcpyDeviceToHost) == hipSuccess &&
-		    hipMemcpy(off.data(), d_offsets, off.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-			long long t_first = LLONG_MAX, t_last = 0;
-			for (int64_t r = 0; r < n_reads; ++r) if (tr[4 * r]) { t_first = std::min(t_first, tr[4 * r]); t_last = std::max(t_last, tr[4 * r + 3]); }
-			std::vector<int64_t> idx;
-			for (int64_t r = 0; r < n_reads; ++r) if (tr[4 * r]) idx.push_back(r);
-			std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b2) { return tr[4 * a + 3] > tr[4 * b2 + 3]; });
-			fprintf(stderr, "[mm2gb post-pass] k_post_chains: first read starts at 0, last ends at %.2f ms; the reads that end last (anchors | start | collect | sort | walks | end, ms):\n", (t_last - t_first) / 1e5);
-			for (size_t k = 0; k < std::min<size_t>(idx.size(), 12); ++k) {
-				const int64_t r = idx[k];
-				fprintf(stderr, "    read %6lld  %7lld | %6.2f | %5.2f | %6.2f | %6.2f | %6.2f\n", (long long)r, (long long)(off[r + 1] - off[r]), (tr[4 * r] - t_first) / 1e5,
-				        (tr[4 * r + 1] - tr[4 * r]) / 1e5, (tr[4 * r + 2] - tr[4 * r + 1]) / 1e5, (tr[4 * r + 3] - tr[4 * r + 2]) / 1e5, (tr[4 * r + 3] - t_first) / 1e5);
-			}
-			// reads in flight over time (how many wave slots still work at t)
-			const int n_bins = 14;
-			std::vector<int> busy(n_bins, 0);
-			const double span = std::max(1.0, (double)(t_last - t_first));
-			for (int64_t r : idx) for (int k = 0; k < n_bins; ++k) { const double at = t_first + span * (k + 0.5) / n_bins; if (tr[4 * r] <= at && at < tr[4 * r + 3]) ++busy[k]; }
-			fprintf(stderr, "    reads in flight at %d points of the kernel's time:", n_bins);
-			for (int k = 0; k < n_bins; ++k) fprintf(stderr, " %d", busy[k]);
-			fprintf(stderr, "\n");
-		}
-	}
+	if (t[21])
+		fprintf(stderr, "[mm2gb post-pass] wave-time summed over reads: collect %.1f ms | sort %.1f ms | chain walks %.1f ms | emit %.1f ms  (%lld reads) | longest sort task %.2f ms, walk task %.2f ms\n",
+		        t[0] / 1e5, t[1] / 1e5, t[2] / 1e5, t[3] / 1e5, (long long)n_reads, t[4] / 1e5, t[5] / 1e5);
 	if (t[42] > 0 && post_dbg_stasks.ptr) {
 		const size_t n_t = (size_t)std::min<long long>(t[42], 262144);
 		std::vector<long long> tk(n_t * 4);
@@ -1568,7 +1503,7 @@ int mm2gb_post_device(mm2gb_engine_t *eng, int64_t n_reads, const int64_t *d_off
 	MM2GB_HIP(hipStreamSynchronize(e.stream));
 	if (n_chains) *n_chains = e.h_post_totals[0];
 	if (n_kept) *n_kept = e.h_post_totals[1];
-	if (e.debug_phases) e.print_post_debug(n_reads, d_offsets);
+	if (e.debug_phases) e.print_post_debug(n_reads);
 	float t = 0;
 	if (ms && hipEventElapsedTime(&t, e.post0, e.post1) == hipSuccess) *ms = t;
 	return 0;

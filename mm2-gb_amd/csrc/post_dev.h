@@ -35,10 +35,8 @@ struct PostBatch {
 	int32_t  *size_bins;       // 2 x N_SIZE_CLASSES: reads per size class (eight classes per power of two), and the fill cursors of the scatter
 	int       min_cnt, min_sc, max_drop;
 	int       grid_waves;      // waves to launch (one read per wave at a time)
-	int       team_reads;      // the largest reads of the batch that a whole workgroup starts on together (k_post_chains)
 	long long *dbg;            // optional (MM2GB_DEBUG_PHASES): summed 100 MHz ticks of [0] candidate collection [1] sort [2] chain walks [3] emit
-	long long *dbg_reads;      // optional (MM2GB_DEBUG_PHASES): per read 4 ticks: start, end of collection, end of sort, end of walks (k_post_chains)
-	// The walks of a read shared out by TREE (round 6; null: one wave sorts and walks a read, k_post_chains).  p[] is a forest and a walk never
+	// The walks of a read shared out by TREE.  p[] is a forest and a walk never
 	// leaves its tree (lchain.c:9-25 follows p; marks are only ever set along it), so walks that start in different trees never meet: every tree
 	// gets a class -- a hash of its root --, a read's sorted candidates are dealt to their classes in order, and (read, class) pairs are walked by
 	// different waves.  What the host appends to u[] / v[] candidate by candidate is put together again from the candidates' sorted positions.
@@ -51,8 +49,8 @@ struct PostBatch {
 	                           // (endslot: by sorted position, the chain slot of the chain that candidate ended, -1 none: n entries of 4 bytes in the read's own part of z, whose candidates live in zc by then)
 	int32_t  *u_loc;           // per chain slot: where the chain's anchors start in the read's picked[]
 	int32_t  *wtask, *wtask_order;   // up to n_reads x N_TREE_CLASSES each: read << 4 | class of every pair with candidates; the same, most candidates first
-	// The sort by LEVELS (round 6): every run of more than 64 candidates that needs a radix pass is a task of its level's launch (k_post_sort_level)
-	// -- the host's recursion bucket by bucket (ksort.h:140-145), breadth first over the whole batch -- instead of one wave sorting a read from top to bottom
+	// The sort by LEVELS: every run of more than 64 candidates that needs a radix pass is a task of its level's launch (k_post_sort_level)
+	// -- the host's recursion bucket by bucket (ksort.h:140-145), breadth first over the whole batch
 	int4     *stask[2];        // two lists (a level reads one and fills the other): read, first candidate, length, key byte's shift; counts in cursor[8 + level], work cursors in cursor[16 + level]
 	int32_t  *stask_order;     // the tasks of the level that runs, longest first
 	int       walk_grid_waves; // waves of k_post_walk (it holds no LDS: more fit than of the sort)
@@ -62,7 +60,7 @@ struct PostBatch {
 };
 constexpr int N_TREE_CLASSES = 16;
 // aux (may be null): a second stream for the pass that gives the anchors their classes, beside the lifting tables' (both only read the scores); fork / join: its events
-void launch_post(const PostBatch &b, hipStream_t s, hipStream_t aux = nullptr, hipEvent_t fork = nullptr, hipEvent_t join = nullptr);
+void launch_post(const PostBatch &b, int n_cu, hipStream_t s, hipStream_t aux = nullptr, hipEvent_t fork = nullptr, hipEvent_t join = nullptr);
 
 // RMQ re-chaining (mg_lchain_rmq, lchain.c:250-369) of reads whose anchors are already chained once: score fill on the device.
 struct RmqParams { int max_dist, max_dist_inner, bw, cap_rmq_size; float pen_gap, pen_skip;

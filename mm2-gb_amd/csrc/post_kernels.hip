@@ -10,11 +10,14 @@
 // sorts, segment discovery, the final gather) and lane 0 for the two chases.  A low-occupancy, latency-bound kernel by
 // design; it runs on the engine's compute stream behind the score kernel of its micro-batch.
 //
-//   k_post_chains   per read: candidates z = (f, i) with f >= min_sc  ->  the host's sort order  ->  chain walks  ->
-//                   picked[] (anchor indices, chain by chain), u_tmp[] (score<<32 | count), n_u, n_kept
-//   k_post_scan     exclusive scans of n_u / n_kept over the reads -> u_off, a_off (+ totals)
-//   k_post_emit     per read: chains ordered by the reference position of their first anchor (same sort), u[] and the
-//                   compacted anchors written to their final place
+//   k_post_classes     per read: the tree of predecessor links every anchor belongs to (its class), and the candidates z = (f, i)
+//                      with f >= min_sc
+//   k_post_sort_level  the host's sort order of the candidates, one radix level at a time over the whole batch
+//   k_post_partition   per read: the sorted candidates dealt to their classes
+//   k_post_walk        per (read, class): chain walks -> picked[] (anchor indices, chain by chain), u_tmp[] (score<<32 | count), n_u, n_kept
+//   k_post_scan        exclusive scans of n_u / n_kept over the reads -> u_off, a_off (+ totals)
+//   k_post_emit        per read: chains ordered by the reference position of their first anchor (same sort), u[] and the
+//                      compacted anchors written to their final place
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -66,16 +69,12 @@ __device__ __forceinline__ void wave_sync()
 #endif
 constexpr int LINE_STORE_BYTES = MM2GB_POST_LINE_BYTES;
 static_assert(LINE_STORE_BYTES % 1024 == 0 && LINE_STORE_BYTES / 8 >= 2 * 256 + 64, "line slots come in whole rounds of 64 for both element kinds (8 and 16 bytes), and every bucket owns at least two (8-byte elements): fewer and the lines cannot be laid out");
-// k_post_chains: registers are budgeted for this many waves per SIMD (= workgroups per CU; its LDS allows 3 at 6 KB of lines).  The kernel is a
-// sum of latencies: 168 registers and three waves per SIMD (6 spilled) against 184 and two: 58.5 -> 55.7 ms per 500 M anchors
+// k_post_sort_level: registers are budgeted for this many waves per SIMD (= workgroups per CU; its LDS allows 3 at 6 KB of lines).  The sort is a
+// sum of latencies: three waves per SIMD with a few registers spilled beat two without
 #ifndef MM2GB_POST_WAVES_PER_SIMD
 #define MM2GB_POST_WAVES_PER_SIMD 3
 #endif
 constexpr int POST_WAVES_PER_SIMD = MM2GB_POST_WAVES_PER_SIMD;
-#ifndef MM2GB_POST_MARKS_IN_MEMORY
-#define MM2GB_POST_MARKS_IN_MEMORY 0            // 1: the walks' "taken" flags in the anchors' records for every read (round 4; A/B builds)
-#endif
-constexpr bool POST_MARKS_IN_MEMORY = MM2GB_POST_MARKS_IN_MEMORY != 0;
 struct alignas(16) PassLds {
 	int where[256];              // histogram first; then line start | line length << 16
 	int head[256], tail[256], anchor[256];
@@ -774,13 +773,10 @@ __device__ __forceinline__ int radix_pass_pair(const PairRun &A, const PairRun &
 // one level up is seen again: a no-op).
 // Passes on bytes in which all keys of the run agree move nothing, so starting at the highest byte in which any two keys
 // differ equals the host's start at byte 7.
-#ifndef MM2GB_POST_SORT_ELEMENTS
-#define MM2GB_POST_SORT_ELEMENTS 0              // 1: the candidates' sort moves elements step by step too (round 4; A/B builds)
-#endif
 template <class E, bool BYTES>
 __device__ __forceinline__ bool one_radix_pass(typename E::T *g, int lo, int hi, int shift, PassLds &L, const SortScratch *sc, long long *dbg, long long *ph = nullptr, FewBuckets *fb = nullptr)
 {
-	if constexpr (BYTES && !MM2GB_POST_SORT_ELEMENTS) return radix_pass_bytes(g, lo, hi, shift, L, *sc, dbg, ph, fb);
+	if constexpr (BYTES) return radix_pass_bytes(g, lo, hi, shift, L, *sc, dbg, ph, fb);
 	else return radix_pass<E>(g, lo, hi, shift, L, dbg);
 }
 
@@ -910,8 +906,8 @@ __device__ __forceinline__ int64_t chain_slot(int64_t off_r, int64_t r, int mc) 
 
 // --------------------------------------------------------------------------------------------------------------
 // reads by size, largest first: N_SIZE_CLASSES classes, eight per power of two, so reads of one class differ by at most an eighth (order
-// inside a class is arbitrary: reads are independent, results do not depend on it).  The kernel ends with its largest reads: they start
-// first, and the very largest are the ones whole workgroups start on (k_post_chains).
+// inside a class is arbitrary: reads are independent, results do not depend on it).  A kernel ends with its largest reads: they start
+// first.
 // --------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int size_class(int64_t n)
 {
@@ -991,24 +987,19 @@ __global__ __launch_bounds__(256) void k_post_lift(PostBatch b, int level)
 }
 
 // --------------------------------------------------------------------------------------------------------------
-// per read: candidates, host order, chain walks (lchain.c:27-76)
+// chain walks (lchain.c:44-74)
 // --------------------------------------------------------------------------------------------------------------
 namespace {
 
 struct WalkDbg { long long load = 0, longt = 0, groups = 0, open = 0, nlong = 0, iters = 0; };
 
-// The chain walks of one read (lchain.c:44-74) over its sorted candidates z[0, n_z): one wave.
-// `bits` (round 5): one "taken" bit per anchor of the read in the wave's LDS (the sort's scratch, free by now) instead of the top bit of the
-// anchor's record in memory.  60 % of all candidates are found taken on their first probe (their chain's best end came earlier): that probe,
-// the marks of every walk and the second looks of a group become LDS traffic, and nothing but scores and links is ever loaded.  Null for a
-// read with more anchors than the scratch has bits: the flag then lives in the record as before.
-// Split form (round 6, k_post_walk): z is ONE CLASS of the read's sorted candidates (the trees whose roots hash to it; sorted order kept), kp
-// their positions in the whole read's order; a chain that is kept is recorded under its end's position (what.endslot: its chain slot, read-relative,
-// what.u_loc: where its anchors start in the read's picked[]), so that the read's chains can be put in the host's order afterwards.
-struct WalkSplit { const int32_t *kp = nullptr; int32_t *endslot = nullptr; int32_t *u_loc = nullptr; int picked_base = 0, slot_base = 0; };
+// The chain walks of one (read, class) over its sorted candidates z[0, n_z): one wave (k_post_walk).  z is ONE CLASS of the read's sorted
+// candidates (the trees whose roots hash to it; sorted order kept), kp their positions in the whole read's order; a chain that is kept is
+// recorded under its end's position (what.endslot: its chain slot, read-relative, what.u_loc: where its anchors start in the read's picked[]),
+// so that the read's chains can be put in the host's order afterwards.  An anchor's "taken" flag is the top bit of its record fp[i].y.
+struct WalkSplit { const int32_t *kp; int32_t *endslot; int32_t *u_loc; int picked_base, slot_base; };
 __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t off, const int n_z, const unsigned long long *z, int2 *fp,
-                                               int32_t *picked, unsigned long long *u_tmp, int &n_u_out, int &n_v_out, WalkDbg &wd, unsigned *bits,
-                                               const WalkSplit &what = WalkSplit())
+                                               int32_t *picked, unsigned long long *u_tmp, int &n_u_out, int &n_v_out, WalkDbg &wd, const WalkSplit &what)
 {
 	const int l = lane();
 	long long &dbg_load = wd.load, &dbg_longt = wd.longt, &dbg_groups = wd.groups, &dbg_open = wd.open, &dbg_long = wd.nlong;
@@ -1019,13 +1010,11 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 	const int32_t *up4 = b.up4 + off, *up16 = b.up16 + off;
 	constexpr int TAKEN = INT_MIN;                           // top bit of fp[i].y
 	int *fpw = (int*)fp;                                     // fpw[2 i + 1] = fp[i].y
-	auto taken = [&](int i) { return (int)((bits[i >> 5] >> (i & 31)) & 1u) != 0; };
-	auto take = [&](int i) { atomicOr(&bits[i >> 5], 1u << (i & 31)); };
 	int n_u = 0, n_v = 0;
 	for (int kb = n_z - 1; kb >= 0; kb -= W) {
 		const int k_l = kb - l;
 		const unsigned long long z_l = k_l >= 0 ? z[k_l] : 0;
-		const int kp_l = what.kp && k_l >= 0 ? what.kp[k_l] : 0;
+		const int kp_l = k_l >= 0 ? what.kp[k_l] : 0;
 		const int n0 = (int)(unsigned)z_l, top_l = (int)(z_l >> 32);
 		unsigned long long pending = __ballot(k_l >= 0);
 		int nx[SPEC], sx[SPEC];                                 // the group's look-ahead: anchors SPEC steps down every candidate's path, and their score drops
@@ -1048,7 +1037,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 				for (int j = 0; j < SPEC; ++j) { nx[j] = -1; sx[j] = top_l; }
 			}
 			if ((pending >> l) & 1) {
-				p0 = bits ? (taken(n0) ? TAKEN : fpw[2 * n0 + 1]) : fpw[2 * n0 + 1];
+				p0 = fpw[2 * n0 + 1];
 				if (fresh) {
 					int pc = p0;
 					if (p0 >= 0) {
@@ -1059,7 +1048,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 							if (!ended) {
 								const int next = pc ? cur - pc : -1;
 								nx[j] = next;
-								if (next >= 0) { const int2 rec = fp[next]; sx[j] = top_l - rec.x; pn[j] = bits && taken(next) ? rec.y | TAKEN : rec.y; pc = rec.y; }
+								if (next >= 0) { const int2 rec = fp[next]; sx[j] = top_l - rec.x; pn[j] = rec.y; pc = rec.y; }
 								if (sx[j] > best) { best = sx[j]; kept = j + 1; }
 								else if (best - sx[j] > b.max_drop) ended = true;
 								if (pn[j] < 0) ended = true;
@@ -1070,7 +1059,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 					}
 				} else {
 #pragma unroll
-					for (int j = 0; j < SPEC; ++j) if (nx[j] >= 0) pn[j] = bits ? (taken(nx[j]) ? TAKEN : 0) : fpw[2 * nx[j] + 1];   // (only the sign is looked at when the marks are bits)
+					for (int j = 0; j < SPEC; ++j) if (nx[j] >= 0) pn[j] = fpw[2 * nx[j] + 1];
 					if (p0 >= 0) {
 						int best = 0, kept = 0;
 						bool ended = false;
@@ -1106,7 +1095,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 						if (j < kept) {
 							const int v = j == 0 ? c0 : __builtin_amdgcn_readlane(nx[j > 0 ? j - 1 : 0], src);
 							const int link = j == 0 ? __builtin_amdgcn_readlane(p0, src) : __builtin_amdgcn_readlane(pn[j > 0 ? j - 1 : 0], src);
-							if (l == 0) { picked[n_v + j] = v; if (bits) take(v); else fpw[2 * v + 1] = link | TAKEN; }
+							if (l == 0) { picked[n_v + j] = v; fpw[2 * v + 1] = link | TAKEN; }
 							const bool hit = (n0 == v) | (nx[0] == v) | (nx[1] == v) | (nx[2] == v) | (nx[3] == v);
 							touched |= hit;
 							p0 |= n0 == v ? TAKEN : 0;
@@ -1116,7 +1105,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 					}
 					if (best >= b.min_sc && kept > 0 && kept >= b.min_cnt) {
 						if (l == 0) u_tmp[n_u] = (unsigned long long)(unsigned)best << 32 | (unsigned)kept;
-						if (what.kp) { const int kp = __builtin_amdgcn_readlane(kp_l, src); if (l == 0) { what.u_loc[n_u] = what.picked_base + n_v; what.endslot[kp] = what.slot_base + n_u; } }
+						{ const int kp = __builtin_amdgcn_readlane(kp_l, src); if (l == 0) { what.u_loc[n_u] = what.picked_base + n_v; what.endslot[kp] = what.slot_base + n_u; } }
 						++n_u; n_v += kept;
 					}
 					continue;
@@ -1148,7 +1137,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 						if (j < kept) {
 							const int v = j == 0 ? c0 : cn[j > 0 ? j - 1 : 0];
 							const int link = j == 0 ? __builtin_amdgcn_readlane(p0, src) : cm[j > 0 ? j - 1 : 0];
-							if (l == 0) { if (bits) take(v); else fpw[2 * v + 1] = link | TAKEN; }
+							if (l == 0) fpw[2 * v + 1] = link | TAKEN;
 							const bool hit = (n0 == v) | (nx[0] == v) | (nx[1] == v) | (nx[2] == v) | (nx[3] == v);
 							touched |= hit;
 							p0 |= n0 == v ? TAKEN : 0;
@@ -1185,7 +1174,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 						if (n_rounds == 1) { t_first = t; pt_first = pt; }
 						const int nx_f = __shfl_down(own.x, 1), nx_y = __shfl_down(own.y, 1);
 						int s = top, m = 1;
-						if (next >= 0) { s = top - nx_f; m = bits ? (int)taken(next) : (int)(nx_y < 0); }
+						if (next >= 0) { s = top - nx_f; m = nx_y < 0; }
 						// best prefix BEFORE this lane's step
 						int inc = valid && l < rd ? s : INT_MIN;
 						for (int o = 1; o < W; o <<= 1) { const int v = __shfl_up(inc, o); if (l >= o) inc = max(inc, v); }
@@ -1206,7 +1195,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 						else { visited += rd; cur = __shfl(t, rd); rw = W; }
 					}
 					wave_sync();
-					if (n_rounds == 1 && !bits) {
+					if (n_rounds == 1) {
 						// the first SPEC anchors it took are the look-ahead's, the others the round's (one per lane)
 #pragma unroll
 						for (int j = 0; j < SPEC; ++j) {
@@ -1232,15 +1221,14 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 						}
 					} else {
 						stale = true;
-						if (bits) for (int q = l; q < kept; q += W) take(picked[n_v + q]);
-						else for (int q = l; q < kept; q += W) { int *w = &fpw[2 * picked[n_v + q] + 1]; *w |= TAKEN; }
+						for (int q = l; q < kept; q += W) { int *w = &fpw[2 * picked[n_v + q] + 1]; *w |= TAKEN; }
 					}
 					if (b.dbg) dbg_longt += (long long)__builtin_amdgcn_s_memrealtime() - tl;
 				}
 				// the chain's score is the best prefix itself (lchain.c:66: f of the end minus f of where it stops)
 				if (best >= b.min_sc && kept > 0 && kept >= b.min_cnt) {
 					if (l == 0) u_tmp[n_u] = (unsigned long long)(unsigned)best << 32 | (unsigned)kept;
-					if (what.kp) { const int kp = __builtin_amdgcn_readlane(kp_l, src); if (l == 0) { what.u_loc[n_u] = what.picked_base + n_v; what.endslot[kp] = what.slot_base + n_u; } }
+					{ const int kp = __builtin_amdgcn_readlane(kp_l, src); if (l == 0) { what.u_loc[n_u] = what.picked_base + n_v; what.endslot[kp] = what.slot_base + n_u; } }
 					++n_u; n_v += kept;
 				}
 			}
@@ -1250,196 +1238,7 @@ __device__ __forceinline__ void post_walk_read(const PostBatch &b, const int64_t
 	n_u_out = n_u; n_v_out = n_v;
 }
 
-// candidates of anchors [i_lo, i_hi) of a read, in index order (lchain.c:35-41), appended at z[at...] (nothing is taken yet: k_post_lift wrote the records).
-// Returns how many; any / all: OR and AND of their keys (which key bytes differ at all).
-__device__ __forceinline__ int post_collect(const PostBatch &b, const int32_t *f, unsigned long long *z, int i_lo, int i_hi, int at, bool write,
-                                            unsigned &any, unsigned &all)
-{
-	const int l = lane();
-	int n_z = 0;
-	for (int base = i_lo; base < i_hi; base += W) {
-		const int i = base + l;
-		const bool in = i < i_hi;
-		const int fi = in ? f[i] : INT_MIN;
-		const bool take = in && fi >= b.min_sc;
-		const unsigned long long m = __ballot(take);
-		if (take) { any |= (unsigned)fi; all &= (unsigned)fi; }
-		if (take && write) z[at + n_z + __popcll(m & ((1ull << l) - 1))] = (unsigned long long)(unsigned)fi << 32 | (unsigned)i;
-		n_z += __popcll(m);
-	}
-	return n_z;
-}
-
 } // namespace
-
-// One wave per read, except at the very start of the launch: reads come largest first, and the kernel ends with the largest ones -- a
-// read is one wave's serial work (the sort's cycle walks, the chain walks), ~0.45 us per anchor, while most of the chip has long run out of
-// reads.  So the FIRST read a workgroup takes (the `team_reads` largest of the batch) is shared by its four waves as far as the
-// reference's algorithm allows: candidates are collected by all four (each a quarter of the anchors), the top radix pass -- one token walk
-// through 256 bucket heads, inherently serial (ksort.h:116-146) -- is wave 0's, and its buckets, which the host sorts independently of each
-// other (rs_sort's recursion, ksort.h:140-145), are dealt to the four waves, largest first.  The chain walks are wave 0's again (they
-// depend on each other through the marks); the other three waves go on to reads of their own.
-// SORT_ONLY (round 6): the same up to the sorted candidates, whose number goes to read_nz[]; the walks are k_post_walk's.
-template <bool SORT_ONLY>
-__device__ __forceinline__ void post_chains_body(const PostBatch &b, int team_reads)
-{
-	__shared__ PassLds lds[POST_THREADS / W];
-	__shared__ int s_team[8];                                // [0] the team's read (position in the order), [1..4] candidates per wave, [5] next task
-	__shared__ unsigned s_bits[2 * (POST_THREADS / W)];      // per wave: OR / AND of its candidates' keys
-	__shared__ int s_bound[257];                             // ends of the top pass's buckets
-	__shared__ int s_task[256];                              // buckets worth a task, largest first
-	PassLds &L = lds[threadIdx.x / W];
-	const int l = lane(), w = uni(threadIdx.x / W);
-	const int mc = b.min_cnt > 1 ? b.min_cnt : 1;
-	// ---- the team's read ----
-	bool walker = false;                                     // wave 0 of a team: sorted candidates wait for its walks
-	int team_r = -1, team_nz = 0, solo_q = -1;
-	if (team_reads > 0) {
-		if (threadIdx.x == 0) s_team[0] = atomicAdd(b.cursor, 1);
-		__syncthreads();
-		const int q = uni(s_team[0]);
-		if (q < team_reads && q < b.n_reads) {
-			const int r = uni(b.order[q]);
-			const int64_t off = b.offsets[r];
-			const int n = (int)(b.offsets[r + 1] - off);
-			const int32_t *f = b.f + off;
-			unsigned long long *z = b.z + off;
-			// candidates: every wave a quarter of the anchors (whole groups of 64), counted first, then written behind the earlier quarters'
-			const int per = ((n + 4 * W - 1) / (4 * W)) * W;
-			const int i_lo = min(n, w * per), i_hi = min(n, (w + 1) * per);
-			unsigned any = 0, all = ~0u;
-			const int mine = post_collect(b, f, z, i_lo, i_hi, 0, false, any, all);
-			for (int o = W / 2; o > 0; o >>= 1) { any |= __shfl_xor(any, o); all &= __shfl_xor(all, o); }
-			if (l == 0) { s_team[1 + w] = mine; s_bits[2 * w] = any; s_bits[2 * w + 1] = all; }
-			__syncthreads();
-			int at = 0, n_z = 0;
-			for (int k = 0; k < POST_THREADS / W; ++k) { const int c = uni(s_team[1 + k]); if (k < w) at += c; n_z += c; any |= s_bits[2 * k]; all &= s_bits[2 * k + 1]; }
-			{ unsigned a2 = 0, b2 = ~0u; post_collect(b, f, z, i_lo, i_hi, at, true, a2, b2); }
-			__threadfence_block();
-			__syncthreads();
-			// the top pass: the highest key byte in which any two candidates differ (sort_like_host), wave 0 alone
-			const unsigned diff = uni((int)(any ^ all));
-			int n_tasks = 0;
-			if (n_z > SMALL_RUN && diff != 0) {
-				int top = 24;                                      // of the key = the score: byte 3 .. 0 (sort_like_host's `top`)
-				while (top > 0 && ((diff >> top) & 255u) == 0) top -= 8;
-				if (w == 0) {
-					const SortScratch sc = { b.sort_s + off, b.sort_perm + off, b.sort_tmp + off };
-					one_radix_pass<ZElem, true>(z, 0, n_z, top, L, &sc, b.dbg ? b.dbg + 24 : nullptr);
-					for (int k = l; k < 256; k += W) s_bound[k + 1] = MM2GB_POST_SORT_ELEMENTS ? L.tail[k] : ((const int4*)L.where)[k].w;   // the buckets' ends: the byte form keeps them in its records
-					if (l == 0) s_bound[0] = 0;
-					wave_sync();
-					// buckets of more than one element are tasks, largest first (a few hold nearly everything: the scores of a read span two
-					// to four values of the top byte): rank of every bucket by (size, number), all 256 against all 256
-					int sz[4], rank[4] = { 0, 0, 0, 0 }, tasks = 0;
-#pragma unroll
-					for (int q = 0; q < 4; ++q) { sz[q] = s_bound[4 * l + q + 1] - s_bound[4 * l + q]; tasks += sz[q] > 1; }
-					for (int k = 0; k < 256; ++k) {
-						const int other = uni(s_bound[k + 1]) - uni(s_bound[k]);
-#pragma unroll
-						for (int q = 0; q < 4; ++q) rank[q] += (other > sz[q]) | ((other == sz[q]) & (k < 4 * l + q));
-					}
-#pragma unroll
-					for (int q = 0; q < 4; ++q) s_task[rank[q]] = 4 * l + q;
-					for (int o = W / 2; o > 0; o >>= 1) tasks += __shfl_xor(tasks, o);
-					if (l == 0) { s_team[6] = tasks; s_team[5] = 0; }
-				}
-				__threadfence_block();
-				__syncthreads();
-				n_tasks = uni(s_team[6]);
-				for (;;) {
-					int t = 0;
-					if (l == 0) t = atomicAdd(&s_team[5], 1);
-					t = uni(t);
-					if (t >= n_tasks) break;
-					const int k = uni(s_task[t]);
-					const int lo = uni(s_bound[k]), hi = uni(s_bound[k + 1]);
-					const SortScratch sc = { b.sort_s + off + lo, b.sort_perm + off + lo, b.sort_tmp + off + lo };
-					sort_like_host<ZElem, true>(z + lo, hi - lo, L, b.dbg, &sc);
-				}
-				__threadfence_block();
-				__syncthreads();
-			} else if (w == 0) { const SortScratch sc = { b.sort_s + off, b.sort_perm + off, b.sort_tmp + off }; sort_like_host<ZElem, true>(z, n_z, L, b.dbg, &sc); }
-			if (w == 0) { walker = true; team_r = r; team_nz = n_z; }
-		} else if (w == 0) solo_q = q;                       // not a team read (any more): wave 0's first read, on its own
-	}
-	for (bool first = true;; first = false) {
-		int r = 0, n_z = 0;
-		const bool team = first && walker;
-		if (team) { r = team_r; n_z = team_nz; }
-		else {
-			if (first && solo_q >= 0) r = solo_q;
-			else { if (l == 0) r = atomicAdd(b.cursor, 1); r = uni(r); }
-			if (r >= b.n_reads) break;
-			r = uni(b.order[r]);
-		}
-		const int64_t off = b.offsets[r];
-		const int n = (int)(b.offsets[r + 1] - off);
-		const int32_t *f = b.f + off;
-		unsigned long long *z = b.z + off;
-		int2 *fp = b.fp + off;
-		int32_t *picked = b.picked + off;
-		unsigned long long *u_tmp = b.u_tmp + chain_slot(off, r, mc);
-		const long long t0 = b.dbg ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
-		long long t1 = t0, t2 = t0;
-		if (!team) {
-			unsigned any = 0, all = ~0u;
-			n_z = post_collect(b, f, z, 0, n, 0, true, any, all);
-			wave_sync();
-			t1 = b.dbg ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
-			const SortScratch sc = { b.sort_s + off, b.sort_perm + off, b.sort_tmp + off };
-			sort_like_host<ZElem, true>(z, n_z, L, b.dbg, &sc);
-			t2 = b.dbg ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
-		}
-		if constexpr (SORT_ONLY) {
-			if (l == 0) {
-				b.read_nz[r] = n_z;
-				if (b.dbg) {
-					if (b.dbg_reads) { b.dbg_reads[4 * r] = t0; b.dbg_reads[4 * r + 1] = t1; b.dbg_reads[4 * r + 2] = t2; b.dbg_reads[4 * r + 3] = team ? (long long)__builtin_amdgcn_s_memrealtime() : t2; }
-					atomicAdd((unsigned long long*)&b.dbg[0], (unsigned long long)(t1 - t0));
-					atomicAdd((unsigned long long*)&b.dbg[1], (unsigned long long)(t2 - t1));
-					atomicMax((unsigned long long*)&b.dbg[4], (unsigned long long)(t2 - t1));
-					atomicAdd((unsigned long long*)&b.dbg[12], (unsigned long long)n_z);
-				}
-			}
-			wave_sync();
-			continue;
-		}
-		int n_u = 0, n_v = 0;
-		WalkDbg wd;
-		// the marks of the walks: a bit per anchor in this wave's LDS (the sort is done with it) when the read fits
-		constexpr int MARK_WORDS = (int)(sizeof(PassLds) / 4);
-		unsigned *bits = n <= MARK_WORDS * 32 && !POST_MARKS_IN_MEMORY ? (unsigned*)&L : nullptr;
-		if (bits) { wave_sync(); for (int k = l; k < (n + 31) / 32; k += W) bits[k] = 0; wave_sync(); }
-		post_walk_read(b, off, n_z, z, fp, picked, u_tmp, n_u, n_v, wd, bits);
-		wave_sync();
-		if (l == 0) {
-			b.n_u[r] = n_u;
-			b.n_kept[r] = n_v;
-			if (b.dbg) {
-				const long long t3 = (long long)__builtin_amdgcn_s_memrealtime();
-				if (b.dbg_reads) { b.dbg_reads[4 * r] = t0; b.dbg_reads[4 * r + 1] = t1; b.dbg_reads[4 * r + 2] = t2; b.dbg_reads[4 * r + 3] = t3; }
-				atomicAdd((unsigned long long*)&b.dbg[0], (unsigned long long)(t1 - t0));
-				atomicAdd((unsigned long long*)&b.dbg[1], (unsigned long long)(t2 - t1));
-				atomicAdd((unsigned long long*)&b.dbg[2], (unsigned long long)(t3 - t2));
-				atomicMax((unsigned long long*)&b.dbg[4], (unsigned long long)(t2 - t1));
-				atomicMax((unsigned long long*)&b.dbg[5], (unsigned long long)(t3 - t2));
-				atomicMax((unsigned long long*)&b.dbg[6], (unsigned long long)(t3 - t0));
-				atomicAdd((unsigned long long*)&b.dbg[7], (unsigned long long)wd.load);
-				atomicAdd((unsigned long long*)&b.dbg[8], (unsigned long long)wd.longt);
-				atomicAdd((unsigned long long*)&b.dbg[9], (unsigned long long)wd.groups);
-				atomicAdd((unsigned long long*)&b.dbg[10], (unsigned long long)wd.open);
-				atomicAdd((unsigned long long*)&b.dbg[11], (unsigned long long)wd.nlong);
-				atomicAdd((unsigned long long*)&b.dbg[12], (unsigned long long)n_z);
-				atomicAdd((unsigned long long*)&b.dbg[20], (unsigned long long)wd.iters);
-			}
-		}
-		wave_sync();
-	}
-}
-
-__global__ __launch_bounds__(POST_THREADS, POST_WAVES_PER_SIMD) void k_post_chains(PostBatch b, int team_reads) { post_chains_body<false>(b, team_reads); }
-__global__ __launch_bounds__(POST_THREADS, POST_WAVES_PER_SIMD) void k_post_sort(PostBatch b, int team_reads) { post_chains_body<true>(b, team_reads); }
 
 // --------------------------------------------------------------------------------------------------------------
 // The sort by levels (round 6).  A read's candidates are collected in index order (lchain.c:35-41) by the pass over its anchors that also gives
@@ -1614,7 +1413,6 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_classes(PostBatch b)
 		const int32_t *p = b.p + off, *f = b.f + off;
 		unsigned char *cls = b.cls + off;
 		// the same pass collects the read's candidates for the sort by levels (lchain.c:35-41: z[k] = (f[i], i) for f[i] >= min_sc, in index order)
-		const bool collect = b.stask[0] != nullptr;
 		unsigned long long *z = b.z + off;
 		int n_z = 0;
 		unsigned any = 0, all = ~0u;
@@ -1625,13 +1423,13 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_classes(PostBatch b)
 		// not -- and a wait for loads that were issued BEFORE the last blocks' stores does not wait for those stores)
 		int pn4[4], fn4[4];
 #pragma unroll
-		for (int u = 0; u < 4; ++u) { pn4[u] = u * W + l < n ? p[u * W + l] : 0; fn4[u] = collect && u * W + l < n ? f[u * W + l] : INT_MIN; }
+		for (int u = 0; u < 4; ++u) { pn4[u] = u * W + l < n ? p[u * W + l] : 0; fn4[u] = u * W + l < n ? f[u * W + l] : INT_MIN; }
 		for (int base0 = 0; base0 < n; base0 += 4 * W) {
 		int pl4[4], fl4[4];
 #pragma unroll
 		for (int u = 0; u < 4; ++u) { pl4[u] = pn4[u]; fl4[u] = fn4[u]; }
 #pragma unroll
-		for (int u = 0; u < 4; ++u) { const int i2 = base0 + (4 + u) * W + l; pn4[u] = i2 < n ? p[i2] : 0; fn4[u] = collect && i2 < n ? f[i2] : INT_MIN; }
+		for (int u = 0; u < 4; ++u) { const int i2 = base0 + (4 + u) * W + l; pn4[u] = i2 < n ? p[i2] : 0; fn4[u] = i2 < n ? f[i2] : INT_MIN; }
 #pragma unroll
 		for (int u = 0; u < 4; ++u) {
 			const int base = base0 + u * W;
@@ -1659,7 +1457,7 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_classes(PostBatch b)
 			if (in) { cls[i] = (unsigned char)c; ring[i & (CLS_RING - 1)] = (unsigned char)c; atomicAdd(&cnt[c], 1); }
 			lds_sync();
 			const int fi = fl4[u];
-			const bool take = in && fi >= b.min_sc;                // (never when nothing is collected: fl4 is INT_MIN then)
+			const bool take = in && fi >= b.min_sc;
 			const unsigned long long m = __ballot(take);
 			if (take) { any |= (unsigned)fi; all &= (unsigned)fi; z[n_z + __popcll(m & ((1ull << l) - 1))] = (unsigned long long)(unsigned)fi << 32 | (unsigned)i; }
 			n_z += __popcll(m);
@@ -1667,44 +1465,42 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_classes(PostBatch b)
 		}
 		wave_sync();
 		if (l < N_TREE_CLASSES) b.cls_cnt[(int64_t)r * N_TREE_CLASSES + l] = cnt[l];
-		if (collect) {
-			for (int o = W / 2; o > 0; o >>= 1) { any |= __shfl_xor(any, o); all &= __shfl_xor(all, o); }
-			if (l == 0) {
-				b.read_nz[r] = n_z;
-				if (b.dbg) { atomicAdd((unsigned long long*)&b.dbg[0], (unsigned long long)((long long)__builtin_amdgcn_s_memrealtime() - t0)); atomicAdd((unsigned long long*)&b.dbg[12], (unsigned long long)n_z); }
-			}
-			const unsigned diff = uni((int)(any ^ all));
-			if (n_z > SMALL_RUN) {
-				if (diff != 0) {
-					int top = 24;                                  // of the key = the score: byte 3 .. 0 (sort_like_host's `top`)
-					while (top > 0 && ((diff >> top) & 255u) == 0) top -= 8;
-					// A long read's top pass right here: its scores take two to four values of their highest byte that differs, and such a pass
-					// needs nothing of the sort's LDS but a histogram (radix_pass_bytes_t<true>: positions in scalar registers, bytes across the
-					// lanes) -- the wave that collected the candidates has them in its caches, and the pass does not wait for the whole batch's
-					// classes.  Its buckets are tasks of the SECOND level; a run that is not of that kind becomes a first-level task as before.
-					int status = 2, shift = top;
-					FewBuckets fb;
-					if (n_z > LINE_STORE_BYTES) {
-						wave_sync();
-						const SortScratch sc = { b.sort_s + off, b.sort_perm + off, b.sort_tmp + off };
-						for (status = 0; shift >= 0 && status == 0; shift -= 8) { fb.n = 0; status = radix_pass_bytes_t<true>(z, 0, n_z, shift, nullptr, s_ring[w], sc, b.dbg ? b.dbg + 24 : nullptr, nullptr, &fb); }
-						// (shift is one byte below the pass that ran last)
-					}
-					if (status == 1) {
-						if (shift >= 0) {
+		for (int o = W / 2; o > 0; o >>= 1) { any |= __shfl_xor(any, o); all &= __shfl_xor(all, o); }
+		if (l == 0) {
+			b.read_nz[r] = n_z;
+			if (b.dbg) { atomicAdd((unsigned long long*)&b.dbg[0], (unsigned long long)((long long)__builtin_amdgcn_s_memrealtime() - t0)); atomicAdd((unsigned long long*)&b.dbg[12], (unsigned long long)n_z); }
+		}
+		const unsigned diff = uni((int)(any ^ all));
+		if (n_z > SMALL_RUN) {
+			if (diff != 0) {
+				int top = 24;                                  // of the key = the score: byte 3 .. 0 (sort_like_host's `top`)
+				while (top > 0 && ((diff >> top) & 255u) == 0) top -= 8;
+				// A long read's top pass right here: its scores take two to four values of their highest byte that differs, and such a pass
+				// needs nothing of the sort's LDS but a histogram (radix_pass_bytes_t<true>: positions in scalar registers, bytes across the
+				// lanes) -- the wave that collected the candidates has them in its caches, and the pass does not wait for the whole batch's
+				// classes.  Its buckets are tasks of the SECOND level; a run that is not of that kind becomes a first-level task as before.
+				int status = 2, shift = top;
+				FewBuckets fb;
+				if (n_z > LINE_STORE_BYTES) {
+					wave_sync();
+					const SortScratch sc = { b.sort_s + off, b.sort_perm + off, b.sort_tmp + off };
+					for (status = 0; shift >= 0 && status == 0; shift -= 8) { fb.n = 0; status = radix_pass_bytes_t<true>(z, 0, n_z, shift, nullptr, s_ring[w], sc, b.dbg ? b.dbg + 24 : nullptr, nullptr, &fb); }
+					// (shift is one byte below the pass that ran last)
+				}
+				if (status == 1) {
+					if (shift >= 0) {
 #pragma unroll
-							for (int j = 0; j < 4; ++j) {
-								if (j < fb.n) {
-									const int first = fb.start[j], n_j = fb.end[j] - fb.start[j];
-									if (n_j > SMALL_RUN) { if (l == 0) b.stask[1][atomicAdd(b.cursor + 9, 1)] = make_int4(r, first, n_j, shift); }
-									else if (n_j > 1) small_run_sort<ZElem>(z, first, n_j);
-								}
+						for (int j = 0; j < 4; ++j) {
+							if (j < fb.n) {
+								const int first = fb.start[j], n_j = fb.end[j] - fb.start[j];
+								if (n_j > SMALL_RUN) { if (l == 0) b.stask[1][atomicAdd(b.cursor + 9, 1)] = make_int4(r, first, n_j, shift); }
+								else if (n_j > 1) small_run_sort<ZElem>(z, first, n_j);
 							}
 						}
-					} else if (status == 2) { if (l == 0) b.stask[0][atomicAdd(b.cursor + 8, 1)] = make_int4(r, 0, n_z, n_z > LINE_STORE_BYTES ? shift + 8 : top); }
-				}
-			} else if (n_z > 1) small_run_sort<ZElem>(z, 0, n_z);
-		}
+					}
+				} else if (status == 2) { if (l == 0) b.stask[0][atomicAdd(b.cursor + 8, 1)] = make_int4(r, 0, n_z, n_z > LINE_STORE_BYTES ? shift + 8 : top); }
+			}
+		} else if (n_z > 1) small_run_sort<ZElem>(z, 0, n_z);
 		wave_sync();
 	}
 }
@@ -1813,11 +1609,10 @@ __global__ __launch_bounds__(POST_THREADS, MM2GB_WALK_WAVES_PER_SIMD) void k_pos
 		const int n_zc = b.cls_nz[(int64_t)r * N_TREE_CLASSES + c];
 		const int64_t slot0 = chain_slot(off, r, mc);
 		const long long t0 = b.dbg ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
-		WalkSplit what;
-		what.kp = b.kpos + off + sub; what.endslot = (int32_t*)(b.z + off); what.u_loc = b.u_loc + slot0 + usub; what.picked_base = sub; what.slot_base = usub;
+		const WalkSplit what = { b.kpos + off + sub, (int32_t*)(b.z + off), b.u_loc + slot0 + usub, sub, usub };
 		int n_u = 0, n_v = 0;
 		WalkDbg wd;
-		post_walk_read(b, off, n_zc, b.zc + off + sub, b.fp + off, b.picked + off + sub, b.u_tmp + slot0 + usub, n_u, n_v, wd, nullptr, what);
+		post_walk_read(b, off, n_zc, b.zc + off + sub, b.fp + off, b.picked + off + sub, b.u_tmp + slot0 + usub, n_u, n_v, wd, what);
 		wave_sync();
 		if (l == 0) {
 			if (n_u) atomicAdd(&b.n_u[r], n_u);
@@ -1894,42 +1689,28 @@ __global__ __launch_bounds__(POST_THREADS) void k_post_emit(PostBatch b)
 		ulonglong2 *heads = b.heads + chain_slot(off, r, mc);
 		unsigned long long *u_out = b.u_out + b.u_off[r];
 		uint4 *a_out = b.a_out + b.a_off[r];
-		// (x of the chain's first anchor, offset << 32 | chain): the first anchor is the last one picked (lchain.c:88-99)
+		// (x of the chain's first anchor, offset << 32 | chain): the first anchor is the last one picked (lchain.c:88-99).  The chains in the order
+		// the host finds them = the candidates from the best one down; endslot[] says which of them ended a chain that was kept, and where
+		// k_post_walk left it (its slot in u_tmp / u_loc; u_loc: its anchors in picked)
 		int k_at = 0;
-		if (b.cls) {
-			// split form: the chains in the order the host finds them = the candidates from the best one down; endslot[] says which of them ended a
-			// chain that was kept, and where k_post_walk left it (its slot in u_tmp / u_loc; u_loc: its anchors in picked)
-			const int32_t *endslot = (const int32_t*)(b.z + off);
-			const int32_t *u_loc = b.u_loc + chain_slot(off, r, mc);
-			const int n_z = b.read_nz[r];
-			for (int kb = n_z - 1; kb >= 0; kb -= 4 * W) {
-				int slot[4];
+		const int32_t *endslot = (const int32_t*)(b.z + off);
+		const int32_t *u_loc = b.u_loc + chain_slot(off, r, mc);
+		const int n_z = b.read_nz[r];
+		for (int kb = n_z - 1; kb >= 0; kb -= 4 * W) {
+			int slot[4];
 #pragma unroll
-				for (int q = 0; q < 4; ++q) { const int k = kb - q * W - l; slot[q] = k >= 0 ? endslot[k] : -1; }
+			for (int q = 0; q < 4; ++q) { const int k = kb - q * W - l; slot[q] = k >= 0 ? endslot[k] : -1; }
 #pragma unroll
-				for (int q = 0; q < 4; ++q) {
-					const unsigned long long m = __ballot(slot[q] >= 0);
-					if (slot[q] >= 0) {
-						const int c = k_at + __popcll(m & ((1ull << l) - 1));
-						const int cnt = (int)(unsigned)u_tmp[slot[q]], k0 = u_loc[slot[q]];
-						const uint4 first = raw[picked[k0 + cnt - 1]];
-						heads[c] = make_ulonglong2((unsigned long long)first.y << 32 | first.x, (unsigned long long)(unsigned)k0 << 32 | (unsigned)slot[q]);
-					}
-					k_at += __popcll(m);
+			for (int q = 0; q < 4; ++q) {
+				const unsigned long long m = __ballot(slot[q] >= 0);
+				if (slot[q] >= 0) {
+					const int c = k_at + __popcll(m & ((1ull << l) - 1));
+					const int cnt = (int)(unsigned)u_tmp[slot[q]], k0 = u_loc[slot[q]];
+					const uint4 first = raw[picked[k0 + cnt - 1]];
+					heads[c] = make_ulonglong2((unsigned long long)first.y << 32 | first.x, (unsigned long long)(unsigned)k0 << 32 | (unsigned)slot[q]);
 				}
+				k_at += __popcll(m);
 			}
-		} else
-		for (int base = 0; base < n_u; base += W) {
-			const int c = base + l;
-			const int cnt = c < n_u ? (int)(unsigned)u_tmp[c] : 0;
-			int inc = cnt;
-			for (int o = 1; o < W; o <<= 1) { const int v = __shfl_up(inc, o); if (l >= o) inc += v; }
-			const int k0 = k_at + inc - cnt;
-			if (c < n_u) {
-				const uint4 first = raw[picked[k0 + cnt - 1]];
-				heads[c] = make_ulonglong2((unsigned long long)first.y << 32 | first.x, (unsigned long long)(unsigned)k0 << 32 | (unsigned)c);
-			}
-			k_at += __builtin_amdgcn_readlane(inc, W - 1);
 		}
 		wave_sync();
 		sort_like_host<HElem>(heads, n_u, L);
@@ -3770,7 +3551,7 @@ void launch_gen_regs(const RegBatch &b, hipStream_t s)
 	hipLaunchKernelGGL(k_gen_regs, dim3(grid), dim3(POST_THREADS), 0, s, b);
 }
 
-void launch_post(const PostBatch &b, hipStream_t s, hipStream_t aux, hipEvent_t fork, hipEvent_t join)
+void launch_post(const PostBatch &b, int n_cu, hipStream_t s, hipStream_t aux, hipEvent_t fork, hipEvent_t join)
 {
 	if (b.n_reads <= 0) return;
 	// MM2GB_DEBUG_LAUNCH=1: wait after every launch and say which one it was (finding a kernel that does not come back)
@@ -3782,47 +3563,41 @@ void launch_post(const PostBatch &b, hipStream_t s, hipStream_t aux, hipEvent_t 
 	hipLaunchKernelGGL(k_post_size_count, dim3(rgrid), dim3(256), 0, s, b); done("k_post_size_count");
 	hipLaunchKernelGGL(k_post_size_bases, dim3(1), dim3(64), 0, s, b); done("k_post_size_bases");
 	hipLaunchKernelGGL(k_post_size_scatter, dim3(rgrid), dim3(256), 0, s, b); done("k_post_size_scatter");
-	const int64_t waves = (int64_t)b.grid_waves;
-	unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b.n_reads + POST_THREADS / W - 1) / (POST_THREADS / W), (waves + POST_THREADS / W - 1) / (POST_THREADS / W)));
-	if (b.team_reads > 0) grid = (unsigned)std::max<int64_t>(grid, std::min<int64_t>(b.team_reads, (waves + POST_THREADS / W - 1) / (POST_THREADS / W)));   // a workgroup per team read
+	// the per-read kernels: one read per wave, at most grid_waves waves; a batch of at most three reads per CU gets a workgroup per read
+	const int64_t read_wgs = b.n_reads <= (int64_t)n_cu * 3 ? b.n_reads : (b.n_reads + POST_THREADS / W - 1) / (POST_THREADS / W);
+	const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(read_wgs, ((int64_t)b.grid_waves + POST_THREADS / W - 1) / (POST_THREADS / W)));
 	const unsigned lgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b.n + 255) / 256, 256 * 64));
-	// split form: only the WALKS need the lifting tables and the walks' records -- where a second stream is given, the two passes that make them
+	// only the WALKS need the lifting tables and the walks' records -- where a second stream is given, the two passes that make them
 	// (bandwidth: 24 bytes per anchor) run beside the classes' pass and the sort (waves that wait for LDS and for each other: the sort's levels
 	// end with a few long tasks and an idle chip)
-	const bool beside = b.cls && aux && fork && join && !step && hipEventRecord(fork, s) == hipSuccess && hipStreamWaitEvent(aux, fork, 0) == hipSuccess;
+	const bool beside = aux && fork && join && !step && hipEventRecord(fork, s) == hipSuccess && hipStreamWaitEvent(aux, fork, 0) == hipSuccess;
 	{
 		hipStream_t ls = beside ? aux : s;
 		hipLaunchKernelGGL(k_post_lift, dim3(lgrid), dim3(256), 0, ls, b, 0); done("k_post_lift");
 		hipLaunchKernelGGL(k_post_lift, dim3(lgrid), dim3(256), 0, ls, b, 1); done("k_post_lift");
 		if (beside) (void)hipEventRecord(join, aux);
 	}
-	if (b.cls) {
-		// split form (round 6): sort | classes of the trees | candidates dealt to their classes | walks per (read, class)
-		(void)hipMemsetAsync(b.n_u, 0, (size_t)b.n_reads * sizeof(int32_t), s);
-		(void)hipMemsetAsync(b.n_kept, 0, (size_t)b.n_reads * sizeof(int32_t), s);
-		hipLaunchKernelGGL(k_post_classes, dim3(grid), dim3(POST_THREADS), 0, s, b); done("k_post_classes");
-		if (b.stask[0]) {
-			for (int level = 0; level < 4; ++level) {           // key bytes 3 .. 0 of the score
-				(void)hipMemsetAsync(b.size_bins, 0, 2 * N_SIZE_CLASSES * sizeof(int32_t), s);
-				hipLaunchKernelGGL(k_post_stask_count, dim3(256), dim3(256), 0, s, b, level); done("k_post_stask_count");
-				hipLaunchKernelGGL(k_post_size_bases, dim3(1), dim3(64), 0, s, b); done("k_post_size_bases");
-				hipLaunchKernelGGL(k_post_stask_scatter, dim3(256), dim3(256), 0, s, b, level); done("k_post_stask_scatter");
-				hipLaunchKernelGGL(k_post_sort_level, dim3((unsigned)std::max<int64_t>(1, ((int64_t)b.grid_waves + POST_THREADS / W - 1) / (POST_THREADS / W))), dim3(POST_THREADS), 0, s, b, level); done("k_post_sort_level");
-			}
-		} else
-		hipLaunchKernelGGL(k_post_sort, dim3(grid), dim3(POST_THREADS), 0, s, b, b.team_reads); done("k_post_sort");
-		hipLaunchKernelGGL(k_post_partition, dim3(grid), dim3(POST_THREADS), 0, s, b); done("k_post_partition");
+	// sort | classes of the trees | candidates dealt to their classes | walks per (read, class)
+	(void)hipMemsetAsync(b.n_u, 0, (size_t)b.n_reads * sizeof(int32_t), s);
+	(void)hipMemsetAsync(b.n_kept, 0, (size_t)b.n_reads * sizeof(int32_t), s);
+	hipLaunchKernelGGL(k_post_classes, dim3(grid), dim3(POST_THREADS), 0, s, b); done("k_post_classes");
+	for (int level = 0; level < 4; ++level) {                   // key bytes 3 .. 0 of the score
 		(void)hipMemsetAsync(b.size_bins, 0, 2 * N_SIZE_CLASSES * sizeof(int32_t), s);
-		const unsigned tgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b.n_reads * N_TREE_CLASSES + 255) / 256, 512));
-		hipLaunchKernelGGL(k_post_task_count, dim3(tgrid), dim3(256), 0, s, b); done("k_post_task_count");
+		hipLaunchKernelGGL(k_post_stask_count, dim3(256), dim3(256), 0, s, b, level); done("k_post_stask_count");
 		hipLaunchKernelGGL(k_post_size_bases, dim3(1), dim3(64), 0, s, b); done("k_post_size_bases");
-		hipLaunchKernelGGL(k_post_task_scatter, dim3(tgrid), dim3(256), 0, s, b); done("k_post_task_scatter");
-		if (beside) (void)hipStreamWaitEvent(s, join, 0);            // the tables are there
-		const int64_t wwaves = std::max<int64_t>(b.walk_grid_waves, 4);
-		const unsigned wgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b.n_reads * N_TREE_CLASSES + POST_THREADS / W - 1) / (POST_THREADS / W), (wwaves + POST_THREADS / W - 1) / (POST_THREADS / W)));
-		hipLaunchKernelGGL(k_post_walk, dim3(wgrid), dim3(POST_THREADS), 0, s, b); done("k_post_walk");
-	} else
-	hipLaunchKernelGGL(k_post_chains, dim3(grid), dim3(POST_THREADS), 0, s, b, b.team_reads); done("k_post_chains");
+		hipLaunchKernelGGL(k_post_stask_scatter, dim3(256), dim3(256), 0, s, b, level); done("k_post_stask_scatter");
+		hipLaunchKernelGGL(k_post_sort_level, dim3((unsigned)std::max<int64_t>(1, ((int64_t)b.grid_waves + POST_THREADS / W - 1) / (POST_THREADS / W))), dim3(POST_THREADS), 0, s, b, level); done("k_post_sort_level");
+	}
+	hipLaunchKernelGGL(k_post_partition, dim3(grid), dim3(POST_THREADS), 0, s, b); done("k_post_partition");
+	(void)hipMemsetAsync(b.size_bins, 0, 2 * N_SIZE_CLASSES * sizeof(int32_t), s);
+	const unsigned tgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b.n_reads * N_TREE_CLASSES + 255) / 256, 512));
+	hipLaunchKernelGGL(k_post_task_count, dim3(tgrid), dim3(256), 0, s, b); done("k_post_task_count");
+	hipLaunchKernelGGL(k_post_size_bases, dim3(1), dim3(64), 0, s, b); done("k_post_size_bases");
+	hipLaunchKernelGGL(k_post_task_scatter, dim3(tgrid), dim3(256), 0, s, b); done("k_post_task_scatter");
+	if (beside) (void)hipStreamWaitEvent(s, join, 0);                // the tables are there
+	const int64_t wwaves = std::max<int64_t>(b.walk_grid_waves, 4);
+	const unsigned wgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((b.n_reads * N_TREE_CLASSES + POST_THREADS / W - 1) / (POST_THREADS / W), (wwaves + POST_THREADS / W - 1) / (POST_THREADS / W)));
+	hipLaunchKernelGGL(k_post_walk, dim3(wgrid), dim3(POST_THREADS), 0, s, b); done("k_post_walk");
 	hipLaunchKernelGGL(k_post_scan, dim3(1), dim3(1024), 0, s, b); done("k_post_scan");
 	hipLaunchKernelGGL(k_post_emit, dim3(grid), dim3(POST_THREADS), 0, s, b); done("k_post_emit");
 }

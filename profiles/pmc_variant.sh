@@ -1,8 +1,8 @@
 # usage: bash profiles/pmc_variant.sh NAME [path/to/lib.so]   -> gpurun_out/pmc_NAME/{sq1,sq2}/...
 set -u
 NAME=$1; [ $# -ge 2 ] && export MM2GB_LIB_PATH=$2
-# KERNEL: which instantiation to report -- batches of up to 150 M anchors launch k_score<0, false, true> (the gang build); fails loudly when no row matches
-KERNEL=${KERNEL:-"k_score<0, false,"}
+# KERNEL: which instantiation to report -- batches of up to 150 M anchors launch k_score<0, true> (the gang build); fails loudly when no row matches
+KERNEL=${KERNEL:-"k_score<0, "}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$NAME; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 run() { local name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -- python3 "$GRAFT_REPO_ROOT/bench.py" --anchors ${ANCHORS:-500000000} --steps 1 --warmup 1 --cpu-seconds 0 --no-pcie --no-e2e --no-bins --no-post --no-config2 > "$OUT/$name.log" 2>&1; }
 run sq1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_INSTS_BRANCH

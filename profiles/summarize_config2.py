@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 import bench as bench_mod  # noqa: E402
 tag = sys.argv[1]
 G = os.path.join(ROOT, "gpurun_out", f"config2_{tag}")
-KERNEL = "k_score<0, false, false>"
+KERNEL = "k_score<0, false>"
 
 
 def one(pattern):

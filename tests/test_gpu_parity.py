@@ -614,11 +614,10 @@ def test_unchecked_sweep_rejects_what_the_range_test_would(monkeypatch, kw):
         check_batch(e, a, off, prm)
 
 
-def test_edge_blocks_with_the_window_test_from_a_prefix_mask(monkeypatch):
-    """MM2GB_EDGE=new (off by default: profiles/r06_narrow_ab.txt): edge blocks of tiles whose window starts rise from lane to lane take "source inside this
-    target's window" from a scalar prefix mask per source instead of a vector compare (chain_kernels.hip, sweep_block_lut_edge_sorted).  Narrow windows --
-    every block of a 60-anchor window is an edge block --, several reads per chunk (starts jump), runs of equal positions, and the dense clouds of the
-    test above: same f / p as the default build, and both equal the oracle's."""
+def test_narrow_window_reads_made_of_edge_blocks(monkeypatch):
+    """Edge blocks (chain_kernels.hip, sweep_block_lut_edge): narrow windows -- every block of a 60-anchor window is an edge block --,
+    several reads per chunk (starts jump), runs of equal positions, and the dense clouds of the test above: equal to the oracle's f / p
+    with the team modes and with every chunk on one wave."""
     a1, o1 = mm.synth_reads(71, 0, 60, 10_000, 30_000)
     parts = [a1[o1[r]:o1[r + 1]] for r in range(60)]
     parts += [band_cloud(9000, 321, xwin=9000, jitter=700), band_cloud(6000, 323, xwin=900, jitter=250, r0=7_000_000), sc.read_like(9000, 324),
@@ -627,17 +626,11 @@ def test_edge_blocks_with_the_window_test_from_a_prefix_mask(monkeypatch):
     off[1:] = np.cumsum([len(x) for x in parts])
     a = np.concatenate(parts)
     prm = orc.default_param()
-    with mm.Engine() as e:
-        check_batch(e, a, off, prm)
-        f0, p0, _ = e.score(a, off)
-    monkeypatch.setenv("MM2GB_EDGE", "new")
     for no_coop in (False, True):
         if no_coop:
             monkeypatch.setenv("MM2GB_NO_COOP", "1")                  # every chunk by one wave
         with mm.Engine() as e:
             check_batch(e, a, off, prm)
-            f1, p1, _ = e.score(a, off)
-        assert np.array_equal(f0, f1) and np.array_equal(p0, p1)
 
 
 def test_without_the_lds_contract_the_checked_builds_run(monkeypatch):
@@ -652,16 +645,10 @@ def test_without_the_lds_contract_the_checked_builds_run(monkeypatch):
 
 
 @pytest.mark.timeout(300)
-def test_one_chunk_on_several_workgroups(monkeypatch):
-    """A batch too small to fill the GPU ends with its largest chunk, which one workgroup scores at the pace of one CU.  In micro-batches
-    of up to MM2GB_SPLIT_MAX_ANCHORS anchors (0 = never, the default: the build is exact but measured slower) such chunks
-    are scored strip by strip (1 024 anchors), the sweeps over the sources before a strip cut into items that idle workgroups take
-    (chain_kernels.hip, split_chunk).  Heavy chunks of every kind -- windows cut by max_iter (the rescue state machine runs), wide and
-    narrow windows, a chunk that ends inside a strip, several owners at once -- against the oracle, every chunk of the big-team list
-    split (MM2GB_WHOLE_WG_PCT=1), and against the same batch with the build switched off."""
-    if not mm.lib().mm2gb_has_split_build():
-        pytest.skip("the SPLIT instantiation of k_score is a build option (make -C mm2-gb_amd SPLIT=1): exact, measured slower, not in the default library")
-    monkeypatch.setenv("MM2GB_SPLIT_MAX_ANCHORS", "200000000")
+def test_heavy_chunks_of_a_batch_too_small_to_fill_the_gpu(monkeypatch):
+    """A batch too small to fill the GPU ends with its largest chunks.  Heavy chunks of every kind -- windows cut by max_iter (the rescue
+    state machine runs), wide and narrow windows, a chunk that ends inside a strip of 1 024 anchors, several of them at once -- against the
+    oracle, repeated runs giving the same results, and every chunk of the big-team list on a whole workgroup (MM2GB_WHOLE_WG_PCT=1)."""
     parts = [sc.sort_by_x(np.concatenate([sc.repeat_block(23000, 401, xwin=4500, ywin=7000), sc.colinear(900, 402)])),
              sc.sort_by_x(sc.repeat_block(9000, 403, xwin=9000, ywin=9000, r0=4_000_000)),
              band_cloud(12345, 404, xwin=11000, jitter=800), sc.read_like(9000, 405),
@@ -672,11 +659,9 @@ def test_one_chunk_on_several_workgroups(monkeypatch):
     a = np.concatenate(parts)
     prm = orc.default_param()
     with mm.Engine() as e:
-        st = check_batch(e, a, off, prm)
+        check_batch(e, a, off, prm)
         f1, p1, _ = e.score(a, off)
-        chunks, helped = e.split_counts()
-        assert chunks >= 3 and helped > 0, (chunks, helped, st)
-        for _ in range(5):                                            # who takes which item changes from run to run; the results must not
+        for _ in range(5):                                            # which workgroup takes which work changes from run to run; the results must not
             f2, p2, _ = e.score(a, off)
             assert np.array_equal(f1, f2) and np.array_equal(p1, p2)
         check_batch(e, a, off, orc.default_param(max_iter=700))
@@ -685,12 +670,6 @@ def test_one_chunk_on_several_workgroups(monkeypatch):
     with mm.Engine() as e:
         for _ in range(3):
             check_batch(e, a, off, prm)
-    monkeypatch.delenv("MM2GB_WHOLE_WG_PCT")
-    monkeypatch.delenv("MM2GB_SPLIT_MAX_ANCHORS")
-    with mm.Engine() as e:
-        f0, p0, _ = e.score(a, off)
-        assert e.split_counts() == (0, 0)
-    assert np.array_equal(f0, f1) and np.array_equal(p0, p1)
 
 
 @pytest.mark.timeout(300)
