@@ -247,7 +247,8 @@ int  mm2gb_gen_regs_gpu(mm2gb_engine_t *eng, int64_t n_reads, const mm2gb_chains
  *      (index.c:81-98, 213-262); mid_occ as mm_mapopt_update computes it (options.c:78-84, index.c:186-211);
  *      mm2gb_collect_matches: mm_collect_matches (seed.c:98-131, with seed.c:5-96) for one read of one segment: the arrays
  *      mm2gb_collect_seeds_gpu takes, plus rep_len and the minimizer positions the host's mapq / divergence estimates use.
- *      Free a matches record with mm2gb_matches_free, a sketch with mm2gb_free. ---- */
+ *      Free a matches record with mm2gb_matches_free, a sketch with mm2gb_free.  Sketch, look-up and match collection have a device
+ *      form too (below: mm2gb_sketch_gpu, mm2gb_collect_matches_gpu); building the index and mid_occ are the host's. ---- */
 typedef struct mm2gb_index mm2gb_index_t;
 typedef struct { int32_t mid_occ, max_max_occ, occ_dist; float q_occ_frac; } mm2gb_seed_opt_t;   /* mm_mapopt_t: mid_occ, max_max_occ, occ_dist, q_occ_frac */
 typedef struct {
@@ -268,6 +269,30 @@ int  mm2gb_collect_seeds_host(int64_t opt_flag, int64_t n_reads, const int64_t *
 int  mm2gb_collect_matches(const mm2gb_index_t *ix, const char *seq, int32_t len, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out);
 void mm2gb_matches_free(mm2gb_matches_t *m);
 
+/* ---- the same stages on the device (csrc/seed_kernels.hip), byte-identical to the host functions above, for a batch of sequences laid
+ *      end to end (seq_off: n + 1 entries, seq_off[0] = 0, fewer than 2^31 bases in all):
+ *      mm2gb_sketch_gpu: for sequence r exactly the pairs mm2gb_sketch(seqs + seq_off[r], len_r, w, k, rid ? rid[r] : 0) returns, in its
+ *      order; mini_off (n_seqs + 1) says where each sequence's pairs begin in *out_xy (malloc'd, free with mm2gb_free);
+ *      mm2gb_index_to_device: the index's copy in a device's memory (keys, first, where, bucket as they are); made on first use otherwise,
+ *      released by mm2gb_index_destroy;
+ *      mm2gb_collect_matches_gpu: for read r, seeds[seed_off[r] .. seed_off[r+1]), their hits, mini_pos and rep_len[r] are what
+ *      mm2gb_collect_matches(ix, read r, opt) returns.  Free the batch with mm2gb_match_batch_free. ---- */
+int  mm2gb_sketch_gpu(mm2gb_engine_t *eng, int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs,
+                      const uint32_t *rid, int64_t *mini_off, uint64_t **out_xy);
+int  mm2gb_index_to_device(mm2gb_index_t *ix, int device);
+typedef struct {
+	int64_t n_seeds, n_hits;
+	int64_t *seed_off;        /* n_reads + 1 */
+	mm2gb_seed_t *seeds;      /* n_seeds, read by read */
+	int64_t *hit_off;         /* n_seeds + 1 */
+	uint64_t *hits;           /* n_hits */
+	uint64_t *mini_pos;       /* n_seeds: as mm2gb_matches_t::mini_pos */
+	int32_t *rep_len;         /* n_reads */
+} mm2gb_match_batch_t;
+int  mm2gb_collect_matches_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_reads,
+                               const int64_t *seq_off, const char *seqs, mm2gb_match_batch_t *out);
+void mm2gb_match_batch_free(mm2gb_match_batch_t *m);
+
 /* ---- reads in, PAF out (csrc/mapper.cpp): seeding on host threads, anchors / chaining / re-chaining / hit records on the
  *      device, primary-secondary decisions, divergence, mapping quality and the PAF line on the host, written from scratch after
  *      mm_map_frag (map.c:630-790) for single-segment reads without base-level alignment.  Options: the fields of mm_mapopt_t this
@@ -286,6 +311,7 @@ typedef struct {
 	int32_t seeds_on_device;   /* matches -> sorted anchors: 1 on the device, -1 on host threads, 0 by batch size */
 	int32_t rechain_on_device; /* mg_lchain_rmq's fill: 0 (default) mm2gb_rmq_chain -- device and host threads at the same time, reads dealt by cost, ties redone on the host; 1 every read on the device first (ties redone on host threads); -1 host threads only */
 	int32_t max_chain_skip;    /* mm_mapopt_t::max_chain_skip; INT32_MAX (the default here): chaining and re-chaining exhaustive.  Below it both keep the limit */
+	int32_t seeding_on_device; /* 1: sketch, look-up and match selection on the device (mm2gb_collect_matches_gpu's kernels), anchors from the resident matches; 0 (default), -1: on host threads */
 } mm2gb_map_opt_t;
 typedef struct { int64_t n_reads, n_mapped, n_anchors, n_chains, n_rechained, n_rmq_tied; double s_seed, s_anchors, s_chain, s_rechain, s_regs, s_post; } mm2gb_map_stats_t;   /* s_*: seconds per stage */
 void mm2gb_map_opt_init(mm2gb_map_opt_t *opt);

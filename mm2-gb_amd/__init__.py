@@ -85,7 +85,8 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_batcher_create", "mm2gb_batcher_add", "mm2gb_batcher_feed", "mm2gb_batcher_flush", "mm2gb_batcher_stats", "mm2gb_batcher_destroy",
                 "mm2gb_plan_batches", "mm2gb_rmq_chain_gpu", "mm2gb_lchain_rmq", "mm2gb_lchain_rmq_counts",
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
-                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream"]
+                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
+                "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -167,6 +168,11 @@ def lib():
         L.mm2gb_collect_matches.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.mm2gb_matches_free.restype = None
         L.mm2gb_matches_free.argtypes = [C.c_void_p]
+        L.mm2gb_sketch_gpu.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.mm2gb_index_to_device.argtypes = [C.c_void_p, C.c_int]
+        L.mm2gb_collect_matches_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_char_p, C.c_void_p]
+        L.mm2gb_match_batch_free.restype = None
+        L.mm2gb_match_batch_free.argtypes = [C.c_void_p]
         L.mm2gb_collect_seeds_gpu.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mm2gb_gen_regs_gpu.argtypes = [C.c_void_p, C.c_int64, C.POINTER(Chains), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -755,6 +761,60 @@ class SeedIndex:
         return out
 
 
+class MatchBatch(C.Structure):
+    _fields_ = [("n_seeds", C.c_int64), ("n_hits", C.c_int64), ("seed_off", C.c_void_p), ("seeds", C.c_void_p), ("hit_off", C.c_void_p),
+                ("hits", C.c_void_p), ("mini_pos", C.c_void_p), ("rep_len", C.c_void_p)]
+
+
+def _lay_end_to_end(seqs):
+    seqs = [bytes(s) for s in seqs]
+    off = np.zeros(len(seqs) + 1, np.int64)
+    off[1:] = np.cumsum([len(s) for s in seqs])
+    return seqs, off, b"".join(seqs)
+
+
+def _take(ptr, n, dt):
+    if n == 0:
+        return np.zeros(0, dt)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
+
+
+def _engine_sketch(self, seqs, w=10, k=15, rid=None):
+    """mm2gb_sketch_gpu: the (w,k)-minimizers of a list of sequences (bytes) on the device: one (n,2) uint64 array per sequence, equal to
+    sketch(seq, w, k, rid[r])."""
+    seqs, off, flat = _lay_end_to_end(seqs)
+    rids = np.ascontiguousarray(rid, dtype=np.uint32) if rid is not None else None
+    mini_off = np.zeros(len(seqs) + 1, np.int64)
+    ptr = C.c_void_p()
+    _check(lib().mm2gb_sketch_gpu(self._h, int(w), int(k), len(seqs), off.ctypes.data, flat, rids.ctypes.data if rids is not None else None,
+                                  mini_off.ctypes.data, C.byref(ptr)))
+    xy = _take(ptr, int(mini_off[-1]) * 2, np.uint64).reshape(-1, 2)
+    lib().mm2gb_free(ptr)
+    return [xy[mini_off[r]:mini_off[r + 1]] for r in range(len(seqs))]
+
+
+def _engine_collect_matches(self, index, seqs, mid_occ, max_max_occ=4095, occ_dist=500, q_occ_frac=0.01):
+    """mm2gb_collect_matches_gpu: for every read (bytes) the dict SeedIndex.matches returns, computed on the device in one call."""
+    seqs, off, flat = _lay_end_to_end(seqs)
+    opt = SeedOpt(int(mid_occ), int(max_max_occ), int(occ_dist), float(q_occ_frac))
+    m = MatchBatch()
+    _check(lib().mm2gb_collect_matches_gpu(self._h, index._h if index is not None else None, C.byref(opt), len(seqs), off.ctypes.data, flat, C.byref(m)))
+    R = len(seqs)
+    seed_off = _take(m.seed_off, R + 1, np.int64)
+    seeds = _take(m.seeds, m.n_seeds * 4, np.uint32).reshape(-1, 4)
+    hit_off = _take(m.hit_off, m.n_seeds + 1, np.int64)
+    hits = _take(m.hits, m.n_hits, np.uint64)
+    mini_pos = _take(m.mini_pos, m.n_seeds, np.uint64)
+    rep_len = _take(m.rep_len, R, np.int32)
+    lib().mm2gb_match_batch_free(C.byref(m))
+    return [dict(seeds=seeds[seed_off[r]:seed_off[r + 1]], hits=hits[hit_off[seed_off[r]]:hit_off[seed_off[r + 1]]], qlen=len(seqs[r]),
+                 rep_len=int(rep_len[r]), mini_pos=mini_pos[seed_off[r]:seed_off[r + 1]]) for r in range(R)]
+
+
+Engine.sketch = _engine_sketch
+Engine.collect_matches = _engine_collect_matches
+
+
 class MapOpt(C.Structure):
     _fields_ = [("flag", C.c_int64), ("seed", C.c_int32), ("mid_occ", C.c_int32), ("min_mid_occ", C.c_int32), ("max_mid_occ", C.c_int32),
                 ("max_max_occ", C.c_int32), ("occ_dist", C.c_int32), ("mid_occ_frac", C.c_float), ("q_occ_frac", C.c_float),
@@ -762,7 +822,7 @@ class MapOpt(C.Structure):
                 ("max_gap_ref", C.c_int32), ("max_chain_iter", C.c_int32), ("rmq_inner_dist", C.c_int32), ("rmq_size_cap", C.c_int32),
                 ("rmq_rescue_size", C.c_int32), ("rmq_rescue_ratio", C.c_float), ("chain_gap_scale", C.c_float), ("chain_skip_scale", C.c_float),
                 ("mask_level", C.c_float), ("mask_len", C.c_int32), ("pri_ratio", C.c_float), ("best_n", C.c_int32), ("host_threads", C.c_int32), ("seeds_on_device", C.c_int32), ("rechain_on_device", C.c_int32),
-                ("max_chain_skip", C.c_int32)]
+                ("max_chain_skip", C.c_int32), ("seeding_on_device", C.c_int32)]
 
 
 class MapStats(C.Structure):

@@ -75,6 +75,7 @@ void retire(void *ptr, size_t bytes, bool pinned)
 	if (g_retired_dev > (limit_mb << 20) || g_retired_host > (limit_mb << 18)) flush_retired_locked();
 }
 } // namespace
+void retire_device_buffer(void *ptr, size_t bytes) { retire(ptr, bytes, false); }
 void flush_retired_buffers()
 {
 	std::lock_guard<std::mutex> lock(g_retired_mu);
@@ -502,6 +503,7 @@ void Engine::shutdown()
 	slice_in.clear();
 	for (DevBuf *b : { &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
+	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
 	                   &post_out[0].u_off, &post_out[0].a_off, &post_out[0].u_out, &post_out[0].a_out, &post_out[1].u_off, &post_out[1].a_off, &post_out[1].u_out, &post_out[1].a_out })
 		b->release();
 	cap_post_n = cap_post_reads = 0;
@@ -1109,6 +1111,93 @@ int Engine::collect_seeds(int64_t opt_flag, int64_t n_reads, const int64_t *seed
 	return 0;
 }
 
+// The minimizer sketch of a batch of sequences (seed_kernels.hip).  Two waits: for the number of pairs (the output is sized by it).
+int Engine::sketch_device(int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini)
+{
+	const int64_t n = seq_off[n_seqs];
+	const size_t ns = (size_t)n_seqs;
+	*n_mini = 0;
+	MM2GB_HIP(hipSetDevice(device));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (sk_seqs.ensure((size_t)n + 1) || sk_seq_off.ensure((ns + 1) * 8) || sk_rid.ensure(std::max<size_t>(ns, 1) * 4) || sk_mini_off.ensure((ns + 1) * 8)) return -1;
+	if (n == 0) { MM2GB_HIP(hipMemsetAsync(sk_mini_off.ptr, 0, (ns + 1) * 8, stream)); MM2GB_HIP(hipStreamSynchronize(stream)); return 0; }
+	MM2GB_HIP(hipMemcpyAsync(sk_seqs.ptr, seqs, (size_t)n, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemsetAsync((char*)sk_seqs.ptr + n, 'N', 1, stream));
+	MM2GB_HIP(hipMemcpyAsync(sk_seq_off.ptr, seq_off, (ns + 1) * 8, hipMemcpyHostToDevice, stream));
+	if (rid) MM2GB_HIP(hipMemcpyAsync(sk_rid.ptr, rid, ns * 4, hipMemcpyHostToDevice, stream));
+	SketchBatch b;
+	memset(&b, 0, sizeof b);
+	b.seqs = (const unsigned char*)sk_seqs.ptr; b.seq_off = (const int64_t*)sk_seq_off.ptr; b.rid = rid ? (const uint32_t*)sk_rid.ptr : nullptr;
+	b.n_seqs = n_seqs; b.n = n; b.w = w; b.k = k;
+	if (sk_work.ensure(sketch_layout(b, nullptr))) return -1;
+	sketch_layout(b, sk_work.ptr);
+	b.mini_off = (int64_t*)sk_mini_off.ptr;
+	if (launch_sketch_count(b, stream)) return fail("mm2gb: a library scan of the sketch refused to run");
+	MM2GB_HIP(hipGetLastError());
+	int64_t total = 0;
+	MM2GB_HIP(hipMemcpyAsync(&total, b.mini_off + n_seqs, 8, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (total < 0 || total >= ((int64_t)1 << 31)) return fail("mm2gb: a batch is limited to 2^31 minimizers");
+	if (sk_mini.ensure(std::max<size_t>((size_t)total, 1) * 16) || sk_mini_read.ensure(std::max<size_t>((size_t)total, 1) * 4)) return -1;
+	b.mini = (ulonglong2*)sk_mini.ptr; b.mini_read = (int32_t*)sk_mini_read.ptr;
+	if (total > 0) { launch_sketch_write(b, stream); MM2GB_HIP(hipGetLastError()); }
+	*n_mini = total;
+	return 0;
+}
+
+// mm_collect_matches for a batch of reads: sketch, q-occurrence filter, look-up, streak thinning, repeat length, the kept seeds' hits.
+int Engine::collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits)
+{
+	int64_t n_mini = 0;
+	*n_seeds = *n_hits = 0;
+	if (sketch_device(ix.w, ix.k, n_reads, seq_off, seqs, nullptr, &n_mini)) return -1;
+	const size_t nr = (size_t)n_reads, nm = (size_t)n_mini;
+	if (sd_seeds.ensure(std::max<size_t>(nm, 1) * 16) || sd_seed_off.ensure((nr + 1) * 8) || sd_hit_off.ensure((nm + 1) * 8) || sd_qlen.ensure(std::max<size_t>(nr, 1) * 4) ||
+	    sd_src_first.ensure(std::max<size_t>(nm, 1) * 8) || sd_mini_pos.ensure(std::max<size_t>(nm, 1) * 8) || sd_rep_len.ensure(std::max<size_t>(nr, 1) * 4)) return -1;
+	if (seq_off[n_reads] == 0) MM2GB_HIP(hipMemcpyAsync(sk_seq_off.ptr, seq_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));   // (the sketch returned before its copies)
+	MatchBatch b;
+	memset(&b, 0, sizeof b);
+	b.ix = ix; b.mid_occ = opt.mid_occ; b.max_max_occ = opt.max_max_occ; b.occ_dist = opt.occ_dist; b.q_occ_frac = opt.q_occ_frac;
+	b.n_reads = n_reads; b.n_mini = n_mini; b.seq_off = (const int64_t*)sk_seq_off.ptr;
+	b.mini = (const ulonglong2*)sk_mini.ptr; b.mini_read = (const int32_t*)sk_mini_read.ptr; b.mini_off = (const int64_t*)sk_mini_off.ptr;
+	// (the sketch's work arrays are done with: the matches' arrays take their place in the arena)
+	if (sk_work.ensure(match_layout(b, nullptr))) return -1;
+	match_layout(b, sk_work.ptr);
+	b.seeds = (SeedRecord*)sd_seeds.ptr; b.seed_off = (int64_t*)sd_seed_off.ptr; b.hit_off = (int64_t*)sd_hit_off.ptr; b.hits = nullptr;
+	b.src_first = (long long*)sd_src_first.ptr; b.mini_pos = (unsigned long long*)sd_mini_pos.ptr; b.rep_len = (int32_t*)sd_rep_len.ptr; b.qlen = (int32_t*)sd_qlen.ptr;
+	if (launch_matches_select(b, stream)) return fail("mm2gb: a library scan or sort of the match selection refused to run");
+	MM2GB_HIP(hipGetLastError());
+	int64_t tot[4] = { 0, 0, 0, 0 };
+	MM2GB_HIP(hipMemcpyAsync(tot, b.tot, sizeof tot, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (sd_hits.ensure(std::max<size_t>((size_t)tot[3], 1) * 8)) return -1;
+	b.hits = (unsigned long long*)sd_hits.ptr;
+	if (tot[3] > 0) { launch_matches_gather(b, stream); MM2GB_HIP(hipGetLastError()); }
+	*n_seeds = tot[2]; *n_hits = tot[3];
+	return 0;
+}
+
+int Engine::collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, int64_t *anchor_off, mm2gb_anchor_t *anchors)
+{
+	anchor_off[0] = 0;
+	if (n_hits == 0) { for (int64_t r = 0; r < n_reads; ++r) anchor_off[r + 1] = 0; return 0; }
+	if (n_hits >= ((int64_t)1 << 31)) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 hits");
+	const size_t nr = (size_t)n_reads, ns = (size_t)std::max<int64_t>(n_seeds, 1), nh = (size_t)n_hits;
+	if (sd_seed_read.ensure(ns * 4) || sd_tmp.ensure(nh * 16) || sd_n_kept.ensure(nr * 4) || sd_a_off.ensure((nr + 1) * 8) || sd_out.ensure(nh * 16)) return -1;
+	SeedBatch sb;
+	sb.seeds = (const SeedRecord*)sd_seeds.ptr; sb.seed_off = (const int64_t*)sd_seed_off.ptr; sb.hit_off = (const int64_t*)sd_hit_off.ptr;
+	sb.hits = (const unsigned long long*)sd_hits.ptr; sb.qlen = (const int32_t*)sd_qlen.ptr; sb.q_rank = nullptr; sb.ref_len = nullptr; sb.ref_rank = nullptr;
+	sb.n_reads = n_reads; sb.n_seeds = n_seeds; sb.n_hits = n_hits; sb.flag = (long long)opt_flag;
+	sb.seed_read = (int32_t*)sd_seed_read.ptr; sb.tmp = (ulonglong2*)sd_tmp.ptr; sb.n_kept = (int32_t*)sd_n_kept.ptr;
+	sb.anchor_off = (int64_t*)sd_a_off.ptr; sb.out = (ulonglong2*)sd_out.ptr; sb.grid_waves = n_cu * 32;
+	launch_collect_seeds(sb, stream);
+	MM2GB_HIP(hipGetLastError());
+	MM2GB_HIP(hipMemcpyAsync(anchor_off, sd_a_off.ptr, (nr + 1) * 8, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (anchor_off[n_reads] > 0) { MM2GB_HIP(hipMemcpyAsync(anchors, sd_out.ptr, (size_t)anchor_off[n_reads] * 16, hipMemcpyDeviceToHost, s_out)); MM2GB_HIP(hipStreamSynchronize(s_out)); }
+	return 0;
+}
+
 // mm_gen_regs (hit.c:52-88) for every read of a batch of chains.
 int Engine::gen_regs(int64_t n_reads, const mm2gb_chains_t *ch, const int32_t *qlen, const uint32_t *hash, int is_qstrand, mm2gb_reg_t *regs)
 {
@@ -1485,6 +1574,78 @@ int mm2gb_collect_seeds_gpu(mm2gb_engine_t *eng, int64_t opt_flag, int64_t n_rea
                             int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors)
 {
 	return eng ? eng->e.collect_seeds(opt_flag, n_reads, seed_off, seeds, hit_off, hits, qlen, q_rank, n_ref, ref_len, ref_rank, anchor_off, anchors) : fail("mm2gb: null engine");
+}
+
+// what both batch calls ask of their offsets: seq_off[0] = 0, non-decreasing, fewer than 2^31 bases (positions are 32-bit on the device)
+static int check_seq_off(const char *who, int64_t n, const int64_t *seq_off, const char *seqs)
+{
+	if (n < 0 || !seq_off) return fail(std::string(who) + ": null argument");
+	if (seq_off[0] != 0) return fail(std::string(who) + ": seq_off[0] must be 0");
+	for (int64_t r = 0; r < n; ++r) if (seq_off[r + 1] < seq_off[r]) return fail(std::string(who) + ": seq_off must be non-decreasing");
+	if (seq_off[n] >= ((int64_t)1 << 31) - 1) return fail(std::string(who) + ": a batch is limited to 2^31 bases");
+	if (seq_off[n] > 0 && !seqs) return fail(std::string(who) + ": null argument");
+	return 0;
+}
+
+int mm2gb_sketch_gpu(mm2gb_engine_t *eng, int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *mini_off, uint64_t **out_xy)
+{
+	if (!eng || !mini_off || !out_xy) return fail("mm2gb_sketch_gpu: null argument");
+	if (w < 1 || w > 255 || k < 1 || k > 28) return fail("mm2gb_sketch_gpu: bad arguments (0 < w < 256, 0 < k <= 28)");
+	if (check_seq_off("mm2gb_sketch_gpu", n_seqs, seq_off, seqs)) return -1;
+	Engine &e = eng->e;
+	*out_xy = nullptr;
+	int64_t n_mini = 0;
+	if (n_seqs == 0) mini_off[0] = 0;
+	else {
+		if (e.sketch_device(w, k, n_seqs, seq_off, seqs, rid, &n_mini)) return -1;
+		MM2GB_HIP(hipMemcpyAsync(mini_off, e.sk_mini_off.ptr, (size_t)(n_seqs + 1) * 8, hipMemcpyDeviceToHost, e.stream));
+	}
+	*out_xy = (uint64_t*)malloc(((size_t)n_mini + 1) * 16);
+	if (!*out_xy) { (void)hipStreamSynchronize(e.stream); return fail("mm2gb_sketch_gpu: out of memory"); }
+	if (n_mini > 0) MM2GB_HIP(hipMemcpyAsync(*out_xy, e.sk_mini.ptr, (size_t)n_mini * 16, hipMemcpyDeviceToHost, e.stream));
+	if (n_seqs > 0) MM2GB_HIP(hipStreamSynchronize(e.stream));
+	return 0;
+}
+
+void mm2gb_match_batch_free(mm2gb_match_batch_t *m)
+{
+	if (!m) return;
+	free(m->seed_off); free(m->seeds); free(m->hit_off); free(m->hits); free(m->mini_pos); free(m->rep_len);
+	memset(m, 0, sizeof(*m));
+}
+
+int mm2gb_collect_matches_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seqs,
+                              mm2gb_match_batch_t *out)
+{
+	if (!eng || !ix || !opt || !out) return fail("mm2gb_collect_matches_gpu: null argument");
+	if (check_seq_off("mm2gb_collect_matches_gpu", n_reads, seq_off, seqs)) return -1;
+	memset(out, 0, sizeof(*out));
+	Engine &e = eng->e;
+	int64_t n_seeds = 0, n_hits = 0;
+	if (n_reads > 0) {
+		DevIndexView view;
+		if (index_on_device(ix, e.device, &view)) return -1;
+		if (e.collect_matches_device(view, *opt, n_reads, seq_off, seqs, &n_seeds, &n_hits)) return -1;
+	}
+	out->n_seeds = n_seeds; out->n_hits = n_hits;
+	out->seed_off = (int64_t*)calloc((size_t)n_reads + 1, 8);
+	out->seeds = (mm2gb_seed_t*)malloc(((size_t)n_seeds + 1) * sizeof(mm2gb_seed_t));
+	out->hit_off = (int64_t*)calloc((size_t)n_seeds + 1, 8);
+	out->hits = (uint64_t*)malloc(((size_t)n_hits + 1) * 8);
+	out->mini_pos = (uint64_t*)malloc(((size_t)n_seeds + 1) * 8);
+	out->rep_len = (int32_t*)calloc((size_t)n_reads + 1, 4);
+	if (!out->seed_off || !out->seeds || !out->hit_off || !out->hits || !out->mini_pos || !out->rep_len) { mm2gb_match_batch_free(out); return fail("mm2gb_collect_matches_gpu: out of memory"); }
+	if (n_reads == 0) return 0;
+	hipError_t err = hipMemcpyAsync(out->seed_off, e.sd_seed_off.ptr, (size_t)(n_reads + 1) * 8, hipMemcpyDeviceToHost, e.stream);
+	if (err == hipSuccess) err = hipMemcpyAsync(out->rep_len, e.sd_rep_len.ptr, (size_t)n_reads * 4, hipMemcpyDeviceToHost, e.stream);
+	if (err == hipSuccess) err = hipMemcpyAsync(out->hit_off, e.sd_hit_off.ptr, (size_t)(n_seeds + 1) * 8, hipMemcpyDeviceToHost, e.stream);
+	if (err == hipSuccess && n_seeds > 0) err = hipMemcpyAsync(out->seeds, e.sd_seeds.ptr, (size_t)n_seeds * 16, hipMemcpyDeviceToHost, e.stream);
+	if (err == hipSuccess && n_seeds > 0) err = hipMemcpyAsync(out->mini_pos, e.sd_mini_pos.ptr, (size_t)n_seeds * 8, hipMemcpyDeviceToHost, e.stream);
+	if (err == hipSuccess && n_hits > 0) err = hipMemcpyAsync(out->hits, e.sd_hits.ptr, (size_t)n_hits * 8, hipMemcpyDeviceToHost, e.stream);
+	const hipError_t done = hipStreamSynchronize(e.stream);
+	if (err == hipSuccess) err = done;
+	if (err != hipSuccess) { mm2gb_match_batch_free(out); return fail(std::string("mm2gb_collect_matches_gpu: ") + hipGetErrorString(err)); }
+	return 0;
 }
 
 int mm2gb_gen_regs_gpu(mm2gb_engine_t *eng, int64_t n_reads, const mm2gb_chains_t *chains, const int32_t *qlen, const uint32_t *hash,

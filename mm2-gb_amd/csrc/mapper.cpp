@@ -298,7 +298,42 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 	std::vector<std::vector<const uint64_t*>> occ(R);     // per read and kept seed: its occurrences, where the index holds them (copied once, into the batch's array)
 	for (auto &m : mt) memset(&m, 0, sizeof m);
 	const mm2gb_seed_opt_t so = { opt.mid_occ, opt.max_max_occ, opt.occ_dist, opt.q_occ_frac };
-	{
+	// seeding_on_device = 1: the reads go up as bytes, sketch / look-up / match selection run as kernels (seed_kernels.hip) and leave the arrays
+	// step 2's kernels read where they are; what comes down is what the host's mapq and divergence code wants (rep_len, mini_pos)
+	const bool dev_seed = opt.seeding_on_device > 0;
+	int64_t dev_seeds = 0, dev_hits = 0;
+	if (dev_seed) {
+		std::vector<int64_t> seq_off(R + 1, 0);
+		for (size_t r = 0; r < R; ++r) seq_off[r + 1] = seq_off[r] + lens[r];
+		if (seq_off[R] >= ((int64_t)1 << 31) - 1) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 bases");
+		BigBuf<uint64_t> &flat = host_scratch(eng).hits;          // (no host array of hits in this form: its memory holds the reads end to end)
+		flat.resize((size_t)seq_off[R] / 8 + 1);
+		char *const bases = (char*)flat.data();
+		{
+			std::atomic<size_t> next(0);
+			auto work = [&]() { for (;;) { const size_t r = next.fetch_add(1); if (r >= R) break; if (lens[r] > 0) memcpy(bases + seq_off[r], seqs[r], (size_t)lens[r]); } };
+			std::vector<std::thread> pool;
+			for (int t = 1; t < std::max(1, opt.host_threads); ++t) pool.emplace_back(work);
+			work();
+			for (auto &th : pool) th.join();
+		}
+		DevIndexView view;
+		if (index_on_device(ix, eng->e.device, &view)) return -1;
+		if (eng->e.collect_matches_device(view, so, n_reads, seq_off.data(), bases, &dev_seeds, &dev_hits)) return -1;
+		std::vector<int64_t> seed_off(R + 1, 0);
+		std::vector<int32_t> rep(R, 0);
+		std::vector<uint64_t> mini_pos((size_t)dev_seeds + 1);
+		if (hipMemcpy(seed_off.data(), eng->e.sd_seed_off.ptr, (R + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rep.data(), eng->e.sd_rep_len.ptr, R * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+		    (dev_seeds > 0 && hipMemcpy(mini_pos.data(), eng->e.sd_mini_pos.ptr, (size_t)dev_seeds * 8, hipMemcpyDeviceToHost) != hipSuccess))
+			return fail("mm2gb_map_reads: the device's matches could not be copied back");
+		for (size_t r = 0; r < R; ++r) {
+			const int64_t n = seed_off[r + 1] - seed_off[r];
+			mt[r].rep_len = rep[r]; mt[r].n_seeds = mt[r].n_mini_pos = (int32_t)n;
+			mt[r].mini_pos = (uint64_t*)malloc(((size_t)n + 1) * 8);
+			if (!mt[r].mini_pos) return fail("mm2gb_map_reads: out of memory");
+			if (n > 0) memcpy(mt[r].mini_pos, mini_pos.data() + seed_off[r], (size_t)n * 8);
+		}
+	} else {
 		std::atomic<int32_t> next(0);
 		std::atomic<int> bad(0);
 		std::string why;                                      // error text is per thread: carry the first one over
@@ -324,6 +359,13 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 	tr.reset(); tr.reset(new TraceRange("mm2gb:map_anchors"));
 
 	// 2. anchors, sorted, on the device
+	std::vector<int32_t> qlen(lens, lens + n_reads);
+	std::vector<int64_t> a_off(R + 1, 0);
+	BigBuf<mm2gb_anchor_t> &anchors = host_scratch(eng).anchors;
+	if (dev_seed) {
+		anchors.resize((size_t)std::max<int64_t>(dev_hits, 1));
+		if (eng->e.collect_seeds_resident(opt.flag, n_reads, dev_seeds, dev_hits, a_off.data(), anchors.data())) { free_matches(); return -1; }
+	} else {
 	std::vector<int64_t> seed_off(R + 1, 0);
 	for (size_t r = 0; r < R; ++r) seed_off[r + 1] = seed_off[r] + mt[r].n_seeds;
 	std::vector<mm2gb_seed_t> seeds((size_t)seed_off[R]);
@@ -336,7 +378,6 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 	}
 	// (the batch's two largest arrays are the engine's from call to call: a gigabyte of fresh pages costs more to touch than to fill)
 	BigBuf<uint64_t> &hits = host_scratch(eng).hits;
-	BigBuf<mm2gb_anchor_t> &anchors = host_scratch(eng).anchors;
 	hits.resize((size_t)n_hits);
 	{
 		uint64_t *const hits_ptr = hits.data();
@@ -355,8 +396,6 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 		work();
 		for (auto &th : pool) th.join();
 	}
-	std::vector<int32_t> qlen(lens, lens + n_reads);
-	std::vector<int64_t> a_off(R + 1, 0);
 	anchors.resize((size_t)std::max<int64_t>(n_hits, 1));
 	// on the device for large batches (mm2gb_collect_seeds_gpu: matches up, anchors down, one wave sorts a read); below that the host
 	// threads are quicker: the largest read's sort alone is hundreds of milliseconds for one wave, milliseconds for a core
@@ -365,6 +404,7 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 	                                              a_off.data(), anchors.data())
 	                    : mm2gb_collect_seeds_host(opt.flag, n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), qlen.data(), nullptr, n_ref, nullptr, nullptr,
 	                                               std::max(1, opt.host_threads), a_off.data(), anchors.data())) { free_matches(); return -1; }
+	}
 	st_local.n_anchors = a_off[R];
 	lap(st_local.s_anchors);
 	tr.reset(); tr.reset(new TraceRange("mm2gb:map_chain"));

@@ -14,6 +14,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -108,6 +109,10 @@ struct SeedIndex {
 	// ~20 dependent probes of a table that does not fit the cache, ~200 ns per minimizer of a read, most of what seeding cost)
 	std::vector<uint32_t> bucket;
 	int bucket_shift = 0;
+	// the four arrays as they are, in a device's memory (index_on_device): one copy per device, made on first use, given up by mm2gb_index_destroy
+	struct DevCopy { int device; void *ptr[4]; size_t bytes[4]; };
+	mutable std::mutex dev_mu;
+	mutable std::vector<DevCopy> dev;
 	void build_buckets()
 	{
 		int bits = 1;
@@ -136,7 +141,8 @@ struct SeedIndex {
 
 namespace {
 
-// max-heap of 64-bit values, sift-down as in ksort.h:43-59 (which element sits where decides which seed is replaced, seed.c:80-85)
+// max-heap of 64-bit values, sift-down as in ksort.h:43-59.  (Where an element sits does not decide the outcome: a replacement needs a strictly
+// smaller n and evicts the largest (n, index), so a streak keeps its K smallest by (n, index) -- the form k_m_select computes on the device)
 void sift_down(size_t i, size_t n, uint64_t *h)
 {
 	const uint64_t v = h[i];
@@ -230,7 +236,20 @@ mm2gb_index_t *mm2gb_index_build(int k, int w, int32_t n_seq, const char *const 
 	return reinterpret_cast<mm2gb_index_t*>(ix);
 }
 
-void mm2gb_index_destroy(mm2gb_index_t *ix) { delete reinterpret_cast<SeedIndex*>(ix); }
+void mm2gb_index_destroy(mm2gb_index_t *ix_)
+{
+	SeedIndex *ix = reinterpret_cast<SeedIndex*>(ix_);
+	if (!ix) return;
+	// the device copies go the way of the engines' outgrown arenas: freed later, not under other engines' kernels (engine.hip)
+	for (const SeedIndex::DevCopy &c : ix->dev) for (int a = 0; a < 4; ++a) retire_device_buffer(c.ptr[a], c.bytes[a]);
+	delete ix;
+}
+
+int mm2gb_index_to_device(mm2gb_index_t *ix, int device)
+{
+	DevIndexView view;
+	return index_on_device(ix, device, &view);
+}
 
 int64_t mm2gb_index_size(const mm2gb_index_t *ix_, int64_t *n_occurrences)
 {
@@ -265,6 +284,42 @@ int mm2gb_collect_matches(const mm2gb_index_t *ix, const char *seq, int32_t len,
 }
 
 } // extern "C"
+
+// The index in a device's memory: keys, first, where, bucket copied as they are; the look-up there is SeedIndex::find as written (k_m_lookup).
+int mm2gb::index_on_device(const mm2gb_index_t *ix_, int device, DevIndexView *out)
+{
+	const SeedIndex *ix = reinterpret_cast<const SeedIndex*>(ix_);
+	if (!ix || !out) return fail("mm2gb_index_to_device: null argument");
+	std::lock_guard<std::mutex> lock(ix->dev_mu);
+	const SeedIndex::DevCopy *have = nullptr;
+	for (const SeedIndex::DevCopy &c : ix->dev) if (c.device == device) have = &c;
+	if (!have) {
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return fail("mm2gb_index_to_device: device " + std::to_string(device) + " not present");
+		MM2GB_HIP(hipSetDevice(device));
+		SeedIndex::DevCopy c;
+		c.device = device;
+		const void *src[4] = { ix->keys.data(), ix->first.data(), ix->where.data(), ix->bucket.data() };
+		const size_t bytes[4] = { ix->keys.size() * 8, ix->first.size() * 8, ix->where.size() * 8, ix->bucket.size() * 4 };
+		for (int a = 0; a < 4; ++a) { c.ptr[a] = nullptr; c.bytes[a] = std::max<size_t>(bytes[a], 8); }
+		hipError_t err = hipSuccess;
+		for (int a = 0; a < 4 && err == hipSuccess; ++a) {
+			err = hipMalloc(&c.ptr[a], c.bytes[a]);
+			if (err == hipSuccess && bytes[a]) err = hipMemcpy(c.ptr[a], src[a], bytes[a], hipMemcpyHostToDevice);
+		}
+		if (err != hipSuccess) {                        // an error of the call, never another way to the result
+			for (int a = 0; a < 4; ++a) if (c.ptr[a]) (void)hipFree(c.ptr[a]);
+			(void)hipGetLastError();
+			return fail(std::string("mm2gb_index_to_device: the index does not fit the device: ") + hipGetErrorString(err));
+		}
+		ix->dev.push_back(c);
+		have = &ix->dev.back();
+	}
+	out->keys = (const unsigned long long*)have->ptr[0]; out->first = (const long long*)have->ptr[1];
+	out->where = (const unsigned long long*)have->ptr[2]; out->bucket = (const uint32_t*)have->ptr[3];
+	out->n_bucket = ix->bucket.size(); out->bucket_shift = ix->bucket_shift; out->k = ix->k; out->w = ix->w;
+	return 0;
+}
 
 // refs == nullptr: out->hits is a copy of every kept seed's occurrences; otherwise out->hits stays null and refs[s] points at seed s's
 // occurrences in the index (the mapper copies them straight into the batch's array: host_chain.h)
