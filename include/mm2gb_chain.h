@@ -248,7 +248,8 @@ int  mm2gb_gen_regs_gpu(mm2gb_engine_t *eng, int64_t n_reads, const mm2gb_chains
  *      mm2gb_collect_matches: mm_collect_matches (seed.c:98-131, with seed.c:5-96) for one read of one segment: the arrays
  *      mm2gb_collect_seeds_gpu takes, plus rep_len and the minimizer positions the host's mapq / divergence estimates use.
  *      Free a matches record with mm2gb_matches_free, a sketch with mm2gb_free.  Sketch, look-up and match collection have a device
- *      form too (below: mm2gb_sketch_gpu, mm2gb_collect_matches_gpu); building the index and mid_occ are the host's. ---- */
+ *      form too (below: mm2gb_sketch_gpu, mm2gb_collect_matches_gpu), and so have building the index and mid_occ (mm2gb_index_build_gpu,
+ *      mm2gb_index_mid_occ_gpu); the host functions here stay the definition and the default. ---- */
 typedef struct mm2gb_index mm2gb_index_t;
 typedef struct { int32_t mid_occ, max_max_occ, occ_dist; float q_occ_frac; } mm2gb_seed_opt_t;   /* mm_mapopt_t: mid_occ, max_max_occ, occ_dist, q_occ_frac */
 typedef struct {
@@ -292,6 +293,35 @@ typedef struct {
 int  mm2gb_collect_matches_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_reads,
                                const int64_t *seq_off, const char *seqs, mm2gb_match_batch_t *out);
 void mm2gb_match_batch_free(mm2gb_match_batch_t *m);
+
+/* ---- the index built on the device (csrc/index_kernels.hip): the sequences are sketched there in chunks of whole sequences (at most
+ *      MM2GB_INDEX_CHUNK_BASES bases, read at call time, default 256 Mbp; a longer sequence is a chunk of its own, one of 2^31 - 1 bases is
+ *      refused), the pairs sorted by (x >> 8, y) and the tables made there.
+ *      mm2gb_index_build_gpu: arguments as mm2gb_index_build.  The host arrays of the result are byte-identical to mm2gb_index_build's, so
+ *      every function that takes an index works on it unchanged; the same arrays stay resident on the engine's device as that device's
+ *      copy (nothing is uploaded on first use).  NULL on error (a HIP error or no room on the device included): never a host build instead.
+ *      mm2gb_index_mid_occ_gpu: the value mm2gb_index_mid_occ returns, the quantile found on the device by an exact radix select over the
+ *      resident first[] (uploaded through mm2gb_index_to_device when the index is not resident there); negative on error.
+ *      mm2gb_index_view: sizes, parameters and read-only pointers to the host arrays (valid until mm2gb_index_destroy); built_on is the
+ *      device of mm2gb_index_build_gpu or -1, uploads counts the host -> device copies made so far.
+ *      mm2gb_index_fetch_device: a device's resident arrays copied into buffers of the view's sizes (keys n_keys, first n_keys + 1,
+ *      where n_occ, bucket n_bucket); an error when the index is not resident there.
+ *      mm2gb_index_build_split: milliseconds of the device build's stages (H2D, sketch, sort, tables, D2H; H2D overlaps the sketch);
+ *      zeros for a host-built index. ---- */
+typedef struct {
+	int64_t n_keys, n_occ, n_bucket;
+	int32_t bucket_shift, k, w, built_on;
+	int64_t uploads;
+	const uint64_t *keys;     /* n_keys */
+	const int64_t  *first;    /* n_keys + 1 */
+	const uint64_t *where;    /* n_occ */
+	const uint32_t *bucket;   /* n_bucket */
+} mm2gb_index_view_t;
+mm2gb_index_t *mm2gb_index_build_gpu(mm2gb_engine_t *eng, int k, int w, int32_t n_seq, const char *const *seqs, const int32_t *lens);
+int32_t mm2gb_index_mid_occ_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, float mid_occ_frac, int32_t min_mid_occ, int32_t max_mid_occ);
+int  mm2gb_index_view(const mm2gb_index_t *ix, mm2gb_index_view_t *out);
+int  mm2gb_index_fetch_device(const mm2gb_index_t *ix, int device, uint64_t *keys, int64_t *first, uint64_t *where, uint32_t *bucket);
+int  mm2gb_index_build_split(const mm2gb_index_t *ix, double *ms5);
 
 /* ---- reads in, PAF out (csrc/mapper.cpp): seeding on host threads, anchors / chaining / re-chaining / hit records on the
  *      device, primary-secondary decisions, divergence, mapping quality and the PAF line on the host, written from scratch after

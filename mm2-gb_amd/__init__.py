@@ -86,7 +86,8 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_plan_batches", "mm2gb_rmq_chain_gpu", "mm2gb_lchain_rmq", "mm2gb_lchain_rmq_counts",
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
                 "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
-                "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free"]
+                "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free",
+                "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -165,6 +166,13 @@ def lib():
         L.mm2gb_index_size.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.mm2gb_index_mid_occ.restype = C.c_int32
         L.mm2gb_index_mid_occ.argtypes = [C.c_void_p, C.c_float, C.c_int32, C.c_int32]
+        L.mm2gb_index_build_gpu.restype = C.c_void_p
+        L.mm2gb_index_build_gpu.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p]
+        L.mm2gb_index_mid_occ_gpu.restype = C.c_int32
+        L.mm2gb_index_mid_occ_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32]
+        L.mm2gb_index_view.argtypes = [C.c_void_p, C.c_void_p]
+        L.mm2gb_index_fetch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mm2gb_index_build_split.argtypes = [C.c_void_p, C.c_void_p]
         L.mm2gb_collect_matches.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.mm2gb_matches_free.restype = None
         L.mm2gb_matches_free.argtypes = [C.c_void_p]
@@ -716,15 +724,24 @@ def sketch(seq, w=10, k=15, rid=0):
     return out
 
 
-class SeedIndex:
-    """Minimizer index of reference sequences (list of bytes) with the look-up semantics of the reference's mm_idx_get."""
+class IndexView(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("n_occ", C.c_int64), ("n_bucket", C.c_int64), ("bucket_shift", C.c_int32), ("k", C.c_int32), ("w", C.c_int32),
+                ("built_on", C.c_int32), ("uploads", C.c_int64), ("keys", C.c_void_p), ("first", C.c_void_p), ("where", C.c_void_p), ("bucket", C.c_void_p)]
 
-    def __init__(self, seqs, k=15, w=10, threads=4):
+
+class SeedIndex:
+    """Minimizer index of reference sequences (list of bytes) with the look-up semantics of the reference's mm_idx_get.  With an engine the
+    index is built on that engine's device (mm2gb_index_build_gpu) and stays resident there; its arrays are the host build's."""
+
+    def __init__(self, seqs, k=15, w=10, threads=4, engine=None):
         self._seqs = [bytes(s) for s in seqs]
         arr = (C.c_char_p * len(self._seqs))(*self._seqs)
         lens = np.ascontiguousarray([len(s) for s in self._seqs], dtype=np.int32)
         self.lens = lens
-        self._h = lib().mm2gb_index_build(k, w, len(self._seqs), arr, lens.ctypes.data, threads)
+        if engine is not None:
+            self._h = lib().mm2gb_index_build_gpu(engine._h, k, w, len(self._seqs), arr, lens.ctypes.data)
+        else:
+            self._h = lib().mm2gb_index_build(k, w, len(self._seqs), arr, lens.ctypes.data, threads)
         if not self._h:
             raise Mm2gbError(lib().mm2gb_last_error().decode())
 
@@ -743,8 +760,43 @@ class SeedIndex:
         occ = C.c_int64()
         return int(lib().mm2gb_index_size(self._h, C.byref(occ))), int(occ.value)
 
-    def mid_occ(self, frac=2e-4, min_mid_occ=10, max_mid_occ=1000000):
-        return int(lib().mm2gb_index_mid_occ(self._h, frac, min_mid_occ, max_mid_occ))
+    def mid_occ(self, frac=2e-4, min_mid_occ=10, max_mid_occ=1000000, engine=None):
+        """mm2gb_index_mid_occ; with an engine mm2gb_index_mid_occ_gpu: the same value, the quantile found on the engine's device."""
+        if engine is None:
+            return int(lib().mm2gb_index_mid_occ(self._h, frac, min_mid_occ, max_mid_occ))
+        occ = int(lib().mm2gb_index_mid_occ_gpu(engine._h, self._h, frac, min_mid_occ, max_mid_occ))
+        if occ < 0:
+            raise Mm2gbError(lib().mm2gb_last_error().decode())
+        return occ
+
+    def _raw_view(self):
+        v = IndexView()
+        _check(lib().mm2gb_index_view(self._h, C.byref(v)))
+        return v
+
+    def view(self):
+        """mm2gb_index_view: dict of numpy copies of keys / first / where / bucket and the scalars n_keys, n_occ, n_bucket, bucket_shift, k, w,
+        built_on (the device the index was built on, or -1) and uploads (host -> device copies made for it so far)."""
+        v = self._raw_view()
+        out = {f: int(getattr(v, f)) for f in ("n_keys", "n_occ", "n_bucket", "bucket_shift", "k", "w", "built_on", "uploads")}
+        out.update(keys=_take(v.keys, v.n_keys, np.uint64), first=_take(v.first, v.n_keys + 1, np.int64), where=_take(v.where, v.n_occ, np.uint64),
+                   bucket=_take(v.bucket, v.n_bucket, np.uint32))
+        return out
+
+    def fetch_device(self, device):
+        """mm2gb_index_fetch_device: the arrays resident on a device, as dict(keys, first, where, bucket); an error if none are."""
+        v = self._raw_view()
+        out = dict(keys=np.zeros(v.n_keys, np.uint64), first=np.zeros(v.n_keys + 1, np.int64), where=np.zeros(v.n_occ, np.uint64),
+                   bucket=np.zeros(v.n_bucket, np.uint32))
+        _check(lib().mm2gb_index_fetch_device(self._h, int(device), out["keys"].ctypes.data, out["first"].ctypes.data, out["where"].ctypes.data,
+                                              out["bucket"].ctypes.data))
+        return out
+
+    def build_split(self):
+        """mm2gb_index_build_split: milliseconds of the device build's stages (zeros for a host build)."""
+        ms = (C.c_double * 5)()
+        _check(lib().mm2gb_index_build_split(self._h, ms))
+        return dict(zip(("h2d", "sketch", "sort", "tables", "d2h"), (float(x) for x in ms)))
 
     def matches(self, seq, mid_occ, max_max_occ=4095, occ_dist=500, q_occ_frac=0.01):
         """mm2gb_collect_matches for one read: dict(seeds (n,4) uint32, hits uint64, qlen, rep_len, mini_pos) -- the record Engine.collect_seeds takes."""

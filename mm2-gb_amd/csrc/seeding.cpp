@@ -20,6 +20,7 @@
 #include <vector>
 #include "engine.h"
 #include "host_chain.h"
+#include "index_dev.h"
 
 namespace mm2gb {
 namespace {
@@ -96,50 +97,7 @@ void sketch(const char *seq, int len, int w, int k, uint32_t rid, std::vector<Mi
 	if (best.x != none) out.push_back(best);    // sketch.c:141-142
 }
 
-} // namespace
-
-struct SeedIndex {
-	int k = 15, w = 10;
-	std::vector<int32_t> lens;
-	std::vector<uint64_t> keys;             // distinct minimizers (x >> 8), ascending
-	std::vector<int64_t> first;             // keys.size() + 1: where each one's occurrences begin
-	std::vector<uint64_t> where;            // occurrences, ascending within a minimizer
-	// keys by their top bits: bucket[b] = first key with (key >> bucket_shift) >= b.  The hash spreads minimizers evenly over their 2k bits,
-	// so a bucket holds a key or two and a look-up is one probe of this table and a search among those (a binary search over all keys:
-	// ~20 dependent probes of a table that does not fit the cache, ~200 ns per minimizer of a read, most of what seeding cost)
-	std::vector<uint32_t> bucket;
-	int bucket_shift = 0;
-	// the four arrays as they are, in a device's memory (index_on_device): one copy per device, made on first use, given up by mm2gb_index_destroy
-	struct DevCopy { int device; void *ptr[4]; size_t bytes[4]; };
-	mutable std::mutex dev_mu;
-	mutable std::vector<DevCopy> dev;
-	void build_buckets()
-	{
-		int bits = 1;
-		while (bits < 2 * k && ((size_t)1 << bits) < keys.size()) ++bits;   // about one key per bucket
-		bits = std::min(bits, 26);
-		bucket_shift = 2 * k - bits;
-		bucket.assign(((size_t)1 << bits) + 1, 0);
-		size_t at = 0;
-		for (size_t b = 0; b <= (size_t)1 << bits; ++b) {
-			while (at < keys.size() && (keys[at] >> bucket_shift) < b) ++at;
-			bucket[b] = (uint32_t)at;
-		}
-	}
-	const uint64_t *find(uint64_t minier, int *n) const
-	{
-		const uint64_t b = minier >> bucket_shift;
-		if (b + 1 >= bucket.size()) { *n = 0; return nullptr; }
-		const auto lo = keys.begin() + bucket[(size_t)b], hi = keys.begin() + bucket[(size_t)b + 1];
-		const auto it = std::lower_bound(lo, hi, minier);
-		if (it == hi || *it != minier) { *n = 0; return nullptr; }
-		const size_t at = (size_t)(it - keys.begin());
-		*n = (int)(first[at + 1] - first[at]);
-		return where.data() + first[at];
-	}
-};
-
-namespace {
+// (struct SeedIndex, the index itself, is in index_dev.h: index_kernels.hip fills the same structure on a device)
 
 // max-heap of 64-bit values, sift-down as in ksort.h:43-59.  (Where an element sits does not decide the outcome: a replacement needs a strictly
 // smaller n and evicts the largest (n, index), so a streak keeps its K smallest by (n, index) -- the form k_m_select computes on the device)
@@ -278,6 +236,48 @@ int32_t mm2gb_index_mid_occ(const mm2gb_index_t *ix_, float frac, int32_t min_mi
 	return occ;
 }
 
+int mm2gb_index_view(const mm2gb_index_t *ix_, mm2gb_index_view_t *out)
+{
+	const SeedIndex *ix = reinterpret_cast<const SeedIndex*>(ix_);
+	if (!ix || !out) return fail("mm2gb_index_view: null argument");
+	std::lock_guard<std::mutex> lock(ix->dev_mu);
+	out->n_keys = (int64_t)ix->keys.size(); out->n_occ = (int64_t)ix->where.size(); out->n_bucket = (int64_t)ix->bucket.size();
+	out->bucket_shift = ix->bucket_shift; out->k = ix->k; out->w = ix->w; out->built_on = ix->built_on; out->uploads = ix->uploads;
+	out->keys = ix->keys.data(); out->first = ix->first.data(); out->where = ix->where.data(); out->bucket = ix->bucket.data();
+	return 0;
+}
+
+// a device's resident arrays as they are, into the caller's buffers (sized by mm2gb_index_view); on a stream of its own
+int mm2gb_index_fetch_device(const mm2gb_index_t *ix_, int device, uint64_t *keys, int64_t *first, uint64_t *where, uint32_t *bucket)
+{
+	const SeedIndex *ix = reinterpret_cast<const SeedIndex*>(ix_);
+	if (!ix || !keys || !first || !where || !bucket) return fail("mm2gb_index_fetch_device: null argument");
+	std::lock_guard<std::mutex> lock(ix->dev_mu);
+	const SeedIndex::DevCopy *have = nullptr;
+	for (const SeedIndex::DevCopy &c : ix->dev) if (c.device == device) have = &c;
+	if (!have) return fail("mm2gb_index_fetch_device: the index is not resident on device " + std::to_string(device));
+	MM2GB_HIP(hipSetDevice(device));
+	hipStream_t s = nullptr;
+	MM2GB_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+	void *dst[4] = { keys, first, where, bucket };
+	const size_t bytes[4] = { ix->keys.size() * 8, ix->first.size() * 8, ix->where.size() * 8, ix->bucket.size() * 4 };
+	hipError_t err = hipSuccess;
+	for (int a = 0; a < 4 && err == hipSuccess; ++a) if (bytes[a]) err = hipMemcpyAsync(dst[a], have->ptr[a], bytes[a], hipMemcpyDeviceToHost, s);
+	const hipError_t done = hipStreamSynchronize(s);
+	(void)hipStreamDestroy(s);
+	if (err == hipSuccess) err = done;
+	if (err != hipSuccess) return fail(std::string("mm2gb_index_fetch_device: ") + hipGetErrorString(err));
+	return 0;
+}
+
+int mm2gb_index_build_split(const mm2gb_index_t *ix_, double *ms)
+{
+	const SeedIndex *ix = reinterpret_cast<const SeedIndex*>(ix_);
+	if (!ix || !ms) return fail("mm2gb_index_build_split: null argument");
+	for (int a = 0; a < 5; ++a) ms[a] = ix->build_ms[a];
+	return 0;
+}
+
 int mm2gb_collect_matches(const mm2gb_index_t *ix, const char *seq, int32_t len, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out)
 {
 	return collect_matches_refs(ix, seq, len, opt, out, nullptr);
@@ -313,6 +313,7 @@ int mm2gb::index_on_device(const mm2gb_index_t *ix_, int device, DevIndexView *o
 			return fail(std::string("mm2gb_index_to_device: the index does not fit the device: ") + hipGetErrorString(err));
 		}
 		ix->dev.push_back(c);
+		++ix->uploads;
 		have = &ix->dev.back();
 	}
 	out->keys = (const unsigned long long*)have->ptr[0]; out->first = (const long long*)have->ptr[1];
