@@ -242,9 +242,13 @@ int  mm2gb_gen_regs_gpu(mm2gb_engine_t *eng, int64_t n_reads, const mm2gb_chains
                         int is_qstrand, mm2gb_reg_t *regs);
 
 /* ---- from sequence to seed matches on the host (csrc/seeding.cpp), the reference's definitions to the letter:
- *      mm2gb_sketch: mm_sketch (sketch.c:77-143, no homopolymer compression): pairs (hash << 8 | span, rid << 32 | last_pos << 1 | strand);
+ *      mm2gb_sketch: mm_sketch (sketch.c:77-143): pairs (hash << 8 | span, rid << 32 | last_pos << 1 | strand).  The *_flag forms take
+ *      MM2GB_I_HPC (= MM_I_HPC): homopolymer-compressed minimizers (minimap2 -H, preset map-pb) -- one base per run in the k-mer, the span the
+ *      bases it covers, k-mers of 256 bases or more left out; the names without _flag are flag 0;
  *      mm2gb_index_*: every minimizer of the reference sequences -> its occurrences in ascending order, what mm_idx_get returns
  *      (index.c:81-98, 213-262); mid_occ as mm_mapopt_update computes it (options.c:78-84, index.c:186-211);
+ *      an index OWNS its flag (mm2gb_index_flag): every function that sketches reads for it -- mm2gb_collect_matches, its device form and
+ *      mm2gb_map_reads* on either side -- sketches them the way the index was;
  *      mm2gb_collect_matches: mm_collect_matches (seed.c:98-131, with seed.c:5-96) for one read of one segment: the arrays
  *      mm2gb_collect_seeds_gpu takes, plus rep_len and the minimizer positions the host's mapq / divergence estimates use.
  *      Free a matches record with mm2gb_matches_free, a sketch with mm2gb_free.  Sketch, look-up and match collection have a device
@@ -259,8 +263,12 @@ typedef struct {
 	uint64_t *hits;           /* n_hits: seed 0's, seed 1's, ... */
 	uint64_t *mini_pos;       /* n_mini_pos: q_span << 32 | position of the minimizer's last base (seed.c:125) */
 } mm2gb_matches_t;
+#define MM2GB_I_HPC 0x1
 int  mm2gb_sketch(const char *seq, int32_t len, int w, int k, uint32_t rid, uint64_t **out_xy, int64_t *n_out);
+int  mm2gb_sketch_flag(const char *seq, int32_t len, int w, int k, uint32_t rid, int flag, uint64_t **out_xy, int64_t *n_out);
 mm2gb_index_t *mm2gb_index_build(int k, int w, int32_t n_seq, const char *const *seqs, const int32_t *lens, int n_threads);
+mm2gb_index_t *mm2gb_index_build_flag(int k, int w, int flag, int32_t n_seq, const char *const *seqs, const int32_t *lens, int n_threads);
+int  mm2gb_index_flag(const mm2gb_index_t *ix);                                /* the MM2GB_I_* bits it was built with; negative on error */
 void mm2gb_index_destroy(mm2gb_index_t *ix);
 int64_t mm2gb_index_size(const mm2gb_index_t *ix, int64_t *n_occurrences);     /* distinct minimizers */
 int32_t mm2gb_index_mid_occ(const mm2gb_index_t *ix, float mid_occ_frac, int32_t min_mid_occ, int32_t max_mid_occ);
@@ -273,13 +281,16 @@ void mm2gb_matches_free(mm2gb_matches_t *m);
 /* ---- the same stages on the device (csrc/seed_kernels.hip), byte-identical to the host functions above, for a batch of sequences laid
  *      end to end (seq_off: n + 1 entries, seq_off[0] = 0, fewer than 2^31 bases in all):
  *      mm2gb_sketch_gpu: for sequence r exactly the pairs mm2gb_sketch(seqs + seq_off[r], len_r, w, k, rid ? rid[r] : 0) returns, in its
- *      order; mini_off (n_seqs + 1) says where each sequence's pairs begin in *out_xy (malloc'd, free with mm2gb_free);
+ *      order; mini_off (n_seqs + 1) says where each sequence's pairs begin in *out_xy (malloc'd, free with mm2gb_free); mm2gb_sketch_gpu_flag
+ *      likewise equals mm2gb_sketch_flag (a run of equal bases never continues into the next sequence);
  *      mm2gb_index_to_device: the index's copy in a device's memory (keys, first, where, bucket as they are); made on first use otherwise,
  *      released by mm2gb_index_destroy;
  *      mm2gb_collect_matches_gpu: for read r, seeds[seed_off[r] .. seed_off[r+1]), their hits, mini_pos and rep_len[r] are what
  *      mm2gb_collect_matches(ix, read r, opt) returns.  Free the batch with mm2gb_match_batch_free. ---- */
 int  mm2gb_sketch_gpu(mm2gb_engine_t *eng, int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs,
                       const uint32_t *rid, int64_t *mini_off, uint64_t **out_xy);
+int  mm2gb_sketch_gpu_flag(mm2gb_engine_t *eng, int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs,
+                           const uint32_t *rid, int64_t *mini_off, uint64_t **out_xy);
 int  mm2gb_index_to_device(mm2gb_index_t *ix, int device);
 typedef struct {
 	int64_t n_seeds, n_hits;
@@ -297,7 +308,7 @@ void mm2gb_match_batch_free(mm2gb_match_batch_t *m);
 /* ---- the index built on the device (csrc/index_kernels.hip): the sequences are sketched there in chunks of whole sequences (at most
  *      MM2GB_INDEX_CHUNK_BASES bases, read at call time, default 256 Mbp; a longer sequence is a chunk of its own, one of 2^31 - 1 bases is
  *      refused), the pairs sorted by (x >> 8, y) and the tables made there.
- *      mm2gb_index_build_gpu: arguments as mm2gb_index_build.  The host arrays of the result are byte-identical to mm2gb_index_build's, so
+ *      mm2gb_index_build_gpu(_flag): arguments as mm2gb_index_build(_flag).  The host arrays of the result are byte-identical to mm2gb_index_build's, so
  *      every function that takes an index works on it unchanged; the same arrays stay resident on the engine's device as that device's
  *      copy (nothing is uploaded on first use).  NULL on error (a HIP error or no room on the device included): never a host build instead.
  *      mm2gb_index_mid_occ_gpu: the value mm2gb_index_mid_occ returns, the quantile found on the device by an exact radix select over the
@@ -318,6 +329,7 @@ typedef struct {
 	const uint32_t *bucket;   /* n_bucket */
 } mm2gb_index_view_t;
 mm2gb_index_t *mm2gb_index_build_gpu(mm2gb_engine_t *eng, int k, int w, int32_t n_seq, const char *const *seqs, const int32_t *lens);
+mm2gb_index_t *mm2gb_index_build_gpu_flag(mm2gb_engine_t *eng, int k, int w, int flag, int32_t n_seq, const char *const *seqs, const int32_t *lens);
 int32_t mm2gb_index_mid_occ_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, float mid_occ_frac, int32_t min_mid_occ, int32_t max_mid_occ);
 int  mm2gb_index_view(const mm2gb_index_t *ix, mm2gb_index_view_t *out);
 int  mm2gb_index_fetch_device(const mm2gb_index_t *ix, int device, uint64_t *keys, int64_t *first, uint64_t *where, uint32_t *bucket);

@@ -87,7 +87,8 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
                 "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
                 "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free",
-                "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split"]
+                "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split",
+                "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -158,6 +159,13 @@ def lib():
         L.mm2gb_lchain_rmq_counts.restype = None
         L.mm2gb_sort_seeds_gpu.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.mm2gb_sketch.argtypes = [C.c_char_p, C.c_int32, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.mm2gb_sketch_flag.argtypes = [C.c_char_p, C.c_int32, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.mm2gb_index_build_flag.restype = C.c_void_p
+        L.mm2gb_index_build_flag.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int]
+        L.mm2gb_index_build_gpu_flag.restype = C.c_void_p
+        L.mm2gb_index_build_gpu_flag.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p]
+        L.mm2gb_index_flag.argtypes = [C.c_void_p]
+        L.mm2gb_sketch_gpu_flag.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.mm2gb_index_build.restype = C.c_void_p
         L.mm2gb_index_build.argtypes = [C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_int]
         L.mm2gb_index_destroy.restype = None
@@ -715,10 +723,25 @@ class Matches(C.Structure):
                 ("seeds", C.c_void_p), ("hits", C.c_void_p), ("mini_pos", C.c_void_p)]
 
 
-def sketch(seq, w=10, k=15, rid=0):
-    """mm2gb_sketch: the (w,k)-minimizers of a sequence (bytes) as an (n,2) uint64 array (x = hash << 8 | span, y = rid << 32 | pos << 1 | strand)."""
+I_HPC = 0x1    # MM2GB_I_HPC
+
+
+def preset(name):
+    """The index and seeding parameters of a minimap2 preset, as keywords for SeedIndex (k, w, hpc) and map_reads (k).  "map-pb" (alias
+    "map10k"): -H -k19 (options.c:102-103), w = 10.  No other preset: their mapping options are not the mapper's."""
+    if name in ("map-pb", "map10k"):
+        return dict(k=19, w=10, hpc=True)
+    raise Mm2gbError(f"preset {name!r} is not supported (map-pb / map10k only)")
+
+
+def sketch(seq, w=10, k=15, rid=0, hpc=False):
+    """mm2gb_sketch: the (w,k)-minimizers of a sequence (bytes) as an (n,2) uint64 array (x = hash << 8 | span, y = rid << 32 | pos << 1 | strand).
+    hpc: homopolymer-compressed (mm2gb_sketch_flag with MM2GB_I_HPC): pos is the last base of the k-mer's last run, span the bases it covers."""
     ptr, n = C.c_void_p(), C.c_int64()
-    _check(lib().mm2gb_sketch(seq, len(seq), w, k, rid, C.byref(ptr), C.byref(n)))
+    if hpc:
+        _check(lib().mm2gb_sketch_flag(seq, len(seq), w, k, rid, I_HPC, C.byref(ptr), C.byref(n)))
+    else:
+        _check(lib().mm2gb_sketch(seq, len(seq), w, k, rid, C.byref(ptr), C.byref(n)))
     out = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint64)), shape=(max(n.value, 1) * 2,))[:n.value * 2].reshape(-1, 2).copy()
     lib().mm2gb_free(ptr)
     return out
@@ -731,19 +754,33 @@ class IndexView(C.Structure):
 
 class SeedIndex:
     """Minimizer index of reference sequences (list of bytes) with the look-up semantics of the reference's mm_idx_get.  With an engine the
-    index is built on that engine's device (mm2gb_index_build_gpu) and stays resident there; its arrays are the host build's."""
+    index is built on that engine's device (mm2gb_index_build_gpu) and stays resident there; its arrays are the host build's.  hpc: the
+    minimizers are homopolymer-compressed; the index owns that choice: reads matched or mapped against it are sketched the same way."""
 
-    def __init__(self, seqs, k=15, w=10, threads=4, engine=None):
+    def __init__(self, seqs, k=15, w=10, threads=4, engine=None, hpc=False):
         self._seqs = [bytes(s) for s in seqs]
         arr = (C.c_char_p * len(self._seqs))(*self._seqs)
         lens = np.ascontiguousarray([len(s) for s in self._seqs], dtype=np.int32)
         self.lens = lens
-        if engine is not None:
+        if hpc:
+            if engine is not None:
+                self._h = lib().mm2gb_index_build_gpu_flag(engine._h, k, w, I_HPC, len(self._seqs), arr, lens.ctypes.data)
+            else:
+                self._h = lib().mm2gb_index_build_flag(k, w, I_HPC, len(self._seqs), arr, lens.ctypes.data, threads)
+        elif engine is not None:
             self._h = lib().mm2gb_index_build_gpu(engine._h, k, w, len(self._seqs), arr, lens.ctypes.data)
         else:
             self._h = lib().mm2gb_index_build(k, w, len(self._seqs), arr, lens.ctypes.data, threads)
         if not self._h:
             raise Mm2gbError(lib().mm2gb_last_error().decode())
+
+    @property
+    def hpc(self):
+        """Whether the index holds homopolymer-compressed minimizers (mm2gb_index_flag & MM2GB_I_HPC)."""
+        flag = int(lib().mm2gb_index_flag(self._h))
+        if flag < 0:
+            raise Mm2gbError(lib().mm2gb_last_error().decode())
+        return bool(flag & I_HPC)
 
     def close(self):
         if self._h:
@@ -831,15 +868,19 @@ def _take(ptr, n, dt):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * np.dtype(dt).itemsize,)).view(dt).copy()
 
 
-def _engine_sketch(self, seqs, w=10, k=15, rid=None):
+def _engine_sketch(self, seqs, w=10, k=15, rid=None, hpc=False):
     """mm2gb_sketch_gpu: the (w,k)-minimizers of a list of sequences (bytes) on the device: one (n,2) uint64 array per sequence, equal to
-    sketch(seq, w, k, rid[r])."""
+    sketch(seq, w, k, rid[r], hpc)."""
     seqs, off, flat = _lay_end_to_end(seqs)
     rids = np.ascontiguousarray(rid, dtype=np.uint32) if rid is not None else None
     mini_off = np.zeros(len(seqs) + 1, np.int64)
     ptr = C.c_void_p()
-    _check(lib().mm2gb_sketch_gpu(self._h, int(w), int(k), len(seqs), off.ctypes.data, flat, rids.ctypes.data if rids is not None else None,
-                                  mini_off.ctypes.data, C.byref(ptr)))
+    if hpc:
+        _check(lib().mm2gb_sketch_gpu_flag(self._h, int(w), int(k), I_HPC, len(seqs), off.ctypes.data, flat, rids.ctypes.data if rids is not None else None,
+                                           mini_off.ctypes.data, C.byref(ptr)))
+    else:
+        _check(lib().mm2gb_sketch_gpu(self._h, int(w), int(k), len(seqs), off.ctypes.data, flat, rids.ctypes.data if rids is not None else None,
+                                      mini_off.ctypes.data, C.byref(ptr)))
     xy = _take(ptr, int(mini_off[-1]) * 2, np.uint64).reshape(-1, 2)
     lib().mm2gb_free(ptr)
     return [xy[mini_off[r]:mini_off[r + 1]] for r in range(len(seqs))]

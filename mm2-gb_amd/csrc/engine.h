@@ -173,7 +173,7 @@ struct Engine {
 	int  collect_seeds(int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off, const uint64_t *hits,
 	                   const int32_t *qlen, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors);
 	// the minimizers of sequences laid end to end, left in sk_mini / sk_mini_read / sk_mini_off (arguments checked by the callers)
-	int  sketch_device(int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini);
+	int  sketch_device(int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini);
 	// mm_collect_matches for a batch, left in sd_seeds / sd_seed_off / sd_hit_off / sd_hits (+ sd_qlen, sd_mini_pos, sd_rep_len)
 	int  collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits);
 	// launch_collect_seeds on what collect_matches_device left (no name tests, no reference lengths: the flags the mapper takes)

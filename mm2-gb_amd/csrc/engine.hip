@@ -1112,7 +1112,7 @@ int Engine::collect_seeds(int64_t opt_flag, int64_t n_reads, const int64_t *seed
 }
 
 // The minimizer sketch of a batch of sequences (seed_kernels.hip).  Two waits: for the number of pairs (the output is sized by it).
-int Engine::sketch_device(int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini)
+int Engine::sketch_device(int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini)
 {
 	const int64_t n = seq_off[n_seqs];
 	const size_t ns = (size_t)n_seqs;
@@ -1128,7 +1128,7 @@ int Engine::sketch_device(int w, int k, int64_t n_seqs, const int64_t *seq_off, 
 	SketchBatch b;
 	memset(&b, 0, sizeof b);
 	b.seqs = (const unsigned char*)sk_seqs.ptr; b.seq_off = (const int64_t*)sk_seq_off.ptr; b.rid = rid ? (const uint32_t*)sk_rid.ptr : nullptr;
-	b.n_seqs = n_seqs; b.n = n; b.w = w; b.k = k;
+	b.n_seqs = n_seqs; b.n = n; b.w = w; b.k = k; b.hpc = (flag & MM2GB_I_HPC) != 0;
 	if (sk_work.ensure(sketch_layout(b, nullptr))) return -1;
 	sketch_layout(b, sk_work.ptr);
 	b.mini_off = (int64_t*)sk_mini_off.ptr;
@@ -1150,7 +1150,7 @@ int Engine::collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_
 {
 	int64_t n_mini = 0;
 	*n_seeds = *n_hits = 0;
-	if (sketch_device(ix.w, ix.k, n_reads, seq_off, seqs, nullptr, &n_mini)) return -1;
+	if (sketch_device(ix.w, ix.k, ix.flag, n_reads, seq_off, seqs, nullptr, &n_mini)) return -1;
 	const size_t nr = (size_t)n_reads, nm = (size_t)n_mini;
 	if (sd_seeds.ensure(std::max<size_t>(nm, 1) * 16) || sd_seed_off.ensure((nr + 1) * 8) || sd_hit_off.ensure((nm + 1) * 8) || sd_qlen.ensure(std::max<size_t>(nr, 1) * 4) ||
 	    sd_src_first.ensure(std::max<size_t>(nm, 1) * 8) || sd_mini_pos.ensure(std::max<size_t>(nm, 1) * 8) || sd_rep_len.ensure(std::max<size_t>(nr, 1) * 4)) return -1;
@@ -1589,7 +1589,14 @@ static int check_seq_off(const char *who, int64_t n, const int64_t *seq_off, con
 
 int mm2gb_sketch_gpu(mm2gb_engine_t *eng, int w, int k, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *mini_off, uint64_t **out_xy)
 {
+	return mm2gb_sketch_gpu_flag(eng, w, k, 0, n_seqs, seq_off, seqs, rid, mini_off, out_xy);
+}
+
+int mm2gb_sketch_gpu_flag(mm2gb_engine_t *eng, int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *mini_off,
+                          uint64_t **out_xy)
+{
 	if (!eng || !mini_off || !out_xy) return fail("mm2gb_sketch_gpu: null argument");
+	if (flag & ~MM2GB_I_HPC) return fail("mm2gb_sketch_gpu: unknown flag (MM2GB_I_HPC only)");
 	if (w < 1 || w > 255 || k < 1 || k > 28) return fail("mm2gb_sketch_gpu: bad arguments (0 < w < 256, 0 < k <= 28)");
 	if (check_seq_off("mm2gb_sketch_gpu", n_seqs, seq_off, seqs)) return -1;
 	Engine &e = eng->e;
@@ -1597,7 +1604,7 @@ int mm2gb_sketch_gpu(mm2gb_engine_t *eng, int w, int k, int64_t n_seqs, const in
 	int64_t n_mini = 0;
 	if (n_seqs == 0) mini_off[0] = 0;
 	else {
-		if (e.sketch_device(w, k, n_seqs, seq_off, seqs, rid, &n_mini)) return -1;
+		if (e.sketch_device(w, k, flag, n_seqs, seq_off, seqs, rid, &n_mini)) return -1;
 		MM2GB_HIP(hipMemcpyAsync(mini_off, e.sk_mini_off.ptr, (size_t)(n_seqs + 1) * 8, hipMemcpyDeviceToHost, e.stream));
 	}
 	*out_xy = (uint64_t*)malloc(((size_t)n_mini + 1) * 16);

@@ -12,6 +12,7 @@ namespace mm2gb {
 
 struct SeedIndex {
 	int k = 15, w = 10;
+	int flag = 0;                           // MM2GB_I_*: how the sequences were sketched, and how every read mapped against it is
 	std::vector<int32_t> lens;
 	std::vector<uint64_t> keys;             // distinct minimizers (x >> 8), ascending
 	std::vector<int64_t> first;             // keys.size() + 1: where each one's occurrences begin

@@ -299,7 +299,7 @@ int copy_back(Build &B, const std::vector<std::pair<char*, const char*>> &arrays
 	return land(pieces.size() - 1);
 }
 
-int build_on_device(Engine &e, SeedIndex *ix, int k, int w, int32_t n_seq, const char *const *seqs, const int32_t *lens)
+int build_on_device(Engine &e, SeedIndex *ix, int k, int w, int flag, int32_t n_seq, const char *const *seqs, const int32_t *lens)
 {
 	// chunks of whole sequences
 	int64_t limit = (int64_t)256 << 20;
@@ -335,7 +335,7 @@ int build_on_device(Engine &e, SeedIndex *ix, int k, int w, int32_t n_seq, const
 		SketchBatch b;
 		memset(&b, 0, sizeof b);
 		b.seq_off = (const int64_t*)d; b.rid = (const uint32_t*)(d + o_rid); b.seqs = (const unsigned char*)(d + o_seq);
-		b.n_seqs = (int64_t)ns; b.n = ch.bases; b.w = w; b.k = k;
+		b.n_seqs = (int64_t)ns; b.n = ch.bases; b.w = w; b.k = k; b.hpc = (flag & MM2GB_I_HPC) != 0;
 		if (e.sk_work.ensure(sketch_layout(b, nullptr)) || e.sk_mini_off.ensure((ns + 1) * 8)) return -1;
 		sketch_layout(b, e.sk_work.ptr);
 		b.mini_off = (int64_t*)e.sk_mini_off.ptr;
@@ -435,12 +435,18 @@ extern "C" {
 
 mm2gb_index_t *mm2gb_index_build_gpu(mm2gb_engine_t *eng, int k, int w, int32_t n_seq, const char *const *seqs, const int32_t *lens)
 {
+	return mm2gb_index_build_gpu_flag(eng, k, w, 0, n_seq, seqs, lens);
+}
+
+mm2gb_index_t *mm2gb_index_build_gpu_flag(mm2gb_engine_t *eng, int k, int w, int flag, int32_t n_seq, const char *const *seqs, const int32_t *lens)
+{
 	if (!eng) { fail("mm2gb_index_build_gpu: null engine"); return nullptr; }
 	if (n_seq < 0 || (n_seq > 0 && (!seqs || !lens)) || w < 1 || w > 255 || k < 1 || k > 28) { fail("mm2gb_index_build_gpu: bad arguments (0 < w < 256, 0 < k <= 28)"); return nullptr; }
+	if (flag & ~MM2GB_I_HPC) { fail("mm2gb_index_build_gpu: unknown flag (MM2GB_I_HPC only)"); return nullptr; }
 	SeedIndex *ix = new SeedIndex;
-	ix->k = k; ix->w = w;
+	ix->k = k; ix->w = w; ix->flag = flag;
 	if (n_seq > 0) ix->lens.assign(lens, lens + n_seq);
-	if (build_on_device(eng->e, ix, k, w, n_seq, seqs, lens)) {                   // an error of the call: never the host build instead
+	if (build_on_device(eng->e, ix, k, w, flag, n_seq, seqs, lens)) {                   // an error of the call: never the host build instead
 		const std::string why = mm2gb_last_error();
 		if (why.rfind("mm2gb_index_build_gpu", 0) != 0) fail("mm2gb_index_build_gpu: " + why);
 		mm2gb_index_destroy(reinterpret_cast<mm2gb_index_t*>(ix));

@@ -15,6 +15,7 @@ struct DevIndexView {
 	const uint32_t           *bucket;   // n_bucket entries
 	unsigned long long        n_bucket;
 	int                       bucket_shift, k, w;
+	int                       flag;     // MM2GB_I_*: reads are sketched the way the index was
 };
 
 // carves arrays out of one arena; base == nullptr: only adds up what is needed
@@ -32,6 +33,8 @@ struct Carver {
 
 // The sketch by POSITION: sequences laid end to end, n bases in all (< 2^31).  Positions are global; a COUNTED position is
 // one the serial loop gives a ring slot to (everything but the k-mers equal to their reverse complement).
+// hpc != 0: homopolymer-compressed.  The loop's steps are the BOUNDARIES -- the first base of every run of equal bases and every ambiguous
+// base; a run ends with its sequence --, the other positions count as skipped; a step's position is its run's last base.
 struct SketchBatch {
 	const unsigned char *seqs;         // n + 1 bytes, the last one 'N'
 	const int64_t  *seq_off;           // n_seqs + 1
@@ -39,12 +42,12 @@ struct SketchBatch {
 	int64_t         n_seqs, n;
 	int             w, k;
 	// scratch (n + 1 entries each)
-	uint32_t *n_valid;                 // A/C/G/T before each position
+	uint32_t *n_valid;                 // A/C/G/T before each position (hpc: run starts before each position)
 	uint32_t *n_skip;                  // skipped positions before each position
 	uint32_t *last_n;                  // 1 + the last ambiguous position at or before each position (0: none)
-	unsigned char *comp;               // the sequences without their ambiguous bases, each at its own offset
-	unsigned char *flags;              // 1 valid | 2 skipped | 4 strand
-	unsigned long long *hx;            // hash << 8 | k of the canonical k-mer ending here
+	unsigned char *comp;               // the sequences without their ambiguous bases, each at its own offset (hpc: a base per run)
+	unsigned char *flags;              // 1 valid | 2 skipped | 4 strand (hpc, before the words: 1 run start | 2 ambiguous)
+	unsigned long long *hx;            // hash << 8 | span of the canonical k-mer ending here (hpc: ~0 where the span is 256 or more)
 	unsigned long long *vx;            // by counted position: the step's value (~0: none)
 	uint32_t *vy;                      // by counted position: position in the sequence << 1 | strand
 	uint32_t *vrun;                    // by counted position: min(run, w + k)
@@ -56,6 +59,10 @@ struct SketchBatch {
 	int64_t  *mini_off;                // n_seqs + 1
 	ulonglong2 *mini;                  // the pairs (set before launch_sketch_write)
 	int32_t  *mini_read;               // their sequence
+	// homopolymer compression (after everything else: the plain kernels' argument offsets stay what they were)
+	int       hpc;
+	uint32_t *n_bnd;                   // scratch, hpc only (n + 1 entries): boundaries before each position
+	uint32_t *bnd_pos;                 // scratch, hpc only (n + 2 entries): the boundaries' positions; position n is the last one
 };
 size_t sketch_layout(SketchBatch &b, void *base);            // sets the scratch pointers inside base; returns the bytes needed
 int    launch_sketch_count(const SketchBatch &b, hipStream_t s);   // through mini_off; -1: a library scan refused

@@ -10,6 +10,11 @@
 // So: prefix sums (library scans), one thread per position for the words, one thread per counted position for what it emits, a scan of
 // the counts, the same threads again to write.  A thread reads its w predecessors' values from memory: neighbours read the same lines.
 //
+// Homopolymer compression (sketch.c:94-105) in the same form: the loop's steps are the BOUNDARIES -- a run's first base, an ambiguous base --,
+// every other position counts as skipped.  Both compactions (a base per run; the boundaries' positions) are scans; a run's last base is the
+// next boundary's position (or the sequence's end) minus one; between two ambiguous bases the runs are contiguous, so the span of the last
+// min(k, m) runs is a difference of two positions.  No thread walks along a run.  k_hp_* below; k_sk_cstart / k_sk_emit / k_sk_mini_off serve both.
+//
 // Matches: q-occurrence filter by a segmented sort of the reads' values, look-up as SeedIndex::find, streak thinning by RANK -- in a streak
 // of matches above mid_occ the survivors are the K smallest by (n, index): a radix select per streak, by a workgroup --, repeat length by a
 // wave per read, offsets by scans, hits gathered 64 seeds per wave.
@@ -212,7 +217,134 @@ __global__ __launch_bounds__(TB) void k_sk_mini_off(SketchBatch b)
 	if (r <= b.n_seqs) b.mini_off[r] = b.emit_off[b.cstart[r]];
 }
 
+// ---- homopolymer-compressed (b.hpc): the boundaries, their compactions, the words and the values; the rest is shared with the plain form
+struct RunOf { __host__ __device__ uint32_t operator()(unsigned char f) const { return f & 1u; } };
+struct BndOf { __host__ __device__ uint32_t operator()(unsigned char f) const { return f ? 1u : 0u; } };
+
+hipError_t scan_runs(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
+{
+	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator((const unsigned char*)b.flags, RunOf()), b.n_valid, 0u, (size_t)b.n + 1, rocprim::plus<uint32_t>(), s);
+}
+hipError_t scan_bnd(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
+{
+	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator((const unsigned char*)b.flags, BndOf()), b.n_bnd, 0u, (size_t)b.n + 1, rocprim::plus<uint32_t>(), s);
+}
+
+// flags: 1 the first base of a run (a run does not continue from the sequence before), 2 an ambiguous base, 0 inside a run.  Position n
+// is a boundary: every run ends before it
+__global__ __launch_bounds__(TB) void k_hp_bound(SketchBatch b)
+{
+	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+	const bool in = i < b.n;
+	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
+	if (i == b.n) b.flags[i] = 2;
+	if (!in) return;
+	const int c = base_code_d(b.seqs[i]);
+	b.flags[i] = (unsigned char)(c >= 4 ? 2 : (i == b.seq_off[r] || base_code_d(b.seqs[i - 1]) != c) ? 1 : 0);
+}
+
+// the boundaries' positions, and the sequences with a base per run and without their ambiguous bases, each from its own offset on
+__global__ __launch_bounds__(TB) void k_hp_compact(SketchBatch b)
+{
+	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+	const bool in = i < b.n;
+	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
+	if (i > b.n) return;
+	const unsigned fl = b.flags[i];
+	if (fl == 0) return;
+	b.bnd_pos[b.n_bnd[i]] = (uint32_t)i;
+	if (fl != 1 || !in) return;
+	const int64_t s0 = b.seq_off[r];
+	b.comp[s0 + (b.n_valid[i] - b.n_valid[s0])] = (unsigned char)base_code_d(b.seqs[i]);
+}
+
+// where the run that begins at boundary i ends: before the next boundary, or with its sequence
+__device__ inline int64_t run_end(const SketchBatch &b, int64_t i, int64_t r)
+{
+	return std::min<int64_t>((int64_t)b.bnd_pos[b.n_bnd[i] + 1], b.seq_off[r + 1]) - 1;
+}
+
+// k_sk_words at a run's first base: the words from the last k runs' bases, the span from the first of the last min(k, m) runs' positions
+// (m: runs since the last ambiguous base, this one included) to this run's end.  flags become what k_sk_words leaves; inside a run: skipped
+__global__ __launch_bounds__(TB) void k_hp_words(SketchBatch b)
+{
+	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+	const bool in = i < b.n;
+	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
+	if (i == b.n) b.flags[i] = 0;
+	if (!in) return;
+	const unsigned bnd = b.flags[i];
+	if (bnd != 1) { b.flags[i] = (unsigned char)(bnd == 0 ? 2 : 0); return; }
+	const int64_t s0 = b.seq_off[r];
+	const int64_t o = (int64_t)(b.n_valid[i] - b.n_valid[s0]);
+	const unsigned char *at = b.comp + s0 + o;
+	const int top = 2 * (b.k - 1);
+	const int have = (int)(o + 1 < b.k ? o + 1 : b.k);
+	unsigned long long f = 0, rv = 0;
+	for (int d = 0; d < have; ++d) {
+		const unsigned long long c = at[-d];
+		f |= c << (2 * d);
+		rv |= (3 ^ c) << (top - 2 * d);
+	}
+	const unsigned long long mask = (1ull << (2 * b.k)) - 1;
+	const bool skip = f == rv;
+	const unsigned strand = f < rv ? 0u : 1u;
+	const int64_t j = std::max<int64_t>((int64_t)b.last_n[i], s0);
+	const uint32_t m = b.n_valid[i] + 1 - b.n_valid[j];
+	const int64_t from = (int64_t)b.bnd_pos[b.n_bnd[i] + 1 - std::min<uint32_t>(m, (uint32_t)b.k)];
+	const int64_t span = run_end(b, i, r) - from + 1;
+	b.hx[i] = span < 256 ? mix_d(strand ? rv : f, mask) << 8 | (unsigned long long)span : NONE;
+	b.flags[i] = (unsigned char)(1u | (skip ? 2u : 0u) | strand << 2);
+}
+
+// k_sk_values: the position is the run's last base, the run of counted steps since the last ambiguous base has only run starts in it
+__global__ __launch_bounds__(TB) void k_hp_values(SketchBatch b)
+{
+	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+	const bool in = i < b.n;
+	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
+	if (!in) return;
+	const unsigned fl = b.flags[i];
+	if (fl & 2u) return;
+	const int64_t g = i - (int64_t)b.n_skip[i];
+	const int64_t s0 = b.seq_off[r];
+	uint32_t run = 0;
+	int64_t end = i;
+	if (fl & 1u) {
+		const int64_t j = std::max<int64_t>((int64_t)b.last_n[i], s0);
+		run = (uint32_t)(i + 1 - j) - (b.n_skip[i + 1] - b.n_skip[j]);
+		end = run_end(b, i, r);
+	}
+	b.vx[g] = ((fl & 1u) && run >= (uint32_t)b.k) ? b.hx[i] : NONE;
+	b.vy[g] = (uint32_t)(end - s0) << 1 | ((fl >> 2) & 1u);
+	b.vrun[g] = std::min<uint32_t>(run, (uint32_t)(b.w + b.k));
+}
+
 unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + TB - 1) / TB); }
+
+int launch_sketch_count_hpc(const SketchBatch &b, hipStream_t s)
+{
+	const unsigned gp = blocks(b.n + 1), gs = blocks(b.n_seqs + 1);
+	size_t q;
+	hipLaunchKernelGGL(k_hp_bound, dim3(gp), dim3(TB), 0, s, b);
+	q = b.tmp_bytes;
+	if (scan_runs(b, b.tmp, q, s) != hipSuccess) return -1;
+	q = b.tmp_bytes;
+	if (scan_bnd(b, b.tmp, q, s) != hipSuccess) return -1;
+	q = b.tmp_bytes;
+	if (scan_last_n(b, b.tmp, q, s) != hipSuccess) return -1;
+	hipLaunchKernelGGL(k_hp_compact, dim3(gp), dim3(TB), 0, s, b);
+	hipLaunchKernelGGL(k_hp_words, dim3(gp), dim3(TB), 0, s, b);
+	q = b.tmp_bytes;
+	if (scan_skip(b, b.tmp, q, s) != hipSuccess) return -1;
+	hipLaunchKernelGGL(k_sk_cstart, dim3(gs), dim3(TB), 0, s, b);
+	hipLaunchKernelGGL(k_hp_values, dim3(gp), dim3(TB), 0, s, b);
+	hipLaunchKernelGGL(k_sk_emit<false>, dim3(gp), dim3(TB), 0, s, b);
+	q = b.tmp_bytes;
+	if (scan_emit(b, b.tmp, q, s) != hipSuccess) return -1;
+	hipLaunchKernelGGL(k_sk_mini_off, dim3(gs), dim3(TB), 0, s, b);
+	return 0;
+}
 
 } // namespace
 
@@ -227,6 +359,12 @@ size_t sketch_layout(SketchBatch &b, void *base)
 	b.cstart = c.take<int64_t>(s1);
 	b.emit_cnt = c.take<uint32_t>(n1); b.emit_off = c.take<int64_t>(n1);
 	size_t need = 0, q = 0;
+	b.n_bnd = b.bnd_pos = nullptr;
+	if (b.hpc) {
+		b.n_bnd = c.take<uint32_t>(n1); b.bnd_pos = c.take<uint32_t>(n1 + 1);
+		(void)scan_runs(b, nullptr, q, 0); need = std::max(need, q);
+		(void)scan_bnd(b, nullptr, q, 0); need = std::max(need, q);
+	}
 	(void)scan_valid(b, nullptr, q, 0); need = std::max(need, q);
 	(void)scan_skip(b, nullptr, q, 0); need = std::max(need, q);
 	(void)scan_last_n(b, nullptr, q, 0); need = std::max(need, q);
@@ -238,6 +376,7 @@ size_t sketch_layout(SketchBatch &b, void *base)
 
 int launch_sketch_count(const SketchBatch &b, hipStream_t s)
 {
+	if (b.hpc) return launch_sketch_count_hpc(b, s);
 	const unsigned gp = blocks(b.n + 1), gs = blocks(b.n_seqs + 1);
 	size_t q = b.tmp_bytes;
 	if (scan_valid(b, b.tmp, q, s) != hipSuccess) return -1;

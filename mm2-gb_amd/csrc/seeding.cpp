@@ -1,7 +1,8 @@
 // seeding.cpp -- from sequence to seed matches, written from scratch (the producer side of the path).
 //
-//   sketch            (w,k)-minimizers of a sequence, the reference's definition to the letter (sketch.c:77-143, non-HPC): the hash of
-//                     the canonical k-mer (sketch.c:29-39), ties inside a window kept, the special first window, ambiguous bases
+//   sketch            (w,k)-minimizers of a sequence, the reference's definition to the letter (sketch.c:77-143, plain and homopolymer-
+//                     compressed): the hash of the canonical k-mer (sketch.c:29-39), ties inside a window kept, the special first window,
+//                     ambiguous bases
 //   Index             every minimizer of the reference sequences -> its occurrences  rid << 32 | last_pos << 1 | strand  in ascending
 //                     order: what mm_idx_get hands out (index.c:81-98; the order is that of radix_sort_64 in index.c:251), and the
 //                     occurrence threshold mid_occ of mm_mapopt_update (options.c:78-84 with index.c:186-211)
@@ -51,21 +52,33 @@ inline uint64_t mix(uint64_t key, uint64_t mask)
 	return key;
 }
 
-// sketch.c:77-143 without homopolymer compression.  A ring of the last w k-mers (slot = k-mer number mod w); the current minimum and
+// sketch.c:77-143.  A ring of the last w k-mers (slot = k-mer number mod w); the current minimum and
 // its slot; what is emitted when, in this order: the k-mers equal to the minimum of the FIRST full window; the old minimum when a
 // k-mer at least as small arrives or when it leaves the window; after a rescan, the other k-mers equal to the new minimum.
-void sketch(const char *seq, int len, int w, int k, uint32_t rid, std::vector<Mini> &out)
+// hpc (sketch.c:94-105): a step per homopolymer run -- i jumps to the run's last base, the words take one base per run, the span is the summed
+// length of the last k runs (a queue of run lengths, emptied at an ambiguous base); a k-mer of 256 bases or more has no value but counts.
+void sketch(const char *seq, int len, int w, int k, uint32_t rid, bool hpc, std::vector<Mini> &out)
 {
 	const uint64_t none = ~0ull, mask = (1ull << 2 * k) - 1, top_shift = 2 * (k - 1);
 	uint64_t fwd = 0, rev = 0;
 	std::vector<Mini> ring((size_t)w, Mini{ none, none });
 	Mini best{ none, none };
 	int run = 0, slot = 0, best_slot = 0;       // run: valid bases since the last ambiguous one (k-mers ending here: run - k + 1)
+	int run_len[32], q_front = 0, q_count = 0, hpc_span = 0;     // hpc: the lengths of the last k runs (tiny_queue_t, sketch.c:41-58) and their sum
 	for (int i = 0; i < len; ++i) {
 		const int c = base_code((unsigned char)seq[i]);
 		Mini cur{ none, none };
 		if (c < 4) {
-			const int span = run + 1 < k ? run + 1 : k;
+			int span;
+			if (hpc) {
+				int skip_len = 1;
+				while (i + skip_len < len && base_code((unsigned char)seq[i + skip_len]) == c) ++skip_len;
+				i += skip_len - 1;                      // at the run's last base
+				run_len[(q_front + q_count++) & 31] = skip_len;
+				hpc_span += skip_len;
+				if (q_count > k) { hpc_span -= run_len[q_front]; q_front = (q_front + 1) & 31; --q_count; }
+				span = hpc_span;
+			} else span = run + 1 < k ? run + 1 : k;
 			fwd = (fwd << 2 | (uint64_t)c) & mask;
 			rev = rev >> 2 | (uint64_t)(3 ^ c) << top_shift;
 			if (fwd == rev) continue;               // its own reverse complement: no strand, and it does not count as a base seen
@@ -75,7 +88,7 @@ void sketch(const char *seq, int len, int w, int k, uint32_t rid, std::vector<Mi
 				cur.x = mix(strand ? rev : fwd, mask) << 8 | (uint64_t)span;
 				cur.y = (uint64_t)rid << 32 | (uint64_t)(uint32_t)i << 1 | (uint64_t)strand;
 			}
-		} else run = 0;
+		} else { run = 0; q_front = q_count = 0; hpc_span = 0; }
 		ring[(size_t)slot] = cur;
 		auto twins = [&](int from, int to) {     // k-mers in slots [from, to) with the minimum's value at another position
 			for (int j = from; j < to; ++j)
@@ -155,9 +168,15 @@ extern "C" {
 
 int mm2gb_sketch(const char *seq, int32_t len, int w, int k, uint32_t rid, uint64_t **out_xy, int64_t *n_out)
 {
+	return mm2gb_sketch_flag(seq, len, w, k, rid, 0, out_xy, n_out);
+}
+
+int mm2gb_sketch_flag(const char *seq, int32_t len, int w, int k, uint32_t rid, int flag, uint64_t **out_xy, int64_t *n_out)
+{
 	if (!seq || !out_xy || !n_out || len < 0 || w < 1 || w > 255 || k < 1 || k > 28) return fail("mm2gb_sketch: bad arguments (0 < w < 256, 0 < k <= 28)");
+	if (flag & ~MM2GB_I_HPC) return fail("mm2gb_sketch: unknown flag (MM2GB_I_HPC only)");
 	std::vector<Mini> v;
-	if (len > 0) sketch(seq, len, w, k, rid, v);
+	if (len > 0) sketch(seq, len, w, k, rid, (flag & MM2GB_I_HPC) != 0, v);
 	*n_out = (int64_t)v.size();
 	*out_xy = (uint64_t*)malloc((v.size() + 1) * 16);
 	if (!*out_xy) return fail("mm2gb_sketch: out of memory");
@@ -167,13 +186,26 @@ int mm2gb_sketch(const char *seq, int32_t len, int w, int k, uint32_t rid, uint6
 
 mm2gb_index_t *mm2gb_index_build(int k, int w, int32_t n_seq, const char *const *seqs, const int32_t *lens, int n_threads)
 {
+	return mm2gb_index_build_flag(k, w, 0, n_seq, seqs, lens, n_threads);
+}
+
+int mm2gb_index_flag(const mm2gb_index_t *ix_)
+{
+	const SeedIndex *ix = reinterpret_cast<const SeedIndex*>(ix_);
+	return ix ? ix->flag : fail("mm2gb_index_flag: null argument");
+}
+
+mm2gb_index_t *mm2gb_index_build_flag(int k, int w, int flag, int32_t n_seq, const char *const *seqs, const int32_t *lens, int n_threads)
+{
 	if (n_seq < 0 || (n_seq > 0 && (!seqs || !lens)) || w < 1 || w > 255 || k < 1 || k > 28) { fail("mm2gb_index_build: bad arguments (0 < w < 256, 0 < k <= 28)"); return nullptr; }
+	if (flag & ~MM2GB_I_HPC) { fail("mm2gb_index_build: unknown flag (MM2GB_I_HPC only)"); return nullptr; }
 	SeedIndex *ix = new SeedIndex;
-	ix->k = k; ix->w = w;
+	ix->k = k; ix->w = w; ix->flag = flag;
+	const bool hpc = (flag & MM2GB_I_HPC) != 0;
 	ix->lens.assign(lens, lens + n_seq);
 	std::vector<std::vector<Mini>> per((size_t)n_seq);
 	std::atomic<int32_t> next(0);
-	auto work = [&]() { for (;;) { const int32_t s = next.fetch_add(1); if (s >= n_seq) break; if (lens[s] > 0) sketch(seqs[s], lens[s], w, k, (uint32_t)s, per[(size_t)s]); } };
+	auto work = [&]() { for (;;) { const int32_t s = next.fetch_add(1); if (s >= n_seq) break; if (lens[s] > 0) sketch(seqs[s], lens[s], w, k, (uint32_t)s, hpc, per[(size_t)s]); } };
 	if (n_threads < 2) work();
 	else { std::vector<std::thread> pool; for (int t = 0; t < n_threads; ++t) pool.emplace_back(work); for (auto &th : pool) th.join(); }
 	size_t total = 0;
@@ -318,7 +350,7 @@ int mm2gb::index_on_device(const mm2gb_index_t *ix_, int device, DevIndexView *o
 	}
 	out->keys = (const unsigned long long*)have->ptr[0]; out->first = (const long long*)have->ptr[1];
 	out->where = (const unsigned long long*)have->ptr[2]; out->bucket = (const uint32_t*)have->ptr[3];
-	out->n_bucket = ix->bucket.size(); out->bucket_shift = ix->bucket_shift; out->k = ix->k; out->w = ix->w;
+	out->n_bucket = ix->bucket.size(); out->bucket_shift = ix->bucket_shift; out->k = ix->k; out->w = ix->w; out->flag = ix->flag;
 	return 0;
 }
 
@@ -330,7 +362,7 @@ int mm2gb::collect_matches_refs(const mm2gb_index_t *ix_, const char *seq, int32
 	if (!ix || !opt || !out || len < 0 || (len > 0 && !seq)) return fail("mm2gb_collect_matches: null argument");
 	memset(out, 0, sizeof(*out));
 	std::vector<Mini> mv;
-	if (len > 0) sketch(seq, len, ix->w, ix->k, 0, mv);                       // map.c:186-199, one segment
+	if (len > 0) sketch(seq, len, ix->w, ix->k, 0, (ix->flag & MM2GB_I_HPC) != 0, mv);                   // map.c:186-199, one segment
 	// seed.c:5-30: a minimizer that makes up more than q_occ_frac of the read's minimizers (and more than mid_occ of them) goes
 	if (opt->q_occ_frac > 0.0f && opt->mid_occ > 0 && (int64_t)mv.size() > opt->mid_occ) {
 		// occurrences of every minimizer value in the read, counted in an open-addressed table (the reference sorts a copy, seed.c:12-16; what

@@ -3,8 +3,9 @@
 csrc/index_kernels.hip: mm2gb_index_build_gpu, mm2gb_index_mid_occ_gpu) on sim_reads.make_genome genomes of three sizes.  Both forms run in
 one process, alternated, `--runs` timed runs each after one untimed warm-up of each; the warm-up also checks that the two indexes are
 identical.  For the host form the time until the index is usable on the device is reported too (build + mm2gb_index_to_device); the device
-form's split (H2D, sketch, sort, tables, D2H) comes from events on the engine's streams (H2D overlaps the sketch).
-The measurement runs in a child process under a time limit of its own:   python profiles/index_rate.py [--mbp 10,100,1000] [--out FILE]"""
+form's split (H2D, sketch, sort, tables, D2H) comes from events on the engine's streams (H2D overlaps the sketch).  --hpc: both forms
+with homopolymer-compressed minimizers at k = 19, w = 10 (preset map-pb; the k_hp_* kernels of csrc/seed_kernels.hip).
+The measurement runs in a child process under a time limit of its own:   python profiles/index_rate.py [--mbp 10,100,1000] [--hpc] [--out FILE]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -31,14 +32,15 @@ def measure(args):
     if mm.device_count() < 1:
         raise SystemExit("index_rate: no GPU visible (nothing is measured without one)")
     L = mm.lib()
-    out = {"host_threads": args.threads, "runs": args.runs, "chunk_bases": int(os.environ.get("MM2GB_INDEX_CHUNK_BASES", 256 << 20)), "sizes": []}
+    kw = mm.preset("map-pb") if args.hpc else {}
+    out = {"host_threads": args.threads, "runs": args.runs, "hpc": bool(args.hpc), "k": kw.get("k", 15), "w": kw.get("w", 10), "chunk_bases": int(os.environ.get("MM2GB_INDEX_CHUNK_BASES", 256 << 20)), "sizes": []}
     with mm.Engine() as e:
         for mbp in args.mbp:
             seqs, t_gen = genome(mbp, 1000 + mbp)
             rec = {"mbp": mbp, "bases": sum(len(s) for s in seqs), "n_seq": len(seqs), "genome_seconds": round(t_gen, 2)}
             print(f"index_rate: {mbp} Mbp generated in {t_gen:.1f} s", file=sys.stderr, flush=True)
             # warm-up of each form, untimed; the two indexes must be the same index
-            with mm.SeedIndex(seqs, threads=args.threads) as h, mm.SeedIndex(seqs, engine=e) as d:
+            with mm.SeedIndex(seqs, threads=args.threads, **kw) as h, mm.SeedIndex(seqs, engine=e, **kw) as d:
                 hv, dv, rv = h.view(), d.view(), d.fetch_device(e.device)
                 rec["identical"] = bool(all(np.array_equal(hv[a], dv[a]) and np.array_equal(hv[a], rv[a]) for a in ("keys", "first", "where", "bucket"))
                                         and hv["bucket_shift"] == dv["bucket_shift"])
@@ -48,7 +50,7 @@ def measure(args):
                 del hv, dv, rv
             rec.update(host_build_s=[], host_to_device_s=[], device_build_s=[], device_split_ms=[], mid_occ_host_s=[], mid_occ_device_s=[])
             for run in range(args.runs):
-                h, t = timed(lambda: mm.SeedIndex(seqs, threads=args.threads))
+                h, t = timed(lambda: mm.SeedIndex(seqs, threads=args.threads, **kw))
                 rec["host_build_s"].append(round(t, 4))
                 rc, t = timed(lambda: L.mm2gb_index_to_device(h._h, e.device))
                 assert rc == 0
@@ -56,7 +58,7 @@ def measure(args):
                 _, t = timed(lambda: h.mid_occ())
                 rec["mid_occ_host_s"].append(round(t, 5))
                 h.close()
-                d, t = timed(lambda: mm.SeedIndex(seqs, engine=e))
+                d, t = timed(lambda: mm.SeedIndex(seqs, engine=e, **kw))
                 rec["device_build_s"].append(round(t, 4))
                 rec["device_split_ms"].append({k: round(v, 3) for k, v in d.build_split().items()})
                 _, t = timed(lambda: d.mid_occ(engine=e))
@@ -75,6 +77,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=1000, help="seconds the measuring child process may take")
+    ap.add_argument("--hpc", action="store_true", help="homopolymer-compressed minimizers, k = 19, w = 10 (preset map-pb)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -82,7 +85,7 @@ def main():
         print(json.dumps(measure(args)))
         return 0
     cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--worker", "--mbp", ",".join(map(str, args.mbp)),
-           "--threads", str(args.threads), "--runs", str(args.runs)]
+           "--threads", str(args.threads), "--runs", str(args.runs)] + (["--hpc"] if args.hpc else [])
     r = subprocess.run(cmd, stdout=subprocess.PIPE)
     if r.returncode != 0:
         print(f"index_rate: the measurement ended with status {r.returncode}", file=sys.stderr)
