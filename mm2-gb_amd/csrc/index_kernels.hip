@@ -27,9 +27,6 @@
 namespace mm2gb {
 namespace {
 
-constexpr int TB = 256;
-unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + TB - 1) / TB); }
-
 __global__ __launch_bounds__(TB) void k_ix_split(const ulonglong2 *mini, int64_t n, unsigned long long *key, unsigned long long *val)
 {
 	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include "post_dev.h"
 
 namespace mm2gb {
@@ -17,6 +18,10 @@ struct DevIndexView {
 	int                       bucket_shift, k, w;
 	int                       flag;     // MM2GB_I_*: reads are sketched the way the index was
 };
+
+// the kernels of seed_kernels.hip and index_kernels.hip: a thread per element, TB threads to a workgroup
+constexpr int TB = 256;
+inline unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + TB - 1) / TB); }
 
 // carves arrays out of one arena; base == nullptr: only adds up what is needed
 struct Carver {
@@ -40,7 +45,7 @@ struct SketchBatch {
 	const int64_t  *seq_off;           // n_seqs + 1
 	const uint32_t *rid;               // per sequence, or null (0)
 	int64_t         n_seqs, n;
-	int             w, k;
+	int             w, k, hpc;
 	// scratch (n + 1 entries each)
 	uint32_t *n_valid;                 // A/C/G/T before each position (hpc: run starts before each position)
 	uint32_t *n_skip;                  // skipped positions before each position
@@ -54,16 +59,17 @@ struct SketchBatch {
 	int64_t  *cstart;                  // n_seqs + 1: where each sequence's counted positions begin
 	uint32_t *emit_cnt;                // by counted position: pairs the step emits
 	int64_t  *emit_off;                // their exclusive scan
+	uint32_t *n_bnd;                   // hpc only: boundaries before each position
+	uint32_t *bnd_pos;                 // hpc only (n + 2 entries): the boundaries' positions; position n is the last one
 	void     *tmp; size_t tmp_bytes;   // the library scans' work space
 	// out
 	int64_t  *mini_off;                // n_seqs + 1
 	ulonglong2 *mini;                  // the pairs (set before launch_sketch_write)
 	int32_t  *mini_read;               // their sequence
-	// homopolymer compression (after everything else: the plain kernels' argument offsets stay what they were)
-	int       hpc;
-	uint32_t *n_bnd;                   // scratch, hpc only (n + 1 entries): boundaries before each position
-	uint32_t *bnd_pos;                 // scratch, hpc only (n + 2 entries): the boundaries' positions; position n is the last one
 };
+// The layout functions size the library calls' work space by running the launch's own list of steps without launching (seed_kernels.hip:
+// Pass), so a step under a condition is sized under that condition: everything above "scratch" -- hpc here, the options and the counts of
+// MatchBatch -- is set BEFORE the layout is asked for and stays as it is until the launch.
 size_t sketch_layout(SketchBatch &b, void *base);            // sets the scratch pointers inside base; returns the bytes needed
 int    launch_sketch_count(const SketchBatch &b, hipStream_t s);   // through mini_off; -1: a library scan refused
 void   launch_sketch_write(const SketchBatch &b, hipStream_t s);

@@ -3,21 +3,28 @@
 //
 // The sketch by POSITION.  seeding.cpp's loop carries state (ring, best, run, slot), but every quantity of a step is a function
 // of the input alone:
-//   * the words fwd / rev at a position are the last k entries of the sequence WITHOUT its ambiguous bases (an N does not clear them);
-//   * a position whose words are equal is SKIPPED (the loop's `continue`); the others are COUNTED, t = 0, 1, ... (slot = t mod w);
-//   * run = counted valid positions since the last N: a difference of two prefix sums;
+//   * the words fwd / rev at a step are the last k entries of the sequence's COMPACTED form (an N does not clear them);
+//   * a step whose words are equal is SKIPPED (the loop's `continue`); the others are COUNTED, t = 0, 1, ... (slot = t mod w);
+//   * run = counted valid steps since the last N: a difference of two prefix sums;
 //   * best after step t = the RIGHTMOST minimum of the values of steps [t - w + 1, t]; what step t emits follows from that of t - 1 and t.
 // So: prefix sums (library scans), one thread per position for the words, one thread per counted position for what it emits, a scan of
 // the counts, the same threads again to write.  A thread reads its w predecessors' values from memory: neighbours read the same lines.
 //
-// Homopolymer compression (sketch.c:94-105) in the same form: the loop's steps are the BOUNDARIES -- a run's first base, an ambiguous base --,
-// every other position counts as skipped.  Both compactions (a base per run; the boundaries' positions) are scans; a run's last base is the
-// next boundary's position (or the sequence's end) minus one; between two ambiguous bases the runs are contiguous, so the span of the last
-// min(k, m) runs is a difference of two positions.  No thread walks along a run.  k_hp_* below; k_sk_cstart / k_sk_emit / k_sk_mini_off serve both.
+// ONE pipeline (sketch_steps) in two FORMS, a template parameter of the kernels that differ (k_sk_words, k_sk_values; the compaction is a
+// kernel per form, k_sk_compact / k_hp_compact: they share four lines):
+//   plain   a step is a position; the compacted form leaves out the ambiguous bases; the span is k;
+//   HPC     homopolymer-compressed (sketch.c:94-105): a step is a BOUNDARY -- a run's first base, an ambiguous base --, every other position
+//           counts as skipped; the compacted form has a base per run; a step's position is its run's last base: the next boundary's
+//           position (or the sequence's end) minus one; between two ambiguous bases the runs are contiguous, so the span of the last
+//           min(k, m) runs is a difference of two positions.  No thread walks along a run.  The boundaries and their scans (k_hp_bound,
+//           n_valid over run starts, n_bnd) are this form's own prologue.
 //
 // Matches: q-occurrence filter by a segmented sort of the reads' values, look-up as SeedIndex::find, streak thinning by RANK -- in a streak
 // of matches above mid_occ the survivors are the K smallest by (n, index): a radix select per streak, by a workgroup --, repeat length by a
 // wave per read, offsets by scans, hits gathered 64 seeds per wave.
+//
+// Both pipelines are written once, against a Pass: the layout functions run them to MEASURE the library calls' work space, the launch
+// functions to launch.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -26,35 +33,43 @@
 #include <rocprim/functional.hpp>
 #include <algorithm>
 #include "seed_dev.h"
+#include "kmer.h"
 
 namespace mm2gb {
 namespace {
 
-constexpr int TB = 256;
 constexpr unsigned long long NONE = ~0ull;
 
-__host__ __device__ inline int base_code_d(unsigned char c)      // seeding.cpp: base_code
-{
-	switch (c) {
-	case 'A': case 'a': return 0;
-	case 'C': case 'c': return 1;
-	case 'G': case 'g': return 2;
-	case 'T': case 't': case 'U': case 'u': return 3;
-	default: return 4;
+// What a pipeline's list of steps runs against.  MEASURING (tmp == nullptr): every library step is asked for its work space and the largest
+// answer is kept; nothing is launched.  LAUNCHING: the library steps get tmp, the kernels are launched; after a refusal nothing more is.
+struct Pass {
+	void *tmp; size_t tmp_bytes; hipStream_t s;
+	size_t need = 0; bool refused = false;
+	bool launching() const { return tmp && !refused; }
+	template <class Call> void lib(Call call)                                  // call(tmp, bytes): a rocPRIM call
+	{
+		if (refused) return;
+		size_t q = tmp_bytes;
+		refused = call(tmp, q) != hipSuccess;
+		if (!tmp) need = std::max(need, q);
 	}
+	template <class Kernel, class... Args> void run(Kernel kernel, unsigned grid, unsigned block, const Args &...args)
+	{
+		if (launching()) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, args...);
+	}
+};
+// the library steps but one: out[i] = in[0] + ... + in[i - 1], and out[i] = op(in[0], ..., in[i])
+template <class In, class Out, class T> void sums(Pass &p, In in, Out out, T zero, size_t n)
+{
+	p.lib([&](void *t, size_t &q) { return rocprim::exclusive_scan(t, q, in, out, zero, n, rocprim::plus<T>(), p.s); });
+}
+template <class In, class Out, class Op> void running(Pass &p, In in, Out out, size_t n, Op op)
+{
+	p.lib([&](void *t, size_t &q) { return rocprim::inclusive_scan(t, q, in, out, n, op, p.s); });
 }
 
-__device__ inline unsigned long long mix_d(unsigned long long key, unsigned long long mask)   // seeding.cpp: mix
-{
-	key = (~key + (key << 21)) & mask;
-	key ^= key >> 24;
-	key = (key + (key << 3) + (key << 8)) & mask;
-	key ^= key >> 14;
-	key = (key + (key << 2) + (key << 4)) & mask;
-	key ^= key >> 28;
-	key = (key + (key << 31)) & mask;
-	return key;
-}
+template <class In, class F> auto via(In in, F f) { return rocprim::make_transform_iterator(in, f); }
+inline auto positions() { return rocprim::make_counting_iterator<uint32_t>(0u); }
 
 // largest r < n_seg with off[r] <= i (off[0] <= i < off[n_seg]); empty segments are passed over
 __device__ inline int64_t seg_of(const int64_t *off, int64_t n_seg, int64_t i)
@@ -74,43 +89,63 @@ __device__ inline int64_t seg_of_block(const int64_t *off, int64_t n_seg, int64_
 	return r;
 }
 
-struct ValidOf { __host__ __device__ uint32_t operator()(unsigned char c) const { return base_code_d(c) < 4 ? 1u : 0u; } };
+struct ValidOf { __host__ __device__ uint32_t operator()(unsigned char c) const { return base_code(c) < 4 ? 1u : 0u; } };
+struct RunOf   { __host__ __device__ uint32_t operator()(unsigned char f) const { return f & 1u; } };
+struct BndOf   { __host__ __device__ uint32_t operator()(unsigned char f) const { return f ? 1u : 0u; } };
 struct SkipOf  { __host__ __device__ uint32_t operator()(unsigned char f) const { return (f >> 1) & 1u; } };
-struct LastN   { const unsigned char *seqs; __host__ __device__ uint32_t operator()(uint32_t i) const { return base_code_d(seqs[i]) >= 4 ? i + 1 : 0u; } };
+struct LastN   { const unsigned char *seqs; __host__ __device__ uint32_t operator()(uint32_t i) const { return base_code(seqs[i]) >= 4 ? i + 1 : 0u; } };
 struct ToI64   { __host__ __device__ long long operator()(uint32_t v) const { return (long long)v; } };
 
-hipError_t scan_valid(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
+// HPC, before the words: flags = 1 the first base of a run (a run does not continue from the sequence before), 2 an ambiguous base,
+// 0 inside a run.  Position n is a boundary: every run ends before it
+__global__ __launch_bounds__(TB) void k_hp_bound(SketchBatch b)
 {
-	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator(b.seqs, ValidOf()), b.n_valid, 0u, (size_t)b.n + 1, rocprim::plus<uint32_t>(), s);
-}
-hipError_t scan_skip(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator((const unsigned char*)b.flags, SkipOf()), b.n_skip, 0u, (size_t)b.n + 1, rocprim::plus<uint32_t>(), s);
-}
-hipError_t scan_last_n(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::inclusive_scan(tmp, bytes, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LastN{ b.seqs }), b.last_n, (size_t)b.n + 1,
-	                               rocprim::maximum<uint32_t>(), s);
-}
-hipError_t scan_emit(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator((const uint32_t*)b.emit_cnt, ToI64()), (long long*)b.emit_off, 0ll, (size_t)b.n + 1, rocprim::plus<long long>(), s);
+	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+	const bool in = i < b.n;
+	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
+	if (i == b.n) b.flags[i] = 2;
+	if (!in) return;
+	const int c = base_code(b.seqs[i]);
+	b.flags[i] = (unsigned char)(c >= 4 ? 2 : (i == b.seq_off[r] || base_code(b.seqs[i - 1]) != c) ? 1 : 0);
 }
 
-// the sequences without their ambiguous bases, each from its own offset on
+// where the run that begins at boundary i ends: before the next boundary, or with its sequence
+__device__ inline int64_t run_end(const SketchBatch &b, int64_t i, int64_t r)
+{
+	return std::min<int64_t>((int64_t)b.bnd_pos[b.n_bnd[i] + 1], b.seq_off[r + 1]) - 1;
+}
+
+// the compacted sequences, each from its own offset on.  Plain: the sequences without their ambiguous bases
 __global__ __launch_bounds__(TB) void k_sk_compact(SketchBatch b)
 {
 	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
 	const bool in = i < b.n;
 	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
 	if (!in) return;
-	const int c = base_code_d(b.seqs[i]);
+	const int c = base_code(b.seqs[i]);
 	if (c >= 4) return;
 	const int64_t s0 = b.seq_off[r];
 	b.comp[s0 + (b.n_valid[i] - b.n_valid[s0])] = (unsigned char)c;
 }
+// HPC: a base per run, and the boundaries' positions
+__global__ __launch_bounds__(TB) void k_hp_compact(SketchBatch b)
+{
+	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+	const bool in = i < b.n;
+	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
+	if (i > b.n) return;
+	const unsigned fl = b.flags[i];
+	if (fl == 0) return;
+	b.bnd_pos[b.n_bnd[i]] = (uint32_t)i;
+	if (fl != 1 || !in) return;
+	const int64_t s0 = b.seq_off[r];
+	b.comp[s0 + (b.n_valid[i] - b.n_valid[s0])] = (unsigned char)base_code(b.seqs[i]);
+}
 
-// the words of every valid position (seeding.cpp:65-70), from the last k bases of its sequence's compacted form
+// the words of every step with a base (seeding.cpp:65-70), from the last k bases of its sequence's compacted form.  HPC: the span from the
+// first of the last min(k, m) runs' positions (m: runs since the last ambiguous base, this one included) to this run's end; the flags of
+// k_hp_bound become what the plain form leaves, inside a run: skipped
+template <bool HPC>
 __global__ __launch_bounds__(TB) void k_sk_words(SketchBatch b)
 {
 	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
@@ -118,7 +153,10 @@ __global__ __launch_bounds__(TB) void k_sk_words(SketchBatch b)
 	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
 	if (i == b.n) b.flags[i] = 0;
 	if (!in) return;
-	if (base_code_d(b.seqs[i]) >= 4) { b.flags[i] = 0; return; }
+	if (HPC) {
+		const unsigned bnd = b.flags[i];
+		if (bnd != 1) { b.flags[i] = (unsigned char)(bnd == 0 ? 2 : 0); return; }
+	} else if (base_code(b.seqs[i]) >= 4) { b.flags[i] = 0; return; }
 	const int64_t s0 = b.seq_off[r];
 	const int64_t o = (int64_t)(b.n_valid[i] - b.n_valid[s0]);
 	const unsigned char *at = b.comp + s0 + o;
@@ -133,7 +171,14 @@ __global__ __launch_bounds__(TB) void k_sk_words(SketchBatch b)
 	const unsigned long long mask = (1ull << (2 * b.k)) - 1;
 	const bool skip = f == rv;
 	const unsigned strand = f < rv ? 0u : 1u;
-	b.hx[i] = mix_d(strand ? rv : f, mask) << 8 | (unsigned long long)b.k;
+	int64_t span = b.k;
+	if (HPC) {
+		const int64_t j = std::max<int64_t>((int64_t)b.last_n[i], s0);
+		const uint32_t m = b.n_valid[i] + 1 - b.n_valid[j];
+		const int64_t from = (int64_t)b.bnd_pos[b.n_bnd[i] + 1 - std::min<uint32_t>(m, (uint32_t)b.k)];
+		span = run_end(b, i, r) - from + 1;
+	}
+	b.hx[i] = (!HPC || span < 256) ? mix(strand ? rv : f, mask) << 8 | (unsigned long long)span : NONE;
 	b.flags[i] = (unsigned char)(1u | (skip ? 2u : 0u) | strand << 2);
 }
 
@@ -143,7 +188,8 @@ __global__ __launch_bounds__(TB) void k_sk_cstart(SketchBatch b)
 	if (r <= b.n_seqs) b.cstart[r] = b.seq_off[r] - (int64_t)b.n_skip[b.seq_off[r]];
 }
 
-// every counted position's value, position and run, at its counted index
+// every counted step's value, position (HPC: its run's last base) and run, at its counted index
+template <bool HPC>
 __global__ __launch_bounds__(TB) void k_sk_values(SketchBatch b)
 {
 	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
@@ -155,12 +201,14 @@ __global__ __launch_bounds__(TB) void k_sk_values(SketchBatch b)
 	const int64_t g = i - (int64_t)b.n_skip[i];
 	const int64_t s0 = b.seq_off[r];
 	uint32_t run = 0;
+	int64_t pos = i;
 	if (fl & 1u) {
 		const int64_t j = std::max<int64_t>((int64_t)b.last_n[i], s0);          // first position after the last N (or the sequence's first)
-		run = (b.n_valid[i + 1] - b.n_skip[i + 1]) - (b.n_valid[j] - b.n_skip[j]);
+		run = (uint32_t)(i + 1 - j) - (b.n_skip[i + 1] - b.n_skip[j]);          // every position of [j, i] is a valid base
+		if (HPC) pos = run_end(b, i, r);
 	}
 	b.vx[g] = ((fl & 1u) && run >= (uint32_t)b.k) ? b.hx[i] : NONE;
-	b.vy[g] = (uint32_t)(i - s0) << 1 | ((fl >> 2) & 1u);
+	b.vy[g] = (uint32_t)(pos - s0) << 1 | ((fl >> 2) & 1u);
 	b.vrun[g] = std::min<uint32_t>(run, (uint32_t)(b.w + b.k));
 }
 
@@ -217,134 +265,29 @@ __global__ __launch_bounds__(TB) void k_sk_mini_off(SketchBatch b)
 	if (r <= b.n_seqs) b.mini_off[r] = b.emit_off[b.cstart[r]];
 }
 
-// ---- homopolymer-compressed (b.hpc): the boundaries, their compactions, the words and the values; the rest is shared with the plain form
-struct RunOf { __host__ __device__ uint32_t operator()(unsigned char f) const { return f & 1u; } };
-struct BndOf { __host__ __device__ uint32_t operator()(unsigned char f) const { return f ? 1u : 0u; } };
-
-hipError_t scan_runs(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator((const unsigned char*)b.flags, RunOf()), b.n_valid, 0u, (size_t)b.n + 1, rocprim::plus<uint32_t>(), s);
-}
-hipError_t scan_bnd(const SketchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator((const unsigned char*)b.flags, BndOf()), b.n_bnd, 0u, (size_t)b.n + 1, rocprim::plus<uint32_t>(), s);
-}
-
-// flags: 1 the first base of a run (a run does not continue from the sequence before), 2 an ambiguous base, 0 inside a run.  Position n
-// is a boundary: every run ends before it
-__global__ __launch_bounds__(TB) void k_hp_bound(SketchBatch b)
-{
-	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-	const bool in = i < b.n;
-	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
-	if (i == b.n) b.flags[i] = 2;
-	if (!in) return;
-	const int c = base_code_d(b.seqs[i]);
-	b.flags[i] = (unsigned char)(c >= 4 ? 2 : (i == b.seq_off[r] || base_code_d(b.seqs[i - 1]) != c) ? 1 : 0);
-}
-
-// the boundaries' positions, and the sequences with a base per run and without their ambiguous bases, each from its own offset on
-__global__ __launch_bounds__(TB) void k_hp_compact(SketchBatch b)
-{
-	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-	const bool in = i < b.n;
-	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
-	if (i > b.n) return;
-	const unsigned fl = b.flags[i];
-	if (fl == 0) return;
-	b.bnd_pos[b.n_bnd[i]] = (uint32_t)i;
-	if (fl != 1 || !in) return;
-	const int64_t s0 = b.seq_off[r];
-	b.comp[s0 + (b.n_valid[i] - b.n_valid[s0])] = (unsigned char)base_code_d(b.seqs[i]);
-}
-
-// where the run that begins at boundary i ends: before the next boundary, or with its sequence
-__device__ inline int64_t run_end(const SketchBatch &b, int64_t i, int64_t r)
-{
-	return std::min<int64_t>((int64_t)b.bnd_pos[b.n_bnd[i] + 1], b.seq_off[r + 1]) - 1;
-}
-
-// k_sk_words at a run's first base: the words from the last k runs' bases, the span from the first of the last min(k, m) runs' positions
-// (m: runs since the last ambiguous base, this one included) to this run's end.  flags become what k_sk_words leaves; inside a run: skipped
-__global__ __launch_bounds__(TB) void k_hp_words(SketchBatch b)
-{
-	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-	const bool in = i < b.n;
-	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
-	if (i == b.n) b.flags[i] = 0;
-	if (!in) return;
-	const unsigned bnd = b.flags[i];
-	if (bnd != 1) { b.flags[i] = (unsigned char)(bnd == 0 ? 2 : 0); return; }
-	const int64_t s0 = b.seq_off[r];
-	const int64_t o = (int64_t)(b.n_valid[i] - b.n_valid[s0]);
-	const unsigned char *at = b.comp + s0 + o;
-	const int top = 2 * (b.k - 1);
-	const int have = (int)(o + 1 < b.k ? o + 1 : b.k);
-	unsigned long long f = 0, rv = 0;
-	for (int d = 0; d < have; ++d) {
-		const unsigned long long c = at[-d];
-		f |= c << (2 * d);
-		rv |= (3 ^ c) << (top - 2 * d);
-	}
-	const unsigned long long mask = (1ull << (2 * b.k)) - 1;
-	const bool skip = f == rv;
-	const unsigned strand = f < rv ? 0u : 1u;
-	const int64_t j = std::max<int64_t>((int64_t)b.last_n[i], s0);
-	const uint32_t m = b.n_valid[i] + 1 - b.n_valid[j];
-	const int64_t from = (int64_t)b.bnd_pos[b.n_bnd[i] + 1 - std::min<uint32_t>(m, (uint32_t)b.k)];
-	const int64_t span = run_end(b, i, r) - from + 1;
-	b.hx[i] = span < 256 ? mix_d(strand ? rv : f, mask) << 8 | (unsigned long long)span : NONE;
-	b.flags[i] = (unsigned char)(1u | (skip ? 2u : 0u) | strand << 2);
-}
-
-// k_sk_values: the position is the run's last base, the run of counted steps since the last ambiguous base has only run starts in it
-__global__ __launch_bounds__(TB) void k_hp_values(SketchBatch b)
-{
-	const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-	const bool in = i < b.n;
-	const int64_t r = seg_of_block(b.seq_off, b.n_seqs, (int64_t)blockIdx.x * TB, i, in);
-	if (!in) return;
-	const unsigned fl = b.flags[i];
-	if (fl & 2u) return;
-	const int64_t g = i - (int64_t)b.n_skip[i];
-	const int64_t s0 = b.seq_off[r];
-	uint32_t run = 0;
-	int64_t end = i;
-	if (fl & 1u) {
-		const int64_t j = std::max<int64_t>((int64_t)b.last_n[i], s0);
-		run = (uint32_t)(i + 1 - j) - (b.n_skip[i + 1] - b.n_skip[j]);
-		end = run_end(b, i, r);
-	}
-	b.vx[g] = ((fl & 1u) && run >= (uint32_t)b.k) ? b.hx[i] : NONE;
-	b.vy[g] = (uint32_t)(end - s0) << 1 | ((fl >> 2) & 1u);
-	b.vrun[g] = std::min<uint32_t>(run, (uint32_t)(b.w + b.k));
-}
-
-unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + TB - 1) / TB); }
-
-int launch_sketch_count_hpc(const SketchBatch &b, hipStream_t s)
+// the sketch through mini_off, in either form.  (The scan of last_n reads the sequences alone: it can stand before the words in both)
+template <bool HPC>
+void sketch_steps(const SketchBatch &b, Pass &p)
 {
 	const unsigned gp = blocks(b.n + 1), gs = blocks(b.n_seqs + 1);
-	size_t q;
-	hipLaunchKernelGGL(k_hp_bound, dim3(gp), dim3(TB), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_runs(b, b.tmp, q, s) != hipSuccess) return -1;
-	q = b.tmp_bytes;
-	if (scan_bnd(b, b.tmp, q, s) != hipSuccess) return -1;
-	q = b.tmp_bytes;
-	if (scan_last_n(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_hp_compact, dim3(gp), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_hp_words, dim3(gp), dim3(TB), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_skip(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_sk_cstart, dim3(gs), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_hp_values, dim3(gp), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_sk_emit<false>, dim3(gp), dim3(TB), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_emit(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_sk_mini_off, dim3(gs), dim3(TB), 0, s, b);
-	return 0;
+	const size_t n1 = (size_t)b.n + 1;
+	const unsigned char *flags = b.flags;
+	if (HPC) {
+		p.run(k_hp_bound, gp, TB, b);
+		sums(p, via(flags, RunOf()), b.n_valid, 0u, n1);
+		sums(p, via(flags, BndOf()), b.n_bnd, 0u, n1);
+	} else sums(p, via(b.seqs, ValidOf()), b.n_valid, 0u, n1);
+	running(p, via(positions(), LastN{ b.seqs }), b.last_n, n1, rocprim::maximum<uint32_t>());
+	p.run(HPC ? k_hp_compact : k_sk_compact, gp, TB, b);
+	p.run(k_sk_words<HPC>, gp, TB, b);
+	sums(p, via(flags, SkipOf()), b.n_skip, 0u, n1);
+	p.run(k_sk_cstart, gs, TB, b);
+	p.run(k_sk_values<HPC>, gp, TB, b);
+	p.run(k_sk_emit<false>, gp, TB, b);
+	sums(p, via((const uint32_t*)b.emit_cnt, ToI64()), (long long*)b.emit_off, 0ll, n1);
+	p.run(k_sk_mini_off, gs, TB, b);
 }
+void sketch_steps(const SketchBatch &b, Pass &p) { if (b.hpc) sketch_steps<true>(b, p); else sketch_steps<false>(b, p); }
 
 } // namespace
 
@@ -358,41 +301,19 @@ size_t sketch_layout(SketchBatch &b, void *base)
 	b.vy = c.take<uint32_t>(n1); b.vrun = c.take<uint32_t>(n1);
 	b.cstart = c.take<int64_t>(s1);
 	b.emit_cnt = c.take<uint32_t>(n1); b.emit_off = c.take<int64_t>(n1);
-	size_t need = 0, q = 0;
-	b.n_bnd = b.bnd_pos = nullptr;
-	if (b.hpc) {
-		b.n_bnd = c.take<uint32_t>(n1); b.bnd_pos = c.take<uint32_t>(n1 + 1);
-		(void)scan_runs(b, nullptr, q, 0); need = std::max(need, q);
-		(void)scan_bnd(b, nullptr, q, 0); need = std::max(need, q);
-	}
-	(void)scan_valid(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_skip(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_last_n(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_emit(b, nullptr, q, 0); need = std::max(need, q);
-	b.tmp_bytes = need + 256;
+	b.n_bnd = b.hpc ? c.take<uint32_t>(n1) : nullptr; b.bnd_pos = b.hpc ? c.take<uint32_t>(n1 + 1) : nullptr;
+	Pass measure{ nullptr, 0, 0 };
+	sketch_steps(b, measure);
+	b.tmp_bytes = measure.need + 256;
 	b.tmp = c.take<unsigned char>(b.tmp_bytes);
 	return c.at + 256;
 }
 
 int launch_sketch_count(const SketchBatch &b, hipStream_t s)
 {
-	if (b.hpc) return launch_sketch_count_hpc(b, s);
-	const unsigned gp = blocks(b.n + 1), gs = blocks(b.n_seqs + 1);
-	size_t q = b.tmp_bytes;
-	if (scan_valid(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_sk_compact, dim3(gp), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_sk_words, dim3(gp), dim3(TB), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_skip(b, b.tmp, q, s) != hipSuccess) return -1;
-	q = b.tmp_bytes;
-	if (scan_last_n(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_sk_cstart, dim3(gs), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_sk_values, dim3(gp), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_sk_emit<false>, dim3(gp), dim3(TB), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_emit(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_sk_mini_off, dim3(gs), dim3(TB), 0, s, b);
-	return 0;
+	Pass p{ b.tmp, b.tmp_bytes, s };
+	sketch_steps(b, p);
+	return p.refused ? -1 : 0;
 }
 
 void launch_sketch_write(const SketchBatch &b, hipStream_t s)
@@ -413,41 +334,6 @@ struct KeptOf  { const unsigned char *flt; const int64_t *tot;
                  __device__ uint32_t operator()(uint32_t i) const { return ((int64_t)i < tot[1] && !flt[i]) ? 1u : 0u; } };
 struct HitsOf  { const unsigned char *flt; const uint32_t *m_n; const int64_t *tot;
                  __device__ long long operator()(uint32_t i) const { return ((int64_t)i < tot[1] && !flt[i]) ? (long long)m_n[i] : 0ll; } };
-
-template <class In, class Out, class Init, class Op>
-hipError_t ex_scan(void *tmp, size_t &bytes, In in, Out out, Init init, size_t n, Op op, hipStream_t s) { return rocprim::exclusive_scan(tmp, bytes, in, out, init, n, op, s); }
-
-hipError_t scan_keepq(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return ex_scan(tmp, bytes, rocprim::make_transform_iterator((const unsigned char*)b.keepq, KeepQ()), b.fpos, 0u, (size_t)b.n_mini + 1, rocprim::plus<uint32_t>(), s);
-}
-hipError_t scan_has(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return ex_scan(tmp, bytes, rocprim::make_transform_iterator((const uint32_t*)b.l_n, HasOcc()), b.mpos, 0u, (size_t)b.n_mini + 1, rocprim::plus<uint32_t>(), s);
-}
-hipError_t scan_low_fwd(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::inclusive_scan(tmp, bytes, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LowFwd{ b.m_n, b.tot, (uint32_t)b.mid_occ }), b.low_before,
-	                               (size_t)b.n_mini, rocprim::maximum<uint32_t>(), s);
-}
-hipError_t scan_low_rev(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::inclusive_scan(tmp, bytes, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), LowRev{ b.m_n, b.tot, (uint32_t)b.mid_occ, (uint32_t)(b.n_mini - 1) }),
-	                               b.low_after, (size_t)b.n_mini, rocprim::minimum<uint32_t>(), s);
-}
-hipError_t scan_kept(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return ex_scan(tmp, bytes, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), KeptOf{ b.flt, b.tot }), b.spos, 0u, (size_t)b.n_mini + 1, rocprim::plus<uint32_t>(), s);
-}
-hipError_t scan_hits(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return ex_scan(tmp, bytes, rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), HitsOf{ b.flt, b.m_n, b.tot }), (long long*)b.hpos, 0ll, (size_t)b.n_mini + 1,
-	               rocprim::plus<long long>(), s);
-}
-hipError_t sort_x(const MatchBatch &b, void *tmp, size_t &bytes, hipStream_t s)
-{
-	return rocprim::segmented_radix_sort_keys(tmp, bytes, b.skey_in, b.skey, (unsigned)std::max<int64_t>(b.n_mini, 1), (unsigned)std::max<int64_t>(b.n_reads, 1), b.mini_off, b.mini_off + 1, 0, 64, s);
-}
 
 __global__ __launch_bounds__(TB) void k_m_copy_x(MatchBatch b)
 {
@@ -682,6 +568,39 @@ __global__ __launch_bounds__(64) void k_m_gather(MatchBatch b, int64_t n_groups)
 	}
 }
 
+// the match selection: everything but the hits.  The steps under a condition are sized under it: the options are set before match_layout
+void match_steps(const MatchBatch &b, Pass &p)
+{
+	const unsigned gr = blocks(b.n_reads + 1), gm = blocks(b.n_mini + 1);
+	if (b.n_mini <= 0) { p.run(k_m_empty, gr, TB, b); return; }
+	const size_t n = (size_t)b.n_mini, n1 = n + 1;
+	const int qflt = b.q_occ_frac > 0.0f && b.mid_occ > 0;
+	if (qflt) {
+		p.run(k_m_copy_x, gm, TB, b);
+		p.lib([&](void *t, size_t &q) { return rocprim::segmented_radix_sort_keys(t, q, b.skey_in, b.skey, (unsigned)b.n_mini, (unsigned)std::max<int64_t>(b.n_reads, 1), b.mini_off, b.mini_off + 1, 0, 64, p.s); });
+	}
+	p.run(k_m_qflt, gm, TB, b, qflt);
+	sums(p, via((const unsigned char*)b.keepq, KeepQ()), b.fpos, 0u, n1);
+	p.run(k_m_filtered, gm, TB, b);
+	p.run(k_m_lookup, gm, TB, b);
+	sums(p, via((const uint32_t*)b.l_n, HasOcc()), b.mpos, 0u, n1);
+	p.run(k_m_matches, gm, TB, b);
+	p.run(k_m_read_off, gr, TB, b);
+	const int thin = b.occ_dist > 0 && b.max_max_occ > b.mid_occ;                 // seed.c:105-111
+	if (thin) {
+		running(p, via(positions(), LowFwd{ b.m_n, b.tot, (uint32_t)b.mid_occ }), b.low_before, n, rocprim::maximum<uint32_t>());
+		running(p, via(positions(), LowRev{ b.m_n, b.tot, (uint32_t)b.mid_occ, (uint32_t)(b.n_mini - 1) }), b.low_after, n, rocprim::minimum<uint32_t>());
+		if (p.launching()) (void)hipMemsetAsync(b.n_streaks, 0, sizeof(int32_t), p.s);
+		p.run(k_m_streaks, gm, TB, b);
+		p.run(k_m_select, (unsigned)std::min<int64_t>(b.n_mini / 2 + 1, 8192), TB, b);
+	}
+	p.run(k_m_flt, gm, TB, b, thin);
+	p.run(k_m_rep_len, (unsigned)std::min<int64_t>(std::max<int64_t>(b.n_reads, 1), 16384), 64, b);
+	sums(p, via(positions(), KeptOf{ b.flt, b.tot }), b.spos, 0u, n1);
+	sums(p, via(positions(), HitsOf{ b.flt, b.m_n, b.tot }), (long long*)b.hpos, 0ll, n1);
+	p.run(k_m_seeds, blocks(std::max(b.n_mini, b.n_reads) + 1), TB, b);
+}
+
 } // namespace
 
 size_t match_layout(MatchBatch &b, void *base)
@@ -701,58 +620,18 @@ size_t match_layout(MatchBatch &b, void *base)
 	b.flt = c.take<unsigned char>(n1);
 	b.spos = c.take<uint32_t>(n1); b.hpos = c.take<int64_t>(n1);
 	b.tot = c.take<int64_t>(4);
-	size_t need = 0, q = 0;
-	(void)scan_keepq(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_has(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_low_fwd(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_low_rev(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_kept(b, nullptr, q, 0); need = std::max(need, q);
-	(void)scan_hits(b, nullptr, q, 0); need = std::max(need, q);
-	(void)sort_x(b, nullptr, q, 0); need = std::max(need, q);
-	b.tmp_bytes = need + 256;
+	Pass measure{ nullptr, 0, 0 };
+	match_steps(b, measure);
+	b.tmp_bytes = measure.need + 256;
 	b.tmp = c.take<unsigned char>(b.tmp_bytes);
 	return c.at + 256;
 }
 
 int launch_matches_select(const MatchBatch &b, hipStream_t s)
 {
-	const unsigned gr = blocks(b.n_reads + 1);
-	if (b.n_mini <= 0) { hipLaunchKernelGGL(k_m_empty, dim3(gr), dim3(TB), 0, s, b); return 0; }
-	const unsigned gm = blocks(b.n_mini + 1);
-	size_t q;
-	const int qflt = b.q_occ_frac > 0.0f && b.mid_occ > 0;
-	if (qflt) {
-		hipLaunchKernelGGL(k_m_copy_x, dim3(gm), dim3(TB), 0, s, b);
-		q = b.tmp_bytes;
-		if (sort_x(b, b.tmp, q, s) != hipSuccess) return -1;
-	}
-	hipLaunchKernelGGL(k_m_qflt, dim3(gm), dim3(TB), 0, s, b, qflt);
-	q = b.tmp_bytes;
-	if (scan_keepq(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_m_filtered, dim3(gm), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_m_lookup, dim3(gm), dim3(TB), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_has(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_m_matches, dim3(gm), dim3(TB), 0, s, b);
-	hipLaunchKernelGGL(k_m_read_off, dim3(gr), dim3(TB), 0, s, b);
-	const int thin = b.occ_dist > 0 && b.max_max_occ > b.mid_occ;                 // seed.c:105-111
-	if (thin) {
-		q = b.tmp_bytes;
-		if (scan_low_fwd(b, b.tmp, q, s) != hipSuccess) return -1;
-		q = b.tmp_bytes;
-		if (scan_low_rev(b, b.tmp, q, s) != hipSuccess) return -1;
-		(void)hipMemsetAsync(b.n_streaks, 0, sizeof(int32_t), s);
-		hipLaunchKernelGGL(k_m_streaks, dim3(gm), dim3(TB), 0, s, b);
-		hipLaunchKernelGGL(k_m_select, dim3((unsigned)std::min<int64_t>(b.n_mini / 2 + 1, 8192)), dim3(TB), 0, s, b);
-	}
-	hipLaunchKernelGGL(k_m_flt, dim3(gm), dim3(TB), 0, s, b, thin);
-	hipLaunchKernelGGL(k_m_rep_len, dim3((unsigned)std::min<int64_t>(std::max<int64_t>(b.n_reads, 1), 16384)), dim3(64), 0, s, b);
-	q = b.tmp_bytes;
-	if (scan_kept(b, b.tmp, q, s) != hipSuccess) return -1;
-	q = b.tmp_bytes;
-	if (scan_hits(b, b.tmp, q, s) != hipSuccess) return -1;
-	hipLaunchKernelGGL(k_m_seeds, dim3(blocks(std::max(b.n_mini, b.n_reads) + 1)), dim3(TB), 0, s, b);
-	return 0;
+	Pass p{ b.tmp, b.tmp_bytes, s };
+	match_steps(b, p);
+	return p.refused ? -1 : 0;
 }
 
 void launch_matches_gather(const MatchBatch &b, hipStream_t s)

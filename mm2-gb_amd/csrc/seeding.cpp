@@ -22,35 +22,12 @@
 #include "engine.h"
 #include "host_chain.h"
 #include "index_dev.h"
+#include "kmer.h"
 
 namespace mm2gb {
 namespace {
 
 struct Mini { uint64_t x, y; };            // x = hash << 8 | span, y = rid << 32 | last_pos << 1 | strand   (sketch.c:66-71)
-
-inline int base_code(unsigned char c)      // A C G T (either case, U as T) -> 0..3, anything else 4
-{
-	switch (c) {
-	case 'A': case 'a': return 0;
-	case 'C': case 'c': return 1;
-	case 'G': case 'g': return 2;
-	case 'T': case 't': case 'U': case 'u': return 3;
-	default: return 4;
-	}
-}
-
-// invertible integer hash of a 2k-bit k-mer (sketch.c:29-39)
-inline uint64_t mix(uint64_t key, uint64_t mask)
-{
-	key = (~key + (key << 21)) & mask;
-	key ^= key >> 24;
-	key = (key + (key << 3) + (key << 8)) & mask;
-	key ^= key >> 14;
-	key = (key + (key << 2) + (key << 4)) & mask;
-	key ^= key >> 28;
-	key = (key + (key << 31)) & mask;
-	return key;
-}
 
 // sketch.c:77-143.  A ring of the last w k-mers (slot = k-mer number mod w); the current minimum and
 // its slot; what is emitted when, in this order: the k-mers equal to the minimum of the FIRST full window; the old minimum when a

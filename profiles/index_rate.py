@@ -4,7 +4,7 @@ csrc/index_kernels.hip: mm2gb_index_build_gpu, mm2gb_index_mid_occ_gpu) on sim_r
 one process, alternated, `--runs` timed runs each after one untimed warm-up of each; the warm-up also checks that the two indexes are
 identical.  For the host form the time until the index is usable on the device is reported too (build + mm2gb_index_to_device); the device
 form's split (H2D, sketch, sort, tables, D2H) comes from events on the engine's streams (H2D overlaps the sketch).  --hpc: both forms
-with homopolymer-compressed minimizers at k = 19, w = 10 (preset map-pb; the k_hp_* kernels of csrc/seed_kernels.hip).
+with homopolymer-compressed minimizers at k = 19, w = 10 (preset map-pb; the HPC form of csrc/seed_kernels.hip's sketch pipeline).
 The measurement runs in a child process under a time limit of its own:   python profiles/index_rate.py [--mbp 10,100,1000] [--hpc] [--out FILE]"""
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

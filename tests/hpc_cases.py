@@ -1,5 +1,5 @@
 """Inputs and models for the homopolymer-compressed sketch (tests/test_hpc_cpu.py, tests/test_gpu_hpc.py, tests/tools/gen_golden_hpc.py):
-sequences with long homopolymers, a Python model of the sketch BY POSITION -- the formulation csrc/seed_kernels.hip's k_hp_* kernels
+sequences with long homopolymers, a Python model of the sketch BY POSITION -- the formulation csrc/seed_kernels.hip's HPC-form kernels
 implement --, and the loaders of tests/golden/hpc."""
 import glob
 import json

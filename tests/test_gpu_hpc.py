@@ -1,4 +1,4 @@
-"""Homopolymer-compressed minimizers on the device (csrc/seed_kernels.hip: k_hp_*; mm2gb_sketch_gpu_flag, mm2gb_index_build_gpu_flag, and
+"""Homopolymer-compressed minimizers on the device (csrc/seed_kernels.hip: the sketch pipeline's HPC form; mm2gb_sketch_gpu_flag, mm2gb_index_build_gpu_flag, and
 every function that takes an index built with MM2GB_I_HPC) against the host functions of csrc/seeding.cpp, which tests/test_hpc_cpu.py
 pins to the reference, and against the reference's recordings and PAF under -H -k19 / -x map-pb (tests/golden/hpc).  Every comparison
 is exact."""

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 mm = pytest.importorskip("mm2gb_amd")
 GOLD = golden_io.GOLD
-TILE = 256                      # positions per workgroup of the sketch kernels (seed_kernels.hip: TB)
+TILE = 256                      # positions per workgroup of the sketch kernels (seed_dev.h: TB)
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 
 
@@ -68,6 +68,15 @@ def test_sketch_equals_the_host_sketch(engine, k, w):
     seqs += [rand_seq(rng, 300_000)]
     lens = [TILE * m + d for m in (1, 2, 3) for d in (-1, 0, 1)] + [TILE - k, TILE + k, TILE - w, TILE + w, 2 * TILE - w - k, 2 * TILE + w + k]
     seqs += [rand_seq(rng, lens[i % len(lens)] if i < 4 * len(lens) else int(rng.integers(0, 4 * TILE))) for i in range(2000)]
+    # an ambiguous base directly before, directly after and in the middle of a stretch of k-mers equal to their reverse complement (even k), at
+    # a workgroup's edge: each of the five begins at a multiple of TILE in the batch (a filler before it), an empty sequence between two of them
+    edge_rng = np.random.default_rng(77)
+    r600 = bytearray(rand_seq(edge_rng, 600))
+    r600[TILE - 1:TILE + 2] = b"NNN"
+    edge = [b"AT" * 120 + b"N" + b"ACGT" * 70, b"N" + b"AT" * 127 + b"N" + b"AT" * 200, bytes(r600),
+            b"AT" * 128 + b"N" + b"TA" * 128, b"ACGT" * 64 + b"AN" + b"CGTA" * 64]
+    for j, s in enumerate(edge):
+        seqs += [rand_seq(edge_rng, -sum(map(len, seqs)) % TILE), s] + ([b""] if j == 1 else [])
     rid = np.arange(len(seqs), dtype=np.uint32) * 7 + 1
     got = engine.sketch(seqs, w=w, k=k, rid=rid)
     twins = skipped = 0

@@ -49,7 +49,7 @@ def test_the_golden_sketches_exercise_compression():
 
 @pytest.mark.parametrize("k,w", hc.KW)
 def test_by_position_model_equals_the_host_sketch(k, w):
-    """The formulation of csrc/seed_kernels.hip's k_hp_* kernels (boundaries, run ends from the next boundary, spans as differences of
+    """The formulation of csrc/seed_kernels.hip's sketch kernels in their HPC form (boundaries, run ends from the next boundary, spans as differences of
     positions), in Python: equal to the serial loop of csrc/seeding.cpp."""
     for r, s in enumerate(hc.load_sketch(k, w)[0] + [b"", b"N", b"a" * 300 + b"CgT" * 30, b"ACGT" * 100]):
         assert np.array_equal(hc.model_sketch(s, w, k, rid=r), mm.sketch(s, w, k, rid=r, hpc=True)), f"k={k} w={w} sequence {r}"
