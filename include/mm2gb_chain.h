@@ -447,6 +447,35 @@ int64_t mm2gb_synth_count(uint64_t seed, int64_t first_read, int64_t n_reads, in
 int     mm2gb_synth_fill(uint64_t seed, int64_t first_read, int64_t n_reads, int len_lo, int len_hi, const int64_t *offsets,
                          mm2gb_anchor_t *anchors, int n_threads);
 
+/* ---- base-level DP, batched: the dual-affine banded extension alignment align.c calls for every stretch between and beyond
+ *      anchors at the long-read presets (ksw2's ksw_extd2_sse, ksw2_extd2_sse.c), field for field and CIGAR word for CIGAR word.
+ *      A job aligns queries[q_off .. q_off+qlen) against targets[t_off .. t_off+tlen), residues 0..m-1 (m-1 the wildcard); w < 0: no band,
+ *      zdrop < 0: no drop.  flag: the MM2GB_KSW_* bits below (= KSW_EZ_*); any other bit is refused by name.  Refused, with the error
+ *      text set and nothing run: a flag outside the list, a residue >= m, a job with qlen * tlen > MM2GB_KSW_MAX_CELLS (mm_align_pair's
+ *      max_sw_mat).  A job the reference returns from at once (m <= 1, an empty side, -min(mat) > 2(q+e)) gives the reset record.
+ *      res[j].cigar_off / n_cigar say where job j's words (len << 4 | op; 0 M, 1 I, 2 D) lie in *cigar (malloc'd, free with mm2gb_free,
+ *      NULL when the batch has none).  The host form is the definition; the device form (csrc/ksw_kernels.hip) equals it. ---- */
+#define MM2GB_KSW_SCORE_ONLY   0x01
+#define MM2GB_KSW_RIGHT        0x02
+#define MM2GB_KSW_GENERIC_SC   0x04
+#define MM2GB_KSW_APPROX_MAX   0x08
+#define MM2GB_KSW_APPROX_DROP  0x10
+#define MM2GB_KSW_EXTZ_ONLY    0x40
+#define MM2GB_KSW_REV_CIGAR    0x80
+#define MM2GB_KSW_NEG_INF      (-0x40000000)
+#define MM2GB_KSW_MAX_CELLS    100000000LL
+typedef struct { int8_t m, mat[25], q, e, q2, e2; } mm2gb_ksw_param_t;                      /* 0 <= m <= 5; mat: m x m, row = target residue */
+typedef struct { int64_t q_off, t_off; int32_t qlen, tlen, w, zdrop, end_bonus, flag; } mm2gb_ksw_job_t;
+typedef struct { int32_t max, zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, reach_end, n_cigar, pad_; int64_t cigar_off; } mm2gb_ksw_res_t;
+int  mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                          int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+int  mm2gb_ksw_extd2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
+                         const uint8_t *targets, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+/* the device form's seams, for tests: [0..2] threads of a workgroup per band class, [3..4] the widest band (rounded, in cells) of the first
+ * two classes, [5] the largest state image (bytes) kept in LDS -- a larger one lives in global memory; ms2 (optional): the last call's
+ * kernel time, [0] fill + backtrack, [1] CIGAR packing */
+int  mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -521,6 +521,99 @@ def collect_seeds_host(flag, reads, ref_len=None, ref_rank=None, threads=4):
 Engine.gen_regs = _engine_gen_regs
 
 
+# ---- base-level DP (mm2gb_ksw_extd2_host / _gpu): the dual-affine extension alignment of ksw2, batched ----
+KSW_SCORE_ONLY, KSW_RIGHT, KSW_GENERIC_SC, KSW_APPROX_MAX, KSW_APPROX_DROP, KSW_EXTZ_ONLY, KSW_REV_CIGAR = 0x01, 0x02, 0x04, 0x08, 0x10, 0x40, 0x80
+KSW_NEG_INF = -0x40000000
+KSW_FIELDS = ("max", "zdropped", "max_q", "max_t", "mqe", "mqe_t", "mte", "mte_q", "score", "reach_end", "n_cigar")
+KSW_JOB_DTYPE = np.dtype([("q_off", "<i8"), ("t_off", "<i8")] + [(k, "<i4") for k in "qlen tlen w zdrop end_bonus flag".split()])      # mm2gb_ksw_job_t
+KSW_RES_DTYPE = np.dtype([(k, "<i4") for k in KSW_FIELDS + ("pad_",)] + [("cigar_off", "<i8")])                                         # mm2gb_ksw_res_t
+
+
+class KswParam(C.Structure):
+    """mm2gb_ksw_param_t: m residue codes (m - 1 the wildcard), the m x m matrix (row = target residue), the two gap pairs."""
+    _fields_ = [("m", C.c_int8), ("mat", C.c_int8 * 25), ("q", C.c_int8), ("e", C.c_int8), ("q2", C.c_int8), ("e2", C.c_int8)]
+
+
+def ksw_param(q=4, e=2, q2=24, e2=1, a=2, b=4, sc_ambi=1, mat=None, m=5):
+    """The parameters of a batch; without mat, ksw_gen_simple_mat's matrix for match a, mismatch -b and wildcard -sc_ambi (align.c:9-21)."""
+    p = KswParam()
+    p.m, p.q, p.e, p.q2, p.e2 = int(m), int(q), int(e), int(q2), int(e2)
+    if mat is None:
+        mat = [[(a if i == j else -abs(b)) if i < m - 1 and j < m - 1 else -abs(sc_ambi) for j in range(m)] for i in range(m)]
+    flat = np.asarray(mat, np.int8).reshape(-1)
+    for k in range(min(len(flat), 25)):
+        p.mat[k] = int(flat[k])
+    return p
+
+
+def ksw_jobs(pairs, w=-1, zdrop=-1, end_bonus=0, flag=0):
+    """pairs: (query, target) or (query, target, dict of w / zdrop / end_bonus / flag for that job), sequences as uint8 codes.
+    Returns the job records and the two concatenated sequence arrays the batch calls take."""
+    jobs = np.zeros(len(pairs), KSW_JOB_DTYPE)
+    qs = [np.asarray(p[0], np.uint8).reshape(-1) for p in pairs]
+    ts = [np.asarray(p[1], np.uint8).reshape(-1) for p in pairs]
+    jobs["qlen"] = [len(x) for x in qs]; jobs["tlen"] = [len(x) for x in ts]
+    jobs["q_off"][1:] = np.cumsum(jobs["qlen"][:-1], dtype=np.int64); jobs["t_off"][1:] = np.cumsum(jobs["tlen"][:-1], dtype=np.int64)
+    for name, dflt in (("w", w), ("zdrop", zdrop), ("end_bonus", end_bonus), ("flag", flag)):
+        jobs[name] = [int(p[2].get(name, dflt)) if len(p) > 2 else int(dflt) for p in pairs]
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0, np.uint8), dtype=np.uint8)
+    return jobs, cat(qs), cat(ts)
+
+
+def _ksw_call(fn, head, param, jobs, queries, targets, tail):
+    jobs = np.ascontiguousarray(jobs, dtype=KSW_JOB_DTYPE)
+    queries = np.ascontiguousarray(queries, dtype=np.uint8); targets = np.ascontiguousarray(targets, dtype=np.uint8)
+    res = np.zeros(len(jobs), KSW_RES_DTYPE)
+    cig, total = C.c_void_p(), C.c_int64(0)
+    fn.argtypes = [C.c_void_p] * len(head) + [C.POINTER(KswParam), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * len(tail) + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    _check(fn(*head, C.byref(param), len(jobs), jobs.ctypes.data, queries.ctypes.data, targets.ctypes.data, *tail, res.ctypes.data, C.byref(cig), C.byref(total)))
+    try:
+        words = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_uint32)), shape=(total.value,)).copy() if total.value else np.zeros(0, np.uint32)
+    finally:
+        lib().mm2gb_free(cig)
+    return res, words
+
+
+def ksw_extd2_host_batch(param, jobs, queries, targets, threads=4):
+    """mm2gb_ksw_extd2_host on packed arrays (ksw_jobs): the result records (KSW_RES_DTYPE) and the batch's CIGAR words."""
+    return _ksw_call(lib().mm2gb_ksw_extd2_host, (), param, jobs, queries, targets, (int(threads),))
+
+
+def _engine_ksw_extd2_batch(self, param, jobs, queries, targets):
+    """mm2gb_ksw_extd2_gpu on packed arrays: as ksw_extd2_host_batch, on the device."""
+    return _ksw_call(lib().mm2gb_ksw_extd2_gpu, (self._h,), param, jobs, queries, targets, ())
+
+
+def _ksw_dicts(res, words):
+    return [dict({k: int(r[k]) for k in KSW_FIELDS}, cigar=words[int(r["cigar_off"]):int(r["cigar_off"]) + int(r["n_cigar"])].copy()) for r in res]
+
+
+def ksw_extd2_host(pairs, param=None, w=-1, zdrop=-1, end_bonus=0, flag=0, threads=4):
+    """The extension DP for every (query, target) of pairs on host threads -- the definition.  One dict per job: the eleven fields of
+    KSW_FIELDS and `cigar`, uint32 words len << 4 | op (0 M, 1 I, 2 D)."""
+    return _ksw_dicts(*ksw_extd2_host_batch(param or ksw_param(), *ksw_jobs(pairs, w, zdrop, end_bonus, flag), threads=threads))
+
+
+def _engine_ksw_extd2(self, pairs, param=None, w=-1, zdrop=-1, end_bonus=0, flag=0):
+    """ksw_extd2_host's arguments and results, computed on the device (csrc/ksw_kernels.hip)."""
+    return _ksw_dicts(*self.ksw_extd2_batch(param or ksw_param(), *ksw_jobs(pairs, w, zdrop, end_bonus, flag)))
+
+
+def _engine_ksw_info(self):
+    """The device form's seams and the last call's kernel times: dict with nt (threads per band class), band (widest rounded band of the
+    first two classes), lds_max (largest image kept in LDS, bytes), ms_fill, ms_pack."""
+    c = (C.c_int64 * 6)(); ms = (C.c_double * 2)()
+    fn = lib().mm2gb_ksw_gpu_info
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(fn(self._h, c, ms))
+    return dict(nt=list(c[0:3]), band=list(c[3:5]), lds_max=int(c[5]), ms_fill=ms[0], ms_pack=ms[1])
+
+
+Engine.ksw_extd2 = _engine_ksw_extd2
+Engine.ksw_extd2_batch = _engine_ksw_extd2_batch
+Engine.ksw_info = _engine_ksw_info
+
+
 def _take_chains(out, R):
     """Copy a mm2gb_chains_t into per-read (u, a_out) arrays and release it."""
     try:

@@ -96,6 +96,10 @@ struct Engine {
 	// sequence bytes -> matches on the device (seed_kernels.hip; mm2gb_sketch_gpu, mm2gb_collect_matches_gpu): the sequences, their offsets and
 	// ids, the minimizers with their reads and offsets, one arena for the work arrays of either stage, what the host's mapq / divergence code wants
 	DevBuf sk_seqs, sk_seq_off, sk_rid, sk_mini, sk_mini_read, sk_mini_off, sk_work, sd_src_first, sd_mini_pos, sd_rep_len;
+	// the extension DP (ksw_kernels.hip; mm2gb_ksw_extd2_gpu): job records, both sequence arrays, result records, the direction bytes of the jobs
+	// of one launch, every job's CIGAR words before and after packing, state images too large for LDS, the launches' job counters, the words' offsets
+	DevBuf kw_jobs, kw_q, kw_t, kw_res, kw_slab, kw_cig, kw_img, kw_cnt, kw_off, kw_pack;
+	double kw_ms[2] = { 0, 0 };            // of the last call: fill + backtrack kernels, packing kernel
 	// what the post-pass leaves for the host, two sets: the boundary keeps two batches in flight (the results of batch k are
 	// fetched after batch k+1 has been launched)
 	struct PostOut {

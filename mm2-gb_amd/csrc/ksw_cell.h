@@ -1,0 +1,249 @@
+// ksw_cell.h -- internal: the dual-affine extension DP's constants, band, cell update, row bookkeeping and backtrack, one definition
+// for the host form (ksw_host.cpp) and the device's (ksw_kernels.hip).  DESIGN 6d says what each piece has to reproduce and why.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/mm2gb_chain.h"
+
+namespace mm2gb {
+
+constexpr int KSW_FLAGS_KNOWN = MM2GB_KSW_SCORE_ONLY | MM2GB_KSW_RIGHT | MM2GB_KSW_GENERIC_SC | MM2GB_KSW_APPROX_MAX | MM2GB_KSW_APPROX_DROP |
+                                MM2GB_KSW_EXTZ_ONLY | MM2GB_KSW_REV_CIGAR;
+
+// What the parameters come to once per batch.  q, e, q2, e2 are the tuple AFTER it has been ordered so that q + e <= q2 + e2;
+// qe0 is q + e BEFORE that (the first cell's H is taken from it: trap 1).
+struct KswConst {
+	int    m, q, e, q2, e2, qe0, long_thres, long_diff, early;
+	int8_t mat[25], sc_mch, sc_mis, sc_N, ini, ini2, q8, q28, qe8, qe28;
+};
+
+__host__ __device__ inline int8_t ksw_i8(int v) { return (int8_t)(uint8_t)(unsigned)v; }      // wrap to 8 bits (trap 7)
+
+inline KswConst ksw_derive(const mm2gb_ksw_param_t &p)
+{
+	KswConst c = {};
+	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = p.e2; c.qe0 = c.q + c.e;
+	for (int i = 0; i < 25; ++i) c.mat[i] = p.mat[i];
+	if (c.m <= 1) { c.early = 1; return c; }
+	if (c.q2 + c.e2 < c.q + c.e) { int t = c.q; c.q = c.q2; c.q2 = t; t = c.e; c.e = c.e2; c.e2 = t; }
+	int min_sc = c.mat[1];                                  // the diagonal's first entry is not looked at
+	for (int t = 1; t < c.m * c.m; ++t) min_sc = min_sc < c.mat[t] ? min_sc : c.mat[t];
+	c.early = -min_sc > 2 * (c.q + c.e);                    // no mismatch could ever be seen
+	c.long_thres = c.e != c.e2 ? (c.q2 - c.q) / (c.e - c.e2) - 1 : 0;
+	if (c.q2 + c.e2 + c.long_thres * c.e2 > c.q + c.e + c.long_thres * c.e) ++c.long_thres;
+	c.long_diff = c.long_thres * (c.e - c.e2) - (c.q2 - c.q) - c.e2;
+	c.sc_mch = c.mat[0]; c.sc_mis = c.mat[1];
+	c.sc_N = c.mat[c.m * c.m - 1] == 0 ? ksw_i8(-c.e2) : c.mat[c.m * c.m - 1];      // trap 10
+	c.ini = ksw_i8(-c.q - c.e); c.ini2 = ksw_i8(-c.q2 - c.e2);
+	c.q8 = ksw_i8(c.q); c.q28 = ksw_i8(c.q2); c.qe8 = ksw_i8(c.q + c.e); c.qe28 = ksw_i8(c.q2 + c.e2);
+	return c;
+}
+
+// a job's band half-width as the recurrences use it, and the width of a row of direction bytes
+__host__ __device__ inline int ksw_width(int qlen, int tlen, int w)
+{
+	const int big = tlen > qlen ? tlen : qlen;
+	return w < 0 || w > big ? big : w;                      // beyond the longer side the band binds nowhere
+}
+__host__ __device__ inline int ksw_ncol16(int qlen, int tlen, int w)
+{
+	int n = qlen < tlen ? qlen : tlen;
+	n = n < w + 1 ? n : w + 1;
+	return ((n + 15) / 16 + 1) * 16;
+}
+__host__ __device__ inline int ksw_round16(int n) { return (n + 15) / 16 * 16; }
+
+// cells [st0, en0] of anti-diagonal r; empty when st0 > en0 (trap 8)
+__host__ __device__ inline void ksw_band(int r, int qlen, int tlen, int w, int *st0, int *en0)
+{
+	int st = 0, en = tlen - 1;
+	if (st < r - qlen + 1) st = r - qlen + 1;
+	if (en > r) en = r;
+	if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
+	if (en > (r + w) >> 1) en = (r + w) >> 1;
+	*st0 = st; *en0 = en;
+}
+
+// u of the cell on the first column / v left of the first row, at anti-diagonal r: the long gap takes over at long_thres
+__host__ __device__ inline int8_t ksw_edge(const KswConst &c, int r)
+{
+	return r == 0 ? c.ini : r < c.long_thres ? ksw_i8(-c.e) : r == c.long_thres ? ksw_i8(c.long_diff) : ksw_i8(-c.e2);
+}
+
+// The byte the score pass finds at target position t.  The pass works in groups of 16 from st0, so it reads up to 15 positions past the
+// target's end: zeros up to the next multiple of 16 (T), then the reversed query, which lies behind the target (trap 2).
+template <class Seq>
+__host__ __device__ inline uint8_t ksw_target_byte(const Seq &target, const Seq &query, int qlen, int tlen, int T, int t)
+{
+	if (t < tlen) return target[t];
+	if (t < T) return 0;
+	return t - T < qlen ? query[qlen - 1 - (t - T)] : 0;
+}
+// ... and at query position r - t (again zeros behind the reversed query's end)
+template <class Seq>
+__host__ __device__ inline uint8_t ksw_query_byte(const Seq &query, int qlen, int r, int t)
+{
+	const int j = r - t;
+	return j >= 0 && j < qlen ? query[j] : 0;
+}
+// mat: the batch's matrix (KswConst::mat, or the kernel's copy of it in LDS: an indexed look-up into a kernel argument would go through scratch)
+__host__ __device__ inline int8_t ksw_score(const KswConst &c, const int8_t *mat, bool generic, uint8_t tb, uint8_t qb)
+{
+	if (generic) return mat[tb * c.m + qb];
+	const uint8_t wild = (uint8_t)(c.m - 1);
+	return tb == wild || qb == wild ? c.sc_N : tb == qb ? c.sc_mch : c.sc_mis;
+}
+
+struct KswCell { int8_t u, v, x, y, x2, y2; uint8_t d; };
+
+// One cell of anti-diagonal r from anti-diagonal r - 1: z the score byte, x1 / v1 / x21 the left neighbour's x, v, x2, and the cell's own
+// u, y, y2.  Every sum wraps in 8 bits.  d: bits 0-2 which of the five candidates won, bits 3-6 whether each gap state goes on.
+// Left and right gap alignment differ in both (trap 6): `>` against `not <` for the winner, `> 0` against `>= 0` for going on.
+__host__ __device__ inline KswCell ksw_cell(const KswConst &c, bool right, int8_t z, int8_t x1, int8_t v1, int8_t x21, int8_t u, int8_t y, int8_t y2)
+{
+	int8_t a = ksw_i8(x1 + v1), b = ksw_i8(y + u), a2 = ksw_i8(x21 + v1), b2 = ksw_i8(y2 + u);
+	uint8_t d;
+	if (!right) {
+		d = a > z ? 1 : 0;  z = a > z ? a : z;
+		if (b > z)  { d = 2; z = b; }
+		if (a2 > z) { d = 3; z = a2; }
+		if (b2 > z) { d = 4; z = b2; }
+	} else {
+		d = z > a ? 0 : 1;  z = z > a ? z : a;
+		if (!(z > b))  { d = 2; z = b; }
+		if (!(z > a2)) { d = 3; z = a2; }
+		if (!(z > b2)) { d = 4; z = b2; }
+	}
+	if (c.sc_mch < z) z = c.sc_mch;
+	KswCell o;
+	o.u = ksw_i8(z - v1); o.v = ksw_i8(z - u);
+	int8_t tmp = ksw_i8(z - c.q8);
+	a = ksw_i8(a - tmp); b = ksw_i8(b - tmp);
+	tmp = ksw_i8(z - c.q28);
+	a2 = ksw_i8(a2 - tmp); b2 = ksw_i8(b2 - tmp);
+	o.x  = ksw_i8((a  > 0 ? a  : 0) - c.qe8);
+	o.y  = ksw_i8((b  > 0 ? b  : 0) - c.qe8);
+	o.x2 = ksw_i8((a2 > 0 ? a2 : 0) - c.qe28);
+	o.y2 = ksw_i8((b2 > 0 ? b2 : 0) - c.qe28);
+	if (!right) d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > 0 ? 0x20 : 0) | (b2 > 0 ? 0x40 : 0);
+	else        d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= 0 ? 0x20 : 0) | (b2 >= 0 ? 0x40 : 0);
+	o.d = d;
+	return o;
+}
+
+// The exact maximum of a row and its ties (trap 5) as one key to maximise: H in the upper half; below it the complement of the cell's rank in
+// the order the ties are settled -- cell en0 first, then the cells of [st0, en1) as four interleaved classes (class, then position), then
+// [en1, en0) in order; en1 = st0 + (en0 - st0) / 4 * 4.
+__host__ __device__ inline uint64_t ksw_max_key(int32_t H, int t, int st0, int en0)
+{
+	const int en1 = st0 + (en0 - st0) / 4 * 4;
+	uint32_t rank;
+	if (t == en0) rank = 0;
+	else if (t < en1) rank = 1u + ((uint32_t)((t - st0) & 3) << 27) + (uint32_t)((t - st0) >> 2);
+	else rank = (1u << 29) + (uint32_t)(t - en1);
+	return (uint64_t)((uint32_t)H ^ 0x80000000u) << 32 | (0xffffffffu - rank);
+}
+__host__ __device__ inline int32_t ksw_key_H(uint64_t key) { return (int32_t)((uint32_t)(key >> 32) ^ 0x80000000u); }
+__host__ __device__ inline int ksw_key_t(uint64_t key, int st0, int en0)
+{
+	const uint32_t rank = 0xffffffffu - (uint32_t)key;
+	if (rank == 0) return en0;
+	if (rank < (1u << 29)) return st0 + (int)((rank - 1) & ((1u << 27) - 1)) * 4 + (int)((rank - 1) >> 27);
+	return st0 + (en0 - st0) / 4 * 4 + (int)(rank - (1u << 29));
+}
+
+struct KswEz { int32_t max, zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, reach_end; };
+
+__host__ __device__ inline void ksw_ez_reset(KswEz &z)
+{
+	z.max_q = z.max_t = z.mqe_t = z.mte_q = -1;
+	z.max = 0; z.score = z.mqe = z.mte = MM2GB_KSW_NEG_INF;
+	z.zdropped = 0; z.reach_end = 0;
+}
+
+// a new best, or, diagonally behind the best by more than zdrop + e * (distance off its diagonal), the end of the job
+__host__ __device__ inline bool ksw_zdrop(KswEz &z, int32_t H, int r, int t, int zdrop, int e)
+{
+	if (H > z.max) { z.max = H; z.max_t = t; z.max_q = r - t; }
+	else if (t >= z.max_t && r - t >= z.max_q) {
+		const int tl = t - z.max_t, ql = (r - t) - z.max_q, l = tl > ql ? tl - ql : ql - tl;
+		if (zdrop >= 0 && z.max - H > zdrop + l * e) { z.zdropped = 1; return true; }
+	}
+	return false;
+}
+
+// After a row in exact mode: H_en0 / H_st0 are H of the band's two end cells, en the band's end rounded to a group (trap 3).  True: stop.
+__host__ __device__ inline bool ksw_row_exact(KswEz &z, const KswConst &c, int qlen, int tlen, int zdrop, int r, int st0, int en0, int en,
+                                              int32_t max_H, int max_t, int32_t H_en0, int32_t H_st0)
+{
+	if (en0 == tlen - 1 && H_en0 > z.mte) { z.mte = H_en0; z.mte_q = r - en; }
+	if (r - st0 == qlen - 1 && H_st0 > z.mqe) { z.mqe = H_st0; z.mqe_t = st0; }
+	if (ksw_zdrop(z, max_H, r, max_t, zdrop, c.e2)) return true;
+	if (r == qlen + tlen - 2 && en0 == tlen - 1) z.score = H_en0;
+	return false;
+}
+
+// After a row in approximate mode: one cell's H is followed down or right, whichever difference is larger.  V(t) / U(t): this row's v, u.
+template <class FV, class FU>
+__host__ __device__ inline bool ksw_row_approx(KswEz &z, const KswConst &c, int qlen, int tlen, int zdrop, int flag, int r, int st0, int en0,
+                                               int32_t &H0, int &H0_t, FV V, FU U)
+{
+	if (r > 0) {
+		if (H0_t >= st0 && H0_t <= en0 && H0_t + 1 >= st0 && H0_t + 1 <= en0) {
+			const int32_t d0 = V(H0_t), d1 = U(H0_t + 1);
+			if (d0 > d1) H0 += d0;
+			else { H0 += d1; ++H0_t; }
+		} else if (H0_t >= st0 && H0_t <= en0) H0 += V(H0_t);
+		else { ++H0_t; H0 += U(H0_t); }
+	} else { H0 = V(0) - c.qe0; H0_t = 0; }
+	if ((flag & MM2GB_KSW_APPROX_DROP) && ksw_zdrop(z, H0, r, H0_t, zdrop, c.e2)) return true;
+	if (r == qlen + tlen - 2 && en0 == tlen - 1) z.score = H0;
+	return false;
+}
+
+// Where the backtrack starts once the rows are done; false: no CIGAR.  A dropped job still walks back from its best cell (trap 9).
+__host__ __device__ inline bool ksw_walk_from(KswEz &z, int qlen, int tlen, int end_bonus, int flag, int *i0, int *j0)
+{
+	if (flag & MM2GB_KSW_SCORE_ONLY) return false;
+	if (!z.zdropped && !(flag & MM2GB_KSW_EXTZ_ONLY)) { *i0 = tlen - 1; *j0 = qlen - 1; return true; }
+	if (!z.zdropped && (flag & MM2GB_KSW_EXTZ_ONLY) && z.mqe + end_bonus > z.max) { z.reach_end = 1; *i0 = z.mqe_t; *j0 = qlen - 1; return true; }
+	if (z.max_t >= 0 && z.max_q >= 0) { *i0 = z.max_t; *j0 = z.max_q; return true; }
+	return false;
+}
+
+// The walk back over the direction bytes, P(row r, column) with columns counted from the row's rounded start.  Outside a row's rounded
+// bounds the move is forced (trap 4).  Moves of one kind in a row make one word, handed to out(position, word) when the kind changes; words
+// come out last operation first, and the caller reverses them unless REV_CIGAR is set.  At most qlen + tlen + 2 words; returns their number.
+template <class FP, class FO>
+__host__ __device__ inline int ksw_walk(int qlen, int tlen, int w, int i, int j, FP P, FO out)
+{
+	int n = 0, state = 0, run_op = -1;
+	uint32_t run_len = 0;
+	auto push = [&](int op, int len) {
+		if (op == run_op) { run_len += (uint32_t)len; return; }
+		if (run_op >= 0) out(n++, run_len << 4 | (uint32_t)run_op);
+		run_op = op; run_len = (uint32_t)len;
+	};
+	while (i >= 0 && j >= 0) {
+		const int r = i + j;
+		int st0, en0, force = -1;
+		ksw_band(r, qlen, tlen, w, &st0, &en0);
+		const int st = st0 / 16 * 16, en = (en0 + 16) / 16 * 16 - 1;
+		if (i < st) force = 2;
+		if (i > en) force = 1;
+		const uint32_t tmp = force < 0 ? P(r, i - st) : 0;
+		if (state == 0) state = tmp & 7;
+		else if (!(tmp >> (state + 2) & 1)) state = 0;
+		if (state == 0) state = tmp & 7;
+		if (force >= 0) state = force;
+		if (state == 0) { push(0, 1); --i; --j; }
+		else if (state == 1 || state == 3) { push(2, 1); --i; }
+		else { push(1, 1); --j; }
+	}
+	if (i >= 0) push(2, i + 1);
+	if (j >= 0) push(1, j + 1);
+	if (run_op >= 0) out(n++, run_len << 4 | (uint32_t)run_op);
+	return n;
+}
+
+} // namespace mm2gb
