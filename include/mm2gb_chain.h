@@ -476,6 +476,57 @@ int  mm2gb_ksw_extd2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, in
  * kernel time, [0] fill + backtrack, [1] CIGAR packing */
 int  mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2);
 
+/* ---- base-level alignment of hits, batched: mm_align_skeleton (align.c:960-1020) for every read of a batch -- which stretches
+ *      between and beyond a chain's anchors are aligned, how ends are extended, when a hit is split at a z-drop and when an inversion is
+ *      tried, then mm_filter_regs, mm_update_dp_max and mm_hit_sort -- record for record and CIGAR word for CIGAR word.
+ *      Options: the fields of mm_mapopt_t those functions read; mm2gb_align_opt_init sets options.c's values for "map-ont" or "map-pb".
+ *      Input per read: the sequence as text, the hit records as map.c has them when it calls align_regs (regs[reg_off[r] .. reg_off[r+1]),
+ *      `as` counted within the read's anchors) and the read's anchors, not yet squeezed (mm_squeeze_a is part of the call).  k and
+ *      idx_flag (MM2GB_I_HPC) are the index's, for mm_adjust_minier.  Reference sequences as text.
+ *      Output (malloc'd, free with mm2gb_align_out_free): the records after the call with their own reg_off, one mm2gb_aln_t per record
+ *      (mm_extra_t without the words; cigar_off = -1 and zeros for a record without one) and the batch's CIGAR words.
+ *      Refused, with the error text set, nothing run and *out zeroed: MM_F_SPLICE, MM_F_SR, MM_F_QSTRAND, MM_F_EQX; q == q2 && e == e2
+ *      (that path is ksw_extz2_sse); max_sw_mat <= 0 or above MM2GB_KSW_MAX_CELLS; a record whose as + cnt leaves its read's anchors;
+ *      multi-segment reads (a record marked seg_split or an anchor of a segment other than 0).
+ *      The host form is the definition; the device form (csrc/align_kernels.hip) equals it.  counts (information): see MM2GB_ALN_N_* . ---- */
+#define MM2GB_F_SPLICE      0x080LL
+#define MM2GB_F_SR          0x1000LL
+#define MM2GB_F_FOR_ONLY    0x100000LL
+#define MM2GB_F_REV_ONLY    0x200000LL
+#define MM2GB_F_EQX         0x4000000LL
+#define MM2GB_F_NO_END_FLT  0x10000000LL
+#define MM2GB_F_QSTRAND     0x100000000LL
+#define MM2GB_F_NO_INV      0x200000000LL
+typedef struct {
+	int64_t flag, max_sw_mat;
+	int32_t a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus;
+	int32_t min_dp_max, min_ksw_len, bw, bw_long, max_gap, min_cnt, min_chain_score, rank_min_len;
+	float   max_clip_ratio, rank_frac;
+} mm2gb_align_opt_t;
+typedef struct { int32_t dp_score, dp_max, dp_max2, n_ambi, trans_strand, n_cigar; int64_t cigar_off; } mm2gb_aln_t;
+/* counts[]: what the call met, summed over the batch */
+enum { MM2GB_ALN_N_GAP_SKIPPED, MM2GB_ALN_N_FILL_ONE_PASS, MM2GB_ALN_N_FILL_TWO_PASS, MM2GB_ALN_N_SPLIT, MM2GB_ALN_N_READS_3_ROUNDS, MM2GB_ALN_N_SPLIT_REFUSED,
+       MM2GB_ALN_N_INV, MM2GB_ALN_N_LEFT_END, MM2GB_ALN_N_LEFT_SHORT, MM2GB_ALN_N_RIGHT_END, MM2GB_ALN_N_RIGHT_SHORT, MM2GB_ALN_N_LEFT_AT_0,
+       MM2GB_ALN_N_REV_CHAIN, MM2GB_ALN_N_SEAM_MERGED, MM2GB_ALN_N_LEAD_GAP_CUT, MM2GB_ALN_N_FILTERED, MM2GB_ALN_N_DP_MAX_REWRITTEN, MM2GB_ALN_N_OVER_SW_MAT,
+       MM2GB_ALN_N_ROUNDS, MM2GB_ALN_N_HPC_MOVED, MM2GB_ALN_N_INV_PROBE_HIT, MM2GB_ALN_N_JOBS, MM2GB_ALN_N_CELLS, MM2GB_ALN_N_CELLS_DISCARDED, MM2GB_ALN_N_COUNTS };
+typedef struct {
+	int64_t n_regs, n_cigar;
+	int64_t *reg_off;          /* n_reads + 1 */
+	mm2gb_reg_t *regs;         /* n_regs */
+	mm2gb_aln_t *aln;          /* n_regs */
+	uint32_t *cigar;           /* n_cigar */
+	int64_t counts[MM2GB_ALN_N_COUNTS];
+	double  seconds[8];        /* device form: upload, planning, gather, first pass, test, second pass, copies back, stitching and extras */
+} mm2gb_align_out_t;
+int  mm2gb_align_opt_init(mm2gb_align_opt_t *opt, const char *preset);
+int  mm2gb_align_regs_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                           int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                           const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out);
+int  mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                          int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                          const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out);
+void mm2gb_align_out_free(mm2gb_align_out_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,7 +88,8 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
                 "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free",
                 "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split",
-                "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag"]
+                "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag",
+                "mm2gb_align_opt_init", "mm2gb_align_regs_host", "mm2gb_align_regs_gpu", "mm2gb_align_out_free"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -612,6 +613,91 @@ def _engine_ksw_info(self):
 Engine.ksw_extd2 = _engine_ksw_extd2
 Engine.ksw_extd2_batch = _engine_ksw_extd2_batch
 Engine.ksw_info = _engine_ksw_info
+
+
+# ---- base-level alignment of hits (mm2gb_align_regs_host / _gpu): mm_align_skeleton for a batch of reads ----
+F_SPLICE, F_SR, F_FOR_ONLY, F_REV_ONLY, F_EQX, F_NO_END_FLT, F_QSTRAND, F_NO_INV = 0x080, 0x1000, 0x100000, 0x200000, 0x4000000, 0x10000000, 0x100000000, 0x200000000
+ALN_DTYPE = np.dtype([(k, "<i4") for k in "dp_score dp_max dp_max2 n_ambi trans_strand n_cigar".split()] + [("cigar_off", "<i8")])      # mm2gb_aln_t
+ALN_COUNTS = ("gap_skipped", "fill_one_pass", "fill_two_pass", "split", "reads_3_rounds", "split_refused", "inv", "left_end", "left_short", "right_end", "right_short",
+              "left_at_0", "rev_chain", "seam_merged", "lead_gap_cut", "filtered", "dp_max_rewritten", "over_sw_mat", "rounds", "hpc_moved", "inv_probe_hit",
+              "jobs", "cells", "cells_discarded")
+ALN_STAGES = ("upload", "planning", "gather", "first_pass", "test", "second_pass", "copies_back", "stitching")
+
+
+class AlignOpt(C.Structure):
+    """mm2gb_align_opt_t: the fields of mm_mapopt_t that mm_align_skeleton and what it calls read."""
+    _fields_ = [("flag", C.c_int64), ("max_sw_mat", C.c_int64)] + [(k, C.c_int32) for k in "a b q e q2 e2 sc_ambi zdrop zdrop_inv end_bonus min_dp_max min_ksw_len bw bw_long max_gap min_cnt min_chain_score rank_min_len".split()] + \
+               [("max_clip_ratio", C.c_float), ("rank_frac", C.c_float)]
+
+
+class _AlignOut(C.Structure):
+    _fields_ = [("n_regs", C.c_int64), ("n_cigar", C.c_int64), ("reg_off", C.c_void_p), ("regs", C.c_void_p), ("aln", C.c_void_p), ("cigar", C.c_void_p),
+                ("counts", C.c_int64 * len(ALN_COUNTS)), ("seconds", C.c_double * 8)]
+
+
+def align_opt(preset="map-ont", **kw):
+    """mm2gb_align_opt_init for "map-ont" or "map-pb", then keyword overrides."""
+    o = AlignOpt()
+    fn = lib().mm2gb_align_opt_init
+    fn.argtypes = [C.POINTER(AlignOpt), C.c_char_p]
+    _check(fn(C.byref(o), preset.encode()))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise Mm2gbError(f"mm2gb_align_opt_t has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def cigar_string(words):
+    """CIGAR words (len << 4 | op) as text, MM_CIGAR_STR's letters."""
+    return "".join(f"{int(w) >> 4}{'MIDNSHP=XB'[int(w) & 0xf]}" for w in words)
+
+
+def _align_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail):
+    """reads: list of bytes; regs / anchors: one REG_DTYPE array / (n,2) uint64 array per read.  Returns per read (regs, aln, words) with
+    aln.cigar_off counted within the read's words, and dict(counts=..., seconds=...)."""
+    refs = [bytes(s) for s in refs]; reads = [bytes(s) for s in reads]
+    R = len(reads)
+    ref_arr = (C.c_char_p * max(len(refs), 1))(*refs); read_arr = (C.c_char_p * max(R, 1))(*reads)
+    ref_len = np.ascontiguousarray([len(s) for s in refs], dtype=np.int32); read_len = np.ascontiguousarray([len(s) for s in reads], dtype=np.int32)
+    reg_off = np.zeros(R + 1, np.int64); a_off = np.zeros(R + 1, np.int64)
+    reg_off[1:] = np.cumsum([len(x) for x in regs]); a_off[1:] = np.cumsum([len(x) for x in anchors])
+    reg_all = np.ascontiguousarray(np.concatenate([np.asarray(x, REG_DTYPE) for x in regs]) if R else np.zeros(0, REG_DTYPE), dtype=REG_DTYPE)
+    a_all = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint64).reshape(-1, 2) for x in anchors]) if R else np.zeros((0, 2), np.uint64), dtype=np.uint64)
+    out = _AlignOut()
+    fn.argtypes = [C.c_void_p] * len(head) + [C.POINTER(AlignOpt), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * len(tail) + [C.POINTER(_AlignOut)]
+    _check(fn(*head, C.byref(opt), int(k), I_HPC if hpc else 0, len(refs), ref_arr, ref_len.ctypes.data, R, read_arr, read_len.ctypes.data,
+              reg_off.ctypes.data, reg_all.ctypes.data, a_off.ctypes.data, a_all.ctypes.data, *tail, C.byref(out)))
+    try:
+        off = _take(out.reg_off, R + 1, np.int64)
+        rg = _take(out.regs, out.n_regs, REG_DTYPE); al = _take(out.aln, out.n_regs, ALN_DTYPE); words = _take(out.cigar, out.n_cigar, np.uint32)
+    finally:
+        free = lib().mm2gb_align_out_free
+        free.argtypes = [C.POINTER(_AlignOut)]; free.restype = None
+        free(C.byref(out))
+    res = []
+    for r in range(R):
+        a = al[off[r]:off[r + 1]].copy()
+        have = a["cigar_off"] >= 0
+        lo = int(a["cigar_off"][have].min()) if have.any() else 0
+        hi = int((a["cigar_off"] + a["n_cigar"])[have].max()) if have.any() else 0
+        a["cigar_off"][have] -= lo
+        res.append((rg[off[r]:off[r + 1]].copy(), a, words[lo:hi].copy()))
+    return res, dict(counts=dict(zip(ALN_COUNTS, (int(x) for x in out.counts))), seconds=dict(zip(ALN_STAGES, (float(x) for x in out.seconds))))
+
+
+def align_regs_host(opt, k, hpc, refs, reads, regs, anchors, threads=4):
+    """mm2gb_align_regs_host: mm_align_skeleton for every read of a batch on host threads -- the definition (see _align_call)."""
+    return _align_call(lib().mm2gb_align_regs_host, (), opt, k, hpc, refs, reads, regs, anchors, (int(threads),))
+
+
+def _engine_align_regs(self, opt, k, hpc, refs, reads, regs, anchors):
+    """mm2gb_align_regs_gpu: align_regs_host's arguments and results, the DP and its sequences on the device (csrc/align_kernels.hip)."""
+    return _align_call(lib().mm2gb_align_regs_gpu, (self._h,), opt, k, hpc, refs, reads, regs, anchors, ())
+
+
+Engine.align_regs = _engine_align_regs
 
 
 def _take_chains(out, R):

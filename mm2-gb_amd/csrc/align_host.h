@@ -1,0 +1,50 @@
+// align_host.h -- internal: what align_host.cpp offers the device form (align_kernels.hip): the batch's context, the jobs of a round and
+// the host half of mm_test_zdrop.  Planning, stitching and the per-read steps are the host's in both forms.
+#pragma once
+#include <vector>
+#include "align_cell.h"
+#include "ksw_cell.h"
+
+namespace mm2gb {
+
+struct AlCtx {
+	mm2gb_align_opt_t opt;
+	int k = 0, idx_flag = 0, a = 0, b = 0, ambi = 0, bw = 0, bw_long = 0;      // a, b, ambi: positive; bw, bw_long: mm_align1's (align.c:588-590)
+	int8_t mat[25];
+	KswConst kc;
+	int32_t n_ref = 0;
+	int64_t n_reads = 0;
+	std::vector<int64_t> ref_at, read_at;      // n + 1 each: where a sequence's residues begin
+	std::vector<uint8_t> refs, reads;          // one residue per base (seq_nt4_table); reads as given, the reverse strand is computed
+};
+
+// a job of a round with its DP parameters (first pass), and what came of it
+struct AlRun {
+	AlJob j;
+	int32_t w, zdrop, end_bonus, flag;
+	int32_t code;                      // gap fills: mm_test_zdrop's answer for the first pass (0, 1, 2); a second pass ran when it is not 0
+	mm2gb_ksw_res_t res;               // of the pass that counts; res.cigar_off: where its words lie in the round's pool
+};
+
+// what runs the DP of a round: every job's first pass, mm_test_zdrop for the gap fills, the second pass where it says so
+struct AlBackend {
+	virtual ~AlBackend() {}
+	virtual int run(const AlCtx &ctx, std::vector<AlRun> &runs, std::vector<uint32_t> &pool) = 0;
+	double seconds[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+};
+
+// mm_align_pair's rule (align.c:326-328): a stretch over max_sw_mat cells is not run
+inline bool al_too_big(const AlCtx &ctx, const AlJob &j) { return (int64_t)j.tlen * j.qlen > ctx.opt.max_sw_mat; }
+// the flag, and the drop, of a gap fill's second pass (align.c:757)
+inline int al_second_flag(int flag) { return flag & ~MM2GB_KSW_APPROX_MAX; }
+inline int al_second_zdrop(const AlCtx &ctx, int code) { return code == 2 ? ctx.opt.zdrop_inv : ctx.opt.zdrop; }
+// the second half of mm_test_zdrop (align.c:70-88): the inversion probe where the drop is deep enough, then the code
+int  al_zdrop_code(const AlCtx &ctx, const AlJob &j, const AlDrop &d);
+
+// the call behind both public forms: backend_for(thread) makes the DP backend of a worker; whole_batch: every read in one sequence of rounds
+// (the device form) instead of read by read on n_threads threads (the host form)
+int  al_align_regs(const char *who, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                   int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                   const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out);
+
+} // namespace mm2gb

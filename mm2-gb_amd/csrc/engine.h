@@ -100,6 +100,9 @@ struct Engine {
 	// of one launch, every job's CIGAR words before and after packing, state images too large for LDS, the launches' job counters, the words' offsets
 	DevBuf kw_jobs, kw_q, kw_t, kw_res, kw_slab, kw_cig, kw_img, kw_cnt, kw_off, kw_pack;
 	double kw_ms[2] = { 0, 0 };            // of the last call: fill + backtrack kernels, packing kernel
+	// the alignment of hits (align_kernels.hip; mm2gb_align_regs_gpu): the batch's resident residues (references, reads), a round's job
+	// descriptors, gather slices, the list of gap fills to test and the test's results
+	DevBuf al_refs, al_reads, al_jobs, al_slices, al_list, al_drop;
 	// what the post-pass leaves for the host, two sets: the boundary keeps two batches in flight (the results of batch k are
 	// fetched after batch k+1 has been launched)
 	struct PostOut {

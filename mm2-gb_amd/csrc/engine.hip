@@ -505,6 +505,7 @@ void Engine::shutdown()
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
 	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
 	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack,
+	                   &al_refs, &al_reads, &al_jobs, &al_slices, &al_list, &al_drop,
 	                   &post_out[0].u_off, &post_out[0].a_off, &post_out[0].u_out, &post_out[0].a_out, &post_out[1].u_off, &post_out[1].a_off, &post_out[1].u_out, &post_out[1].a_out })
 		b->release();
 	cap_post_n = cap_post_reads = 0;

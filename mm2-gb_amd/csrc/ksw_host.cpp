@@ -112,6 +112,12 @@ void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query
 
 } // namespace
 
+void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
+{
+	static thread_local Scratch S;
+	one_job(c, job, query, target, S, out, words);
+}
+
 int ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	int64_t total = 0;

@@ -180,12 +180,13 @@ int launch_one(Engine &e, const KswConst &c, const Launch &L, int k, int grid)
 
 } // namespace
 
-int ksw_extd2_gpu(Engine &e, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+// The planning and the launches behind mm2gb_ksw_extd2_gpu.  resident: the jobs' sequences already lie in kw_q / kw_t at their q_off / t_off
+// (the alignment call's gather kernel put them there, align_kernels.hip) and nothing is uploaded.  Either way the records (n_cigar set) stay in
+// kw_res, the packed words in kw_pack and their offsets in kw_off until the engine's next call.
+int ksw_extd2_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, bool resident,
                   mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
-	if (ksw_check("mm2gb_ksw_extd2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
 	if (n_jobs >= ((int64_t)1 << 31)) return fail("mm2gb_ksw_extd2_gpu: a batch is limited to 2^31 jobs");
-	const KswConst c = ksw_derive(*param);
 	e.kw_ms[0] = e.kw_ms[1] = 0;
 	*cigar = nullptr; *n_cigar_total = 0;
 	// the jobs that run, each with its classes, cost and needs; the others get the reset record here
@@ -235,15 +236,17 @@ int ksw_extd2_gpu(Engine &e, const mm2gb_ksw_param_t *param, int64_t n_jobs, con
 
 	MM2GB_HIP(hipSetDevice(e.device));
 	MM2GB_HIP(hipStreamSynchronize(e.stream));
-	if (e.kw_jobs.ensure(dev.size() * sizeof(KswDevJob)) || e.kw_q.ensure((size_t)q_bytes) || e.kw_t.ensure((size_t)t_bytes) || e.kw_res.ensure((size_t)n_jobs * sizeof(mm2gb_ksw_res_t)) ||
+	if (e.kw_jobs.ensure(dev.size() * sizeof(KswDevJob)) || (!resident && (e.kw_q.ensure((size_t)q_bytes) || e.kw_t.ensure((size_t)t_bytes))) || e.kw_res.ensure((size_t)n_jobs * sizeof(mm2gb_ksw_res_t)) ||
 	    e.kw_slab.ensure((size_t)std::max<int64_t>(slab_max, 16)) || e.kw_cig.ensure((size_t)std::max<int64_t>(cig_words, 4) * 4) || e.kw_img.ensure((size_t)std::max<int64_t>(img_max, 16)) ||
 	    e.kw_cnt.ensure(launches.size() * 4) || e.kw_off.ensure((size_t)n_jobs * 8)) return -1;
 	hipEvent_t ev[4] = {};
 	struct Events { hipEvent_t *e; ~Events() { for (int k = 0; k < 4; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } guard{ ev };
 	for (hipEvent_t &x : ev) MM2GB_HIP(hipEventCreate(&x));
 	MM2GB_HIP(hipMemcpyAsync(e.kw_jobs.ptr, dev.data(), dev.size() * sizeof(KswDevJob), hipMemcpyHostToDevice, e.stream));
-	MM2GB_HIP(hipMemcpyAsync(e.kw_q.ptr, queries, (size_t)q_bytes, hipMemcpyHostToDevice, e.stream));
-	MM2GB_HIP(hipMemcpyAsync(e.kw_t.ptr, targets, (size_t)t_bytes, hipMemcpyHostToDevice, e.stream));
+	if (!resident) {
+		MM2GB_HIP(hipMemcpyAsync(e.kw_q.ptr, queries, (size_t)q_bytes, hipMemcpyHostToDevice, e.stream));
+		MM2GB_HIP(hipMemcpyAsync(e.kw_t.ptr, targets, (size_t)t_bytes, hipMemcpyHostToDevice, e.stream));
+	} else if ((size_t)q_bytes > e.kw_q.bytes || (size_t)t_bytes > e.kw_t.bytes) return fail("mm2gb_ksw_extd2_gpu: a resident job lies outside the sequence arenas");
 	MM2GB_HIP(hipMemcpyAsync(e.kw_res.ptr, res, (size_t)n_jobs * sizeof(mm2gb_ksw_res_t), hipMemcpyHostToDevice, e.stream));
 	MM2GB_HIP(hipMemsetAsync(e.kw_cnt.ptr, 0, launches.size() * 4, e.stream));
 	MM2GB_HIP(hipEventRecord(ev[0], e.stream));
@@ -289,6 +292,13 @@ int ksw_extd2_gpu(Engine &e, const mm2gb_ksw_param_t *param, int64_t n_jobs, con
 	};
 	if (pack()) { free(*cigar); *cigar = nullptr; *n_cigar_total = 0; return -1; }
 	return 0;
+}
+
+int ksw_extd2_gpu(Engine &e, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                  mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	if (ksw_check("mm2gb_ksw_extd2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
+	return ksw_extd2_run(e, ksw_derive(*param), n_jobs, jobs, queries, targets, false, res, cigar, n_cigar_total);
 }
 
 } // namespace mm2gb
