@@ -808,12 +808,15 @@ __device__ __forceinline__ void sweep_block(const DevBatch &b, const Target &T, 
 // far: the block goes through the FAR build of the unchecked sweep only, which wants the span term folded into the score term and, in
 // place of the span, the source's DIAGONAL 4 * ((x - x0) - (y - y0)) with the top bit flipped (d0 = 4 * (x0 - y0), x0 / y0 the block's
 // first source: small numbers whatever the positions; the flipped bit makes their unsigned order the signed one, for v_sad_u32)
-__device__ __forceinline__ void stage_block_lut(int xs, int ys, int sf, int sq, int4 *stage, bool far = false, int d0 = 0)
+__device__ __forceinline__ void stage_block_lut_at(const int k, int xs, int ys, int sf, int sq, int4 *stage, bool far = false, int d0 = 0)
 {
-	const int k = lane_id();
 	const int x4 = (int)((unsigned)xs << 2), y4 = (int)((unsigned)ys << 2);
 	stage[k] = make_int4(((sf + 1) << 7) + k + 1 - LUT_BIAS + (far ? (sq - 1) << 7 : 0), far ? (int)((unsigned)(x4 - y4 - d0) ^ 0x80000000u) : (sq - 1) * 4, x4, y4);
 	__builtin_amdgcn_wave_barrier();                        // LDS is in-order per wave; keep the compiler from reordering
+}
+__device__ __forceinline__ void stage_block_lut(int xs, int ys, int sf, int sq, int4 *stage, bool far = false, int d0 = 0)
+{
+	stage_block_lut_at(lane_id(), xs, ys, sf, sq, stage, far, d0);
 }
 __device__ __forceinline__ void stage_block_lut(const DevBatch &b, int jb, int sf, int sq, int4 *stage)
 {
@@ -1657,6 +1660,27 @@ __device__ __forceinline__ void sweep_a_into_b(const DevBatch &b, TilePair &t, i
 // equals, and all band sources are older than all dense ones.
 __device__ __forceinline__ int wave_min_i32(int v) { return -wave_max_i32_dpp(-v); }   // (v > INT_MIN)
 
+// The band pass is ONE function per kernel, called (band_slab_part is __noinline__), not a copy in every chunk runner: inlined six times
+// it more than doubled k_score and cost the dense code beside it registers.  A call hands its arguments over in vector
+// registers, so what it takes is passed by value -- never the kernel-argument structs: a reference to one of those would be a copy in
+// private memory -- with the address spaces in the types (a plain pointer would make every access a flat one), and the callee tells the
+// compiler again that they are wave-uniform (v_readfirstlane).
+typedef const int __attribute__((address_space(1))) *glb_i32_cptr;
+typedef int __attribute__((address_space(1))) *glb_i32_ptr;
+typedef int4 __attribute__((address_space(3))) *lds_i32x4_ptr;
+// (the lane from the execution mask, all 64 lanes on: a called function that asked for threadIdx would make every caller keep the
+// launch's packed work-item ids in a register of their own for the whole kernel)
+__device__ __forceinline__ int lane_by_count() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+struct BandParams { int bw, dq_lim, lut_base, free_sweep, band_slab; };   // what the band pass needs of DevParams
+template <class T> __device__ __forceinline__ T uniform_glb(T p)
+{
+	const unsigned long long v = (unsigned long long)(uintptr_t)p;
+	return (T)(uintptr_t)(((unsigned long long)(unsigned)first_lane((int)(v >> 32)) << 32) | (unsigned)first_lane((int)v));
+}
+__device__ __forceinline__ int r_x(glb_i32_cptr raw, int i) { return raw[(size_t)i * 4]; }
+__device__ __forceinline__ int r_y(glb_i32_cptr raw, int i) { return raw[(size_t)i * 4 + 2]; }
+__device__ __forceinline__ int r_span(glb_i32_cptr raw, int i) { return (int)((unsigned)raw[(size_t)i * 4 + 3] & 0xffu); }
+
 // A staged block whose sources are not consecutive, some target's window starting inside it: sweep_block_lut_edge with the source's
 // index taken from lane k of `idx`.
 __device__ __forceinline__ void sweep_block_lut_band(int t_st, int tx4, int ty4, int idx, const int4 *stage, const DevParams &P, int &bestv)
@@ -1689,14 +1713,17 @@ __device__ __forceinline__ void sweep_block_lut_band(int t_st, int tx4, int ty4,
 	}
 }
 
+// What the band pass reads and writes of the batch (band_slab_part makes it from its arguments).
+struct BandIO { glb_i32_cptr raw, st, f, diag; glb_i32_ptr res; };
+
 // One group of targets (lane: target index, -1 = none; at least one lane holds one) against the sources [smallest window start, jl).
-__device__ __forceinline__ int band_group(const DevBatch &b, const DevParams &P, int4 *stage, const int tgt, const int jl)
+__device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, int4 *stage, const int tgt, const int jl)
 {
-	const int lane = lane_id();
+	const int lane = lane_by_count();
 	const int l0 = __builtin_ctzll(__ballot(tgt >= 0));
 	const int t = tgt >= 0 ? tgt : bcast(tgt, l0);                 // empty lanes repeat a target of the group
-	const int x = a_x(b, t), y = a_y(b, t), st = b.st[t];
-	int best = a_span(b, t) + 1, arg = -1;                         // threshold form, as the dense sweep
+	const int x = r_x(b.raw, t), y = r_y(b.raw, t), st = b.st[t];
+	int best = r_span(b.raw, t) + 1, arg = -1;                     // threshold form, as the dense sweep
 	const int lo = wave_min_i32(st), hi_st = wave_max_i32_dpp(st);
 	if (lo < jl) {
 		const int d = x - y;
@@ -1708,9 +1735,44 @@ __device__ __forceinline__ int band_group(const DevBatch &b, const DevParams &P,
 		const unsigned width = (unsigned)(dmax - dmin) + 2u * (unsigned)P.bw;
 		const int tx4 = (int)(((unsigned)x - 1u) << 2), ty4 = (int)(((unsigned)y - 1u) << 2);
 		const unsigned free_span = (unsigned)(P.dq_lim - P.bw);
-		auto sweep = [&](const int idx) __attribute__((always_inline)) {
+		// scan: the hits of 64 sources go, in index order, to the lanes after those already staged (ds_permute pushes each hit to its
+		// lane; what does not fit goes round to the first lanes and waits for the next stage); diagonals are read one step ahead,
+		// past the CU's cache (written by other waves of the workgroup, or by this one from other lanes).  Every stage -- the full
+		// ones, and the last, partial one in one more trip after the scan -- goes through the ONE sweep at the loop's end: each of the
+		// four unrolled forms exists once.
+		int sidx = 0, n_st = 0;
+		int jb = lo;
+		int dn = jb + lane < jl ? __hip_atomic_load(b.diag + jb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+		while (true) {
+			int idx, carry = 0, n_next = 0;
+			if (jb < jl) {
+				const int j = jb + lane;
+				const int dj = dn;
+				dn = j + WAVE < jl ? __hip_atomic_load(b.diag + j + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+				jb += WAVE;
+				const bool hit = j < jl && (unsigned)(dj - band_lo) <= width;
+				const unsigned long long m = __ballot(hit);
+				if (m == 0) continue;
+				const int c = __popcll(m);
+				const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+				// (a lane without a hit writes to the first lane that takes none, so no hit is overwritten)
+				const int dst = (hit ? n_st + rank : n_st + c) & (WAVE - 1);
+				const int recv = __builtin_amdgcn_ds_permute(dst << 2, j);
+				if (n_st + c < WAVE) {
+					sidx = lane >= n_st && lane < n_st + c ? recv : sidx;
+					n_st += c;
+					continue;
+				}
+				idx = lane >= n_st ? recv : sidx;
+				n_next = n_st + c - WAVE;
+				carry = recv;                                       // lanes below n_next: the hits that did not fit
+			} else {
+				if (n_st == 0) break;
+				// the last stage, filled up with copies of its last source (same score, same index: nothing changes)
+				idx = lane < n_st ? sidx : bcast(sidx, n_st - 1);
+			}
 			// lane k: the k-th staged source, indices ascending (the tie rule: a later source wins an equal score)
-			const int xs = a_x(b, idx), ys = a_y(b, idx), sq = a_span(b, idx), sf = b.f[idx];
+			const int xs = r_x(b.raw, idx), ys = r_y(b.raw, idx), sq = r_span(b.raw, idx), sf = b.f[idx];
 			const int sx_min = wave_min_i32(xs), sx_max = wave_max_i32_dpp(xs);
 			// every source inside every target's window (hence of its read) and left of every target: no test; then the dense
 			// sweep's free and FAR forms on the block's own extent (sweep_block_lut2_free)
@@ -1718,7 +1780,7 @@ __device__ __forceinline__ int band_group(const DevBatch &b, const DevParams &P,
 			const bool free_block = no_check && P.free_sweep && (unsigned)(gx_max - sx_min) <= free_span;
 			const bool far_block = free_block && __ballot(sq + P.bw > gx_min - xs) == 0;
 			const int d0 = (first_lane(xs) - first_lane(ys)) * 4;
-			stage_block_lut(xs, ys, sf, sq, stage, far_block, d0);
+			stage_block_lut_at(lane, xs, ys, sf, sq, stage, far_block, d0);
 			int bestv = best << 7;
 			if (far_block) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
 			else if (free_block) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
@@ -1729,55 +1791,37 @@ __device__ __forceinline__ int band_group(const DevBatch &b, const DevParams &P,
 			arg = (unsigned)(won - 1) < (unsigned)WAVE ? wj : arg;
 			best = bestv >> 7;
 			__builtin_amdgcn_wave_barrier();
-		};
-		// scan: the hits of 64 sources go, in index order, to the lanes after those already staged (ds_permute pushes each hit to its
-		// lane; what does not fit goes round to the first lanes and waits for the next stage); diagonals are read one step ahead,
-		// past the CU's cache (written by other waves of the workgroup, or by this one from other lanes)
-		int sidx = 0, n_st = 0;
-		int jb = lo;
-		int dn = jb + lane < jl ? __hip_atomic_load(b.diag + jb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-		for (; jb < jl; jb += WAVE) {
-			const int j = jb + lane;
-			const int dj = dn;
-			dn = j + WAVE < jl ? __hip_atomic_load(b.diag + j + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-			const bool hit = j < jl && (unsigned)(dj - band_lo) <= width;
-			const unsigned long long m = __ballot(hit);
-			if (m == 0) continue;
-			const int c = __popcll(m);
-			const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-			// (a lane without a hit writes to the first lane that takes none, so no hit is overwritten)
-			const int dst = (hit ? n_st + rank : n_st + c) & (WAVE - 1);
-			const int recv = __builtin_amdgcn_ds_permute(dst << 2, j);
-			if (n_st + c < WAVE) {
-				sidx = lane >= n_st && lane < n_st + c ? recv : sidx;
-				n_st += c;
-			} else {
-				sweep(lane >= n_st ? recv : sidx);
-				n_st += c - WAVE;
-				sidx = recv;                                        // lanes below n_st: the hits that did not fit
-			}
+			sidx = carry; n_st = n_next;
 		}
-		// the last stage, filled up with copies of its last source (same score, same index: nothing changes)
-		if (n_st > 0) sweep(lane < n_st ? sidx : bcast(sidx, n_st - 1));
 	}
-	if (tgt >= 0) { b.band_res[2 * tgt] = best; b.band_res[2 * tgt + 1] = arg; }
+	if (tgt >= 0) { b.res[2 * tgt] = best; b.res[2 * tgt + 1] = arg; }
 	return lo < jl;
 }
 
-// Groups [g_from, g_to) of the slab [s0, s0 + n) (n <= 512): the targets sorted by (diagonal, index) -- a bitonic sort of one key per
-// target, eight per lane, element r * 64 + lane in register r --, group g = register g.  A slab whose diagonals all lie within 2 bw is
-// left in index order (a stretch of one chain: nothing to gain from the sort).
-__device__ __forceinline__ int band_slab_part(const DevBatch &b, const DevParams &P, int4 *stage, const int s0, const int n, const int jl,
-                                              const int g_from, const int g_to)
+// Groups [g_from, g_to) of the slab [s0, min(s0 + band_slab, ce)) (at most 512 anchors): the targets sorted by (diagonal, index) -- a
+// bitonic sort of one key per target, eight per lane, element r * 64 + lane in register r --, group g = register g.  A slab whose
+// diagonals all lie within 2 bw is left in index order (a stretch of one chain: nothing to gain from the sort).
+// Called, not inlined; every argument is wave-uniform, `stage` is the calling wave's LDS scratch.  Returns the groups that had sources
+// before jl (wave-uniform, in a vector register: the caller takes first_lane of it).
+__device__ __noinline__ int band_slab_part(const glb_i32_cptr raw_, const glb_i32_cptr st_, const glb_i32_cptr f_, const glb_i32_cptr diag_, const glb_i32_ptr res_,
+                                           const BandParams bp, const lds_i32x4_ptr stage_, const int s0_, const int ce_, const int jl_, const int g_from_, const int g_to_)
 {
 	constexpr int R = 8;
-	const int lane = lane_id();
-	unsigned key[R];
+	const BandIO b = { uniform_glb(raw_), uniform_glb(st_), uniform_glb(f_), uniform_glb(diag_), uniform_glb(res_) };
+	DevParams P = {};                                               // the fields the sweeps read (never lut_clamp's: the band pass runs without it)
+	P.bw = first_lane(bp.bw); P.dq_lim = first_lane(bp.dq_lim); P.lut_base = first_lane(bp.lut_base); P.free_sweep = first_lane(bp.free_sweep);
+	// (an LDS pointer cast to a plain one inside the function: the compiler follows it to the accesses, which stay LDS ones)
+	int4 *stage = (int4*)(lds_i32x4_ptr)(uintptr_t)(unsigned)first_lane((int)(unsigned)(uintptr_t)stage_);
+	const int s0 = first_lane(s0_), jl = first_lane(jl_), g_from = first_lane(g_from_), g_to = first_lane(g_to_);
+	const int n = min(first_lane(bp.band_slab), first_lane(ce_) - s0);
+	const int lane = lane_by_count();
+	unsigned key[R];                                                // first the diagonal x - y, read once; then the sort key made of it
 	int lo = INT_MAX, hi = INT_MIN, st_lo = INT_MAX;
 #pragma unroll
 	for (int r = 0; r < R; ++r) {
 		const int e = r * WAVE + lane;
-		const int d = e < n ? a_x(b, s0 + e) - a_y(b, s0 + e) : 0;
+		const int d = e < n ? r_x(b.raw, s0 + e) - r_y(b.raw, s0 + e) : 0;
+		key[r] = (unsigned)d;
 		if (e < n) { lo = min(lo, d); hi = max(hi, d); st_lo = min(st_lo, b.st[s0 + e]); }
 	}
 	// no window of the slab reaches before jl: nothing to do (band_merge is skipped for tiles whose windows all start at jl or later)
@@ -1792,7 +1836,7 @@ __device__ __forceinline__ int band_slab_part(const DevBatch &b, const DevParams
 #pragma unroll
 		for (int r = 0; r < R; ++r) {
 			const int e = r * WAVE + lane;
-			key[r] = e < n ? (((unsigned)(a_x(b, s0 + e) - a_y(b, s0 + e) - dmin) >> sh) << 9) | (unsigned)e : ~0u;
+			key[r] = e < n ? (((unsigned)((int)key[r] - dmin) >> sh) << 9) | (unsigned)e : ~0u;
 		}
 #pragma unroll
 		for (int k = 2; k <= R * WAVE; k <<= 1) {
@@ -1829,6 +1873,13 @@ __device__ __forceinline__ int band_slab_part(const DevBatch &b, const DevParams
 		swept += band_group(b, P, stage, tgt, jl);
 	}
 	return swept;
+}
+// The callers' side: the batch's arrays and the parameters by value, this wave's scratch as an LDS pointer.
+__device__ __forceinline__ int band_pass(const DevBatch &b, const DevParams &P, int4 *stage, const int s0, const int ce, const int jl, const int g_from, const int g_to)
+{
+	const BandParams bp = { P.bw, P.dq_lim, P.lut_base, P.free_sweep, P.band_slab };
+	return first_lane(band_slab_part((glb_i32_cptr)(const int*)b.raw, (glb_i32_cptr)b.st, (glb_i32_cptr)b.f, (glb_i32_cptr)b.diag, (glb_i32_ptr)b.band_res,
+	                                 bp, (lds_i32x4_ptr)stage, s0, ce, jl, g_from, g_to));
 }
 // A team's wave waits, before a tile's in-tile phase, for every band part of the tile's slab, and a slab's parts are taken by the
 // waves that own its tiles (or pairs).  That is deadlock-free only while those are distinct waves of the team: parts per slab <= team size.
@@ -1875,16 +1926,17 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 	const bool band = band_on;
 	int band_groups = 0;
 	for (int i0 = cs; i0 < ce; i0 += 2 * WAVE) {
-		TilePair t = load_pair(b, i0, ce);
-		int jb = cs + ((t.lo_a - cs) & ~(WAVE - 1));
-		// band pass (band_slab_part): the whole slab at its first pair; the dense sweep starts at jl
+		// band pass (band_slab_part): the whole slab at its first pair; the dense sweep starts at jl.  A call: it comes before the pair
+		// is loaded, so that no tile state is live across it (the pair's diagonals are for the band passes of LATER slabs)
 		const int s0 = band ? i0 - (i0 - cs) % P.band_slab : cs, jl = s0 - P.band_lag;
 		const bool in_band = band && jl > cs;
-		if (band) band_store_diag(b, t, i0);
 		if (in_band && i0 == s0) {
-			band_groups += band_slab_part(b, P, stage, s0, min(P.band_slab, ce - s0), jl, 0, P.band_slab / WAVE);
+			band_groups += band_pass(b, P, stage, s0, ce, jl, 0, P.band_slab / WAVE);
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (band_merge reads the results past the CU's cache)
 		}
+		TilePair t = load_pair(b, i0, ce);
+		int jb = cs + ((t.lo_a - cs) & ~(WAVE - 1));
+		if (band) band_store_diag(b, t, i0);
 		if (in_band && jb < jl) jb = jl;
 		if (jb < i0) {
 			const int eq_lo = equal_x_run_start(b, cs, i0, first_lane(t.A.x));
@@ -1996,23 +2048,25 @@ __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P
 	int band_groups = 0;
 	for (int t = wave; t < n_tiles; t += n_waves) {
 		const int i0 = cs + t * WAVE;
+		const int sl = t / tps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
+		const bool in_band = band && jl > cs;
+		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
+		// (the band pass is a call: it comes before the tile is loaded, so that no tile state is live across it; the tile's diagonals only have
+		// to be out before the tile is published)
+		if (in_band) {
+			const int part = t - sl * tps;
+			wait_done((jl - cs) / WAVE);                               // the band's sources are final
+			band_groups += band_pass(b, P, stage, s0, ce, jl, part, part + 1);
+			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+		}
 		const Target T = load_target(b, i0, ce, TRACK);
 		const int n_here = min(WAVE, ce - i0);
 		int best = T.q + 1, arg = -1;
 		const int tile_lo = first_lane(T.st);
 		const int st_hi = bcast(T.st, n_here - 1);
 		int jb = cs + ((tile_lo - cs) & ~(WAVE - 1));
-		const int sl = t / tps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
-		const bool in_band = band && jl > cs;
-		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
 		if (band && T.live) b.diag[i0 + lane] = T.x - T.y;
-		if (in_band) {
-			const int part = t - sl * tps;
-			wait_done((jl - cs) / WAVE);                               // the band's sources are final
-			band_groups += band_slab_part(b, P, stage, s0, min(P.band_slab, ce - s0), jl, part, part + 1);
-			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-			if (jb < jl) jb = jl;
-		}
+		if (in_band && jb < jl) jb = jl;
 		const int eq_lo = MODE == MODE_LUT && jb < i0 ? equal_x_run_start(b, cs, i0, first_lane(T.x)) : i0;
 		// tile k of the chunk lives in ring slot k mod n_slots (64 scores per slot; the planner made sure the slots cover
 		// this chunk's widest window plus the tile being written)
@@ -2087,19 +2141,21 @@ __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevPar
 	int band_groups = 0;
 	for (int pr = wave; 2 * pr < n_tiles; pr += n_waves) {
 		const int ta = 2 * pr, i0 = cs + ta * WAVE;              // tile A = tile ta of the chunk, tile B = ta + 1
-		TilePair t = load_pair(b, i0, ce);
-		int jb = cs + ((t.lo_a - cs) & ~(WAVE - 1));
 		const int sl = pr / pps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
 		const bool in_band = band && jl > cs;
 		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
-		if (band) band_store_diag(b, t, i0);
+		// (the band pass is a call: it comes before the pair is loaded, so that no tile state is live across it; the pair's diagonals only have
+		// to be out before tile A is published)
 		if (in_band) {
 			const int part = pr - sl * pps;
 			wait_done((jl - cs) / WAVE);                               // the band's sources are final
-			band_groups += band_slab_part(b, P, stage, s0, min(P.band_slab, ce - s0), jl, 2 * part, 2 * part + 2);
+			band_groups += band_pass(b, P, stage, s0, ce, jl, 2 * part, 2 * part + 2);
 			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-			if (jb < jl) jb = jl;
 		}
+		TilePair t = load_pair(b, i0, ce);
+		int jb = cs + ((t.lo_a - cs) & ~(WAVE - 1));
+		if (band) band_store_diag(b, t, i0);
+		if (in_band && jb < jl) jb = jl;
 		const int eq_lo = jb < i0 ? equal_x_run_start(b, cs, i0, first_lane(t.A.x)) : i0;
 		int slot = (int)((unsigned)((jb - cs) / WAVE) % (unsigned)n_slots);
 		const int first_in_ring = ta - n_slots;                      // tiles from this one on are in the ring
