@@ -527,6 +527,51 @@ int  mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int
                           const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out);
 void mm2gb_align_out_free(mm2gb_align_out_t *out);
 
+/* ---- the text of a PAF line's alignment tags, batched: for record i the bytes text[text_off[i] .. text_off[i+1]) are what
+ *      mm_write_paf3 appends after rl:i (format.c:322-329): "\tcg:Z:" and "%d%c" per CIGAR word with MM2GB_TEXT_CG, then "\tcs:Z:..." with
+ *      MM2GB_TEXT_CS (the long form, =ACGT instead of :n, with MM2GB_TEXT_CS_LONG as well) or "\tMD:Z:..." with MM2GB_TEXT_MD (write_cs_core,
+ *      write_MD_core, format.c:141-218); with both CS and MD it is MD, as there.  regs / aln / cigar: as mm2gb_align_out_t holds them
+ *      (aln[i].cigar_off counted in cigar[]); read_of_reg[i]: the read of record i.  Sequences as text; residues compare as seq_nt4_table
+ *      codes (N against N is a match); a reverse-strand record reads its query reverse-complemented.  A record with cigar_off < 0 gets
+ *      no bytes.  *text_off (n_regs + 1) and *text are malloc'd, free with mm2gb_free.
+ *      Refused, with the error text set and nothing run: a bit outside MM2GB_TEXT_*; a CIGAR operation other than M, I, D (the alignment
+ *      call refuses splice and EQX); a word of length 0; a record whose words do not sum to qe - qs and re - rs; a record outside its sequences.
+ *      The host form is the definition; the device form (csrc/aln_text_kernels.hip) equals it byte for byte. ---- */
+#define MM2GB_TEXT_CG       0x1
+#define MM2GB_TEXT_CS       0x2
+#define MM2GB_TEXT_CS_LONG  0x4
+#define MM2GB_TEXT_MD       0x8
+int  mm2gb_aln_text_host(int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens,
+                         int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar, int n_threads,
+                         int64_t **text_off, char **text);
+int  mm2gb_aln_text_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                        const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
+                        int64_t **text_off, char **text);
+/* the device form's seams, for tests: consts2 [0] columns (words, for cg:Z) per slice, [1] threads of a workgroup; s4 (optional): the last
+ * call's seconds: [0] residues to the device (0 where they were resident), [1] the host's pass over the words (checks, word starts, slices),
+ * [2] words and slices up, kernels, [3] the text back */
+int  mm2gb_aln_text_gpu_info(mm2gb_engine_t *eng, int64_t *consts2, double *s4);
+
+/* ---- the mapper with base-level alignment (minimap2 -c, --cs, --MD; csrc/mapper.cpp): mm2gb_map_reads / mm2gb_map_reads_stream with a
+ *      mm2gb_map_aln_t.  After mm_filter_strand_retained the batch's surviving records go through mm2gb_align_regs_* in one call (map.c:342-352;
+ *      k and the HPC flag are the index's; what that call refuses fails the mapping call with the same text), then per read mm_set_parent,
+ *      mm_select_sub and mm_set_mapq in their forms with an alignment, and every PAF line is format.c:274-329's: columns 10 and 11 from the
+ *      alignment, NM ms AS nn tp cm s1 s2 de zd rl, then the text mm2gb_aln_text_* gives for `what` (one call for the batch's lines).
+ *      s_extra (optional): seconds for the alignment call, the steps after it and the text; stats->s_post holds the rest of the host's share. ---- */
+typedef struct {
+	const char *const *ref_seqs;      /* the reference sequences as text, n_ref of them */
+	mm2gb_align_opt_t  opt;
+	int32_t what;                     /* MM2GB_TEXT_*; 0: the tags without cg / cs / MD (minimap2 has no such form; allowed here) */
+	int32_t align_on_device;          /* 1: the device form of the alignment call, and so is 0, the value a zeroed structure has (the default); -1: host threads */
+	int32_t text_on_device;           /* 1: the device form of the text call; -1: host threads; 0 (default): host threads, by profiles/aln_text_rate.json */
+} mm2gb_map_aln_t;
+int  mm2gb_map_reads_aln(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                         const mm2gb_map_opt_t *opt, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                         char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra /* 3, optional */);
+int  mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra /* 3, optional; summed over chunks */);
+
 #ifdef __cplusplus
 }
 #endif

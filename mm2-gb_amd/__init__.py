@@ -700,6 +700,72 @@ def _engine_align_regs(self, opt, k, hpc, refs, reads, regs, anchors):
 Engine.align_regs = _engine_align_regs
 
 
+# ---- the text of a PAF line's alignment tags (mm2gb_aln_text_host / _gpu): cg:Z, cs:Z, MD:Z for a batch of records ----
+TEXT_CG, TEXT_CS, TEXT_CS_LONG, TEXT_MD = 0x1, 0x2, 0x4, 0x8
+
+
+def flatten_aligned(res):
+    """What align_regs_host / Engine.align_regs return per read, as aln_text_* takes it: (regs, read_of_reg, aln, cigar), flat, with
+    aln.cigar_off counted in cigar."""
+    regs = np.concatenate([x[0] for x in res]) if res else np.zeros(0, REG_DTYPE)
+    aln = np.concatenate([x[1] for x in res]).copy() if res else np.zeros(0, ALN_DTYPE)
+    cigar = np.concatenate([x[2] for x in res]) if res else np.zeros(0, np.uint32)
+    read_of = np.concatenate([np.full(len(x[0]), r, np.int32) for r, x in enumerate(res)]) if res else np.zeros(0, np.int32)
+    base = np.concatenate([np.full(len(x[0]), b, np.int64) for x, b in zip(res, np.cumsum([0] + [len(x[2]) for x in res[:-1]]))]) if res else np.zeros(0, np.int64)
+    have = aln["cigar_off"] >= 0
+    aln["cigar_off"][have] += base[have]
+    return regs, read_of, aln, cigar
+
+
+def _aln_text_call(fn, head, what, refs, reads, regs, read_of_reg, aln, cigar, tail):
+    refs = [bytes(s) for s in refs]; reads = [bytes(s) for s in reads]
+    ref_arr = (C.c_char_p * max(len(refs), 1))(*refs); read_arr = (C.c_char_p * max(len(reads), 1))(*reads)
+    ref_len = np.ascontiguousarray([len(s) for s in refs], dtype=np.int32); read_len = np.ascontiguousarray([len(s) for s in reads], dtype=np.int32)
+    regs = np.ascontiguousarray(regs, dtype=REG_DTYPE); aln = np.ascontiguousarray(aln, dtype=ALN_DTYPE)
+    read_of_reg = np.ascontiguousarray(read_of_reg, dtype=np.int32); cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    if not len(regs) == len(aln) == len(read_of_reg):
+        raise Mm2gbError("aln_text: regs, read_of_reg and aln must have one entry per record")
+    have = aln["cigar_off"] >= 0
+    if have.any() and (int((aln["cigar_off"] + aln["n_cigar"])[have].max()) > len(cigar) or int(aln["n_cigar"][have].min()) < 0):
+        raise Mm2gbError("aln_text: a record's CIGAR words lie outside cigar")
+    off, text = C.c_void_p(0), C.c_void_p(0)
+    fn.argtypes = [C.c_void_p] * len(head) + [C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p] + [C.c_int] * len(tail) + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    _check(fn(*head, int(what), len(refs), ref_arr, ref_len.ctypes.data, len(reads), read_arr, read_len.ctypes.data, len(regs), regs.ctypes.data, read_of_reg.ctypes.data,
+              aln.ctypes.data, cigar.ctypes.data, *tail, C.byref(off), C.byref(text)))
+    try:
+        o = _take(off.value, len(regs) + 1, np.int64)
+        return o, C.string_at(text.value, int(o[-1]))
+    finally:
+        lib().mm2gb_free(off); lib().mm2gb_free(text)
+
+
+def aln_text_host(what, refs, reads, regs, read_of_reg, aln, cigar, threads=4):
+    """mm2gb_aln_text_host: what mm_write_paf3 appends after rl:i for every record -- cg:Z (TEXT_CG), cs:Z (TEXT_CS, with TEXT_CS_LONG the long
+    form) or MD:Z (TEXT_MD) -- the definition.  regs / aln: REG_DTYPE / ALN_DTYPE arrays, one entry per record, aln.cigar_off counted in cigar;
+    read_of_reg: the read of every record (flatten_aligned makes all four from an alignment call's result).  Returns (offsets, bytes): record
+    i's text is bytes[offsets[i]:offsets[i + 1]]."""
+    return _aln_text_call(lib().mm2gb_aln_text_host, (), what, refs, reads, regs, read_of_reg, aln, cigar, (int(threads),))
+
+
+def _engine_aln_text(self, what, refs, reads, regs, read_of_reg, aln, cigar):
+    """mm2gb_aln_text_gpu: aln_text_host's arguments and results, every column on the device (csrc/aln_text_kernels.hip)."""
+    return _aln_text_call(lib().mm2gb_aln_text_gpu, (self._h,), what, refs, reads, regs, read_of_reg, aln, cigar, ())
+
+
+def _engine_aln_text_info(self):
+    """The device form's seams and the last call's seconds: dict with slice (columns per slice), wg (threads of a workgroup), s_upload (residues), s_prepare (the host's pass over the words), s_kernels (words up and kernels), s_back."""
+    c = (C.c_int64 * 2)(); s = (C.c_double * 4)()
+    fn = lib().mm2gb_aln_text_gpu_info
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(fn(self._h, c, s))
+    return dict(slice=int(c[0]), wg=int(c[1]), s_upload=s[0], s_prepare=s[1], s_kernels=s[2], s_back=s[3])
+
+
+Engine.aln_text = _engine_aln_text
+Engine.aln_text_info = _engine_aln_text_info
+
+
 def _take_chains(out, R):
     """Copy a mm2gb_chains_t into per-read (u, a_out) arrays and release it."""
     try:
@@ -1113,23 +1179,62 @@ def map_opt(**kw):
     return o
 
 
-def map_reads(engine, index, ref_names, reads, opt=None, k=15):
-    """mm2gb_map_reads: reads = list of (name, sequence bytes); returns (PAF text, stats dict).  index: a SeedIndex of the references."""
+class MapAln(C.Structure):
+    """mm2gb_map_aln_t: what mm2gb_map_reads_aln needs beside the mapping options (make one with map_align)."""
+    _fields_ = [("ref_seqs", C.POINTER(C.c_char_p)), ("opt", AlignOpt), ("what", C.c_int32), ("align_on_device", C.c_int32), ("text_on_device", C.c_int32)]
+
+
+def map_align(refs, preset="map-ont", cigar=True, cs=None, md=False, align_on_device=0, text_on_device=0, **align_opt_fields):
+    """Base-level alignment for map_reads / map_reads_stream (their align= argument; minimap2 -c): refs: the reference sequences as bytes, in the
+    index's order; preset: "map-ont" or "map-pb" (align_opt), keyword overrides for its fields; cigar: cg:Z; cs: None, "short" or "long"
+    (--cs, --cs=long); md: MD:Z (--MD; it is written instead of cs when both are asked for, as by minimap2).  align_on_device / text_on_device:
+    1 the device form, -1 host threads, 0 the default (alignment on the device; text on host threads)."""
+    if cs not in (None, "short", "long"):
+        raise Mm2gbError('map_align: cs is None, "short" or "long"')
+    a = MapAln()
+    a._refs = [bytes(s) for s in refs]                                                  # (kept alive with the structure)
+    a._arr = (C.c_char_p * max(len(a._refs), 1))(*a._refs)
+    a.ref_seqs = C.cast(a._arr, C.POINTER(C.c_char_p))
+    a.opt = align_opt(preset, **align_opt_fields)
+    a.what = (TEXT_CG if cigar else 0) | (TEXT_CS if cs else 0) | (TEXT_CS_LONG if cs == "long" else 0) | (TEXT_MD if md else 0)
+    a.align_on_device, a.text_on_device = int(align_on_device), int(text_on_device)
+    return a
+
+
+def _check_align_refs(align, ref_names):
+    if len(align._refs) != len(ref_names):
+        raise Mm2gbError("map_reads: align holds another number of reference sequences than ref_names")
+
+
+def _stats_with_extra(st, extra):
+    return dict(st.as_dict(), s_align=round(extra[0], 4), s_post_align=round(extra[1], 4), s_text=round(extra[2], 4))
+
+
+def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
+    """mm2gb_map_reads: reads = list of (name, sequence bytes); returns (PAF text, stats dict).  index: a SeedIndex of the references.
+    align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln); the stats then hold s_align, s_post_align and s_text as well."""
     L = lib()
-    L.mm2gb_map_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                  C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
+    head = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
+    tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
+    L.mm2gb_map_reads.argtypes = head + tail
+    L.mm2gb_map_reads_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
     opt = opt or map_opt()
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
     names = (C.c_char_p * len(reads))(*[n.encode() for n, _ in reads])
     seqs_b = [bytes(s) for _, s in reads]
     seqs = (C.c_char_p * len(reads))(*seqs_b)
     lens = np.ascontiguousarray([len(s) for s in seqs_b], dtype=np.int32)
-    out, n, st = C.c_void_p(), C.c_int64(), MapStats()
-    _check(L.mm2gb_map_reads(engine._h, index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt), len(reads), names, seqs, lens.ctypes.data,
-                             C.byref(out), C.byref(n), C.byref(st)))
+    out, n, st, extra = C.c_void_p(), C.c_int64(), MapStats(), (C.c_double * 3)()
+    first = (engine._h, index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt))
+    rest = (len(reads), names, seqs, lens.ctypes.data, C.byref(out), C.byref(n), C.byref(st))
+    if align is None:
+        _check(L.mm2gb_map_reads(*first, *rest))
+    else:
+        _check_align_refs(align, ref_names)
+        _check(L.mm2gb_map_reads_aln(*first, C.byref(align), *rest, extra))
     text = C.string_at(out, n.value).decode()
     L.mm2gb_free(out)
-    return text, st.as_dict()
+    return text, st.as_dict() if align is None else _stats_with_extra(st, extra)
 
 
 def map_reads_multi(engines, index, ref_names, reads, opt=None, k=15):
@@ -1162,13 +1267,15 @@ def _engine_release_host_scratch(self):
 Engine.release_host_scratch = _engine_release_host_scratch
 
 
-def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0):
+def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0, align=None):
     """mm2gb_map_reads_stream: a run of any size as a stream of chunks of about chunk_bases bases; every engine (several per device overlap
     host stages with kernels, engines on several devices shard the reads) takes the next chunk.  Returns (PAF text in read order, stats:
-    counts summed, s_* summed over chunks)."""
+    counts summed, s_* summed over chunks).  align: as for map_reads (mm2gb_map_reads_stream_aln)."""
     L = lib()
-    L.mm2gb_map_reads_stream.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
-                                         C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
+    head = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
+    tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
+    L.mm2gb_map_reads_stream.argtypes = head + tail
+    L.mm2gb_map_reads_stream_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
     opt = opt or map_opt()
     hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
@@ -1176,9 +1283,14 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
     seqs_b = [s if isinstance(s, bytes) else bytes(s) for _, s in reads]
     seqs = (C.c_char_p * len(reads))(*seqs_b)
     lens = np.ascontiguousarray([len(s) for s in seqs_b], dtype=np.int32)
-    out, n, st = C.c_void_p(), C.c_int64(), MapStats()
-    _check(L.mm2gb_map_reads_stream(hs, len(engines), index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt), len(reads), names, seqs, lens.ctypes.data,
-                                    int(chunk_bases), C.byref(out), C.byref(n), C.byref(st)))
+    out, n, st, extra = C.c_void_p(), C.c_int64(), MapStats(), (C.c_double * 3)()
+    first = (hs, len(engines), index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt))
+    rest = (len(reads), names, seqs, lens.ctypes.data, int(chunk_bases), C.byref(out), C.byref(n), C.byref(st))
+    if align is None:
+        _check(L.mm2gb_map_reads_stream(*first, *rest))
+    else:
+        _check_align_refs(align, ref_names)
+        _check(L.mm2gb_map_reads_stream_aln(*first, C.byref(align), *rest, extra))
     text = C.string_at(out, n.value).decode()
     L.mm2gb_free(out)
-    return text, st.as_dict()
+    return text, st.as_dict() if align is None else _stats_with_extra(st, extra)

@@ -834,12 +834,6 @@ struct HostBackend : AlBackend {
 	}
 };
 
-inline uint8_t nt4(char ch)
-{
-	switch (ch) { case 0: case 1: case 2: case 3: return (uint8_t)ch;          // seq_nt4_table (sketch.c) leaves bytes 0..3 as they are
-	              case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
-}
-
 } // namespace
 
 int al_zdrop_code(const AlCtx &c, const AlJob &j, const AlDrop &d)

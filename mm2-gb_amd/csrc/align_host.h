@@ -18,6 +18,13 @@ struct AlCtx {
 	std::vector<uint8_t> refs, reads;          // one residue per base (seq_nt4_table); reads as given, the reverse strand is computed
 };
 
+// a base as text -> its residue
+inline uint8_t nt4(char ch)
+{
+	switch (ch) { case 0: case 1: case 2: case 3: return (uint8_t)ch;          // seq_nt4_table (sketch.c) leaves bytes 0..3 as they are
+	              case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
+}
+
 // a job of a round with its DP parameters (first pass), and what came of it
 struct AlRun {
 	AlJob j;

@@ -67,6 +67,7 @@ struct DevBackend : AlBackend {
 		if (!c.refs.empty()) MM2GB_HIP(hipMemcpyAsync(e.al_refs.ptr, c.refs.data(), c.refs.size(), hipMemcpyHostToDevice, e.stream));
 		if (!c.reads.empty()) MM2GB_HIP(hipMemcpyAsync(e.al_reads.ptr, c.reads.data(), c.reads.size(), hipMemcpyHostToDevice, e.stream));
 		MM2GB_HIP(hipStreamSynchronize(e.stream));
+		e.al_resident[0] = (int64_t)c.refs.size(); e.al_resident[1] = (int64_t)c.reads.size();
 		uploaded = true;
 		seconds[0] += since(t0);
 		return 0;
@@ -185,6 +186,7 @@ int mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int 
                          const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out)
 {
 	if (!eng) { if (out) memset(out, 0, sizeof *out); return fail("mm2gb: null engine"); }
+	eng->e.al_resident[0] = eng->e.al_resident[1] = -1;          // until this call's backend has uploaded its batch
 	DevBackend be(eng->e);
 	return al_align_regs("mm2gb_align_regs_gpu", opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors,
 	                     std::min(usable_cpus(), 16), &be, out);

@@ -103,6 +103,13 @@ struct Engine {
 	// the alignment of hits (align_kernels.hip; mm2gb_align_regs_gpu): the batch's resident residues (references, reads), a round's job
 	// descriptors, gather slices, the list of gap fills to test and the test's results
 	DevBuf al_refs, al_reads, al_jobs, al_slices, al_list, al_drop;
+	// the text of the alignment tags (aln_text_kernels.hip; mm2gb_aln_text_gpu): records, words, slices, the slices' counts and carries, their
+	// byte counts and destinations, the scan's work space, the text
+	DevBuf tx_recs, tx_words, tx_slices, tx_cnt, tx_run, tx_bytes, tx_dest, tx_tmp, tx_text;
+	double tx_s[4] = { 0, 0, 0, 0 };       // of the last call: residues up, the host's pass over the words (checks, slices), words up + kernels, text back
+	// residues of al_refs / al_reads that the LAST alignment call (mm2gb_align_regs_gpu) or text call uploaded, laid end to end in the call's order:
+	// their numbers of bytes, -1 when that call uploaded nothing.  What lets a later step of the same batch use them without uploading again.
+	int64_t al_resident[2] = { -1, -1 };
 	// what the post-pass leaves for the host, two sets: the boundary keeps two batches in flight (the results of batch k are
 	// fetched after batch k+1 has been launched)
 	struct PostOut {

@@ -506,6 +506,7 @@ void Engine::shutdown()
 	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
 	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack,
 	                   &al_refs, &al_reads, &al_jobs, &al_slices, &al_list, &al_drop,
+	                   &tx_recs, &tx_words, &tx_slices, &tx_cnt, &tx_run, &tx_bytes, &tx_dest, &tx_tmp, &tx_text,
 	                   &post_out[0].u_off, &post_out[0].a_off, &post_out[0].u_out, &post_out[0].a_out, &post_out[1].u_off, &post_out[1].a_off, &post_out[1].u_out, &post_out[1].a_out })
 		b->release();
 	cap_post_n = cap_post_reads = 0;

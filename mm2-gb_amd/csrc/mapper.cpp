@@ -7,8 +7,12 @@
 //   secondaries stay (mm_select_sub, hit.c:272-295, mm_sync_regs hit.c:247-270), divergence estimate (mm_est_err, esterr.c:31-64),
 //   mm_filter_strand_retained (hit.c:297-309), mapping quality (mm_set_mapq, hit.c:420-466), PAF line (format.c:274-321).
 //
-// Not reproduced: more than one query segment, base-level alignment and everything that depends on it (inversions, cs/MD, SAM),
-// ALT contigs, the heap variant of seed collection, homopolymer-compressed indexes, --qstrand, multi-part indexes.
+//   With a mm2gb_map_aln_t (mm2gb_map_reads_aln; minimap2 -c): after mm_filter_strand_retained the batch's surviving records go through
+//   mm2gb_align_regs_* in one call (map.c:342-352), then per read mm_set_parent, mm_select_sub and mm_set_mapq in their forms with an
+//   alignment, and the PAF line gets NM/ms/AS/nn/de and cg:Z / cs:Z / MD:Z (the text of the whole batch from one mm2gb_aln_text_* call).
+//
+// Not reproduced: more than one query segment, spliced and short-read alignment, --eqx, SAM output, ALT contigs, the heap variant of
+// seed collection, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -23,6 +27,8 @@
 #include <vector>
 #include "engine.h"
 #include "host_chain.h"
+#include "align_host.h"
+#include "aln_text_host.h"
 #include "trace.h"
 
 namespace mm2gb {
@@ -34,6 +40,11 @@ struct Hit {                                   // mm_reg1_t without the alignmen
 	bool rev, strand_retained;
 	uint32_t hash;
 	float div;
+	// with an alignment (mm_extra_t, minimap.h:94-102; the record's split and inv bits): none of it is set or looked at without one
+	bool has_p = false, inv = false;
+	int split = 0, dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0, trans_strand = 0, n_cigar = 0;
+	uint32_t flags = 0;                        // mm_reg1_t's bit-field word as the record carries it between the calls
+	int64_t aln = -1;                          // its place in the alignment call's result
 };
 
 enum { PARENT_UNSET = -1, PARENT_TMP_PRI = -2 };   // mmpriv.h:13-14
@@ -42,9 +53,10 @@ enum { PARENT_UNSET = -1, PARENT_TMP_PRI = -2 };   // mmpriv.h:13-14
 uint32_t name_hash(const char *s) { uint32_t h = (uint32_t)(unsigned char)*s; if (h) for (++s; *s; ++s) h = (h << 5) - h + (uint32_t)(unsigned char)*s; return h; }
 uint32_t wang(uint32_t k) { k += ~(k << 15); k ^= k >> 10; k += k << 3; k ^= k >> 6; k += ~(k << 11); k ^= k >> 16; return k; }
 
-// hit.c:125-198 without alignments and ALT: hits come best first; a hit is secondary to the first earlier primary it overlaps by
-// more than mask_level of the shorter of the two (less what earlier primaries leave uncovered of it)
-void set_parent(float mask_level, int mask_len, std::vector<Hit> &r, bool hard_mask_level)
+// hit.c:125-198 without ALT: hits come best first; a hit is secondary to the first earlier primary it overlaps by
+// more than mask_level of the shorter of the two (less what earlier primaries leave uncovered of it).  Where both carry an alignment
+// the primary's dp_max2 follows, and a secondary within sub_diff of it counts as a sub-optimal hit (hit.c:171-176)
+void set_parent(float mask_level, int mask_len, std::vector<Hit> &r, bool hard_mask_level, int sub_diff = 0)
 {
 	const int n = (int)r.size();
 	if (n == 0) return;
@@ -86,7 +98,12 @@ void set_parent(float mask_level, int mask_len, std::vector<Hit> &r, bool hard_m
 				if ((float)ol / lmin - (float)uncov / lmax > mask_level && uncov <= mask_len) {
 					ri.parent = rp.parent;
 					rp.subsc = std::max(rp.subsc, ri.score);
-					if (ri.cnt >= rp.cnt) ++rp.n_sub;
+					bool cnt_sub = ri.cnt >= rp.cnt;
+					if (rp.has_p && ri.has_p && (rp.rid != ri.rid || rp.rs != ri.rs || rp.re != ri.re || ol != lmin)) {      // (the last condition: not the same hit after DP)
+						rp.dp_max2 = std::max(rp.dp_max2, ri.dp_max);
+						if (rp.dp_max - ri.dp_max <= sub_diff) cnt_sub = true;
+					}
+					if (cnt_sub) ++rp.n_sub;
 					secondary = true;
 					break;
 				}
@@ -121,7 +138,7 @@ void select_sub(float pri_ratio, int min_diff, int best_n, bool check_strand, in
 	int n_2nd = 0;
 	for (size_t i = 0; i < n; ++i) {
 		const int p = r[i].parent;
-		if (p == (int)i) { r[k++] = r[i]; continue; }
+		if (p == (int)i || r[i].inv) { r[k++] = r[i]; continue; }          // primary, or an inversion (only an alignment makes one)
 		const Hit &rp = r[(size_t)p];                 // parents precede their secondaries and are never dropped: still at index p? see below
 		if ((r[i].score >= rp.score * pri_ratio || r[i].score + min_diff >= rp.score) && n_2nd < best_n) {
 			if (!(r[i].qs == rp.qs && r[i].qe == rp.qe && r[i].rid == rp.rid && r[i].rs == rp.rs && r[i].re == rp.re)) { r[k++] = r[i]; ++n_2nd; }
@@ -178,46 +195,83 @@ void filter_strand_retained(std::vector<Hit> &r)
 	r.resize(k);
 }
 
-// hit.c:420-466 without alignments
-void set_mapq(std::vector<Hit> &r, int min_chain_sc, int rep_len)
+// hit.c:420-466 for long reads (is_sr = 0); match_sc: the alignment's match score, looked at only where a hit carries an alignment
+void set_mapq(std::vector<Hit> &r, int min_chain_sc, int rep_len, int match_sc = 1)
 {
 	if (r.empty()) return;
 	int64_t sum_sc = 0;
 	for (const Hit &h : r) if (h.parent == h.id) sum_sc += h.score;
 	const float uniq_ratio = (float)sum_sc / (sum_sc + rep_len);
+	bool any_inv = false;
 	for (Hit &h : r) {
+		if (h.inv) { h.mapq = 0; any_inv = true; continue; }
 		if (h.parent != h.id) { h.mapq = 0; continue; }
 		const float pen_s1 = (h.score > 100 ? 1.0f : 0.01f * h.score) * uniq_ratio;
 		float pen_cm = h.cnt > 10 ? 1.0f : 0.1f * h.cnt;
 		pen_cm = pen_s1 < pen_cm ? pen_s1 : pen_cm;
 		const int subsc = h.subsc > min_chain_sc ? h.subsc : min_chain_sc;
-		const float x = (float)subsc / h.score0;
-		int mapq = (int)(pen_cm * 40.0f * (1.0f - x) * logf((float)h.score));
+		int mapq;
+		if (h.has_p && h.dp_max2 > 0 && h.dp_max > 0) {
+			const float identity = (float)h.mlen / h.blen;
+			const float x = (float)h.dp_max2 * subsc / h.dp_max / h.score0;
+			mapq = (int)(identity * pen_cm * 40.0f * (1.0f - x * x) * logf((float)h.dp_max / match_sc));
+			const int mapq_alt = (int)(6.02f * identity * identity * (h.dp_max - h.dp_max2) / match_sc + .499f);      // "BWA-MEM like", in case the long-read heuristic fails
+			mapq = mapq < mapq_alt ? mapq : mapq_alt;
+		} else {
+			const float x = (float)subsc / h.score0;
+			if (h.has_p) {
+				const float identity = (float)h.mlen / h.blen;
+				mapq = (int)(identity * pen_cm * 40.0f * (1.0f - x) * logf((float)h.dp_max / match_sc));
+			} else mapq = (int)(pen_cm * 40.0f * (1.0f - x) * logf((float)h.score));
+		}
 		mapq -= (int)(4.343f * logf((float)(h.n_sub + 1)) + .499f);
 		mapq = mapq > 0 ? mapq : 0;
 		h.mapq = mapq < 60 ? mapq : 60;
+		if (h.has_p && h.dp_max > h.dp_max2 && h.mapq == 0) h.mapq = 1;
+	}
+	// mm_set_inv_mapq (hit.c:395-419): an inversion between two primaries on the reference takes the smaller of their qualities
+	if (!any_inv || r.size() < 3) return;
+	std::vector<mm2gb_anchor_t> aux;
+	for (size_t i = 0; i < r.size(); ++i) if (r[i].parent == (int)i || r[i].parent < 0) aux.push_back({ (uint64_t)r[i].rid << 32 | (uint32_t)r[i].rs, (uint64_t)i });
+	sort_by_x_like_host(aux.data(), aux.data() + aux.size());
+	for (size_t i = 1; i + 1 < aux.size(); ++i) {
+		Hit &h = r[(size_t)aux[i].y];
+		if (h.inv) h.mapq = std::min(r[(size_t)aux[i - 1].y].mapq, r[(size_t)aux[i + 1].y].mapq);
 	}
 }
 
 void append_int(std::string &s, long long v) { char buf[24]; snprintf(buf, sizeof buf, "%lld", v); s += buf; }
 
-// format.c:274-321
-void write_paf(std::string &out, const char *qname, int qlen, const Hit &h, const char *rname, int rlen, int rep_len)
+// format.c:274-321; words: the hit's CIGAR words where it carries an alignment (mm_event_identity, align.c:895-915, counts its gaps);
+// the line ends after rl:i -- what follows it (cg:Z, cs:Z, MD:Z) and the line's end are the caller's
+void write_paf(std::string &out, const char *qname, int qlen, const Hit &h, const char *rname, int rlen, int rep_len, const uint32_t *words = nullptr)
 {
 	out += qname; out += '\t'; append_int(out, qlen); out += '\t'; append_int(out, h.qs); out += '\t'; append_int(out, h.qe); out += '\t';
 	out += h.rev ? '-' : '+'; out += '\t'; out += rname; out += '\t'; append_int(out, rlen); out += '\t'; append_int(out, h.rs); out += '\t';
 	append_int(out, h.re); out += '\t'; append_int(out, h.mlen); out += '\t'; append_int(out, h.blen); out += '\t'; append_int(out, h.mapq);
-	out += "\ttp:A:"; out += h.id == h.parent ? 'P' : 'S';
+	if (h.has_p) {
+		out += "\tNM:i:"; append_int(out, h.blen - h.mlen + h.n_ambi); out += "\tms:i:"; append_int(out, h.dp_max); out += "\tAS:i:"; append_int(out, h.dp_score);
+		out += "\tnn:i:"; append_int(out, h.n_ambi);
+		if (h.trans_strand == 1 || h.trans_strand == 2) { out += "\tts:A:"; out += "?+-?"[h.trans_strand]; }
+	}
+	out += "\ttp:A:"; out += h.id == h.parent ? (h.inv ? 'I' : 'P') : (h.inv ? 'i' : 'S');
 	out += "\tcm:i:"; append_int(out, h.cnt);
 	out += "\ts1:i:"; append_int(out, h.score);
 	if (h.parent == h.id) { out += "\ts2:i:"; append_int(out, h.subsc); }
-	if (h.div >= 0.0f && h.div <= 1.0f) {
+	if (h.has_p) {
+		int32_t n_gap = 0, n_gapo = 0;
+		for (int32_t k = 0; k < h.n_cigar; ++k) if ((words[k] & 0xf) == 1 || (words[k] & 0xf) == 2) { ++n_gapo; n_gap += (int32_t)(words[k] >> 4); }
+		const double ident = (double)h.mlen / (h.blen + h.n_ambi - n_gap + n_gapo), de = 1.0 - ident;
+		out += "\tde:f:";
+		if (de == 0.0) out += '0';
+		else { char buf[16]; snprintf(buf, sizeof buf, "%.4f", de); out += buf; }
+	} else if (h.div >= 0.0f && h.div <= 1.0f) {
 		out += "\tdv:f:";
 		if (h.div == 0.0f) out += '0';
 		else { char buf[16]; snprintf(buf, sizeof buf, "%.4f", h.div); out += buf; }
 	}
+	if (h.split) { out += "\tzd:i:"; append_int(out, h.split); }
 	out += "\trl:i:"; append_int(out, rep_len);
-	out += '\n';
 }
 
 } // namespace
@@ -259,20 +313,46 @@ int mm2gb_engine_release_host_scratch(mm2gb_engine_t *eng)
 
 static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
                           const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                          char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats);
+                          char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra);
+
+// nullptr, or why a mm2gb_map_aln_t cannot be used
+static const char *bad_aln(const mm2gb_map_aln_t *aln)
+{
+	if (!aln || !aln->ref_seqs) return "null argument";
+	if (aln->what & ~(MM2GB_TEXT_CG | MM2GB_TEXT_CS | MM2GB_TEXT_CS_LONG | MM2GB_TEXT_MD)) return "what has a bit outside MM2GB_TEXT_*";
+	return nullptr;
+}
+
+static int map_reads_try(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                         const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                         char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra)
+{
+	// a batch's arrays are gigabytes: running out of host memory on this thread is an error of the call, not the end of the process
+	try { return map_reads_body(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s_extra); }
+	catch (const std::bad_alloc&) { return fail("mm2gb_map_reads: out of host memory"); }
+}
+
+int mm2gb_map_reads_aln(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                        const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                        char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
+{
+	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_aln: ") + why);
+	double s3[3] = { 0, 0, 0 };
+	const int rc = map_reads_try(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3);
+	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
+	return rc;
+}
 
 int mm2gb_map_reads(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
                     const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                     char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
 {
-	// a batch's arrays are gigabytes: running out of host memory on this thread is an error of the call, not the end of the process
-	try { return map_reads_body(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats); }
-	catch (const std::bad_alloc&) { return fail("mm2gb_map_reads: out of host memory"); }
+	return map_reads_try(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, nullptr, nullptr);
 }
 
 static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
                           const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                          char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
+                          char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra)
 {
 	if (!eng || !ix || !opt_in || !paf_out || !paf_len || n_reads < 0 || n_ref <= 0 || !ref_names || !ref_lens || (n_reads > 0 && (!names || !seqs || !lens)))
 		return fail("mm2gb_map_reads: null argument");
@@ -590,36 +670,123 @@ static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, c
 	tr.reset(); tr.reset(new TraceRange("mm2gb:map_hits_to_paf"));
 	// 6. per read on the host
 	std::vector<std::string> lines(R);
-	{
+	auto on_threads = [&](auto one) {                     // one(read, the worker's scratch) for every read, on the call's host threads
 		std::atomic<int32_t> next(0);
-		auto work = [&]() {
-			std::vector<Hit> hs;
-			for (;;) {
-				const int32_t ri = next.fetch_add(1);
-				if (ri >= n_reads) break;
-				const size_t r = (size_t)ri;
-				hs.clear();
-				for (int64_t j = u_off[r]; j < u_off[r + 1]; ++j) {
-					const mm2gb_reg_t &g = regs[(size_t)j];
-					Hit h;
-					h.id = g.id; h.cnt = g.cnt; h.rid = g.rid; h.score = g.score; h.qs = g.qs; h.qe = g.qe; h.rs = g.rs; h.re = g.re; h.parent = g.parent;
-					h.subsc = g.subsc; h.as = g.as; h.mlen = g.mlen; h.blen = g.blen; h.n_sub = g.n_sub; h.score0 = g.score0;
-					h.mapq = 0; h.rev = (g.flags >> 10) & 1; h.strand_retained = false; h.hash = g.hash; h.div = g.div;
-					hs.push_back(h);
-				}
-				if (hs.empty()) continue;
-				set_parent(opt.mask_level, opt.mask_len, hs, false);                                     // map.c:336
-				select_sub(opt.pri_ratio, k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);          // map.c:337
-				estimate_divergence(lens[r], ref_len_v, hs, ca + c_off[r], mt[r].n_mini_pos, mt[r].mini_pos);   // map.c:751
-				filter_strand_retained(hs);                                                              // map.c:752
-				set_mapq(hs, opt.min_chain_score, mt[r].rep_len);                                        // map.c:758
-				for (const Hit &h : hs) write_paf(lines[r], names[r] ? names[r] : "*", lens[r], h, ref_names[h.rid], ref_lens[h.rid], mt[r].rep_len);
-			}
-		};
+		auto work = [&]() { std::vector<Hit> hs; for (;;) { const int32_t ri = next.fetch_add(1); if (ri >= n_reads) break; one((size_t)ri, hs); } };
 		const int nt = std::max(1, opt.host_threads);
 		std::vector<std::thread> pool;
 		for (int t = 0; t < nt; ++t) pool.emplace_back(work);
 		for (auto &th : pool) th.join();
+	};
+	// the hits of a read up to mm_filter_strand_retained (map.c:749-752)
+	auto chain_hits = [&](size_t r, std::vector<Hit> &hs) {
+		hs.clear();
+		for (int64_t j = u_off[r]; j < u_off[r + 1]; ++j) {
+			const mm2gb_reg_t &g = regs[(size_t)j];
+			Hit h;
+			h.id = g.id; h.cnt = g.cnt; h.rid = g.rid; h.score = g.score; h.qs = g.qs; h.qe = g.qe; h.rs = g.rs; h.re = g.re; h.parent = g.parent;
+			h.subsc = g.subsc; h.as = g.as; h.mlen = g.mlen; h.blen = g.blen; h.n_sub = g.n_sub; h.score0 = g.score0;
+			h.mapq = 0; h.rev = (g.flags >> 10) & 1; h.strand_retained = false; h.hash = g.hash; h.div = g.div; h.flags = g.flags;
+			hs.push_back(h);
+		}
+		if (hs.empty()) return;
+		set_parent(opt.mask_level, opt.mask_len, hs, false);                                     // map.c:336
+		select_sub(opt.pri_ratio, k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);          // map.c:337
+		estimate_divergence(lens[r], ref_len_v, hs, ca + c_off[r], mt[r].n_mini_pos, mt[r].mini_pos);   // map.c:751
+		filter_strand_retained(hs);                                                              // map.c:752
+	};
+	if (!aln) {
+		on_threads([&](size_t r, std::vector<Hit> &hs) {
+			chain_hits(r, hs);
+			set_mapq(hs, opt.min_chain_score, mt[r].rep_len);                                        // map.c:758
+			for (const Hit &h : hs) { write_paf(lines[r], names[r] ? names[r] : "*", lens[r], h, ref_names[h.rid], ref_lens[h.rid], mt[r].rep_len); lines[r] += '\n'; }
+		});
+	} else {
+		// 6a. the surviving records of every read, as map.c has them when it calls align_regs (map.c:756), through the alignment call
+		std::vector<std::vector<Hit>> kept(R);
+		on_threads([&](size_t r, std::vector<Hit>&) { chain_hits(r, kept[r]); });
+		std::vector<int64_t> reg_off(R + 1, 0);
+		for (size_t r = 0; r < R; ++r) reg_off[r + 1] = reg_off[r] + (int64_t)kept[r].size();
+		std::vector<mm2gb_reg_t> rin((size_t)std::max<int64_t>(reg_off[R], 1));
+		for (size_t r = 0; r < R; ++r)
+			for (size_t i = 0; i < kept[r].size(); ++i) {
+				const Hit &h = kept[r][i];
+				mm2gb_reg_t &g = rin[(size_t)reg_off[r] + i];
+				g.id = h.id; g.cnt = h.cnt; g.rid = h.rid; g.score = h.score; g.qs = h.qs; g.qe = h.qe; g.rs = h.rs; g.re = h.re; g.parent = h.parent; g.subsc = h.subsc; g.as = h.as;
+				g.mlen = h.mlen; g.blen = h.blen; g.n_sub = h.n_sub; g.score0 = h.score0; g.hash = h.hash; g.div = h.div;
+				g.flags = h.flags | (h.strand_retained ? 1u << 26 : 0u);
+			}
+		lap(st_local.s_post);
+		struct AlignOut { mm2gb_align_out_t o; AlignOut() { memset(&o, 0, sizeof o); } ~AlignOut() { mm2gb_align_out_free(&o); } } ao;      // (freed on every way out)
+		const int idx_flag = mm2gb_index_flag(ix);
+		if (idx_flag < 0) { free_matches(); return -1; }
+		if (aln->align_on_device < 0 ? mm2gb_align_regs_host(&aln->opt, k, idx_flag, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, reg_off.data(), rin.data(), c_off.data(), ca,
+		                                                     std::max(1, opt.host_threads), &ao.o)
+		                             : mm2gb_align_regs_gpu(eng, &aln->opt, k, idx_flag, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, reg_off.data(), rin.data(), c_off.data(), ca, &ao.o)) {
+			free_matches();
+			return -1;                                    // (the alignment call's own text stays)
+		}
+		lap(s_extra[0]);
+		// 6b. per read: primary / secondary, which secondaries stay and the mapping quality, all with the alignment (map.c:347-348, 758)
+		const mm2gb_align_out_t &A = ao.o;
+		on_threads([&](size_t r, std::vector<Hit>&) {
+			std::vector<Hit> &hs = kept[r];
+			hs.clear();
+			for (int64_t j = A.reg_off[r]; j < A.reg_off[r + 1]; ++j) {
+				const mm2gb_reg_t &g = A.regs[j];
+				const mm2gb_aln_t &x = A.aln[j];
+				Hit h;
+				h.id = g.id; h.cnt = g.cnt; h.rid = g.rid; h.score = g.score; h.qs = g.qs; h.qe = g.qe; h.rs = g.rs; h.re = g.re; h.parent = g.parent;
+				h.subsc = g.subsc; h.as = g.as; h.mlen = g.mlen; h.blen = g.blen; h.n_sub = g.n_sub; h.score0 = g.score0;
+				h.mapq = 0; h.rev = (g.flags >> 10) & 1; h.strand_retained = (g.flags >> 26) & 1; h.hash = g.hash; h.div = g.div; h.flags = g.flags;
+				h.inv = (g.flags >> 11) & 1; h.split = (int)(g.flags >> 8 & 3);
+				h.has_p = x.cigar_off >= 0; h.aln = j;
+				if (h.has_p) { h.dp_score = x.dp_score; h.dp_max = x.dp_max; h.dp_max2 = x.dp_max2; h.n_ambi = x.n_ambi; h.trans_strand = x.trans_strand; h.n_cigar = x.n_cigar; }
+				hs.push_back(h);
+			}
+			set_parent(opt.mask_level, opt.mask_len, hs, false, aln->opt.a * 2 + aln->opt.b);
+			select_sub(opt.pri_ratio, k * 2, opt.best_n, false, (int)(opt.max_gap * 0.8), hs);
+			set_mapq(hs, opt.min_chain_score, mt[r].rep_len, aln->opt.a);
+		});
+		lap(s_extra[1]);
+		// 6c. the text of the tags for the records that are left, in one call; then the lines
+		std::vector<int64_t> line_off(R + 1, 0);
+		for (size_t r = 0; r < R; ++r) line_off[r + 1] = line_off[r] + (int64_t)kept[r].size();
+		const int64_t n_out = line_off[R];
+		std::vector<mm2gb_reg_t> treg((size_t)std::max<int64_t>(n_out, 1));
+		std::vector<mm2gb_aln_t> taln((size_t)std::max<int64_t>(n_out, 1));
+		std::vector<int32_t> tread((size_t)std::max<int64_t>(n_out, 1));
+		for (size_t r = 0; r < R; ++r)
+			for (size_t i = 0; i < kept[r].size(); ++i) {
+				const size_t j = (size_t)line_off[r] + i;
+				treg[j] = A.regs[kept[r][i].aln]; taln[j] = A.aln[kept[r][i].aln]; tread[j] = (int32_t)r;
+			}
+		struct Text { int64_t *off = nullptr; char *text = nullptr; ~Text() { free(off); free(text); } } tx;
+		if (aln->what && n_out > 0) {
+			int rc;
+			if (aln->text_on_device > 0) {
+				std::vector<int64_t> ref_at((size_t)n_ref + 1, 0), read_at(R + 1, 0);
+				for (int32_t i = 0; i < n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + ref_lens[i];
+				for (size_t i = 0; i < R; ++i) read_at[i + 1] = read_at[i] + lens[i];
+				// the alignment call's device backend says what it left resident (engine.h: al_resident): this batch's residues, or nothing
+				if (aln->align_on_device >= 0 && eng->e.al_resident[0] == ref_at.back() && eng->e.al_resident[1] == read_at.back()) {
+					rc = aln_text_resident(eng->e, "mm2gb_map_reads_aln", aln->what, n_ref, ref_lens, ref_at.data(), n_reads, lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
+					                       A.cigar, &tx.off, &tx.text);
+				} else rc = mm2gb_aln_text_gpu(eng, aln->what, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, n_out, treg.data(), tread.data(), taln.data(), A.cigar, &tx.off, &tx.text);
+			} else rc = mm2gb_aln_text_host(aln->what, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, n_out, treg.data(), tread.data(), taln.data(), A.cigar, std::max(1, opt.host_threads),
+			                                &tx.off, &tx.text);          // text_on_device 0: the host form (profiles/aln_text_rate.json)
+			if (rc) { free_matches(); return -1; }
+		}
+		lap(s_extra[2]);
+		on_threads([&](size_t r, std::vector<Hit>&) {
+			for (size_t i = 0; i < kept[r].size(); ++i) {
+				const Hit &h = kept[r][i];
+				const size_t j = (size_t)line_off[r] + i;
+				write_paf(lines[r], names[r] ? names[r] : "*", lens[r], h, ref_names[h.rid], ref_lens[h.rid], mt[r].rep_len, h.has_p ? A.cigar + A.aln[h.aln].cigar_off : nullptr);
+				if (tx.off) lines[r].append(tx.text + tx.off[j], (size_t)(tx.off[j + 1] - tx.off[j]));
+				lines[r] += '\n';
+			}
+		});
 	}
 	free_matches();
 	lap(st_local.s_post);
@@ -696,9 +863,9 @@ int mm2gb_map_reads_multi(mm2gb_engine_t *const *engines, int n_engines, const m
 // being seeded or post-processed while another one's kernels run; with engines on several GPUs the reads shard (no
 // exchange).  The host threads of opt are shared out with over-subscription (2.5 x), because a chunk's threads idle while its kernels run.
 // PAF in read order; stats: counts summed, s_* = seconds of each stage SUMMED over chunks (they overlap: not wall time).
-int mm2gb_map_reads_stream(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
-                           int32_t n_ref, const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                           int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
+static int stream_body(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                       int32_t n_ref, const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                       int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra)
 {
 	if (!engines || n_engines < 1 || !ix || !opt_in || !paf_out || !paf_len || n_reads < 0 || (n_reads > 0 && (!lens || !names || !seqs)) || (n_ref > 0 && (!ref_names || !ref_lens)))
 		return fail("mm2gb_map_reads_stream: null argument");
@@ -721,6 +888,7 @@ int mm2gb_map_reads_stream(mm2gb_engine_t *const *engines, int n_engines, const 
 	std::vector<char*> part(n_chunks, nullptr);
 	std::vector<int64_t> part_len(n_chunks, 0);
 	std::vector<mm2gb_map_stats_t> st(n_chunks);
+	std::vector<double> extra(n_chunks * 3, 0.0);         // with an alignment: seconds for align, the steps after it, text, per chunk
 	std::atomic<size_t> next(0);
 	std::atomic<int> failed(0);
 	std::string why;
@@ -731,7 +899,7 @@ int mm2gb_map_reads_stream(mm2gb_engine_t *const *engines, int n_engines, const 
 			if (c >= n_chunks || failed.load()) break;
 			const int32_t from = cut[c], n = cut[c + 1] - from;
 			memset(&st[c], 0, sizeof(st[c]));
-			if (mm2gb_map_reads(engines[e], ix, k, ref_names, ref_lens, n_ref, &opt, n, names + from, seqs + from, lens + from, &part[c], &part_len[c], &st[c])) {
+			if (map_reads_try(engines[e], ix, k, ref_names, ref_lens, n_ref, &opt, n, names + from, seqs + from, lens + from, &part[c], &part_len[c], &st[c], aln, &extra[c * 3])) {
 				std::lock_guard<std::mutex> g(why_lock);
 				if (!failed.exchange(1)) why = "chunk " + std::to_string(c) + " on engine " + std::to_string(e) + ": " + mm2gb_last_error();
 			}
@@ -756,11 +924,30 @@ int mm2gb_map_reads_stream(mm2gb_engine_t *const *engines, int n_engines, const 
 		const mm2gb_map_stats_t &q = st[c];
 		sum.n_reads += q.n_reads; sum.n_mapped += q.n_mapped; sum.n_anchors += q.n_anchors; sum.n_chains += q.n_chains; sum.n_rechained += q.n_rechained; sum.n_rmq_tied += q.n_rmq_tied;
 		sum.s_seed += q.s_seed; sum.s_anchors += q.s_anchors; sum.s_chain += q.s_chain; sum.s_rechain += q.s_rechain; sum.s_regs += q.s_regs; sum.s_post += q.s_post;
+		if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] += extra[c * 3 + (size_t)i];
 	}
 	buf[all] = 0;
 	*paf_out = buf; *paf_len = all;
 	if (stats) *stats = sum;
 	return 0;
+}
+
+int mm2gb_map_reads_stream(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                           int32_t n_ref, const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                           int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
+{
+	return stream_body(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, nullptr, nullptr);
+}
+
+int mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                               int32_t n_ref, const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs,
+                               const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
+{
+	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_stream_aln: ") + why);
+	double s3[3] = { 0, 0, 0 };
+	const int rc = stream_body(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, aln, s3);
+	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
+	return rc;
 }
 
 } // extern "C"
