@@ -11,9 +11,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "align_host.h"
 #include "host_chain.h"
 #include "ksw_host.h"
@@ -735,16 +735,15 @@ void hit_sort(Read &R)
 	R.regs.swap(t);
 }
 
-// every read of `reads` through rounds of planning, DP and stitching; par(n, fn): fn(i) for i < n, possibly on several threads
-template <class Par>
-int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, Par par, double *seconds)
+// every read of `reads` through rounds of planning, DP and stitching; the per-read steps on nt threads
+int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, int nt, double *seconds)
 {
 	using clk = std::chrono::steady_clock;
 	std::vector<AlRun> runs;
 	std::vector<uint32_t> pool;
 	for (;;) {
 		auto t0 = clk::now();
-		par(reads.size(), [&](size_t k) {
+		for_each_on_threads(reads.size(), nt, 1, [&](size_t k) {
 			Read &R = *reads[k];
 			std::vector<int> K;
 			R.runs.clear(); R.plans.clear();
@@ -766,7 +765,7 @@ int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, Par par, dou
 		pool.clear();
 		if (be.run(c, runs, pool)) return -1;
 		t0 = clk::now();
-		par(reads.size(), [&](size_t k) {
+		for_each_on_threads(reads.size(), nt, 1, [&](size_t k) {
 			Read &R = *reads[k];
 			if (R.runs.empty()) return;
 			const AlRun *ru = runs.data() + R.first_run;
@@ -790,7 +789,7 @@ int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, Par par, dou
 		if (seconds) seconds[7] += std::chrono::duration<double>(clk::now() - t0).count();
 	}
 	auto t0 = clk::now();
-	par(reads.size(), [&](size_t k) {
+	for_each_on_threads(reads.size(), nt, 1, [&](size_t k) {
 		Read &R = *reads[k];
 		filter_regs(c, R);
 		if (R.qlen >= c.opt.rank_min_len) { update_dp_max(c, R); filter_regs(c, R); }
@@ -851,6 +850,17 @@ int al_zdrop_code(const AlCtx &c, const AlJob &j, const AlDrop &d)
 	return d.max_zdrop > o.zdrop ? 1 : 0;
 }
 
+void pack_residues(int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, int nt,
+                   std::vector<int64_t> &ref_at, std::vector<int64_t> &read_at, std::vector<uint8_t> &refs, std::vector<uint8_t> &reads)
+{
+	ref_at.assign((size_t)n_ref + 1, 0); read_at.assign((size_t)n_reads + 1, 0);
+	for (int32_t i = 0; i < n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + ref_lens[i];
+	for (int64_t i = 0; i < n_reads; ++i) read_at[(size_t)i + 1] = read_at[(size_t)i] + read_lens[i];
+	refs.resize((size_t)ref_at.back()); reads.resize((size_t)read_at.back());
+	for_each_on_threads((size_t)n_ref, nt, 1, [&](size_t i) { for (int32_t p = 0; p < ref_lens[i]; ++p) refs[(size_t)(ref_at[i] + p)] = nt4(ref_seqs[i][p]); });
+	for_each_on_threads((size_t)n_reads, nt, 1, [&](size_t i) { for (int32_t p = 0; p < read_lens[i]; ++p) reads[(size_t)(read_at[i] + p)] = nt4(read_seqs[i][p]); });
+}
+
 int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                   int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
                   const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out)
@@ -891,23 +901,10 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx
 	kp.m = 5; memcpy(kp.mat, c.mat, 25); kp.q = (int8_t)opt->q; kp.e = (int8_t)opt->e; kp.q2 = (int8_t)opt->q2; kp.e2 = (int8_t)opt->e2;
 	c.kc = ksw_derive(kp);
 	c.n_ref = n_ref; c.n_reads = n_reads;
-	c.ref_at.assign((size_t)n_ref + 1, 0); c.read_at.assign((size_t)n_reads + 1, 0);
-	for (int32_t i = 0; i < n_ref; ++i) c.ref_at[(size_t)i + 1] = c.ref_at[(size_t)i] + ref_lens[i];
-	for (int64_t i = 0; i < n_reads; ++i) c.read_at[(size_t)i + 1] = c.read_at[(size_t)i] + read_lens[i];
-	c.refs.resize((size_t)c.ref_at.back()); c.reads.resize((size_t)c.read_at.back());
-	const int nt = std::max(1, std::min(n_threads, 256));
-	auto par = [nt](size_t n, auto fn) {
-		const int t = (int)std::min<size_t>((size_t)nt, n);
-		if (t <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
-		std::atomic<size_t> next(0);
-		std::vector<std::thread> th;
-		for (int k = 0; k < t; ++k) th.emplace_back([&]() { for (size_t i; (i = next.fetch_add(1)) < n;) fn(i); });
-		for (std::thread &x : th) x.join();
-	};
-	par((size_t)n_ref, [&](size_t i) { for (int32_t p = 0; p < ref_lens[i]; ++p) c.refs[(size_t)(c.ref_at[i] + p)] = nt4(ref_seqs[i][p]); });
-	par((size_t)n_reads, [&](size_t i) { for (int32_t p = 0; p < read_lens[i]; ++p) c.reads[(size_t)(c.read_at[i] + p)] = nt4(read_seqs[i][p]); });
+	const int nt = std::min(n_threads, 256);
+	pack_residues(n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, nt, c.ref_at, c.read_at, c.refs, c.reads);
 	std::vector<Read> R((size_t)n_reads);
-	par((size_t)n_reads, [&](size_t r) {
+	for_each_on_threads((size_t)n_reads, nt, 1, [&](size_t r) {
 		Read &x = R[r];
 		x.id = (int64_t)r; x.qlen = read_lens[r];
 		x.a.assign(anchors + anchor_off[r], anchors + anchor_off[r + 1]);
@@ -919,15 +916,14 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx
 	if (whole_batch) {
 		std::vector<Read*> all;
 		for (Read &x : R) all.push_back(&x);
-		rc = drive(c, all, *whole_batch, par, out->seconds);
+		rc = drive(c, all, *whole_batch, nt, out->seconds);
 		for (int s : { 0, 2, 3, 4, 5, 6 }) out->seconds[s] = whole_batch->seconds[s];
 	} else {
 		std::atomic<int> bad(0);
-		auto serial = [](size_t n, auto fn) { for (size_t i = 0; i < n; ++i) fn(i); };
-		par((size_t)n_reads, [&](size_t r) {
-			static thread_local HostBackend be;
+		for_each_on_threads((size_t)n_reads, nt, 1, [&](size_t r) {
+			static thread_local HostBackend be;               // carries only the capacity of q and t between calls: run() sizes and fills both for every job
 			std::vector<Read*> one{ &R[r] };
-			if (drive(c, one, be, serial, nullptr)) bad = 1;
+			if (drive(c, one, be, 1, nullptr)) bad = 1;
 		});
 		rc = bad ? -1 : 0;
 	}

@@ -25,6 +25,10 @@ inline uint8_t nt4(char ch)
 	              case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': case 'U': case 'u': return 3; default: return 4; }
 }
 
+// the sequences of a call as residues end to end (ref_at / read_at: n + 1 each, where a sequence's begin), packed on nt host threads
+void pack_residues(int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, int nt,
+                   std::vector<int64_t> &ref_at, std::vector<int64_t> &read_at, std::vector<uint8_t> &refs, std::vector<uint8_t> &reads);
+
 // a job of a round with its DP parameters (first pass), and what came of it
 struct AlRun {
 	AlJob j;

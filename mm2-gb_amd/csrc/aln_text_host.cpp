@@ -4,13 +4,12 @@
 // aln_text_cell.h and a running count; the device form (aln_text_kernels.hip) takes the same columns in parallel.  The host form is the
 // definition.  This unit also checks a call and lays it out for either form (tx_prepare).
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "align_host.h"
 #include "aln_text_host.h"
 
@@ -131,14 +130,7 @@ int mm2gb_aln_text_host(int what, int32_t n_ref, const char *const *ref_seqs, co
 		tx_walk(p, x, [&](int k) { return (int)nt4(ref[x.t_at + k]); },
 		        [&](int k) { if (!x.rev) return (int)nt4(read[x.q_at + k]); const int c = nt4(read[x.q_at - k]); return c < 4 ? 3 - c : 4; }, out[i]);
 	};
-	const int nt = (int)std::min<size_t>((size_t)std::max(1, std::min(n_threads, 256)), n);
-	if (nt <= 1) for (size_t i = 0; i < n; ++i) one(i);
-	else {
-		std::atomic<size_t> next(0);
-		std::vector<std::thread> th;
-		for (int k = 0; k < nt; ++k) th.emplace_back([&]() { for (size_t i; (i = next.fetch_add(1)) < n;) one(i); });
-		for (std::thread &x : th) x.join();
-	}
+	for_each_on_threads(n, std::min(n_threads, 256), 1, one);
 	int64_t *off = (int64_t*)malloc(((size_t)n_regs + 1) * sizeof(int64_t));
 	if (!off) return fail(who + ": out of memory");
 	int64_t total = 0;

@@ -13,12 +13,10 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 #include "engine.h"
 #include "align_host.h"
@@ -251,21 +249,9 @@ int mm2gb_aln_text_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char 
 	for (int64_t i = 0; i < n_reads; ++i) if (read_lens[i] < 0) return fail(who + ": a negative length");
 	// the residues, one byte per base, as the alignment call keeps them
 	const auto t0 = clk::now();
-	std::vector<int64_t> ref_at((size_t)n_ref + 1, 0), read_at((size_t)n_reads + 1, 0);
-	for (int32_t i = 0; i < n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + ref_lens[i];
-	for (int64_t i = 0; i < n_reads; ++i) read_at[(size_t)i + 1] = read_at[(size_t)i] + read_lens[i];
-	std::vector<uint8_t> refs((size_t)ref_at.back()), reads((size_t)read_at.back());
-	const int nt = std::max(1, std::min(usable_cpus(), 16));
-	auto par = [nt](size_t n, auto fn) {
-		const int t = (int)std::min<size_t>((size_t)nt, n);
-		if (t <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
-		std::atomic<size_t> next(0);
-		std::vector<std::thread> th;
-		for (int k = 0; k < t; ++k) th.emplace_back([&]() { for (size_t i; (i = next.fetch_add(1)) < n;) fn(i); });
-		for (std::thread &x : th) x.join();
-	};
-	par((size_t)n_ref, [&](size_t i) { for (int32_t q = 0; q < ref_lens[i]; ++q) refs[(size_t)(ref_at[i] + q)] = nt4(ref_seqs[i][q]); });
-	par((size_t)n_reads, [&](size_t i) { for (int32_t q = 0; q < read_lens[i]; ++q) reads[(size_t)(read_at[i] + q)] = nt4(read_seqs[i][q]); });
+	std::vector<int64_t> ref_at, read_at;
+	std::vector<uint8_t> refs, reads;
+	pack_residues(n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, std::min(usable_cpus(), 16), ref_at, read_at, refs, reads);
 	MM2GB_HIP(hipSetDevice(e.device));
 	if (e.al_refs.ensure(std::max<size_t>(refs.size(), 16)) || e.al_reads.ensure(std::max<size_t>(reads.size(), 16))) return -1;
 	if (!refs.empty()) MM2GB_HIP(hipMemcpyAsync(e.al_refs.ptr, refs.data(), refs.size(), hipMemcpyHostToDevice, e.stream));

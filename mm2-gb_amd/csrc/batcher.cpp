@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "trace.h"
 
 namespace mm2gb {
@@ -255,24 +256,15 @@ int mm2gb_batcher_add(mm2gb_batcher_t *b, int64_t read_id, const mm2gb_anchor_t 
 int mm2gb_batcher_feed(mm2gb_batcher_t *b, int64_t n_reads, int64_t first_id, const int64_t *offsets, const mm2gb_anchor_t *anchors, int n_producers)
 {
 	if (!b || n_reads < 0 || !offsets) return fail("mm2gb_batcher_feed: bad argument");
-	std::atomic<int64_t> next(0);
 	std::atomic<int> bad(0);
-	std::string why;
+	std::string why;                                      // error text is per thread: carry the first one over
 	std::mutex why_lock;
-	auto work = [&]() {
-		for (;;) {
-			const int64_t r = next.fetch_add(1);
-			if (r >= n_reads || bad.load()) break;
-			if (mm2gb_batcher_add(b, first_id + r, anchors + offsets[r], offsets[r + 1] - offsets[r])) {
-				std::lock_guard<std::mutex> g(why_lock);
-				if (!bad.exchange(1)) why = mm2gb_last_error();
-			}
+	for_each_on_threads((size_t)n_reads, n_producers, 1, [&](size_t r) {
+		if (!bad.load() && mm2gb_batcher_add(b, first_id + (int64_t)r, anchors + offsets[r], offsets[r + 1] - offsets[r])) {
+			std::lock_guard<std::mutex> g(why_lock);
+			if (!bad.exchange(1)) why = mm2gb_last_error();
 		}
-	};
-	std::vector<std::thread> pool;
-	for (int t = 1; t < std::max(1, n_producers); ++t) pool.emplace_back(work);
-	work();
-	for (auto &th : pool) th.join();
+	});
 	return bad.load() ? fail(why) : 0;
 }
 

@@ -7,9 +7,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "ksw_cell.h"
 #include "ksw_host.h"
 
@@ -114,7 +114,7 @@ void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query
 
 void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
 {
-	static thread_local Scratch S;
+	static thread_local Scratch S;                        // carries only capacity between calls: one_job sizes and writes every array for a job before it reads it
 	one_job(c, job, query, target, S, out, words);
 }
 
@@ -153,12 +153,7 @@ int mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const m
 			}
 		}
 	};
-	if (nt == 1) work(0);
-	else {
-		std::vector<std::thread> th;
-		for (int k = 0; k < nt; ++k) th.emplace_back(work, k);
-		for (std::thread &t : th) t.join();
-	}
+	run_on_threads(nt, work);
 	if (ksw_gather(n_jobs, res, cigar, n_cigar_total)) return -1;
 	for (int64_t j = 0; j < n_jobs; ++j)
 		if (res[j].n_cigar > 0) memcpy(*cigar + res[j].cigar_off, words[(size_t)who[(size_t)j]].data() + where[(size_t)j], (size_t)res[j].n_cigar * 4);

@@ -1,15 +1,15 @@
 // mapper.cpp -- reads in, PAF out, without the reference's sources: the host side around the device path, written
 // from scratch to give the reference's output for single-segment reads mapped without base-level alignment (no -a / -c).
 //
-//   per batch of reads:   matches (seeding.cpp, host threads)  ->  anchors, sorted (collect_seed_hits: device for large batches, host threads otherwise)  ->  chains (device:
-//   chaining DP + backtrack)  ->  re-chaining of reads whose chains look broken (host threads: mg_lchain_rmq with the reference's tree, csrc/rmq_host.cpp, map.c:697-708)
-//   ->  hit records (device: mm_gen_regs)  ->  per read on the host: primary / secondary (mm_set_parent, hit.c:125-198), which
+//   per batch of reads (map_reads_body: one function per step):   1 matches (seeding.cpp on host threads, or seed_kernels.hip)  ->  2 anchors, sorted (collect_seed_hits: device for large batches, host threads otherwise)  ->  3 chains (device:
+//   chaining DP + backtrack)  ->  4 re-chaining of reads whose chains look broken (host threads: mg_lchain_rmq with the reference's tree, csrc/rmq_host.cpp, map.c:697-708)
+//   ->  5 hit records (device: mm_gen_regs)  ->  6 per read on the host: primary / secondary (mm_set_parent, hit.c:125-198), which
 //   secondaries stay (mm_select_sub, hit.c:272-295, mm_sync_regs hit.c:247-270), divergence estimate (mm_est_err, esterr.c:31-64),
 //   mm_filter_strand_retained (hit.c:297-309), mapping quality (mm_set_mapq, hit.c:420-466), PAF line (format.c:274-321).
 //
-//   With a mm2gb_map_aln_t (mm2gb_map_reads_aln; minimap2 -c): after mm_filter_strand_retained the batch's surviving records go through
-//   mm2gb_align_regs_* in one call (map.c:342-352), then per read mm_set_parent, mm_select_sub and mm_set_mapq in their forms with an
-//   alignment, and the PAF line gets NM/ms/AS/nn/de and cg:Z / cs:Z / MD:Z (the text of the whole batch from one mm2gb_aln_text_* call).
+//   With a mm2gb_map_aln_t (mm2gb_map_reads_aln; minimap2 -c): 6a after mm_filter_strand_retained the batch's surviving records go through
+//   mm2gb_align_regs_* in one call (map.c:342-352), 6b then per read mm_set_parent, mm_select_sub and mm_set_mapq in their forms with an
+//   alignment, 6c and the PAF line gets NM/ms/AS/nn/de and cg:Z / cs:Z / MD:Z (the text of the whole batch from one mm2gb_aln_text_* call).
 //
 // Not reproduced: more than one query segment, spliced and short-read alignment, --eqx, SAM output, ALT contigs, the heap variant of
 // seed collection, --qstrand, multi-part indexes.
@@ -23,9 +23,9 @@
 #include <memory>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "host_chain.h"
 #include "align_host.h"
 #include "aln_text_host.h"
@@ -274,6 +274,634 @@ void write_paf(std::string &out, const char *qname, int qlen, const Hit &h, cons
 	out += "\trl:i:"; append_int(out, rep_len);
 }
 
+// a hit record as a Hit; x: its alignment, where the record has been through the alignment call
+Hit hit_from(const mm2gb_reg_t &g, const mm2gb_aln_t *x = nullptr)
+{
+	Hit h;
+	h.id = g.id; h.cnt = g.cnt; h.rid = g.rid; h.score = g.score; h.qs = g.qs; h.qe = g.qe; h.rs = g.rs; h.re = g.re; h.parent = g.parent;
+	h.subsc = g.subsc; h.as = g.as; h.mlen = g.mlen; h.blen = g.blen; h.n_sub = g.n_sub; h.score0 = g.score0;
+	h.mapq = 0; h.rev = (g.flags >> 10) & 1; h.hash = g.hash; h.div = g.div; h.flags = g.flags;
+	h.strand_retained = x && ((g.flags >> 26) & 1);       // (bit 26 is reg_from's: it means something only after the alignment call)
+	if (!x) return h;
+	h.inv = (g.flags >> 11) & 1; h.split = (int)(g.flags >> 8 & 3);
+	h.has_p = x->cigar_off >= 0;
+	if (h.has_p) { h.dp_score = x->dp_score; h.dp_max = x->dp_max; h.dp_max2 = x->dp_max2; h.n_ambi = x->n_ambi; h.trans_strand = x->trans_strand; h.n_cigar = x->n_cigar; }
+	return h;
+}
+
+// a Hit as the record the alignment call takes; strand_retained travels in bit 26
+void reg_from(const Hit &h, mm2gb_reg_t &g)
+{
+	g.id = h.id; g.cnt = h.cnt; g.rid = h.rid; g.score = h.score; g.qs = h.qs; g.qe = h.qe; g.rs = h.rs; g.re = h.re; g.parent = h.parent; g.subsc = h.subsc; g.as = h.as;
+	g.mlen = h.mlen; g.blen = h.blen; g.n_sub = h.n_sub; g.score0 = h.score0; g.hash = h.hash; g.div = h.div;
+	g.flags = h.flags | (h.strand_retained ? 1u << 26 : 0u);
+}
+
+// the arguments of a mapping call (eng: the one engine of mm2gb_map_reads, unused by the stream)
+struct MapCall {
+	mm2gb_engine_t *eng; const mm2gb_index_t *ix; int k; const char *const *ref_names; const int32_t *ref_lens; int32_t n_ref;
+	const mm2gb_map_opt_t *opt; int32_t n_reads; const char *const *names; const char *const *seqs; const int32_t *lens;
+	char **paf_out; int64_t *paf_len; mm2gb_map_stats_t *stats; const mm2gb_map_aln_t *aln; double *s_extra;
+};
+
+// what the stages of one batch share
+struct Batch {
+	const MapCall &c;
+	mm2gb_map_opt_t opt;                                 // the call's, resolved
+	const mm2gb_map_aln_t *const aln;
+	const size_t R;
+	const int nt;                                        // host threads
+	const mm2gb_seed_opt_t so;
+	mm2gb_misc_t misc;
+	std::vector<mm2gb_matches_t> mt;                     // (freed on every way out)
+	std::vector<std::vector<const uint64_t*>> occ;       // per read and kept seed: its occurrences, where the index holds them (copied once, into the batch's array)
+	int64_t dev_seeds = 0, dev_hits = 0;                 // seeded on the device: what lies there
+	std::vector<int32_t> qlen, ref_len;
+	std::vector<int64_t> a_off;
+	BigBuf<mm2gb_anchor_t> &anchors;                     // the engine's
+	// the current chains, read where they lie: the chaining call's (ch_own) until re-chaining splices new ones into the engine's arrays
+	ChainsOwner ch_own;
+	std::vector<int64_t> u_off, c_off;
+	const uint64_t *u = nullptr;
+	const mm2gb_anchor_t *ca = nullptr;
+	std::vector<mm2gb_reg_t> regs;
+	std::vector<std::string> lines;
+	mm2gb_map_stats_t st = {};
+	double *const s_extra;
+
+	Batch(const MapCall &call, const mm2gb_map_opt_t &o)
+		: c(call), opt(o), aln(call.aln), R((size_t)call.n_reads), nt(std::max(1, o.host_threads)), so{ o.mid_occ, o.max_max_occ, o.occ_dist, o.q_occ_frac }, mt(R), occ(R),
+		  qlen(call.lens, call.lens + R), ref_len(call.ref_lens, call.ref_lens + call.n_ref), a_off(R + 1, 0), anchors(host_scratch(call.eng).anchors), lines(R), s_extra(call.s_extra) {}
+	~Batch() { release_matches(); }
+	void release_matches() { for (auto &m : mt) mm2gb_matches_free(&m); }
+};
+
+// 1. matches on host threads
+int seed_on_host(Batch &B)
+{
+	std::atomic<int> bad(0);
+	std::string why;                                      // error text is per thread: carry the first one over
+	std::mutex why_lock;
+	for_each_on_threads(B.R, B.nt, 1, [&](size_t r) {
+		if (B.c.lens[r] > 0 && collect_matches_refs(B.c.ix, B.c.seqs[r], B.c.lens[r], &B.so, &B.mt[r], &B.occ[r])) {
+			std::lock_guard<std::mutex> g(why_lock);
+			if (!bad.exchange(1)) why = mm2gb_last_error();
+		}
+	});
+	return bad ? fail(why) : 0;
+}
+
+// 1. on the device (seeding_on_device = 1): the reads go up as bytes, sketch / look-up / match selection run as kernels (seed_kernels.hip) and leave
+//    the arrays step 2's kernels read where they are; what comes down is what the host's mapq and divergence code wants (rep_len, mini_pos)
+int seed_on_device(Batch &B)
+{
+	const size_t R = B.R;
+	const int32_t *lens = B.c.lens;
+	Engine &e = B.c.eng->e;
+	std::vector<int64_t> seq_off(R + 1, 0);
+	for (size_t r = 0; r < R; ++r) seq_off[r + 1] = seq_off[r] + lens[r];
+	if (seq_off[R] >= ((int64_t)1 << 31) - 1) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 bases");
+	BigBuf<uint64_t> &flat = host_scratch(B.c.eng).hits;      // (no host array of hits in this form: its memory holds the reads end to end)
+	flat.resize((size_t)seq_off[R] / 8 + 1);
+	char *const bases = (char*)flat.data();
+	for_each_on_threads(R, B.nt, 1, [&](size_t r) { if (lens[r] > 0) memcpy(bases + seq_off[r], B.c.seqs[r], (size_t)lens[r]); });
+	DevIndexView view;
+	if (index_on_device(B.c.ix, e.device, &view)) return -1;
+	if (e.collect_matches_device(view, B.so, B.c.n_reads, seq_off.data(), bases, &B.dev_seeds, &B.dev_hits)) return -1;
+	std::vector<int64_t> seed_off(R + 1, 0);
+	std::vector<int32_t> rep(R, 0);
+	std::vector<uint64_t> mini_pos((size_t)B.dev_seeds + 1);
+	if (hipMemcpy(seed_off.data(), e.sd_seed_off.ptr, (R + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rep.data(), e.sd_rep_len.ptr, R * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+	    (B.dev_seeds > 0 && hipMemcpy(mini_pos.data(), e.sd_mini_pos.ptr, (size_t)B.dev_seeds * 8, hipMemcpyDeviceToHost) != hipSuccess))
+		return fail("mm2gb_map_reads: the device's matches could not be copied back");
+	for (size_t r = 0; r < R; ++r) {
+		const int64_t n = seed_off[r + 1] - seed_off[r];
+		mm2gb_matches_t &m = B.mt[r];
+		m.rep_len = rep[r]; m.n_seeds = m.n_mini_pos = (int32_t)n;
+		m.mini_pos = (uint64_t*)malloc(((size_t)n + 1) * 8);
+		if (!m.mini_pos) return fail("mm2gb_map_reads: out of memory");
+		if (n > 0) memcpy(m.mini_pos, mini_pos.data() + seed_off[r], (size_t)n * 8);
+	}
+	return 0;
+}
+
+// 2. anchors, sorted: from the matches resident on the device, or from the host's matches -- on the device for large batches
+//    (mm2gb_collect_seeds_gpu: matches up, anchors down, one wave sorts a read); below that the host threads are quicker: the largest
+//    read's sort alone is hundreds of milliseconds for one wave, milliseconds for a core
+int collect_anchors(Batch &B, bool dev_seed)
+{
+	const size_t R = B.R;
+	mm2gb_engine_t *eng = B.c.eng;
+	if (dev_seed) {
+		B.anchors.resize((size_t)std::max<int64_t>(B.dev_hits, 1));
+		return B.c.eng->e.collect_seeds_resident(B.opt.flag, B.c.n_reads, B.dev_seeds, B.dev_hits, B.a_off.data(), B.anchors.data()) ? -1 : 0;
+	}
+	const std::vector<mm2gb_matches_t> &mt = B.mt;
+	std::vector<int64_t> seed_off(R + 1, 0);
+	for (size_t r = 0; r < R; ++r) seed_off[r + 1] = seed_off[r] + mt[r].n_seeds;
+	std::vector<mm2gb_seed_t> seeds((size_t)seed_off[R]);
+	std::vector<int64_t> hit_off((size_t)seed_off[R] + 1, 0);
+	int64_t n_hits = 0;
+	for (size_t r = 0; r < R; ++r) {
+		if (mt[r].n_seeds) memcpy(seeds.data() + seed_off[r], mt[r].seeds, (size_t)mt[r].n_seeds * sizeof(mm2gb_seed_t));
+		for (int s = 0; s < mt[r].n_seeds; ++s) { hit_off[(size_t)(seed_off[r] + s) + 1] = hit_off[(size_t)(seed_off[r] + s)] + mt[r].seeds[s].n; }
+		n_hits += mt[r].n_hits;
+	}
+	// (the batch's two largest arrays are the engine's from call to call: a gigabyte of fresh pages costs more to touch than to fill)
+	BigBuf<uint64_t> &hits = host_scratch(eng).hits;
+	hits.resize((size_t)n_hits);
+	uint64_t *const hits_ptr = hits.data();
+	for_each_on_threads(R, B.nt, 16, [&](size_t r) {
+		for (int32_t q = 0; q < mt[r].n_seeds; ++q)
+			memcpy(hits_ptr + hit_off[(size_t)seed_off[r] + (size_t)q], B.occ[r][(size_t)q], (size_t)mt[r].seeds[q].n * 8);
+	});
+	B.anchors.resize((size_t)std::max<int64_t>(n_hits, 1));
+	const bool seeds_on_device = B.opt.seeds_on_device > 0 || (B.opt.seeds_on_device == 0 && n_hits >= 400000000);
+	return seeds_on_device ? mm2gb_collect_seeds_gpu(eng, B.opt.flag, B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
+	                                                 B.a_off.data(), B.anchors.data())
+	                       : mm2gb_collect_seeds_host(B.opt.flag, B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
+	                                                  B.nt, B.a_off.data(), B.anchors.data());
+}
+
+// 3. chains on the device; map.c:393-426 for the parameters (the GPU path chains with max-chain-skip = infinity unless the options set
+//    a finite one: then the engine keeps it for this call, and the re-chaining call gets it too)
+int chain(Batch &B)
+{
+	mm2gb_engine_t *eng = B.c.eng;
+	const mm2gb_map_opt_t &opt = B.opt;
+	mm2gb_misc_t &misc = B.misc;
+	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = opt.max_gap; misc.max_dist_x = opt.max_gap_ref > 0 ? opt.max_gap_ref : opt.max_gap;
+	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
+	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * B.c.k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * B.c.k);
+	if (mm2gb_engine_set_misc(eng, &misc)) return -1;
+	mm2gb_chains_t &ch = B.ch_own.c;
+	struct ChainSkipMode {                               // the engine's own mode comes back on every way out of the chaining call
+		bool &mode; const bool before;
+		ChainSkipMode(bool &m, bool keep) : mode(m), before(m) { mode = keep; }
+		~ChainSkipMode() { mode = before; }
+	} guard(eng->e.chain_skip, opt.max_chain_skip != INT32_MAX);
+	// backtrack + compaction as kernels for large batches; below that on host threads, overlapped with the device: a single huge read (a
+	// tandem array) keeps one wave busy for hundreds of milliseconds where a core needs tens
+	if (B.a_off[B.R] >= 200000000 ? mm2gb_chain_gpu(eng, B.c.n_reads, B.a_off.data(), B.anchors.data(), &ch, nullptr)
+	                              : mm2gb_chain_host(eng, B.c.n_reads, B.a_off.data(), B.anchors.data(), B.nt, &ch, nullptr)) return -1;
+	// (the chains are read where the chaining call left them -- a gigabyte of kept anchors per batch is not copied again)
+	B.u_off.assign(ch.u_off, ch.u_off + B.R + 1); B.c_off.assign(ch.a_off, ch.a_off + B.R + 1);
+	B.u = ch.u; B.ca = ch.a;
+	return 0;
+}
+
+// ---- 4. re-chaining of long reads whose best chain leaves much of the read uncovered (map.c:697-708): the chained anchors, sorted again,
+//      through mg_lchain_rmq's fill, and the new chains spliced in ----
+
+// the reads to do again (largest first: a read is one wave's, or one thread's, work from start to end, and the call ends with its longest
+// read), and their anchors end to end, sorted, in the engine's `ra` (ro: where each read's begin)
+void rechain_pick(Batch &B, std::vector<int32_t> &redo, std::vector<int64_t> &ro)
+{
+	const std::vector<int64_t> &u_off = B.u_off, &c_off = B.c_off;
+	const int32_t *lens = B.c.lens;
+	if (B.opt.bw_long > B.opt.bw) {
+		for (size_t r = 0; r < B.R; ++r) {
+			if (u_off[r + 1] - u_off[r] <= 1) continue;
+			const mm2gb_anchor_t *a = B.ca + c_off[r];
+			const int st = (int32_t)a[0].y, en = (int32_t)a[(int32_t)B.u[(size_t)u_off[r]] - 1].y;
+			if (lens[r] - (en - st) > B.opt.rmq_rescue_size || en - st > lens[r] * B.opt.rmq_rescue_ratio) redo.push_back((int32_t)r);
+		}
+	}
+	std::sort(redo.begin(), redo.end(), [&](int32_t u, int32_t v) { const int64_t nu = c_off[(size_t)u + 1] - c_off[(size_t)u], nv = c_off[(size_t)v + 1] - c_off[(size_t)v]; return nu != nv ? nu > nv : u < v; });
+	if (redo.empty()) return;
+	ro.assign(redo.size() + 1, 0);
+	for (size_t q = 0; q < redo.size(); ++q) ro[q + 1] = ro[q] + (c_off[(size_t)redo[q] + 1] - c_off[(size_t)redo[q]]);
+	// (the engine's, kept between calls like the gathers of mm2gb_rmq_chain: fresh pages cost more to touch than to fill)
+	BigBuf<mm2gb_anchor_t> &ra = host_scratch(B.c.eng).ra;
+	ra.resize((size_t)ro.back());
+	mm2gb_anchor_t *const ra_ptr = ra.data();
+	for_each_on_threads(redo.size(), B.nt, 1, [&](size_t q) {
+		memcpy(ra_ptr + ro[q], B.ca + c_off[(size_t)redo[q]], (size_t)(ro[q + 1] - ro[q]) * sizeof(mm2gb_anchor_t));
+		sort_by_x_like_host(ra_ptr + ro[q], ra_ptr + ro[q + 1]);
+	});
+	if (const char *path = getenv("MM2GB_DUMP_RECHAIN")) {       // the re-chaining call's input, for profiling csrc/rmq_host.cpp off the box: offsets, then anchors
+		if (FILE *fp = fopen(path, "wb")) {
+			const int64_t nr = (int64_t)redo.size();
+			fwrite(&nr, 8, 1, fp); fwrite(ro.data(), 8, ro.size(), fp); fwrite(ra.data(), sizeof(mm2gb_anchor_t), ra.size(), fp);
+			fclose(fp);
+		}
+	}
+}
+
+// the new chains of the re-chained reads, where the fill's form left them
+struct Refill {
+	ChainsOwner rc, rc_tie;                              // rechain_on_device != 0: the one call's result, and that of the host call for the tied reads
+	RmqParts parts;                                      // the default: the results of the call's three sides
+	std::vector<int32_t> tied;                           // per re-chained read: done again on the host after a tie
+	std::vector<unsigned char> side;                     // ... which result holds it (0: rc, 1: rc_tie, 2 + k: parts.chains[k]) ...
+	std::vector<int64_t> slot;                           // ... and where
+	explicit Refill(size_t n) : tied(n, 0), side(n, 0), slot(n, 0) {}
+	const mm2gb_chains_t &at(size_t q) const { return side[q] == 0 ? rc.c : side[q] == 1 ? rc_tie.c : parts.chains[side[q] - 2]; }
+};
+
+// mg_lchain_rmq's fill.  Default: mm2gb_rmq_chain (csrc/rmq_hybrid.cpp) -- the kernel form takes the bulk of the reads, the host
+// threads, at the same time, the few whose windows are so dense that one wave would still be on them long after the rest of the
+// batch is done, and afterwards the reads the kernel reported a tie for (where the reference's answer follows from the shape of
+// its tree; the host form keeps that tree's rules).  rechain_on_device = 1: every read on the device first; -1: host threads only.
+int rechain_fill(Batch &B, const std::vector<int64_t> &ro, const mm2gb_anchor_t *ra, bool verbose, Refill &F)
+{
+	const mm2gb_map_opt_t &opt = B.opt;
+	const mm2gb_rmq_param_t rp = { opt.max_gap, opt.rmq_inner_dist, opt.bw_long, opt.max_chain_skip, opt.rmq_size_cap, opt.min_cnt, opt.min_chain_score, B.misc.chn_pen_gap, B.misc.chn_pen_skip };
+	const size_t n = ro.size() - 1;
+	if (opt.rechain_on_device == 0) {
+		std::vector<int32_t> where(n, 0);
+		mm2gb_rmq_deal_t deal = {};
+		if (rmq_chain_parts(B.c.eng, &rp, (int64_t)n, ro.data(), ra, B.nt, F.parts, where.data(), &deal)) return -1;
+		for (size_t q = 0; q < n; ++q) { F.tied[q] = where[q] == 2; F.side[q] = (unsigned char)(2 + F.parts.which[q]); F.slot[q] = F.parts.slot[q]; }
+		if (verbose) fprintf(stderr, "[mm2gb] re-chaining deal: %lld reads on the device, %d of them a whole workgroup's (%.3f s, estimated %.3f), %lld on host threads by cost (%.3f s, estimated %.3f), %lld redone after a tie (%.3f s)\n",
+		                     (long long)deal.n_device, (int)deal.n_team, deal.device_s, deal.est_device_s, (long long)deal.n_host_cost, deal.host_s, deal.est_host_s, (long long)deal.n_host_tie, deal.tie_s);
+		return 0;
+	}
+	for (size_t q = 0; q < n; ++q) F.slot[q] = (int64_t)q;
+	if (opt.rechain_on_device < 0) return mm2gb_rmq_chain_host(&rp, (int64_t)n, ro.data(), ra, B.nt, &F.rc.c, F.tied.data());
+	if (mm2gb_rmq_chain_gpu(B.c.eng, &rp, (int64_t)n, ro.data(), ra, &F.rc.c, F.tied.data(), nullptr)) return -1;
+	std::vector<int64_t> to(1, 0);                       // the tied reads, again on host threads
+	std::vector<mm2gb_anchor_t> ta;
+	for (size_t q = 0; q < n; ++q)
+		if (F.tied[q]) {
+			F.side[q] = 1; F.slot[q] = (int64_t)to.size() - 1;
+			ta.insert(ta.end(), ra + ro[q], ra + ro[q + 1]);
+			to.push_back((int64_t)ta.size());
+		}
+	return to.size() > 1 ? mm2gb_rmq_chain_host(&rp, (int64_t)to.size() - 1, to.data(), ta.data(), B.nt, &F.rc_tie.c, nullptr) : 0;
+}
+
+// the batch's chains with the re-chained reads' new ones in place, in the engine's arrays (touched pages); the chaining call's result goes
+void splice(Batch &B, const std::vector<int32_t> &redo, const Refill &F)
+{
+	const size_t R = B.R;
+	std::vector<int64_t> nu_off(R + 1, 0), nc_off(R + 1, 0);
+	std::vector<int> which(R, -1);
+	for (size_t q = 0; q < redo.size(); ++q) { which[(size_t)redo[q]] = (int)q; if (F.tied[q]) ++B.st.n_rmq_tied; }
+	for (size_t r = 0; r < R; ++r) {
+		const int q = which[r];
+		if (q < 0) { nu_off[r + 1] = nu_off[r] + (B.u_off[r + 1] - B.u_off[r]); nc_off[r + 1] = nc_off[r] + (B.c_off[r + 1] - B.c_off[r]); continue; }
+		const mm2gb_chains_t &from = F.at((size_t)q);
+		const int64_t qq = F.slot[(size_t)q];
+		nu_off[r + 1] = nu_off[r] + (from.u_off[qq + 1] - from.u_off[qq]);
+		nc_off[r + 1] = nc_off[r] + (from.a_off[qq + 1] - from.a_off[qq]);
+	}
+	BigBuf<uint64_t> &nu = host_scratch(B.c.eng).nu;
+	BigBuf<mm2gb_anchor_t> &nc = host_scratch(B.c.eng).nc;
+	nu.resize((size_t)nu_off[R]); nc.resize((size_t)nc_off[R]);
+	uint64_t *const nu_ptr = nu.data();
+	mm2gb_anchor_t *const nc_ptr = nc.data();
+	// (a batch's kept anchors are a gigabyte: the copies go to all host threads)
+	for_each_on_threads(R, B.nt, 32, [&](size_t r) {
+		const int q = which[r];
+		const mm2gb_chains_t *from = q < 0 ? nullptr : &F.at((size_t)q);
+		const int64_t qq = q < 0 ? 0 : F.slot[(size_t)q];
+		const uint64_t *su = q < 0 ? B.u + B.u_off[r] : from->u + from->u_off[qq];
+		const mm2gb_anchor_t *sa = q < 0 ? B.ca + B.c_off[r] : from->a + from->a_off[qq];
+		if (nu_off[r + 1] > nu_off[r]) memcpy(nu_ptr + nu_off[r], su, (size_t)(nu_off[r + 1] - nu_off[r]) * 8);
+		if (nc_off[r + 1] > nc_off[r]) memcpy(nc_ptr + nc_off[r], sa, (size_t)(nc_off[r + 1] - nc_off[r]) * sizeof(mm2gb_anchor_t));
+	});
+	B.u = nu_ptr; B.ca = nc_ptr; B.u_off.swap(nu_off); B.c_off.swap(nc_off);
+	mm2gb_chains_free(&B.ch_own.c);
+}
+
+int rechain(Batch &B)
+{
+	using clk = std::chrono::steady_clock;
+	auto seconds = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+	const auto t_rechain = clk::now();
+	std::vector<int32_t> redo;
+	std::vector<int64_t> ro;
+	rechain_pick(B, redo, ro);
+	B.st.n_rechained = (int64_t)redo.size();
+	if (!redo.empty()) {
+		const auto t_sorted = clk::now();
+		const bool verbose = getenv("MM2GB_DEBUG_PHASES") != nullptr;
+		Refill F(redo.size());
+		if (rechain_fill(B, ro, host_scratch(B.c.eng).ra.data(), verbose, F)) return -1;
+		const auto t_filled = clk::now();
+		splice(B, redo, F);
+		if (verbose) fprintf(stderr, "[mm2gb] re-chaining %zu reads (%lld redone on the host after a tie), %lld anchors: sort %.3f s, fill %.3f s, splice %.3f s\n", redo.size(), (long long)B.st.n_rmq_tied, (long long)ro.back(),
+		                     seconds(t_rechain, t_sorted), seconds(t_sorted, t_filled), seconds(t_filled, clk::now()));
+	}
+	B.st.n_chains = B.u_off[B.R];
+	return 0;
+}
+
+// 5. hit records on the device (hit.c:52-88); the hash of map.c:660-662
+int hit_records(Batch &B)
+{
+	std::vector<uint32_t> hash(B.R);
+	for (size_t r = 0; r < B.R; ++r) {
+		uint32_t h = B.c.names[r] ? name_hash(B.c.names[r]) : 0;
+		h ^= wang((uint32_t)B.c.lens[r]) + wang((uint32_t)B.opt.seed);
+		hash[r] = wang(h);
+	}
+	B.regs.resize((size_t)std::max<int64_t>(B.u_off[B.R], 1));
+	mm2gb_chains_t view; view.u_off = B.u_off.data(); view.u = const_cast<uint64_t*>(B.u); view.a_off = B.c_off.data(); view.a = const_cast<mm2gb_anchor_t*>(B.ca);
+	return mm2gb_gen_regs_gpu(B.c.eng, B.c.n_reads, &view, B.qlen.data(), hash.data(), 0, B.regs.data());
+}
+
+// ---- 6. per read on the host ----
+
+// the hits of a read up to mm_filter_strand_retained (map.c:749-752)
+void chain_hits(const Batch &B, size_t r, std::vector<Hit> &hs)
+{
+	const mm2gb_map_opt_t &opt = B.opt;
+	hs.clear();
+	for (int64_t j = B.u_off[r]; j < B.u_off[r + 1]; ++j) hs.push_back(hit_from(B.regs[(size_t)j]));
+	if (hs.empty()) return;
+	set_parent(opt.mask_level, opt.mask_len, hs, false);                                              // map.c:336
+	select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);              // map.c:337
+	estimate_divergence(B.c.lens[r], B.ref_len, hs, B.ca + B.c_off[r], B.mt[r].n_mini_pos, B.mt[r].mini_pos);   // map.c:751
+	filter_strand_retained(hs);                                                                       // map.c:752
+}
+
+void paf_line(Batch &B, size_t r, const Hit &h, const uint32_t *words = nullptr)
+{
+	write_paf(B.lines[r], B.c.names[r] ? B.c.names[r] : "*", B.c.lens[r], h, B.c.ref_names[h.rid], B.c.ref_lens[h.rid], B.mt[r].rep_len, words);
+}
+
+// without an alignment: mapping quality and the lines
+void finish_reads(Batch &B)
+{
+	std::atomic<size_t> next(0);
+	run_on_threads(B.nt, [&](int) {
+		std::vector<Hit> hs;                                 // a worker's own
+		for (size_t r; (r = next.fetch_add(1)) < B.R;) {
+			chain_hits(B, r, hs);
+			set_mapq(hs, B.opt.min_chain_score, B.mt[r].rep_len);                                       // map.c:758
+			for (const Hit &h : hs) { paf_line(B, r, h); B.lines[r] += '\n'; }
+		}
+	});
+}
+
+// with one: what 6a, 6b and 6c share
+struct Aligned {
+	std::vector<std::vector<Hit>> kept;                  // per read: the records that are left
+	std::vector<int64_t> reg_off, line_off;
+	std::vector<mm2gb_reg_t> rin;
+	mm2gb_align_out_t o;
+	int64_t *tx_off = nullptr;
+	char *tx = nullptr;
+	Aligned() { memset(&o, 0, sizeof o); }
+	Aligned(const Aligned&) = delete;
+	~Aligned() { mm2gb_align_out_free(&o); free(tx_off); free(tx); }       // (freed on every way out)
+};
+
+// 6a. the surviving records of every read, as map.c has them when it calls align_regs (map.c:756) ...
+void kept_records(Batch &B, Aligned &A)
+{
+	const size_t R = B.R;
+	A.kept.resize(R);
+	for_each_on_threads(R, B.nt, 1, [&](size_t r) { chain_hits(B, r, A.kept[r]); });
+	A.reg_off.assign(R + 1, 0);
+	for (size_t r = 0; r < R; ++r) A.reg_off[r + 1] = A.reg_off[r] + (int64_t)A.kept[r].size();
+	A.rin.resize((size_t)std::max<int64_t>(A.reg_off[R], 1));
+	for (size_t r = 0; r < R; ++r)
+		for (size_t i = 0; i < A.kept[r].size(); ++i) reg_from(A.kept[r][i], A.rin[(size_t)A.reg_off[r] + i]);
+}
+
+// ... through the alignment call (on an error the call's own text stays)
+int align_kept(Batch &B, Aligned &A)
+{
+	const MapCall &c = B.c;
+	const int idx_flag = mm2gb_index_flag(c.ix);
+	if (idx_flag < 0) return -1;
+	return B.aln->align_on_device < 0 ? mm2gb_align_regs_host(&B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca,
+	                                                          B.nt, &A.o)
+	                                  : mm2gb_align_regs_gpu(c.eng, &B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca, &A.o);
+}
+
+// 6b. per read: primary / secondary, which secondaries stay and the mapping quality, all with the alignment (map.c:347-348, 758)
+void rank_aligned(Batch &B, Aligned &A)
+{
+	const mm2gb_map_opt_t &opt = B.opt;
+	for_each_on_threads(B.R, B.nt, 1, [&](size_t r) {
+		std::vector<Hit> &hs = A.kept[r];
+		hs.clear();
+		for (int64_t j = A.o.reg_off[r]; j < A.o.reg_off[r + 1]; ++j) { hs.push_back(hit_from(A.o.regs[j], &A.o.aln[j])); hs.back().aln = j; }
+		set_parent(opt.mask_level, opt.mask_len, hs, false, B.aln->opt.a * 2 + B.aln->opt.b);
+		select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, false, (int)(opt.max_gap * 0.8), hs);
+		set_mapq(hs, opt.min_chain_score, B.mt[r].rep_len, B.aln->opt.a);
+	});
+}
+
+// 6c. the text of the tags for the records that are left, in one call ...
+int tag_text(Batch &B, Aligned &A)
+{
+	const MapCall &c = B.c;
+	const mm2gb_map_aln_t *aln = B.aln;
+	const size_t R = B.R;
+	A.line_off.assign(R + 1, 0);
+	for (size_t r = 0; r < R; ++r) A.line_off[r + 1] = A.line_off[r] + (int64_t)A.kept[r].size();
+	const int64_t n_out = A.line_off[R];
+	if (!aln->what || n_out == 0) return 0;
+	std::vector<mm2gb_reg_t> treg((size_t)n_out);
+	std::vector<mm2gb_aln_t> taln((size_t)n_out);
+	std::vector<int32_t> tread((size_t)n_out);
+	for (size_t r = 0; r < R; ++r)
+		for (size_t i = 0; i < A.kept[r].size(); ++i) {
+			const size_t j = (size_t)A.line_off[r] + i;
+			treg[j] = A.o.regs[A.kept[r][i].aln]; taln[j] = A.o.aln[A.kept[r][i].aln]; tread[j] = (int32_t)r;
+		}
+	if (aln->text_on_device <= 0)                         // text_on_device 0: the host form (profiles/aln_text_rate.json)
+		return mm2gb_aln_text_host(aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, B.nt, &A.tx_off, &A.tx);
+	std::vector<int64_t> ref_at((size_t)c.n_ref + 1, 0), read_at(R + 1, 0);
+	for (int32_t i = 0; i < c.n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + c.ref_lens[i];
+	for (size_t i = 0; i < R; ++i) read_at[i + 1] = read_at[i] + c.lens[i];
+	// the alignment call's device backend says what it left resident (engine.h: al_resident): this batch's residues, or nothing
+	Engine &e = c.eng->e;
+	if (aln->align_on_device >= 0 && e.al_resident[0] == ref_at.back() && e.al_resident[1] == read_at.back())
+		return aln_text_resident(e, "mm2gb_map_reads_aln", aln->what, c.n_ref, c.ref_lens, ref_at.data(), c.n_reads, c.lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
+		                         A.o.cigar, &A.tx_off, &A.tx);
+	return mm2gb_aln_text_gpu(c.eng, aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, &A.tx_off, &A.tx);
+}
+
+// ... then the lines
+void aligned_lines(Batch &B, const Aligned &A)
+{
+	for_each_on_threads(B.R, B.nt, 1, [&](size_t r) {
+		for (size_t i = 0; i < A.kept[r].size(); ++i) {
+			const Hit &h = A.kept[r][i];
+			const size_t j = (size_t)A.line_off[r] + i;
+			paf_line(B, r, h, h.has_p ? A.o.cigar + A.o.aln[h.aln].cigar_off : nullptr);
+			if (A.tx_off) B.lines[r].append(A.tx + A.tx_off[j], (size_t)(A.tx_off[j + 1] - A.tx_off[j]));
+			B.lines[r] += '\n';
+		}
+	});
+}
+
+// the lines end to end
+int emit_paf(Batch &B)
+{
+	size_t total = 0;
+	for (const auto &l : B.lines) total += l.size();
+	char *buf = (char*)malloc(total + 1);
+	if (!buf) return fail("mm2gb_map_reads: out of memory");
+	size_t at = 0;
+	for (const auto &l : B.lines) { memcpy(buf + at, l.data(), l.size()); at += l.size(); if (!l.empty()) ++B.st.n_mapped; }
+	buf[total] = 0;
+	*B.c.paf_out = buf; *B.c.paf_len = (int64_t)total;
+	B.st.n_reads = B.c.n_reads;
+	if (B.c.stats) *B.c.stats = B.st;
+	return 0;
+}
+
+int map_reads_body(const MapCall &c)
+{
+	if (!c.eng || !c.ix || !c.opt || !c.paf_out || !c.paf_len || c.n_reads < 0 || c.n_ref <= 0 || !c.ref_names || !c.ref_lens || (c.n_reads > 0 && (!c.names || !c.seqs || !c.lens)))
+		return fail("mm2gb_map_reads: null argument");
+	mm2gb_map_opt_t opt = *c.opt;
+	if (opt.flag & ~(int64_t)(0x100000 | 0x200000)) return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported");
+	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(c.ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);   // options.c:78-84
+	if (opt.bw_long < opt.bw) opt.bw_long = opt.bw;
+	if (opt.host_threads <= 0) opt.host_threads = std::min(32, usable_cpus());
+	auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+	double t_mark = now();
+	auto lap = [&](double &slot) { const double t = now(); slot += t - t_mark; t_mark = t; };
+	*c.paf_out = nullptr; *c.paf_len = 0;
+	if (c.n_reads == 0) {
+		*c.paf_out = (char*)calloc(1, 1);
+		if (c.stats) memset(c.stats, 0, sizeof *c.stats);
+		return *c.paf_out ? 0 : fail("mm2gb_map_reads: out of memory");
+	}
+	Batch B(c, opt);
+	std::unique_ptr<TraceRange> tr;                       // stage ranges for rocprofv3 --marker-trace / rocprof-sys
+	auto stage = [&](const char *name) { tr.reset(); if (name) tr.reset(new TraceRange(name)); };
+	const bool dev_seed = opt.seeding_on_device > 0;
+
+	stage("mm2gb:map_seed");
+	if (dev_seed ? seed_on_device(B) : seed_on_host(B)) return -1;                                    // 1
+	lap(B.st.s_seed);
+	stage("mm2gb:map_anchors");
+	if (collect_anchors(B, dev_seed)) return -1;                                                      // 2
+	B.st.n_anchors = B.a_off[B.R];
+	lap(B.st.s_anchors);
+	stage("mm2gb:map_chain");
+	if (chain(B)) return -1;                                                                          // 3
+	lap(B.st.s_chain);
+	stage("mm2gb:map_rechain");
+	if (rechain(B)) return -1;                                                                        // 4
+	lap(B.st.s_rechain);
+	stage("mm2gb:map_hit_records");
+	if (hit_records(B)) return -1;                                                                    // 5
+	lap(B.st.s_regs);
+	stage("mm2gb:map_hits_to_paf");
+	if (!B.aln) finish_reads(B);                                                                      // 6
+	else {
+		Aligned A;
+		kept_records(B, A);                                                                           // 6a
+		lap(B.st.s_post);
+		if (align_kept(B, A)) return -1;
+		lap(B.s_extra[0]);
+		rank_aligned(B, A);                                                                           // 6b
+		lap(B.s_extra[1]);
+		if (tag_text(B, A)) return -1;                                                                // 6c
+		lap(B.s_extra[2]);
+		aligned_lines(B, A);
+	}
+	B.release_matches();
+	lap(B.st.s_post);
+	stage(nullptr);
+	return emit_paf(B);
+}
+
+// a batch's arrays are gigabytes: running out of host memory on this thread is an error of the call, not the end of the process
+int map_reads_try(const MapCall &c)
+{
+	try { return map_reads_body(c); }
+	catch (const std::bad_alloc&) { return fail("mm2gb_map_reads: out of host memory"); }
+}
+
+// nullptr, or why a mm2gb_map_aln_t cannot be used
+const char *bad_aln(const mm2gb_map_aln_t *aln)
+{
+	if (!aln || !aln->ref_seqs) return "null argument";
+	if (aln->what & ~(MM2GB_TEXT_CG | MM2GB_TEXT_CS | MM2GB_TEXT_CS_LONG | MM2GB_TEXT_MD)) return "what has a bit outside MM2GB_TEXT_*";
+	return nullptr;
+}
+
+// the parts' PAF end to end (the parts are freed) and their stats as one: counts summed, stage seconds summed or the largest taken
+int join_parts(const std::string &who, std::vector<char*> &part, const std::vector<int64_t> &part_len, const std::vector<mm2gb_map_stats_t> &st, bool sum_seconds,
+               char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
+{
+	int64_t all = 0;
+	for (int64_t l : part_len) all += l;
+	char *buf = (char*)malloc((size_t)all + 1);
+	int64_t at = 0;
+	mm2gb_map_stats_t sum; memset(&sum, 0, sizeof sum);
+	static double mm2gb_map_stats_t::*const seconds[] = { &mm2gb_map_stats_t::s_seed, &mm2gb_map_stats_t::s_anchors, &mm2gb_map_stats_t::s_chain, &mm2gb_map_stats_t::s_rechain, &mm2gb_map_stats_t::s_regs, &mm2gb_map_stats_t::s_post };
+	for (size_t i = 0; i < part.size(); ++i) {
+		if (buf && part_len[i]) memcpy(buf + at, part[i], (size_t)part_len[i]);
+		at += part_len[i]; free(part[i]); part[i] = nullptr;
+		const mm2gb_map_stats_t &q = st[i];
+		sum.n_reads += q.n_reads; sum.n_mapped += q.n_mapped; sum.n_anchors += q.n_anchors; sum.n_chains += q.n_chains; sum.n_rechained += q.n_rechained; sum.n_rmq_tied += q.n_rmq_tied;
+		for (auto s : seconds) sum.*s = sum_seconds ? sum.*s + q.*s : std::max(sum.*s, q.*s);
+	}
+	if (!buf) return fail(who + ": out of memory");
+	buf[all] = 0;
+	*paf_out = buf; *paf_len = all;
+	if (stats) *stats = sum;
+	return 0;
+}
+
+// A run of any size as a stream of batches (role of the batch rotation of worker_for, map.c:924-1153: seed batch k+1 while batch k is
+// chained and batch k-1 is finished): the reads are cut into consecutive chunks of about chunk_bases bases, and every engine -- several
+// per device are the point: each has its own streams and arenas -- has a host thread that takes the next chunk and maps it from
+// seeding to PAF.  A chunk's stages alternate between host threads and the device, so with two or three engines on a GPU one chunk is
+// being seeded or post-processed while another one's kernels run; with engines on several GPUs the reads shard (SURVEY 8e: no
+// exchange).  The host threads of opt are shared out with over-subscription (2.5 x), because a chunk's threads idle while its kernels run.
+// PAF in read order; stats: counts summed, s_* = seconds of each stage SUMMED over chunks (they overlap: not wall time).
+int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bases, const MapCall &c)
+{
+	const int32_t n_reads = c.n_reads;
+	if (!engines || n_engines < 1 || !c.ix || !c.opt || !c.paf_out || !c.paf_len || n_reads < 0 || (n_reads > 0 && (!c.lens || !c.names || !c.seqs)) || (c.n_ref > 0 && (!c.ref_names || !c.ref_lens)))
+		return fail("mm2gb_map_reads_stream: null argument");
+	for (int e = 0; e < n_engines; ++e) if (!engines[e]) return fail("mm2gb_map_reads_stream: null engine");
+	*c.paf_out = nullptr; *c.paf_len = 0;
+	if (chunk_bases <= 0) chunk_bases = 96 * 1000 * 1000;
+	std::vector<int32_t> cut(1, 0);
+	{ int64_t acc = 0; for (int32_t r = 0; r < n_reads; ++r) { acc += c.lens[r]; if (acc >= chunk_bases && r + 1 < n_reads) { cut.push_back(r + 1); acc = 0; } } }
+	cut.push_back(n_reads);
+	const size_t n_chunks = cut.size() - 1;
+	mm2gb_map_opt_t opt = *c.opt;
+	const int all_threads = opt.host_threads > 0 ? opt.host_threads : std::min(32, usable_cpus());
+	const int workers = (int)std::min<size_t>((size_t)n_engines, std::max<size_t>(1, n_chunks));
+	// host threads of all workers together, in % of opt's (MM2GB_STREAM_THREADS_PCT): a chunk's threads idle while its kernels run, and the reads its
+	// re-chaining gives to host threads want a core each when they come.  1.05 Gbp, four engines, 16 threads: 100 % 8.0 s, 150 % 6.8-7.1, 250 % 6.3-6.5, 400 % 6.6-6.9
+	int oversub_pct = 250;
+	if (const char *v = getenv("MM2GB_STREAM_THREADS_PCT")) oversub_pct = std::max(25, atoi(v));
+	opt.host_threads = std::max(1, workers == 1 ? all_threads : (all_threads * oversub_pct / 100 + workers - 1) / workers);
+	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(c.ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);     // once, not per chunk
+	std::vector<char*> part(n_chunks, nullptr);
+	std::vector<int64_t> part_len(n_chunks, 0);
+	std::vector<mm2gb_map_stats_t> st(n_chunks);
+	std::vector<double> extra(n_chunks * 3, 0.0);         // with an alignment: seconds for align, the steps after it, text, per chunk
+	std::atomic<size_t> next(0);
+	std::atomic<int> failed(0);
+	std::string why;                                      // error text is per thread: carry the first one over
+	std::mutex why_lock;
+	run_on_threads(workers, [&](int e) {                  // a worker keeps its engine from chunk to chunk
+		for (;;) {
+			const size_t k = next.fetch_add(1);
+			if (k >= n_chunks || failed.load()) break;
+			memset(&st[k], 0, sizeof(st[k]));
+			MapCall one = c;
+			one.eng = engines[e]; one.opt = &opt; one.n_reads = cut[k + 1] - cut[k]; one.names += cut[k]; one.seqs += cut[k]; one.lens += cut[k];
+			one.paf_out = &part[k]; one.paf_len = &part_len[k]; one.stats = &st[k]; one.s_extra = &extra[k * 3];
+			if (map_reads_try(one)) {
+				std::lock_guard<std::mutex> g(why_lock);
+				if (!failed.exchange(1)) why = "chunk " + std::to_string(k) + " on engine " + std::to_string(e) + ": " + mm2gb_last_error();
+			}
+		}
+	});
+	if (failed.load()) { for (char *p : part) free(p); return fail("mm2gb_map_reads_stream: " + why); }
+	if (join_parts("mm2gb_map_reads_stream", part, part_len, st, true, c.paf_out, c.paf_len, c.stats)) return -1;
+	if (c.s_extra) for (size_t i = 0; i < extra.size(); ++i) c.s_extra[i % 3] += extra[i];
+	return 0;
+}
+
 } // namespace
 } // namespace mm2gb
 
@@ -311,34 +939,13 @@ int mm2gb_engine_release_host_scratch(mm2gb_engine_t *eng)
 	return 0;
 }
 
-static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
-                          const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                          char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra);
-
-// nullptr, or why a mm2gb_map_aln_t cannot be used
-static const char *bad_aln(const mm2gb_map_aln_t *aln)
-{
-	if (!aln || !aln->ref_seqs) return "null argument";
-	if (aln->what & ~(MM2GB_TEXT_CG | MM2GB_TEXT_CS | MM2GB_TEXT_CS_LONG | MM2GB_TEXT_MD)) return "what has a bit outside MM2GB_TEXT_*";
-	return nullptr;
-}
-
-static int map_reads_try(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
-                         const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                         char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra)
-{
-	// a batch's arrays are gigabytes: running out of host memory on this thread is an error of the call, not the end of the process
-	try { return map_reads_body(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s_extra); }
-	catch (const std::bad_alloc&) { return fail("mm2gb_map_reads: out of host memory"); }
-}
-
 int mm2gb_map_reads_aln(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
                         const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                         char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
 {
 	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_aln: ") + why);
 	double s3[3] = { 0, 0, 0 };
-	const int rc = map_reads_try(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3);
+	const int rc = map_reads_try({ eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 });
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
 }
@@ -347,461 +954,7 @@ int mm2gb_map_reads(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const c
                     const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                     char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
 {
-	return map_reads_try(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, nullptr, nullptr);
-}
-
-static int map_reads_body(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
-                          const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                          char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra)
-{
-	if (!eng || !ix || !opt_in || !paf_out || !paf_len || n_reads < 0 || n_ref <= 0 || !ref_names || !ref_lens || (n_reads > 0 && (!names || !seqs || !lens)))
-		return fail("mm2gb_map_reads: null argument");
-	mm2gb_map_opt_t opt = *opt_in;
-	if (opt.flag & ~(int64_t)(0x100000 | 0x200000)) return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported");
-	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);   // options.c:78-84
-	if (opt.bw_long < opt.bw) opt.bw_long = opt.bw;
-	if (opt.host_threads <= 0) opt.host_threads = std::min(32, usable_cpus());
-	mm2gb_map_stats_t st_local; memset(&st_local, 0, sizeof st_local);
-	auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	double t_mark = now();
-	auto lap = [&](double &slot) { const double t = now(); slot += t - t_mark; t_mark = t; };
-	*paf_out = nullptr; *paf_len = 0;
-	if (n_reads == 0) { *paf_out = (char*)calloc(1, 1); if (stats) *stats = st_local; return *paf_out ? 0 : fail("mm2gb_map_reads: out of memory"); }
-	const size_t R = (size_t)n_reads;
-	std::vector<int32_t> ref_len_v(ref_lens, ref_lens + n_ref);
-
-	// 1. matches on host threads
-	std::unique_ptr<TraceRange> tr(new TraceRange("mm2gb:map_seed"));   // stage ranges for rocprofv3 --marker-trace / rocprof-sys
-	struct MatchSet { std::vector<mm2gb_matches_t> v; ~MatchSet() { for (auto &m : v) mm2gb_matches_free(&m); } } mt_own;   // (freed on every way out)
-	std::vector<mm2gb_matches_t> &mt = mt_own.v;
-	mt.resize(R);
-	std::vector<std::vector<const uint64_t*>> occ(R);     // per read and kept seed: its occurrences, where the index holds them (copied once, into the batch's array)
-	for (auto &m : mt) memset(&m, 0, sizeof m);
-	const mm2gb_seed_opt_t so = { opt.mid_occ, opt.max_max_occ, opt.occ_dist, opt.q_occ_frac };
-	// seeding_on_device = 1: the reads go up as bytes, sketch / look-up / match selection run as kernels (seed_kernels.hip) and leave the arrays
-	// step 2's kernels read where they are; what comes down is what the host's mapq and divergence code wants (rep_len, mini_pos)
-	const bool dev_seed = opt.seeding_on_device > 0;
-	int64_t dev_seeds = 0, dev_hits = 0;
-	if (dev_seed) {
-		std::vector<int64_t> seq_off(R + 1, 0);
-		for (size_t r = 0; r < R; ++r) seq_off[r + 1] = seq_off[r] + lens[r];
-		if (seq_off[R] >= ((int64_t)1 << 31) - 1) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 bases");
-		BigBuf<uint64_t> &flat = host_scratch(eng).hits;          // (no host array of hits in this form: its memory holds the reads end to end)
-		flat.resize((size_t)seq_off[R] / 8 + 1);
-		char *const bases = (char*)flat.data();
-		{
-			std::atomic<size_t> next(0);
-			auto work = [&]() { for (;;) { const size_t r = next.fetch_add(1); if (r >= R) break; if (lens[r] > 0) memcpy(bases + seq_off[r], seqs[r], (size_t)lens[r]); } };
-			std::vector<std::thread> pool;
-			for (int t = 1; t < std::max(1, opt.host_threads); ++t) pool.emplace_back(work);
-			work();
-			for (auto &th : pool) th.join();
-		}
-		DevIndexView view;
-		if (index_on_device(ix, eng->e.device, &view)) return -1;
-		if (eng->e.collect_matches_device(view, so, n_reads, seq_off.data(), bases, &dev_seeds, &dev_hits)) return -1;
-		std::vector<int64_t> seed_off(R + 1, 0);
-		std::vector<int32_t> rep(R, 0);
-		std::vector<uint64_t> mini_pos((size_t)dev_seeds + 1);
-		if (hipMemcpy(seed_off.data(), eng->e.sd_seed_off.ptr, (R + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rep.data(), eng->e.sd_rep_len.ptr, R * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-		    (dev_seeds > 0 && hipMemcpy(mini_pos.data(), eng->e.sd_mini_pos.ptr, (size_t)dev_seeds * 8, hipMemcpyDeviceToHost) != hipSuccess))
-			return fail("mm2gb_map_reads: the device's matches could not be copied back");
-		for (size_t r = 0; r < R; ++r) {
-			const int64_t n = seed_off[r + 1] - seed_off[r];
-			mt[r].rep_len = rep[r]; mt[r].n_seeds = mt[r].n_mini_pos = (int32_t)n;
-			mt[r].mini_pos = (uint64_t*)malloc(((size_t)n + 1) * 8);
-			if (!mt[r].mini_pos) return fail("mm2gb_map_reads: out of memory");
-			if (n > 0) memcpy(mt[r].mini_pos, mini_pos.data() + seed_off[r], (size_t)n * 8);
-		}
-	} else {
-		std::atomic<int32_t> next(0);
-		std::atomic<int> bad(0);
-		std::string why;                                      // error text is per thread: carry the first one over
-		std::mutex why_lock;
-		auto work = [&]() {
-			for (;;) {
-				const int32_t r = next.fetch_add(1);
-				if (r >= n_reads) break;
-				if (lens[r] > 0 && collect_matches_refs(ix, seqs[r], lens[r], &so, &mt[(size_t)r], &occ[(size_t)r])) {
-					std::lock_guard<std::mutex> g(why_lock);
-					if (!bad.exchange(1)) why = mm2gb_last_error();
-				}
-			}
-		};
-		const int nt = std::max(1, opt.host_threads);
-		std::vector<std::thread> pool;
-		for (int t = 0; t < nt; ++t) pool.emplace_back(work);
-		for (auto &th : pool) th.join();
-		if (bad) { for (auto &m : mt) mm2gb_matches_free(&m); return fail(why); }
-	}
-	auto free_matches = [&]() { for (auto &m : mt) mm2gb_matches_free(&m); };
-	lap(st_local.s_seed);
-	tr.reset(); tr.reset(new TraceRange("mm2gb:map_anchors"));
-
-	// 2. anchors, sorted, on the device
-	std::vector<int32_t> qlen(lens, lens + n_reads);
-	std::vector<int64_t> a_off(R + 1, 0);
-	BigBuf<mm2gb_anchor_t> &anchors = host_scratch(eng).anchors;
-	if (dev_seed) {
-		anchors.resize((size_t)std::max<int64_t>(dev_hits, 1));
-		if (eng->e.collect_seeds_resident(opt.flag, n_reads, dev_seeds, dev_hits, a_off.data(), anchors.data())) { free_matches(); return -1; }
-	} else {
-	std::vector<int64_t> seed_off(R + 1, 0);
-	for (size_t r = 0; r < R; ++r) seed_off[r + 1] = seed_off[r] + mt[r].n_seeds;
-	std::vector<mm2gb_seed_t> seeds((size_t)seed_off[R]);
-	std::vector<int64_t> hit_off((size_t)seed_off[R] + 1, 0);
-	int64_t n_hits = 0;
-	for (size_t r = 0; r < R; ++r) {
-		if (mt[r].n_seeds) memcpy(seeds.data() + seed_off[r], mt[r].seeds, (size_t)mt[r].n_seeds * sizeof(mm2gb_seed_t));
-		for (int s = 0; s < mt[r].n_seeds; ++s) { hit_off[(size_t)(seed_off[r] + s) + 1] = hit_off[(size_t)(seed_off[r] + s)] + mt[r].seeds[s].n; }
-		n_hits += mt[r].n_hits;
-	}
-	// (the batch's two largest arrays are the engine's from call to call: a gigabyte of fresh pages costs more to touch than to fill)
-	BigBuf<uint64_t> &hits = host_scratch(eng).hits;
-	hits.resize((size_t)n_hits);
-	{
-		uint64_t *const hits_ptr = hits.data();
-		std::atomic<size_t> next(0);
-		auto work = [&]() {
-			for (;;) {
-				const size_t lo = next.fetch_add(16);
-				if (lo >= R) break;
-				for (size_t r = lo; r < std::min(R, lo + 16); ++r)
-					for (int32_t q = 0; q < mt[r].n_seeds; ++q)
-						memcpy(hits_ptr + hit_off[(size_t)seed_off[r] + (size_t)q], occ[r][(size_t)q], (size_t)mt[r].seeds[q].n * 8);
-			}
-		};
-		std::vector<std::thread> pool;
-		for (int t = 1; t < std::max(1, opt.host_threads); ++t) pool.emplace_back(work);
-		work();
-		for (auto &th : pool) th.join();
-	}
-	anchors.resize((size_t)std::max<int64_t>(n_hits, 1));
-	// on the device for large batches (mm2gb_collect_seeds_gpu: matches up, anchors down, one wave sorts a read); below that the host
-	// threads are quicker: the largest read's sort alone is hundreds of milliseconds for one wave, milliseconds for a core
-	const bool seeds_on_device = opt.seeds_on_device > 0 || (opt.seeds_on_device == 0 && n_hits >= 400000000);
-	if (seeds_on_device ? mm2gb_collect_seeds_gpu(eng, opt.flag, n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), qlen.data(), nullptr, n_ref, nullptr, nullptr,
-	                                              a_off.data(), anchors.data())
-	                    : mm2gb_collect_seeds_host(opt.flag, n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), qlen.data(), nullptr, n_ref, nullptr, nullptr,
-	                                               std::max(1, opt.host_threads), a_off.data(), anchors.data())) { free_matches(); return -1; }
-	}
-	st_local.n_anchors = a_off[R];
-	lap(st_local.s_anchors);
-	tr.reset(); tr.reset(new TraceRange("mm2gb:map_chain"));
-
-	// 3. chains on the device; map.c:393-426 for the parameters (the GPU path chains with max-chain-skip = infinity unless the options set
-	//    a finite one: then the engine keeps it for this call, and the re-chaining call below gets it too)
-	mm2gb_misc_t misc;
-	const bool skip_limit = opt.max_chain_skip != INT32_MAX;
-	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = opt.max_gap; misc.max_dist_x = opt.max_gap_ref > 0 ? opt.max_gap_ref : opt.max_gap;
-	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
-	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * k);
-	if (mm2gb_engine_set_misc(eng, &misc)) { free_matches(); return -1; }
-	ChainsOwner ch_own;                                  // (freed on every way out)
-	mm2gb_chains_t &ch = ch_own.c;
-	// backtrack + compaction as kernels for large batches; below that on host threads, overlapped with the device: a single huge read (a
-	// tandem array) keeps one wave busy for hundreds of milliseconds where a core needs tens
-	struct ChainSkipMode {                               // the engine's own mode comes back on every way out of the chaining call
-		bool &mode; const bool before;
-		ChainSkipMode(bool &m, bool keep) : mode(m), before(m) { mode = keep; }
-		~ChainSkipMode() { mode = before; }
-	};
-	int chained;
-	{
-		ChainSkipMode guard(eng->e.chain_skip, skip_limit);
-		chained = a_off[R] >= 200000000 ? mm2gb_chain_gpu(eng, n_reads, a_off.data(), anchors.data(), &ch, nullptr)
-		                                : mm2gb_chain_host(eng, n_reads, a_off.data(), anchors.data(), std::max(1, opt.host_threads), &ch, nullptr);
-	}
-	if (chained) { free_matches(); return -1; }
-
-	// 4. re-chaining of long reads whose best chain leaves much of the read uncovered (map.c:697-708): the chained anchors, sorted
-	//    again, through mg_lchain_rmq's fill
-	std::vector<int64_t> u_off(ch.u_off, ch.u_off + R + 1), c_off(ch.a_off, ch.a_off + R + 1);
-	// (the chains are read where the chaining call left them -- a gigabyte of kept anchors per batch is not copied again)
-	const uint64_t *u = ch.u;
-	const mm2gb_anchor_t *ca = ch.a;
-	lap(st_local.s_chain);
-	tr.reset(); tr.reset(new TraceRange("mm2gb:map_rechain"));
-	std::vector<int32_t> redo;
-	const auto t_rechain = std::chrono::steady_clock::now();
-	if (opt.bw_long > opt.bw) {
-		for (size_t r = 0; r < R; ++r) {
-			if (u_off[r + 1] - u_off[r] <= 1) continue;
-			const mm2gb_anchor_t *a = ca + c_off[r];
-			const int st = (int32_t)a[0].y, en = (int32_t)a[(int32_t)u[(size_t)u_off[r]] - 1].y;
-			if (lens[r] - (en - st) > opt.rmq_rescue_size || en - st > lens[r] * opt.rmq_rescue_ratio) redo.push_back((int32_t)r);
-		}
-	}
-	st_local.n_rechained = (int64_t)redo.size();
-	// largest first: a read is one wave's (or one thread's) work from start to end, and the call ends with its longest read
-	std::sort(redo.begin(), redo.end(), [&](int32_t u, int32_t v) { const int64_t nu = c_off[(size_t)u + 1] - c_off[(size_t)u], nv = c_off[(size_t)v + 1] - c_off[(size_t)v]; return nu != nv ? nu > nv : u < v; });
-	if (!redo.empty()) {
-		std::vector<int64_t> ro(redo.size() + 1, 0);
-		for (size_t q = 0; q < redo.size(); ++q) ro[q + 1] = ro[q] + (c_off[(size_t)redo[q] + 1] - c_off[(size_t)redo[q]]);
-		// (the engine's, kept between calls like the gathers of mm2gb_rmq_chain: fresh pages cost more to touch than to fill)
-		BigBuf<mm2gb_anchor_t> &ra = host_scratch(eng).ra;
-		ra.resize((size_t)ro.back());
-		mm2gb_anchor_t *const ra_ptr = ra.data();               // (for the threads below: `ra` names each thread's own)
-		{
-			std::atomic<int64_t> next(0);
-			auto work = [&]() {
-				for (;;) {
-					const int64_t q = next.fetch_add(1);
-					if (q >= (int64_t)redo.size()) break;
-					const size_t r = (size_t)redo[(size_t)q];
-					memcpy(ra_ptr + ro[(size_t)q], ca + c_off[r], (size_t)(ro[(size_t)q + 1] - ro[(size_t)q]) * sizeof(mm2gb_anchor_t));
-					sort_by_x_like_host(ra_ptr + ro[(size_t)q], ra_ptr + ro[(size_t)q + 1]);
-				}
-			};
-			const int nt = std::max(1, std::min<int>(opt.host_threads, (int)redo.size()));
-			std::vector<std::thread> pool;
-			for (int t = 1; t < nt; ++t) pool.emplace_back(work);
-			work();
-			for (auto &th : pool) th.join();
-		}
-		const bool verbose = getenv("MM2GB_DEBUG_PHASES") != nullptr;
-		if (const char *path = getenv("MM2GB_DUMP_RECHAIN")) {       // the re-chaining call's input, for profiling csrc/rmq_host.cpp off the box: offsets, then anchors
-			if (FILE *fp = fopen(path, "wb")) {
-				const int64_t nr = (int64_t)redo.size();
-				fwrite(&nr, 8, 1, fp); fwrite(ro.data(), 8, ro.size(), fp); fwrite(ra.data(), sizeof(mm2gb_anchor_t), ra.size(), fp);
-				fclose(fp);
-			}
-		}
-		const auto t_sorted = std::chrono::steady_clock::now();
-		const mm2gb_rmq_param_t rp = { opt.max_gap, opt.rmq_inner_dist, opt.bw_long, opt.max_chain_skip, opt.rmq_size_cap, opt.min_cnt, opt.min_chain_score, misc.chn_pen_gap, misc.chn_pen_skip };
-		ChainsOwner rc_own, rc_tie_own;
-		mm2gb_chains_t &rc = rc_own.c, &rc_tie = rc_tie_own.c;
-		std::vector<int32_t> tied(redo.size(), 0);
-		std::vector<int> tie_slot(redo.size(), -1);          // reads the device reported a tie for: their place in the host call that follows
-		RmqParts parts;                                      // the default path: the results of the call's three sides, spliced from where they are
-		std::vector<unsigned char> q_side(redo.size(), 0);   // per re-chained read: which result holds it (0: rc, 1: rc_tie, 2 + k: parts.chains[k]) ...
-		std::vector<int64_t> q_slot(redo.size(), 0);         // ... and where
-		// mg_lchain_rmq's fill.  Default: mm2gb_rmq_chain (csrc/rmq_hybrid.cpp) -- the kernel form takes the bulk of the reads, the host
-		// threads, at the same time, the few whose windows are so dense that one wave would still be on them long after the rest of the
-		// batch is done, and afterwards the reads the kernel reported a tie for (where the reference's answer follows from the shape of
-		// its tree; the host form keeps that tree's rules).  rechain_on_device = 1: every read on the device first; -1: host threads only.
-		if (opt.rechain_on_device == 0) {
-			std::vector<int32_t> where(redo.size(), 0);
-			mm2gb_rmq_deal_t deal = {};
-			if (rmq_chain_parts(eng, &rp, (int64_t)redo.size(), ro.data(), ra.data(), std::max(1, opt.host_threads), parts, where.data(), &deal)) { free_matches(); return -1; }
-			for (size_t q = 0; q < redo.size(); ++q) { tied[q] = where[q] == 2; q_side[q] = (unsigned char)(2 + parts.which[q]); q_slot[q] = parts.slot[q]; }
-			if (verbose) fprintf(stderr, "[mm2gb] re-chaining deal: %lld reads on the device, %d of them a whole workgroup's (%.3f s, estimated %.3f), %lld on host threads by cost (%.3f s, estimated %.3f), %lld redone after a tie (%.3f s)\n",
-			                     (long long)deal.n_device, (int)deal.n_team, deal.device_s, deal.est_device_s, (long long)deal.n_host_cost, deal.host_s, deal.est_host_s, (long long)deal.n_host_tie, deal.tie_s);
-		} else if (opt.rechain_on_device > 0) {
-			if (mm2gb_rmq_chain_gpu(eng, &rp, (int64_t)redo.size(), ro.data(), ra.data(), &rc, tied.data(), nullptr)) { free_matches(); return -1; }
-			std::vector<int64_t> to(1, 0);
-			std::vector<mm2gb_anchor_t> ta;
-			for (size_t q = 0; q < redo.size(); ++q)
-				if (tied[q]) {
-					tie_slot[q] = (int)to.size() - 1;
-					ta.insert(ta.end(), ra.begin() + ro[q], ra.begin() + ro[q + 1]);
-					to.push_back((int64_t)ta.size());
-				}
-			if (to.size() > 1 && mm2gb_rmq_chain_host(&rp, (int64_t)to.size() - 1, to.data(), ta.data(), std::max(1, opt.host_threads), &rc_tie, nullptr)) { mm2gb_chains_free(&rc); free_matches(); return -1; }
-		} else if (mm2gb_rmq_chain_host(&rp, (int64_t)redo.size(), ro.data(), ra.data(), std::max(1, opt.host_threads), &rc, tied.data())) { free_matches(); return -1; }
-		if (opt.rechain_on_device != 0)
-			for (size_t q = 0; q < redo.size(); ++q) { q_side[q] = tie_slot[q] >= 0 ? 1 : 0; q_slot[q] = tie_slot[q] >= 0 ? tie_slot[q] : (int64_t)q; }
-		const mm2gb_chains_t *const side[5] = { &rc, &rc_tie, &parts.chains[0], &parts.chains[1], &parts.chains[2] };
-		const auto t_filled = std::chrono::steady_clock::now();
-		// splice the re-chained reads back in
-		std::vector<int64_t> nu_off(R + 1, 0), nc_off(R + 1, 0);
-		std::vector<int> which(R, -1);
-		for (size_t q = 0; q < redo.size(); ++q) { which[(size_t)redo[q]] = (int)q; if (tied[q]) ++st_local.n_rmq_tied; }
-		for (size_t r = 0; r < R; ++r) {
-			const int q = which[r];
-			const mm2gb_chains_t &from = *side[q >= 0 ? q_side[(size_t)q] : 0];
-			const int64_t qq = q >= 0 ? q_slot[(size_t)q] : 0;
-			nu_off[r + 1] = nu_off[r] + (q < 0 ? u_off[r + 1] - u_off[r] : from.u_off[qq + 1] - from.u_off[qq]);
-			nc_off[r + 1] = nc_off[r] + (q < 0 ? c_off[r + 1] - c_off[r] : from.a_off[qq + 1] - from.a_off[qq]);
-		}
-		// (the engine's from call to call: touched pages)
-		BigBuf<uint64_t> &nu = host_scratch(eng).nu;
-		BigBuf<mm2gb_anchor_t> &nc = host_scratch(eng).nc;
-		nu.resize((size_t)nu_off[R]); nc.resize((size_t)nc_off[R]);
-		uint64_t *const nu_ptr = nu.data();
-		mm2gb_anchor_t *const nc_ptr = nc.data();
-		{
-			// (a batch's kept anchors are a gigabyte: the copies go to all host threads)
-			std::atomic<size_t> next(0);
-			auto work = [&]() {
-				for (;;) {
-					const size_t lo = next.fetch_add(32);
-					if (lo >= R) break;
-					for (size_t r = lo; r < std::min(R, lo + 32); ++r) {
-						const int q = which[r];
-						const mm2gb_chains_t &from = *side[q >= 0 ? q_side[(size_t)q] : 0];
-						const int64_t qq = q >= 0 ? q_slot[(size_t)q] : 0;
-						const uint64_t *su = q < 0 ? u + u_off[r] : from.u + from.u_off[qq];
-						const mm2gb_anchor_t *sa = q < 0 ? ca + c_off[r] : from.a + from.a_off[qq];
-						if (nu_off[r + 1] > nu_off[r]) memcpy(nu_ptr + nu_off[r], su, (size_t)(nu_off[r + 1] - nu_off[r]) * 8);
-						if (nc_off[r + 1] > nc_off[r]) memcpy(nc_ptr + nc_off[r], sa, (size_t)(nc_off[r + 1] - nc_off[r]) * sizeof(mm2gb_anchor_t));
-					}
-				}
-			};
-			std::vector<std::thread> pool;
-			for (int t = 1; t < std::max(1, opt.host_threads); ++t) pool.emplace_back(work);
-			work();
-			for (auto &th : pool) th.join();
-		}
-		mm2gb_chains_free(&rc); mm2gb_chains_free(&rc_tie);
-		u = nu_ptr; ca = nc_ptr; u_off.swap(nu_off); c_off.swap(nc_off);
-		mm2gb_chains_free(&ch);
-		if (verbose) fprintf(stderr, "[mm2gb] re-chaining %zu reads (%lld redone on the host after a tie), %lld anchors: sort %.3f s, fill %.3f s, splice %.3f s\n", redo.size(), (long long)st_local.n_rmq_tied, (long long)ro.back(), std::chrono::duration<double>(t_sorted - t_rechain).count(),
-		                     std::chrono::duration<double>(t_filled - t_sorted).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - t_filled).count());
-	}
-	st_local.n_chains = u_off[R];
-	lap(st_local.s_rechain);
-	tr.reset(); tr.reset(new TraceRange("mm2gb:map_hit_records"));
-
-	// 5. hit records on the device (hit.c:52-88); the hash of map.c:660-662
-	std::vector<uint32_t> hash(R);
-	for (size_t r = 0; r < R; ++r) {
-		uint32_t h = names[r] ? name_hash(names[r]) : 0;
-		h ^= wang((uint32_t)lens[r]) + wang((uint32_t)opt.seed);
-		hash[r] = wang(h);
-	}
-	std::vector<mm2gb_reg_t> regs((size_t)std::max<int64_t>(u_off[R], 1));
-	{
-		mm2gb_chains_t view; view.u_off = u_off.data(); view.u = const_cast<uint64_t*>(u); view.a_off = c_off.data(); view.a = const_cast<mm2gb_anchor_t*>(ca);
-		if (mm2gb_gen_regs_gpu(eng, n_reads, &view, qlen.data(), hash.data(), 0, regs.data())) { free_matches(); return -1; }
-	}
-
-	lap(st_local.s_regs);
-	tr.reset(); tr.reset(new TraceRange("mm2gb:map_hits_to_paf"));
-	// 6. per read on the host
-	std::vector<std::string> lines(R);
-	auto on_threads = [&](auto one) {                     // one(read, the worker's scratch) for every read, on the call's host threads
-		std::atomic<int32_t> next(0);
-		auto work = [&]() { std::vector<Hit> hs; for (;;) { const int32_t ri = next.fetch_add(1); if (ri >= n_reads) break; one((size_t)ri, hs); } };
-		const int nt = std::max(1, opt.host_threads);
-		std::vector<std::thread> pool;
-		for (int t = 0; t < nt; ++t) pool.emplace_back(work);
-		for (auto &th : pool) th.join();
-	};
-	// the hits of a read up to mm_filter_strand_retained (map.c:749-752)
-	auto chain_hits = [&](size_t r, std::vector<Hit> &hs) {
-		hs.clear();
-		for (int64_t j = u_off[r]; j < u_off[r + 1]; ++j) {
-			const mm2gb_reg_t &g = regs[(size_t)j];
-			Hit h;
-			h.id = g.id; h.cnt = g.cnt; h.rid = g.rid; h.score = g.score; h.qs = g.qs; h.qe = g.qe; h.rs = g.rs; h.re = g.re; h.parent = g.parent;
-			h.subsc = g.subsc; h.as = g.as; h.mlen = g.mlen; h.blen = g.blen; h.n_sub = g.n_sub; h.score0 = g.score0;
-			h.mapq = 0; h.rev = (g.flags >> 10) & 1; h.strand_retained = false; h.hash = g.hash; h.div = g.div; h.flags = g.flags;
-			hs.push_back(h);
-		}
-		if (hs.empty()) return;
-		set_parent(opt.mask_level, opt.mask_len, hs, false);                                     // map.c:336
-		select_sub(opt.pri_ratio, k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);          // map.c:337
-		estimate_divergence(lens[r], ref_len_v, hs, ca + c_off[r], mt[r].n_mini_pos, mt[r].mini_pos);   // map.c:751
-		filter_strand_retained(hs);                                                              // map.c:752
-	};
-	if (!aln) {
-		on_threads([&](size_t r, std::vector<Hit> &hs) {
-			chain_hits(r, hs);
-			set_mapq(hs, opt.min_chain_score, mt[r].rep_len);                                        // map.c:758
-			for (const Hit &h : hs) { write_paf(lines[r], names[r] ? names[r] : "*", lens[r], h, ref_names[h.rid], ref_lens[h.rid], mt[r].rep_len); lines[r] += '\n'; }
-		});
-	} else {
-		// 6a. the surviving records of every read, as map.c has them when it calls align_regs (map.c:756), through the alignment call
-		std::vector<std::vector<Hit>> kept(R);
-		on_threads([&](size_t r, std::vector<Hit>&) { chain_hits(r, kept[r]); });
-		std::vector<int64_t> reg_off(R + 1, 0);
-		for (size_t r = 0; r < R; ++r) reg_off[r + 1] = reg_off[r] + (int64_t)kept[r].size();
-		std::vector<mm2gb_reg_t> rin((size_t)std::max<int64_t>(reg_off[R], 1));
-		for (size_t r = 0; r < R; ++r)
-			for (size_t i = 0; i < kept[r].size(); ++i) {
-				const Hit &h = kept[r][i];
-				mm2gb_reg_t &g = rin[(size_t)reg_off[r] + i];
-				g.id = h.id; g.cnt = h.cnt; g.rid = h.rid; g.score = h.score; g.qs = h.qs; g.qe = h.qe; g.rs = h.rs; g.re = h.re; g.parent = h.parent; g.subsc = h.subsc; g.as = h.as;
-				g.mlen = h.mlen; g.blen = h.blen; g.n_sub = h.n_sub; g.score0 = h.score0; g.hash = h.hash; g.div = h.div;
-				g.flags = h.flags | (h.strand_retained ? 1u << 26 : 0u);
-			}
-		lap(st_local.s_post);
-		struct AlignOut { mm2gb_align_out_t o; AlignOut() { memset(&o, 0, sizeof o); } ~AlignOut() { mm2gb_align_out_free(&o); } } ao;      // (freed on every way out)
-		const int idx_flag = mm2gb_index_flag(ix);
-		if (idx_flag < 0) { free_matches(); return -1; }
-		if (aln->align_on_device < 0 ? mm2gb_align_regs_host(&aln->opt, k, idx_flag, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, reg_off.data(), rin.data(), c_off.data(), ca,
-		                                                     std::max(1, opt.host_threads), &ao.o)
-		                             : mm2gb_align_regs_gpu(eng, &aln->opt, k, idx_flag, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, reg_off.data(), rin.data(), c_off.data(), ca, &ao.o)) {
-			free_matches();
-			return -1;                                    // (the alignment call's own text stays)
-		}
-		lap(s_extra[0]);
-		// 6b. per read: primary / secondary, which secondaries stay and the mapping quality, all with the alignment (map.c:347-348, 758)
-		const mm2gb_align_out_t &A = ao.o;
-		on_threads([&](size_t r, std::vector<Hit>&) {
-			std::vector<Hit> &hs = kept[r];
-			hs.clear();
-			for (int64_t j = A.reg_off[r]; j < A.reg_off[r + 1]; ++j) {
-				const mm2gb_reg_t &g = A.regs[j];
-				const mm2gb_aln_t &x = A.aln[j];
-				Hit h;
-				h.id = g.id; h.cnt = g.cnt; h.rid = g.rid; h.score = g.score; h.qs = g.qs; h.qe = g.qe; h.rs = g.rs; h.re = g.re; h.parent = g.parent;
-				h.subsc = g.subsc; h.as = g.as; h.mlen = g.mlen; h.blen = g.blen; h.n_sub = g.n_sub; h.score0 = g.score0;
-				h.mapq = 0; h.rev = (g.flags >> 10) & 1; h.strand_retained = (g.flags >> 26) & 1; h.hash = g.hash; h.div = g.div; h.flags = g.flags;
-				h.inv = (g.flags >> 11) & 1; h.split = (int)(g.flags >> 8 & 3);
-				h.has_p = x.cigar_off >= 0; h.aln = j;
-				if (h.has_p) { h.dp_score = x.dp_score; h.dp_max = x.dp_max; h.dp_max2 = x.dp_max2; h.n_ambi = x.n_ambi; h.trans_strand = x.trans_strand; h.n_cigar = x.n_cigar; }
-				hs.push_back(h);
-			}
-			set_parent(opt.mask_level, opt.mask_len, hs, false, aln->opt.a * 2 + aln->opt.b);
-			select_sub(opt.pri_ratio, k * 2, opt.best_n, false, (int)(opt.max_gap * 0.8), hs);
-			set_mapq(hs, opt.min_chain_score, mt[r].rep_len, aln->opt.a);
-		});
-		lap(s_extra[1]);
-		// 6c. the text of the tags for the records that are left, in one call; then the lines
-		std::vector<int64_t> line_off(R + 1, 0);
-		for (size_t r = 0; r < R; ++r) line_off[r + 1] = line_off[r] + (int64_t)kept[r].size();
-		const int64_t n_out = line_off[R];
-		std::vector<mm2gb_reg_t> treg((size_t)std::max<int64_t>(n_out, 1));
-		std::vector<mm2gb_aln_t> taln((size_t)std::max<int64_t>(n_out, 1));
-		std::vector<int32_t> tread((size_t)std::max<int64_t>(n_out, 1));
-		for (size_t r = 0; r < R; ++r)
-			for (size_t i = 0; i < kept[r].size(); ++i) {
-				const size_t j = (size_t)line_off[r] + i;
-				treg[j] = A.regs[kept[r][i].aln]; taln[j] = A.aln[kept[r][i].aln]; tread[j] = (int32_t)r;
-			}
-		struct Text { int64_t *off = nullptr; char *text = nullptr; ~Text() { free(off); free(text); } } tx;
-		if (aln->what && n_out > 0) {
-			int rc;
-			if (aln->text_on_device > 0) {
-				std::vector<int64_t> ref_at((size_t)n_ref + 1, 0), read_at(R + 1, 0);
-				for (int32_t i = 0; i < n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + ref_lens[i];
-				for (size_t i = 0; i < R; ++i) read_at[i + 1] = read_at[i] + lens[i];
-				// the alignment call's device backend says what it left resident (engine.h: al_resident): this batch's residues, or nothing
-				if (aln->align_on_device >= 0 && eng->e.al_resident[0] == ref_at.back() && eng->e.al_resident[1] == read_at.back()) {
-					rc = aln_text_resident(eng->e, "mm2gb_map_reads_aln", aln->what, n_ref, ref_lens, ref_at.data(), n_reads, lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
-					                       A.cigar, &tx.off, &tx.text);
-				} else rc = mm2gb_aln_text_gpu(eng, aln->what, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, n_out, treg.data(), tread.data(), taln.data(), A.cigar, &tx.off, &tx.text);
-			} else rc = mm2gb_aln_text_host(aln->what, n_ref, aln->ref_seqs, ref_lens, n_reads, seqs, lens, n_out, treg.data(), tread.data(), taln.data(), A.cigar, std::max(1, opt.host_threads),
-			                                &tx.off, &tx.text);          // text_on_device 0: the host form (profiles/aln_text_rate.json)
-			if (rc) { free_matches(); return -1; }
-		}
-		lap(s_extra[2]);
-		on_threads([&](size_t r, std::vector<Hit>&) {
-			for (size_t i = 0; i < kept[r].size(); ++i) {
-				const Hit &h = kept[r][i];
-				const size_t j = (size_t)line_off[r] + i;
-				write_paf(lines[r], names[r] ? names[r] : "*", lens[r], h, ref_names[h.rid], ref_lens[h.rid], mt[r].rep_len, h.has_p ? A.cigar + A.aln[h.aln].cigar_off : nullptr);
-				if (tx.off) lines[r].append(tx.text + tx.off[j], (size_t)(tx.off[j + 1] - tx.off[j]));
-				lines[r] += '\n';
-			}
-		});
-	}
-	free_matches();
-	lap(st_local.s_post);
-	tr.reset();
-	size_t total = 0;
-	for (const auto &l : lines) total += l.size();
-	char *buf = (char*)malloc(total + 1);
-	if (!buf) return fail("mm2gb_map_reads: out of memory");
-	size_t at = 0;
-	for (const auto &l : lines) { memcpy(buf + at, l.data(), l.size()); at += l.size(); if (!l.empty()) ++st_local.n_mapped; }
-	buf[total] = 0;
-	*paf_out = buf; *paf_len = (int64_t)total;
-	st_local.n_reads = n_reads;
-	if (stats) *stats = st_local;
-	return 0;
+	return map_reads_try({ eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, nullptr, nullptr });
 }
 
 // Several devices (reads shard, no exchange): the batch is cut into contiguous runs of reads balanced by bases, every engine
@@ -826,117 +979,22 @@ int mm2gb_map_reads_multi(mm2gb_engine_t *const *engines, int n_engines, const m
 	std::vector<mm2gb_map_stats_t> st((size_t)n_engines);
 	std::vector<int> rc((size_t)n_engines, 0);
 	std::vector<std::string> err((size_t)n_engines);
-	std::vector<std::thread> pool;
-	for (int e = 0; e < n_engines; ++e)
-		pool.emplace_back([&, e]() {
-			const int32_t from = cut[(size_t)e], n = cut[(size_t)e + 1] - from;
-			rc[(size_t)e] = mm2gb_map_reads(engines[e], ix, k, ref_names, ref_lens, n_ref, &opt, n, names + from, seqs + from, lens + from, &part[(size_t)e], &part_len[(size_t)e], &st[(size_t)e]);
-			if (rc[(size_t)e]) err[(size_t)e] = mm2gb_last_error();
-		});
-	for (auto &th : pool) th.join();
+	run_on_threads(n_engines, [&](int e) {
+		const int32_t from = cut[(size_t)e], n = cut[(size_t)e + 1] - from;
+		rc[(size_t)e] = mm2gb_map_reads(engines[e], ix, k, ref_names, ref_lens, n_ref, &opt, n, names + from, seqs + from, lens + from, &part[(size_t)e], &part_len[(size_t)e], &st[(size_t)e]);
+		if (rc[(size_t)e]) err[(size_t)e] = mm2gb_last_error();          // error text is per thread: carry it over
+	});
 	int bad = -1;
 	for (int e = 0; e < n_engines; ++e) if (rc[(size_t)e] && bad < 0) bad = e;
 	if (bad >= 0) { for (char *p : part) free(p); return fail("mm2gb_map_reads_multi: engine " + std::to_string(bad) + ": " + err[(size_t)bad]); }
-	int64_t all = 0;
-	for (int64_t l : part_len) all += l;
-	char *buf = (char*)malloc((size_t)all + 1);
-	if (!buf) { for (char *p : part) free(p); return fail("mm2gb_map_reads_multi: out of memory"); }
-	int64_t at = 0;
-	mm2gb_map_stats_t sum; memset(&sum, 0, sizeof sum);
-	for (int e = 0; e < n_engines; ++e) {
-		memcpy(buf + at, part[(size_t)e], (size_t)part_len[(size_t)e]); at += part_len[(size_t)e]; free(part[(size_t)e]);
-		const mm2gb_map_stats_t &q = st[(size_t)e];
-		sum.n_reads += q.n_reads; sum.n_mapped += q.n_mapped; sum.n_anchors += q.n_anchors; sum.n_chains += q.n_chains; sum.n_rechained += q.n_rechained; sum.n_rmq_tied += q.n_rmq_tied;
-		sum.s_seed = std::max(sum.s_seed, q.s_seed); sum.s_anchors = std::max(sum.s_anchors, q.s_anchors); sum.s_chain = std::max(sum.s_chain, q.s_chain);
-		sum.s_rechain = std::max(sum.s_rechain, q.s_rechain); sum.s_regs = std::max(sum.s_regs, q.s_regs); sum.s_post = std::max(sum.s_post, q.s_post);
-	}
-	buf[all] = 0;
-	*paf_out = buf; *paf_len = all;
-	if (stats) *stats = sum;
-	return 0;
-}
-
-// A run of any size as a stream of batches (role of the batch rotation of worker_for, map.c:924-1153: seed batch k+1 while batch k is
-// chained and batch k-1 is finished): the reads are cut into consecutive chunks of about chunk_bases bases, and every engine -- several
-// per device are the point: each has its own streams and arenas -- has a host thread that takes the next chunk and maps it from
-// seeding to PAF.  A chunk's stages alternate between host threads and the device, so with two or three engines on a GPU one chunk is
-// being seeded or post-processed while another one's kernels run; with engines on several GPUs the reads shard (SURVEY 8e: no
-// exchange).  The host threads of opt are shared out with over-subscription (2.5 x), because a chunk's threads idle while its kernels run.
-// PAF in read order; stats: counts summed, s_* = seconds of each stage SUMMED over chunks (they overlap: not wall time).
-static int stream_body(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
-                       int32_t n_ref, const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
-                       int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, const mm2gb_map_aln_t *aln, double *s_extra)
-{
-	if (!engines || n_engines < 1 || !ix || !opt_in || !paf_out || !paf_len || n_reads < 0 || (n_reads > 0 && (!lens || !names || !seqs)) || (n_ref > 0 && (!ref_names || !ref_lens)))
-		return fail("mm2gb_map_reads_stream: null argument");
-	for (int e = 0; e < n_engines; ++e) if (!engines[e]) return fail("mm2gb_map_reads_stream: null engine");
-	*paf_out = nullptr; *paf_len = 0;
-	if (chunk_bases <= 0) chunk_bases = 96 * 1000 * 1000;
-	std::vector<int32_t> cut(1, 0);
-	{ int64_t acc = 0; for (int32_t r = 0; r < n_reads; ++r) { acc += lens[r]; if (acc >= chunk_bases && r + 1 < n_reads) { cut.push_back(r + 1); acc = 0; } } }
-	cut.push_back(n_reads);
-	const size_t n_chunks = cut.size() - 1;
-	mm2gb_map_opt_t opt = *opt_in;
-	const int all_threads = opt_in->host_threads > 0 ? opt_in->host_threads : std::min(32, usable_cpus());
-	const int workers = (int)std::min<size_t>((size_t)n_engines, std::max<size_t>(1, n_chunks));
-	// host threads of all workers together, in % of opt's (MM2GB_STREAM_THREADS_PCT): a chunk's threads idle while its kernels run, and the reads its
-	// re-chaining gives to host threads want a core each when they come.  1.05 Gbp, four engines, 16 threads: 100 % 8.0 s, 150 % 6.8-7.1, 250 % 6.3-6.5, 400 % 6.6-6.9
-	int oversub_pct = 250;
-	if (const char *v = getenv("MM2GB_STREAM_THREADS_PCT")) oversub_pct = std::max(25, atoi(v));
-	opt.host_threads = std::max(1, workers == 1 ? all_threads : (all_threads * oversub_pct / 100 + workers - 1) / workers);
-	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);     // once, not per chunk
-	std::vector<char*> part(n_chunks, nullptr);
-	std::vector<int64_t> part_len(n_chunks, 0);
-	std::vector<mm2gb_map_stats_t> st(n_chunks);
-	std::vector<double> extra(n_chunks * 3, 0.0);         // with an alignment: seconds for align, the steps after it, text, per chunk
-	std::atomic<size_t> next(0);
-	std::atomic<int> failed(0);
-	std::string why;
-	std::mutex why_lock;
-	auto work = [&](int e) {
-		for (;;) {
-			const size_t c = next.fetch_add(1);
-			if (c >= n_chunks || failed.load()) break;
-			const int32_t from = cut[c], n = cut[c + 1] - from;
-			memset(&st[c], 0, sizeof(st[c]));
-			if (map_reads_try(engines[e], ix, k, ref_names, ref_lens, n_ref, &opt, n, names + from, seqs + from, lens + from, &part[c], &part_len[c], &st[c], aln, &extra[c * 3])) {
-				std::lock_guard<std::mutex> g(why_lock);
-				if (!failed.exchange(1)) why = "chunk " + std::to_string(c) + " on engine " + std::to_string(e) + ": " + mm2gb_last_error();
-			}
-		}
-	};
-	{
-		std::vector<std::thread> pool;
-		for (int e = 1; e < workers; ++e) pool.emplace_back(work, e);
-		work(0);
-		for (auto &th : pool) th.join();
-	}
-	if (failed.load()) { for (char *p : part) free(p); return fail("mm2gb_map_reads_stream: " + why); }
-	int64_t all = 0;
-	for (int64_t l : part_len) all += l;
-	char *buf = (char*)malloc((size_t)all + 1);
-	if (!buf) { for (char *p : part) free(p); return fail("mm2gb_map_reads_stream: out of memory"); }
-	int64_t at = 0;
-	mm2gb_map_stats_t sum; memset(&sum, 0, sizeof sum);
-	for (size_t c = 0; c < n_chunks; ++c) {
-		if (part_len[c]) memcpy(buf + at, part[c], (size_t)part_len[c]);
-		at += part_len[c]; free(part[c]);
-		const mm2gb_map_stats_t &q = st[c];
-		sum.n_reads += q.n_reads; sum.n_mapped += q.n_mapped; sum.n_anchors += q.n_anchors; sum.n_chains += q.n_chains; sum.n_rechained += q.n_rechained; sum.n_rmq_tied += q.n_rmq_tied;
-		sum.s_seed += q.s_seed; sum.s_anchors += q.s_anchors; sum.s_chain += q.s_chain; sum.s_rechain += q.s_rechain; sum.s_regs += q.s_regs; sum.s_post += q.s_post;
-		if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] += extra[c * 3 + (size_t)i];
-	}
-	buf[all] = 0;
-	*paf_out = buf; *paf_len = all;
-	if (stats) *stats = sum;
-	return 0;
+	return join_parts("mm2gb_map_reads_multi", part, part_len, st, false, paf_out, paf_len, stats);
 }
 
 int mm2gb_map_reads_stream(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
                            int32_t n_ref, const mm2gb_map_opt_t *opt_in, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                            int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats)
 {
-	return stream_body(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, nullptr, nullptr);
+	return stream_body(engines, n_engines, chunk_bases, { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, nullptr, nullptr });
 }
 
 int mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
@@ -945,7 +1003,7 @@ int mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, co
 {
 	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_stream_aln: ") + why);
 	double s3[3] = { 0, 0, 0 };
-	const int rc = stream_body(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, aln, s3);
+	const int rc = stream_body(engines, n_engines, chunk_bases, { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 });
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
 }

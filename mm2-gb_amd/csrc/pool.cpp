@@ -5,7 +5,6 @@
 // Both run the host post-pass (host_chain.cpp) on reads as soon as the slice that holds them is back from the device, while
 // later slices are still being copied and scored, so the devices and the host threads work at the same time.
 // Replaces plchain_cal_score_async + plchain_post_gpu_helper for callers that own whole batches (plchain.cu:201-464).
-#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -18,6 +17,7 @@
 #include <vector>
 #include <sys/mman.h>
 #include "engine.h"
+#include "host_threads.h"
 #include "host_chain.h"
 
 struct mm2gb_pool {
@@ -127,7 +127,7 @@ int score_on_engines(const std::vector<mm2gb_engine_t*> &engines, int64_t n_read
 		if (rc[d]) err[d] = mm2gb_last_error();          // the error text is per thread: carry it to the caller's
 	};
 	if (n_dev == 1) run(0);
-	else {
+	else {                                                // (every device's thread is spawned, none is the caller: run() pins the thread it is on for good)
 		std::vector<std::thread> th;
 		for (int d = 0; d < n_dev; ++d) th.emplace_back(run, d);
 		for (auto &t : th) t.join();
@@ -147,15 +147,6 @@ struct PostSlab {
 	std::vector<int32_t> idx;
 };
 struct ReadChains { int32_t slab = 0, n_u = 0; int64_t n_kept = 0; size_t u_at = 0, idx_at = 0; };
-
-template <typename F>
-void on_threads(int n_threads, F fn)
-{
-	if (n_threads <= 1) { fn(0); return; }
-	std::vector<std::thread> th;
-	for (int t = 0; t < n_threads; ++t) th.emplace_back(fn, t);
-	for (auto &t : th) t.join();
-}
 
 int chain_on_engines(const std::vector<mm2gb_engine_t*> &engines, int64_t n_reads, const int64_t *offsets, const mm2gb_anchor_t *anchors,
                      int n_threads, mm2gb_chains_t *out, mm2gb_stats_t *stats)
@@ -208,22 +199,15 @@ int chain_on_engines(const std::vector<mm2gb_engine_t*> &engines, int64_t n_read
 	}
 	out->u = (uint64_t*)malloc((size_t)(out->u_off[n_reads] + 1) * 8);
 	out->a = (mm2gb_anchor_t*)result_alloc((size_t)(out->a_off[n_reads] + 1) * 16);   // (huge pages if it is large)
-	std::atomic<int64_t> next(0);
-	on_threads(n_reads < 128 ? 1 : n_threads, [&](int) {
-		for (;;) {
-			const int64_t r0 = next.fetch_add(16), r1 = std::min(n_reads, r0 + 16);
-			if (r0 >= n_reads) break;
-			for (int64_t r = r0; r < r1; ++r) {
-				const ReadChains &rc = of[(size_t)r];
-				if (rc.n_u == 0) continue;
-				const PostSlab &slab = slabs[(size_t)rc.slab];
-				memcpy(out->u + out->u_off[r], slab.u.data() + rc.u_at, (size_t)rc.n_u * 8);
-				const mm2gb_anchor_t *src = anchors + offsets[r];
-				const int32_t *idx = slab.idx.data() + rc.idx_at;
-				mm2gb_anchor_t *dst = out->a + out->a_off[r];
-				for (int64_t j = 0; j < rc.n_kept; ++j) dst[j] = src[idx[j]];
-			}
-		}
+	for_each_on_threads((size_t)n_reads, n_reads < 128 ? 1 : n_threads, 16, [&](size_t r) {
+		const ReadChains &rc = of[r];
+		if (rc.n_u == 0) return;
+		const PostSlab &slab = slabs[(size_t)rc.slab];
+		memcpy(out->u + out->u_off[r], slab.u.data() + rc.u_at, (size_t)rc.n_u * 8);
+		const mm2gb_anchor_t *src = anchors + offsets[r];
+		const int32_t *idx = slab.idx.data() + rc.idx_at;
+		mm2gb_anchor_t *dst = out->a + out->a_off[r];
+		for (int64_t j = 0; j < rc.n_kept; ++j) dst[j] = src[idx[j]];
 	});
 	if (dbg) fprintf(stderr, "[mm2gb chain_host] scores back %.1f ms | post-pass done %.1f ms | chains gathered %.1f ms (%lld chains, %lld anchors kept)\n",
 	                 t_scored, t_post, since(), (long long)out->u_off[n_reads], (long long)out->a_off[n_reads]);

@@ -13,12 +13,11 @@
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include "engine.h"
+#include "host_threads.h"
 #include "rechain_ahead.h"
 
 namespace mm2gb {
@@ -26,16 +25,6 @@ namespace mm2gb {
 namespace {
 constexpr int64_t F_SPLICE = 0x080, F_NO_LJOIN = 0x400, F_SR = 0x1000;   // minimap.h:15,18,20
 
-template <class F>
-void for_reads(size_t n, int nt, F &&fn)
-{
-	std::atomic<size_t> next(0);
-	auto work = [&]() { for (;;) { const size_t k = next.fetch_add(1); if (k >= n) break; fn(k); } };
-	std::vector<std::thread> pool;
-	for (int t = 1; t < std::max(1, std::min<int>(nt, (int)n)); ++t) pool.emplace_back(work);
-	work();
-	for (auto &th : pool) th.join();
-}
 double seconds_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); }
 } // namespace
 
@@ -83,7 +72,7 @@ int rechain_ahead(mm2gb_engine_t *eng, const mm2gb_mapopt_head_t &opt, const mm2
 	                             misc.chn_pen_gap, misc.chn_pen_skip };
 	const auto t1 = std::chrono::steady_clock::now();
 	try { out.sorted.resize((size_t)out.off.back()); } catch (const std::bad_alloc&) { out.clear(); return fail("rechain_ahead: out of host memory"); }
-	for_reads(picked.size(), n_threads, [&](size_t s) {
+	for_each_on_threads(picked.size(), n_threads, 1, [&](size_t s) {
 		const RechainRead &rd = reads[picked[s]];
 		mm2gb_anchor_t *dst = out.sorted.data() + out.off[s];
 		const size_t n = (size_t)(out.off[s + 1] - out.off[s]);

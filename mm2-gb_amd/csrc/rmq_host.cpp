@@ -17,9 +17,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "host_chain.h"
 
 namespace mm2gb {
@@ -665,7 +665,7 @@ static int rmq_chain_host_impl(const mm2gb_rmq_param_t *prm, int64_t n_reads, co
 	const char *force = getenv("MM2GB_RMQ_TREE");
 	const bool exact_only = reference_tree_only || (force && !strcmp(force, "avl"));   // MM2GB_RMQ_TREE=avl: the reference's tree for every read
 	std::atomic<long long> ties_met(0), ties_that_decide(0);
-	auto work = [&]() {
+	auto work = [&](int) {
 		FillScratch ws;
 		BacktrackScratch bs;
 		std::vector<int32_t> f, p;
@@ -686,9 +686,7 @@ static int rmq_chain_host_impl(const mm2gb_rmq_param_t *prm, int64_t n_reads, co
 		}
 		ties_met += ws.ties_met; ties_that_decide += ws.ties_that_decide;
 	};
-	const int nt = std::max(1, n_threads);
-	if (nt == 1) work();
-	else { std::vector<std::thread> pool; for (int t = 0; t < nt; ++t) pool.emplace_back(work); for (auto &th : pool) th.join(); }
+	run_on_threads(n_threads, work);
 	if (getenv("MM2GB_DEBUG_PHASES") && !exact_only) {
 		long long redone = 0;
 		if (n_tied) for (int64_t r = 0; r < n_reads; ++r) redone += n_tied[r];

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "host_chain.h"
 
 namespace mm2gb {
@@ -90,18 +91,6 @@ ReadCost estimate(const mm2gb_rmq_param_t &P, const mm2gb_anchor_t *a, int64_t n
 	return c;
 }
 
-// copies of read-sized pieces, dealt to threads (a batch's anchors are a gigabyte: one thread copies at ~5 GB/s)
-template <class F>
-void parallel_reads(size_t n, int nt, F &&fn)
-{
-	std::atomic<size_t> next(0);
-	auto work = [&]() { for (;;) { const size_t lo = next.fetch_add(64); if (lo >= n) break; for (size_t k = lo; k < std::min(n, lo + 64); ++k) fn(k); } };
-	std::vector<std::thread> pool;
-	for (int t = 1; t < std::max(1, std::min<int>(nt, (int)((n + 63) / 64))); ++t) pool.emplace_back(work);
-	work();
-	for (auto &th : pool) th.join();
-}
-
 void append(mm2gb_chains_t &dst, size_t r, const mm2gb_chains_t &src, size_t q)
 {
 	const int64_t nu = src.u_off[q + 1] - src.u_off[q], na = src.a_off[q + 1] - src.a_off[q];
@@ -129,14 +118,7 @@ int rmq_chain_impl(mm2gb_engine_t *eng, const mm2gb_rmq_param_t *prm, int64_t n_
 
 	// ---- the deal ----
 	std::vector<ReadCost> cost(R);
-	{
-		std::atomic<int64_t> next(0);
-		auto work = [&]() { for (;;) { const int64_t r = next.fetch_add(1); if (r >= n_reads) break; cost[(size_t)r] = estimate(*prm, anchors + offsets[r], offsets[r + 1] - offsets[r]); } };
-		std::vector<std::thread> pool;
-		for (int t = 1; t < std::min<int>(nt, (int)std::max<int64_t>(1, n_reads)); ++t) pool.emplace_back(work);
-		work();
-		for (auto &th : pool) th.join();
-	}
+	for_each_on_threads(R, nt, 1, [&](size_t r) { cost[r] = estimate(*prm, anchors + offsets[r], offsets[r + 1] - offsets[r]); });
 	// (a skip limit that can end an inner walk -- below the size cap, lchain.c:329-333 --: the one-anchor-per-step kernel, which keeps the counter)
 	const bool limited = [&] { const char *sk = getenv("MM2GB_RMQ_SKIP"); return !(sk && !strcmp(sk, "ignore")) && prm->max_chn_skip != INT32_MAX && !(prm->cap_rmq_size > 0 && prm->max_chn_skip >= prm->cap_rmq_size); }();
 	const bool steps_kernel = [&] { const char *kv = getenv("MM2GB_RMQ_KERNEL"); return limited || (kv && !strcmp(kv, "steps")); }();
@@ -205,7 +187,7 @@ int rmq_chain_impl(mm2gb_engine_t *eng, const mm2gb_rmq_param_t *prm, int64_t n_
 		off.assign(to - from + 1, 0);
 		for (size_t q = from; q < to; ++q) off[q - from + 1] = off[q - from] + (offsets[by_dev[q] + 1] - offsets[by_dev[q]]);
 		buf.resize((size_t)std::max<int64_t>(off.back(), 1));
-		parallel_reads(to - from, gather_threads, [&](size_t k) {
+		for_each_on_threads(to - from, gather_threads, 64, [&](size_t k) {
 			const int64_t r = by_dev[from + k], n = offsets[r + 1] - offsets[r];
 			if (n) memcpy(buf.data() + off[k], anchors + offsets[r], (size_t)n * sizeof(mm2gb_anchor_t));
 		});
@@ -343,7 +325,7 @@ int rmq_chain_impl(mm2gb_engine_t *eng, const mm2gb_rmq_param_t *prm, int64_t n_
 	out->u = (uint64_t*)malloc(((size_t)out->u_off[R] + 1) * 8);
 	out->a = (mm2gb_anchor_t*)result_alloc(((size_t)out->a_off[R] + 1) * 16);
 	if (!out->u || !out->a) { mm2gb_chains_free(out); return give_up("mm2gb_rmq_chain: out of memory"); }
-	parallel_reads(R, nt, [&](size_t r) {
+	for_each_on_threads(R, nt, 64, [&](size_t r) {
 		const mm2gb_chains_t &c = *src[r].c;
 		const size_t q = src[r].q;
 		const int64_t nu = c.u_off[q + 1] - c.u_off[q], na = c.a_off[q + 1] - c.a_off[q];

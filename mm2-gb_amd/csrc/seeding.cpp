@@ -12,14 +12,13 @@
 // The output of collect_matches is the input of mm2gb_collect_seeds_gpu.  One query segment per read (n_segs = 1).
 // Host code: an index look-up per minimizer is a pointer chase through a structure the size of the genome -- not a kernel.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 #include "host_chain.h"
 #include "index_dev.h"
 #include "kmer.h"
@@ -181,10 +180,7 @@ mm2gb_index_t *mm2gb_index_build_flag(int k, int w, int flag, int32_t n_seq, con
 	const bool hpc = (flag & MM2GB_I_HPC) != 0;
 	ix->lens.assign(lens, lens + n_seq);
 	std::vector<std::vector<Mini>> per((size_t)n_seq);
-	std::atomic<int32_t> next(0);
-	auto work = [&]() { for (;;) { const int32_t s = next.fetch_add(1); if (s >= n_seq) break; if (lens[s] > 0) sketch(seqs[s], lens[s], w, k, (uint32_t)s, hpc, per[(size_t)s]); } };
-	if (n_threads < 2) work();
-	else { std::vector<std::thread> pool; for (int t = 0; t < n_threads; ++t) pool.emplace_back(work); for (auto &th : pool) th.join(); }
+	for_each_on_threads((size_t)n_seq, n_threads, 1, [&](size_t s) { if (lens[s] > 0) sketch(seqs[s], lens[s], w, k, (uint32_t)s, hpc, per[s]); });
 	size_t total = 0;
 	for (auto &v : per) total += v.size();
 	std::vector<Mini> all;
@@ -427,54 +423,46 @@ int mm2gb_collect_seeds_host(int64_t opt_flag, int64_t n_reads, const int64_t *s
 	if (hit_off[n_seeds] > 0 && (!hits || !anchors)) return fail("mm2gb_collect_seeds_host: null buffer");
 	// every read writes at its hits' offset first (an upper bound of where it ends up), sorts there, and is moved down afterwards
 	std::vector<int64_t> kept((size_t)n_reads, 0);
-	std::atomic<int64_t> next(0);
-	auto work = [&]() {
-		for (;;) {
-			const int64_t r = next.fetch_add(1);
-			if (r >= n_reads) break;
-			mm2gb_anchor_t *out = anchors + hit_off[seed_off[r]];
-			int64_t n_a = 0;
-			for (int64_t k = seed_off[r]; k < seed_off[r + 1]; ++k) {
-				const mm2gb_seed_t &q = seeds[k];
-				const uint32_t q_span = q.span_flt & 0x7fffffffu, seg_id = q.seg_tandem & 0x7fffffffu;
-				for (int64_t h = hit_off[k]; h < hit_off[k + 1]; ++h) {
-					const uint64_t rr = hits[h];
-					const int32_t rpos = (int32_t)((uint32_t)rr >> 1);
-					const bool same_strand = (rr & 1) == (q.q_pos & 1);
-					bool skip = false, is_self = false;
-					if (names) {                                                                      // map.c:208-219
-						const int32_t rid = (int32_t)(rr >> 32);
-						if ((opt_flag & F_NO_DIAG) && q_rank[r] == ref_rank[rid] && ref_len[rid] == qlen[r]) {
-							if ((uint32_t)rr >> 1 == (q.q_pos >> 1)) skip = true;
-							else if (same_strand) is_self = true;
-						}
-						if (!skip && (opt_flag & F_NO_DUAL) && q_rank[r] > ref_rank[rid]) skip = true;
+	for_each_on_threads((size_t)n_reads, n_threads, 1, [&](size_t r) {
+		mm2gb_anchor_t *out = anchors + hit_off[seed_off[r]];
+		int64_t n_a = 0;
+		for (int64_t k = seed_off[r]; k < seed_off[r + 1]; ++k) {
+			const mm2gb_seed_t &q = seeds[k];
+			const uint32_t q_span = q.span_flt & 0x7fffffffu, seg_id = q.seg_tandem & 0x7fffffffu;
+			for (int64_t h = hit_off[k]; h < hit_off[k + 1]; ++h) {
+				const uint64_t rr = hits[h];
+				const int32_t rpos = (int32_t)((uint32_t)rr >> 1);
+				const bool same_strand = (rr & 1) == (q.q_pos & 1);
+				bool skip = false, is_self = false;
+				if (names) {                                                                      // map.c:208-219
+					const int32_t rid = (int32_t)(rr >> 32);
+					if ((opt_flag & F_NO_DIAG) && q_rank[r] == ref_rank[rid] && ref_len[rid] == qlen[r]) {
+						if ((uint32_t)rr >> 1 == (q.q_pos >> 1)) skip = true;
+						else if (same_strand) is_self = true;
 					}
-					if (!skip && (opt_flag & (F_FOR_ONLY | F_REV_ONLY))) skip = same_strand ? (opt_flag & F_REV_ONLY) != 0 : (opt_flag & F_FOR_ONLY) != 0;   // map.c:220-226
-					if (skip) continue;
-					mm2gb_anchor_t &p = out[n_a++];
-					if (same_strand) {                                                                // map.c:311-313
-						p.x = (rr & 0xffffffff00000000ULL) | (uint32_t)rpos;
-						p.y = (uint64_t)q_span << 32 | q.q_pos >> 1;
-					} else if (!(opt_flag & F_QSTRAND)) {                                             // map.c:314-316
-						p.x = 1ULL << 63 | (rr & 0xffffffff00000000ULL) | (uint32_t)rpos;
-						p.y = (uint64_t)q_span << 32 | (uint32_t)(qlen[r] - (int32_t)((q.q_pos >> 1) + 1 - q_span) - 1);
-					} else {                                                                          // map.c:317-321
-						p.x = 1ULL << 63 | (rr & 0xffffffff00000000ULL) | (uint32_t)(ref_len[rr >> 32] - (rpos + 1 - (int32_t)q_span) - 1);
-						p.y = (uint64_t)q_span << 32 | q.q_pos >> 1;
-					}
-					p.y |= (uint64_t)seg_id << 48;                                                     // MM_SEED_SEG_SHIFT
-					if (q.seg_tandem >> 31) p.y |= 1ULL << 42;                                         // MM_SEED_TANDEM
-					if (is_self) p.y |= 1ULL << 43;                                                    // MM_SEED_SELF
+					if (!skip && (opt_flag & F_NO_DUAL) && q_rank[r] > ref_rank[rid]) skip = true;
 				}
+				if (!skip && (opt_flag & (F_FOR_ONLY | F_REV_ONLY))) skip = same_strand ? (opt_flag & F_REV_ONLY) != 0 : (opt_flag & F_FOR_ONLY) != 0;   // map.c:220-226
+				if (skip) continue;
+				mm2gb_anchor_t &p = out[n_a++];
+				if (same_strand) {                                                                // map.c:311-313
+					p.x = (rr & 0xffffffff00000000ULL) | (uint32_t)rpos;
+					p.y = (uint64_t)q_span << 32 | q.q_pos >> 1;
+				} else if (!(opt_flag & F_QSTRAND)) {                                             // map.c:314-316
+					p.x = 1ULL << 63 | (rr & 0xffffffff00000000ULL) | (uint32_t)rpos;
+					p.y = (uint64_t)q_span << 32 | (uint32_t)(qlen[r] - (int32_t)((q.q_pos >> 1) + 1 - q_span) - 1);
+				} else {                                                                          // map.c:317-321
+					p.x = 1ULL << 63 | (rr & 0xffffffff00000000ULL) | (uint32_t)(ref_len[rr >> 32] - (rpos + 1 - (int32_t)q_span) - 1);
+					p.y = (uint64_t)q_span << 32 | q.q_pos >> 1;
+				}
+				p.y |= (uint64_t)seg_id << 48;                                                     // MM_SEED_SEG_SHIFT
+				if (q.seg_tandem >> 31) p.y |= 1ULL << 42;                                         // MM_SEED_TANDEM
+				if (is_self) p.y |= 1ULL << 43;                                                    // MM_SEED_SELF
 			}
-			sort_by_x_like_host(out, out + n_a);                                                       // map.c:329
-			kept[(size_t)r] = n_a;
 		}
-	};
-	const int nt = std::max(1, n_threads);
-	if (nt == 1) work();
-	else { std::vector<std::thread> pool; for (int t = 0; t < nt; ++t) pool.emplace_back(work); for (auto &th : pool) th.join(); }
+		sort_by_x_like_host(out, out + n_a);                                                       // map.c:329
+		kept[(size_t)r] = n_a;
+	});
 	for (int64_t r = 0; r < n_reads; ++r) {
 		anchor_off[r + 1] = anchor_off[r] + kept[(size_t)r];
 		const int64_t from = hit_off[seed_off[r]];

@@ -16,6 +16,7 @@
 #include <vector>
 #include "../../include/mm2gb_plutils.h"
 #include "engine.h"
+#include "host_threads.h"
 #include "host_chain.h"
 #include "rechain_ahead.h"
 #include "trace.h"
@@ -36,30 +37,6 @@ static_assert(sizeof(mm2gb_chain_read_t) == 312 && offsetof(mm2gb_chain_read_t, 
               offsetof(mm2gb_chain_read_t, u) == 296 && offsetof(mm2gb_chain_read_t, n_u) == 304, "chain_read_t layout");
 
 namespace mm2gb {
-
-// Run fn(r, scratch) for r in [0, n) on n_threads threads, dynamic dealing.
-template <typename F>
-static void parallel_reads(int64_t n, int n_threads, F fn)
-{
-	if (n_threads < 1) n_threads = 1;
-	if (n_threads == 1 || n < 2) {
-		BacktrackScratch ws;
-		for (int64_t r = 0; r < n; ++r) fn(r, ws);
-		return;
-	}
-	std::atomic<int64_t> next(0);
-	std::vector<std::thread> pool;
-	for (int t = 0; t < n_threads; ++t)
-		pool.emplace_back([&]() {
-			BacktrackScratch ws;
-			for (;;) {
-				const int64_t r = next.fetch_add(1);
-				if (r >= n) break;
-				fn(r, ws);
-			}
-		});
-	for (auto &th : pool) th.join();
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // drop-in boundary state: one slot per stream / host thread id
@@ -196,8 +173,11 @@ static int finish_compute(StreamSlot &slot, HostStage &st)
 		st.u_of.assign((size_t)n_read, nullptr); st.a_of.assign((size_t)n_read, nullptr); st.nu_of.assign((size_t)n_read, 0);
 		{
 			TraceRange post("mm2gb:backtrack_compact");
-			parallel_reads(n_read, g_streams.post_threads, [&](int64_t r, BacktrackScratch &ws) {
-				st.nu_of[r] = backtrack_compact(misc, reads[r].n, reads[r].a, f + off[r], p + off[r], libc_mem, ws, &st.u_of[r], &st.a_of[r]);
+			std::atomic<int> next(0);
+			run_on_threads(std::min(g_streams.post_threads, n_read), [&](int) {
+				BacktrackScratch ws;                              // a worker's own
+				for (int r; (r = next.fetch_add(1)) < n_read;)
+					st.nu_of[r] = backtrack_compact(misc, reads[r].n, reads[r].a, f + off[r], p + off[r], libc_mem, ws, &st.u_of[r], &st.a_of[r]);
 			});
 		}
 		st.ms_wait = t_wait - t0; st.ms_post = now_ms() - t_wait;
@@ -340,7 +320,7 @@ static int launch_stage(StreamSlot &slot, HostStage &st, mm2gb_chain_read_t *rea
 	// pack the reads' anchor arrays into the pinned staging buffer (MM2GB_POST_THREADS host threads)
 	{
 		TraceRange pack("mm2gb:pack_anchors");
-		parallel_reads(n_read, g_streams.post_threads, [&](int64_t r, BacktrackScratch &) {
+		for_each_on_threads((size_t)n_read, g_streams.post_threads, 1, [&](size_t r) {
 			const int64_t n = off[r + 1] - off[r];
 			if (n) memcpy(raw + off[r], reads[r].a, (size_t)n * 16);
 		});

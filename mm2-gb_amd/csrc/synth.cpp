@@ -7,12 +7,11 @@
 //                      chain's (rid, strand) and y inside a 6 kb window  (windows saturate max_iter when the block has > 5000)
 //   q_span = 15, seg_id = 0, sorted by x.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
 #include "engine.h"
+#include "host_threads.h"
 
 namespace mm2gb {
 namespace {
@@ -115,21 +114,7 @@ int mm2gb_synth_fill(uint64_t seed, int64_t first_read, int64_t n_reads, int len
                      mm2gb_anchor_t *anchors, int n_threads)
 {
 	if (n_reads < 0 || !offsets || (offsets[n_reads] > 0 && !anchors)) return fail("mm2gb_synth_fill: bad arguments");
-	if (n_threads < 1) n_threads = 1;
-	std::atomic<int64_t> next(0);
-	auto work = [&]() {
-		for (;;) {
-			const int64_t r = next.fetch_add(1);
-			if (r >= n_reads) break;
-			fill_read(seed, first_read + r, len_lo, len_hi, anchors + offsets[r], offsets[r + 1] - offsets[r]);
-		}
-	};
-	if (n_threads == 1) work();
-	else {
-		std::vector<std::thread> pool;
-		for (int t = 0; t < n_threads; ++t) pool.emplace_back(work);
-		for (auto &th : pool) th.join();
-	}
+	for_each_on_threads((size_t)n_reads, n_threads, 1, [&](size_t r) { fill_read(seed, first_read + (int64_t)r, len_lo, len_hi, anchors + offsets[r], offsets[r + 1] - offsets[r]); });
 	return 0;
 }
 
