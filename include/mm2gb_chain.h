@@ -95,6 +95,10 @@ int  mm2gb_engine_last_score_form(const mm2gb_engine_t *eng);
 /* measurement aid: groups of 64 targets that k_score's band pass (far predecessors by diagonal band; MM2GB_BAND, MM2GB_BAND_SLAB,
  * MM2GB_BAND_LAG when the engine is made) swept in the engine's calls since its stats were last reset: out[0] the wave path, out[1] the teams */
 int  mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out);
+/* measurement aid: the band pass's shape as the engine's score kernel is configured now: out[0] the slab (0: the band pass is off), out[1..4] the
+ * lag of the wave path, the 4-wave teams, the 8-wave teams and whole-workgroup teams (MM2GB_BAND_LAG_WAVE, _TEAM4, _TEAM8, _WG; MM2GB_BAND_LAG
+ * sets all four), out[5] the mean window, in anchors, above which a chunk takes the band pass */
+int  mm2gb_engine_band_shape(const mm2gb_engine_t *eng, int *out6);
 /* measurement aid: with MM2GB_SKIP_STATS=1 set when the engine was made, the skip-limited walk of its last micro-batch counts, and this waits for
  * the engine and gives: [0] walk rounds of 64 candidates, [1] rounds of the max_ii search, [2] targets, [3] the slowest chunk's time and [4] its
  * anchors, [5] the walk's span from the first chunk's start to the last chunk's end; times in ticks of the 100 MHz s_memrealtime clock */

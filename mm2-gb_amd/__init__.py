@@ -85,7 +85,7 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_batcher_create", "mm2gb_batcher_add", "mm2gb_batcher_feed", "mm2gb_batcher_flush", "mm2gb_batcher_stats", "mm2gb_batcher_destroy",
                 "mm2gb_plan_batches", "mm2gb_rmq_chain_gpu", "mm2gb_lchain_rmq", "mm2gb_lchain_rmq_counts",
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
-                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
+                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_engine_band_shape", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
                 "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free",
                 "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split",
                 "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag",
@@ -308,6 +308,14 @@ class Engine:
         out = (C.c_int64 * 2)()
         _check(lib().mm2gb_engine_band_groups(self._h, out))
         return int(out[0]), int(out[1])
+
+    def band_shape(self):
+        """The band pass's shape as configured: the slab (0: off), the lag of each path and the mean window above which a chunk takes it."""
+        L = lib()
+        L.mm2gb_engine_band_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        out = (C.c_int * 6)()
+        _check(L.mm2gb_engine_band_shape(self._h, out))
+        return dict(zip(("slab", "lag_wave", "lag_team4", "lag_team8", "lag_wg", "min_window"), (int(v) for v in out)))
 
     def skip_stats(self):
         """Counters of the skip-limited walk's last micro-batch (engine made with MM2GB_SKIP_STATS=1): rounds of 64 candidates, max_ii search

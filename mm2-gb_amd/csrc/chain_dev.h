@@ -13,10 +13,19 @@ struct DevParams {
 	int   lut_base;          // LDS byte address of the table's entry 0: LUT_LDS_TOTAL - 4 * (lut_last + 1), so that it ends where LDS ends
 	int   lut_clamp;         // 1: the sweeps clamp the table index to lut_last; 0: an index beyond it reads beyond LDS, i.e. 0 = reject
 	int   free_sweep;        // 1 (only without lut_clamp): source blocks whose every pair has bw < dr <= dq_lim - bw are swept without range test
-	int   band_slab;         // MODE_LUT without lut_clamp: predecessors older than band_lag anchors before a target's slab of band_slab anchors are swept by
-	int   band_lag;          // diagonal band (chain_kernels.hip, band_slab_part); 0 = off.  band_slab in {128, 256, 512}, band_lag a multiple of 64 <= band_slab
+	int   band_slab;         // MODE_LUT without lut_clamp: predecessors older than a lag before a target's slab of band_slab anchors are swept by
+	                         // diagonal band (chain_kernels.hip, band_slab_part); 0 = off.  band_slab in {128, 256, 512}
+	int   band_lag_wave;     // the lag of each path that runs a chunk, a multiple of 64 <= band_slab: a wave that owns the chunk (run_chunk_pairs: every
+	int   band_lag_team4;    // source before the slab is final when the slab begins, so it needs none), a 4-wave and an 8-wave pair team
+	int   band_lag_team8;    // (coop_chunk_pairs: the team's newest tiles are not final when a slab's band pass starts) and the whole workgroup
+	int   band_lag_wg;       // (coop_chunk)
+	int   band_min_window;   // a chunk takes the band pass only if its mean window is wider than this many anchors (band_chunk)
 	float gap, skip;
 };
+// The band pass's default shape (the engine's MM2GB_BAND_* knobs override it): the lag of each path, and the mean window, in
+// anchors, above which a chunk takes the band pass.
+constexpr int BAND_LAG_WAVE = 0, BAND_LAG_TEAM4 = 256, BAND_LAG_TEAM8 = 512, BAND_LAG_WG = 512;
+constexpr int BAND_MIN_WINDOW = 256;
 
 // bits of DevBatch::flags[0]
 enum : unsigned { FLAG_ANY_SEGID = 1u,     // some anchor carries a segment id -> MODE_GENERAL
@@ -77,6 +86,9 @@ struct DevBatch {
 	int32_t  *p;               // i - predecessor, 0 = none                            4 B
 	int32_t  *diag;            // x - y of each anchor, written by k_score when P.band_slab > 0 (the band pass reads 4 B per source)
 	int32_t  *band_res;        // two per anchor: the band pass's best score and predecessor (-1: none) for the target's later sweep
+	uint16_t *band_ord;        // teams: a slab's targets in band order (index within the slab), published once per slab by the wave that takes its part 0
+	int32_t  *band_hdr;        // ... and the slab's header, word s0 / 128: band_epoch << 2 | state (chain_kernels.hip, band_slab_publish)
+	int32_t   band_epoch;      // this launch's tag, 1 .. 2^30 - 1: what an earlier launch left in band_hdr never reads as published
 	// planner (per PLAN_BLOCK anchors)
 	int32_t  *blk_firstcut;    // smallest i in block with st[i] == i, INT32_MAX if none
 	int64_t  *blk_pairs;       // sum of window sizes in block

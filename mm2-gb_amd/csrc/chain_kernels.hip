@@ -1649,7 +1649,8 @@ __device__ __forceinline__ void sweep_a_into_b(const DevBatch &b, TilePair &t, i
 // ---- band pass: predecessors far behind a target by diagonal (MODE_LUT without lut_clamp; P.band_slab > 0) -------------------
 // A pair scores only if |dr - dq| <= bw, and dr - dq = d_i - d_j with d = x - y, the anchor's diagonal.  A tile of 64 consecutive
 // targets of a repeat block covers every diagonal, so the dense sweep cannot use that; a group of targets with similar diagonals can.
-// A chunk is cut into slabs of band_slab anchors.  For the targets of slab [s0, s0 + S) the sources older than jl = s0 - band_lag go
+// A chunk is cut into slabs of band_slab anchors.  For the targets of slab [s0, s0 + S) the sources older than jl = s0 - lag (the lag of
+// the path that runs the chunk: DevParams::band_lag_*) go
 // through this pass; those from jl on keep the dense sweep (sweep_pair_block, then the in-tile phase), started from jl.  The slab's
 // targets are dealt into groups of 64 by diagonal (band_slab_part); a group scans its sources [smallest window start, jl) in index
 // order, 64 at a time, reading 4 B per source (diag[], written as tiles are loaded), and stages those whose diagonal lies within
@@ -1667,6 +1668,7 @@ __device__ __forceinline__ int wave_min_i32(int v) { return -wave_max_i32_dpp(-v
 // compiler again that they are wave-uniform (v_readfirstlane).
 typedef const int __attribute__((address_space(1))) *glb_i32_cptr;
 typedef int __attribute__((address_space(1))) *glb_i32_ptr;
+typedef unsigned short __attribute__((address_space(1))) *glb_u16_ptr;
 typedef int4 __attribute__((address_space(3))) *lds_i32x4_ptr;
 // (the lane from the execution mask, all 64 lanes on: a called function that asked for threadIdx would make every caller keep the
 // launch's packed work-item ids in a register of their own for the whole kernel)
@@ -1798,16 +1800,107 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 	return lo < jl;
 }
 
-// Groups [g_from, g_to) of the slab [s0, min(s0 + band_slab, ce)) (at most 512 anchors): the targets sorted by (diagonal, index) -- a
-// bitonic sort of one key per target, eight per lane, element r * 64 + lane in register r --, group g = register g.  A slab whose
-// diagonals all lie within 2 bw is left in index order (a stretch of one chain: nothing to gain from the sort).
+// The order of a slab's targets [s0, s0 + n) (n <= 512): sorted by (diagonal, index) -- a bitonic sort of one key per target, eight per
+// lane, element r * 64 + lane in register r; the target's index within the slab is the key's low 9 bits, empty elements sort last.
+// A slab whose diagonals all lie within 2 bw is left in index order (a stretch of one chain: nothing to gain from the sort); one none of
+// whose windows reaches before jl has nothing to do.  The order depends on the inputs (raw, st) only, never on a score.
+enum { BAND_SLAB_SKIP = 1, BAND_SLAB_INDEX = 2, BAND_SLAB_SORTED = 3 };
+__device__ __forceinline__ int band_slab_order(const glb_i32_cptr raw, const glb_i32_cptr st, const int bw, const int s0, const int n, const int jl, const int lane, unsigned (&key)[8])
+{
+	constexpr int R = 8;
+	int lo = INT_MAX, hi = INT_MIN, st_lo = INT_MAX;                // first the diagonal x - y, read once; then the sort key made of it
+#pragma unroll
+	for (int r = 0; r < R; ++r) {
+		const int e = r * WAVE + lane;
+		const int d = e < n ? r_x(raw, s0 + e) - r_y(raw, s0 + e) : 0;
+		key[r] = (unsigned)d;
+		if (e < n) { lo = min(lo, d); hi = max(hi, d); st_lo = min(st_lo, st[s0 + e]); }
+	}
+	// no window of the slab reaches before jl: nothing to do (band_merge is skipped for tiles whose windows all start at jl or later)
+	if (wave_min_i32(st_lo) >= jl) return BAND_SLAB_SKIP;
+	const int dmin = wave_min_i32(lo), dmax = wave_max_i32_dpp(hi);
+	const unsigned range = (unsigned)(dmax - dmin);
+	if (range <= 2u * (unsigned)bw) {
+#pragma unroll
+		for (int r = 0; r < R; ++r) key[r] = r * WAVE + lane < n ? (unsigned)(r * WAVE + lane) : ~0u;
+		return BAND_SLAB_INDEX;
+	}
+	const int sh = (range >> 22) ? 32 - __clz((int)(range >> 22)) : 0;     // (diagonal - dmin) >> sh < 2^22: keys below 2^31
+#pragma unroll
+	for (int r = 0; r < R; ++r) {
+		const int e = r * WAVE + lane;
+		key[r] = e < n ? (((unsigned)((int)key[r] - dmin) >> sh) << 9) | (unsigned)e : ~0u;
+	}
+#pragma unroll
+	for (int k = 2; k <= R * WAVE; k <<= 1) {
+#pragma unroll
+		for (int j = k >> 1; j > 0; j >>= 1) {
+			if (j >= WAVE) {
+				const int jr = j / WAVE;
+#pragma unroll
+				for (int r = 0; r < R; ++r) {
+					if (r & jr) continue;
+					const bool up = ((r * WAVE) & k) == 0;              // (k > 64 here: the direction is the register's)
+					const unsigned a = key[r], c = key[r | jr];
+					key[r] = up ? min(a, c) : max(a, c);
+					key[r | jr] = up ? max(a, c) : min(a, c);
+				}
+			} else {
+#pragma unroll
+				for (int r = 0; r < R; ++r) {
+					const unsigned o = (unsigned)__shfl_xor((int)key[r], j);
+					const bool up = ((r * WAVE + lane) & k) == 0, lower = (lane & j) == 0;
+					key[r] = up == lower ? min(key[r], o) : max(key[r], o);
+				}
+			}
+		}
+	}
+	return BAND_SLAB_SORTED;
+}
+
+// Teams: ONE wave of the team orders a slab -- the one that takes its part 0 -- and publishes what it found for the others
+// (band_slab_part with `ord`): the targets' indices within the slab in band order, 2 B each, at ord[s0 + e] for element e < n (elements
+// from n on are the empty ones: they sort last, so nobody needs them), then the header word hdr[s0 / 128] = epoch << 2 | BAND_SLAB_*.
+// Slabs of one launch never share a word: two slabs of a chunk start at least 128 anchors apart, and a slab that takes the band pass
+// starts at least 128 anchors into its chunk, behind every slab of the chunk before.  The epoch is the launch's (DevBatch::band_epoch):
+// a word an earlier launch left -- the same batch scored again leaves the very same order -- is never taken for this launch's.
+// Called, not inlined, as band_slab_part.
+__device__ __noinline__ void band_slab_publish(const glb_i32_cptr raw_, const glb_i32_cptr st_, const glb_u16_ptr ord_, const glb_i32_ptr hdr_, const int epoch_,
+                                               const int bw_, const int band_slab_, const int s0_, const int ce_, const int jl_)
+{
+	constexpr int R = 8;
+	const glb_i32_cptr raw = uniform_glb(raw_), st = uniform_glb(st_);
+	const glb_u16_ptr ord = uniform_glb(ord_);
+	const glb_i32_ptr hdr = uniform_glb(hdr_);
+	const int s0 = first_lane(s0_), jl = first_lane(jl_);
+	const int n = min(first_lane(band_slab_), first_lane(ce_) - s0);
+	const int lane = lane_by_count();
+	unsigned key[R];
+	const int state = band_slab_order(raw, st, first_lane(bw_), s0, n, jl, lane, key);
+	if (state == BAND_SLAB_SORTED) {
+#pragma unroll
+		for (int r = 0; r < R; ++r) {
+			const int e = r * WAVE + lane;
+			if (e < n) ord[s0 + e] = (unsigned short)(key[r] & 511u);
+		}
+	}
+	// the order is out (stores go through to the L2, where the other parts read it) before the header says so
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+	if (lane == 0) __hip_atomic_store(hdr + (s0 >> 7), (int)(((unsigned)first_lane(epoch_) << 2) | (unsigned)state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Groups [g_from, g_to) of the slab [s0, min(s0 + band_slab, ce)) (at most 512 anchors), group g = elements [64 g, 64 g + 64) of the
+// slab's order (band_slab_order).  ord == null (the wave path): the order is made here, group g = register g.  Otherwise (teams) it is
+// read: the slab's header, and for a sorted slab this part's own elements of the published order.
 // Called, not inlined; every argument is wave-uniform, `stage` is the calling wave's LDS scratch.  Returns the groups that had sources
 // before jl (wave-uniform, in a vector register: the caller takes first_lane of it).
 __device__ __noinline__ int band_slab_part(const glb_i32_cptr raw_, const glb_i32_cptr st_, const glb_i32_cptr f_, const glb_i32_cptr diag_, const glb_i32_ptr res_,
+                                           const glb_u16_ptr ord_, const glb_i32_ptr hdr_, const int epoch_,
                                            const BandParams bp, const lds_i32x4_ptr stage_, const int s0_, const int ce_, const int jl_, const int g_from_, const int g_to_)
 {
 	constexpr int R = 8;
 	const BandIO b = { uniform_glb(raw_), uniform_glb(st_), uniform_glb(f_), uniform_glb(diag_), uniform_glb(res_) };
+	const glb_u16_ptr ord = uniform_glb(ord_);
 	DevParams P = {};                                               // the fields the sweeps read (never lut_clamp's: the band pass runs without it)
 	P.bw = first_lane(bp.bw); P.dq_lim = first_lane(bp.dq_lim); P.lut_base = first_lane(bp.lut_base); P.free_sweep = first_lane(bp.free_sweep);
 	// (an LDS pointer cast to a plain one inside the function: the compiler follows it to the accesses, which stay LDS ones)
@@ -1815,71 +1908,59 @@ __device__ __noinline__ int band_slab_part(const glb_i32_cptr raw_, const glb_i3
 	const int s0 = first_lane(s0_), jl = first_lane(jl_), g_from = first_lane(g_from_), g_to = first_lane(g_to_);
 	const int n = min(first_lane(bp.band_slab), first_lane(ce_) - s0);
 	const int lane = lane_by_count();
-	unsigned key[R];                                                // first the diagonal x - y, read once; then the sort key made of it
-	int lo = INT_MAX, hi = INT_MIN, st_lo = INT_MAX;
-#pragma unroll
-	for (int r = 0; r < R; ++r) {
-		const int e = r * WAVE + lane;
-		const int d = e < n ? r_x(b.raw, s0 + e) - r_y(b.raw, s0 + e) : 0;
-		key[r] = (unsigned)d;
-		if (e < n) { lo = min(lo, d); hi = max(hi, d); st_lo = min(st_lo, b.st[s0 + e]); }
-	}
-	// no window of the slab reaches before jl: nothing to do (band_merge is skipped for tiles whose windows all start at jl or later)
-	if (wave_min_i32(st_lo) >= jl) return 0;
-	const int dmin = wave_min_i32(lo), dmax = wave_max_i32_dpp(hi);
-	const unsigned range = (unsigned)(dmax - dmin);
-	if (range <= 2u * (unsigned)P.bw) {
-#pragma unroll
-		for (int r = 0; r < R; ++r) key[r] = r * WAVE + lane < n ? (unsigned)(r * WAVE + lane) : ~0u;
-	} else {
-		const int sh = (range >> 22) ? 32 - __clz((int)(range >> 22)) : 0;     // (diagonal - dmin) >> sh < 2^22: keys below 2^31
-#pragma unroll
-		for (int r = 0; r < R; ++r) {
-			const int e = r * WAVE + lane;
-			key[r] = e < n ? (((unsigned)((int)key[r] - dmin) >> sh) << 9) | (unsigned)e : ~0u;
+	unsigned key[R];
+	int state;
+	if (ord) {
+		// Wait for the slab's header.  No deadlock: the wave that publishes it is the one that takes the slab's first pair (or tile), a
+		// resident wave of this workgroup, and it publishes BEFORE it waits for any score of the slab's band (the order needs inputs
+		// only).  What it does wait for before it gets there belongs to tiles before the slab's first -- its own previous turn and what
+		// that turn needed -- and every wave that can be waiting here has finished its own turn before this slab's: waits only ever
+		// point to earlier tiles of the chunk.  (A plain while loop: the band pass has no persistent loop headed by an atomic.)
+		const glb_i32_ptr hw = uniform_glb(hdr_) + (s0 >> 7);
+		const unsigned epoch = (unsigned)first_lane(epoch_);
+		unsigned h = (unsigned)first_lane(__hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+		while ((h >> 2) != epoch) {
+			__builtin_amdgcn_s_sleep(4);
+			h = (unsigned)first_lane(__hip_atomic_load(hw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 		}
+		// (the order is read after the header, and past the CU's cache as the header was: the publisher's stores were out before it)
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		state = (int)(h & 3u);
 #pragma unroll
-		for (int k = 2; k <= R * WAVE; k <<= 1) {
-#pragma unroll
-			for (int j = k >> 1; j > 0; j >>= 1) {
-				if (j >= WAVE) {
-					const int jr = j / WAVE;
-#pragma unroll
-					for (int r = 0; r < R; ++r) {
-						if (r & jr) continue;
-						const bool up = ((r * WAVE) & k) == 0;              // (k > 64 here: the direction is the register's)
-						const unsigned a = key[r], c = key[r | jr];
-						key[r] = up ? min(a, c) : max(a, c);
-						key[r | jr] = up ? max(a, c) : min(a, c);
-					}
-				} else {
-#pragma unroll
-					for (int r = 0; r < R; ++r) {
-						const unsigned o = (unsigned)__shfl_xor((int)key[r], j);
-						const bool up = ((r * WAVE + lane) & k) == 0, lower = (lane & j) == 0;
-						key[r] = up == lower ? min(key[r], o) : max(key[r], o);
-					}
-				}
-			}
-		}
-	}
+		for (int r = 0; r < R; ++r) key[r] = 0;
+	} else state = band_slab_order(b.raw, b.st, P.bw, s0, n, jl, lane, key);
+	if (state == BAND_SLAB_SKIP) return 0;                          // (a team's part has loaded nothing but the header)
 	int swept = 0;                                                  // groups that had sources before jl (MM2GB counters CNT_BAND_*)
 	for (int g = g_from; g < g_to; ++g) {
-		unsigned kg = key[0];
+		int tgt;
+		if (ord) {
+			// element e of the order: empty from n on, the target's index within the slab otherwise -- e itself in an index-order slab
+			const int e = g * WAVE + lane;
+			tgt = -1;
+			if (e < n) tgt = s0 + (state == BAND_SLAB_SORTED ? (int)__hip_atomic_load(ord + s0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : e);
+		} else {
+			unsigned kg = key[0];
 #pragma unroll
-		for (int r = 1; r < R; ++r) kg = g == r ? key[r] : kg;
-		const int tgt = kg == ~0u ? -1 : s0 + (int)(kg & 511u);
-		if (__ballot(tgt >= 0) == 0) break;                         // (empty keys sort last)
+			for (int r = 1; r < R; ++r) kg = g == r ? key[r] : kg;
+			tgt = kg == ~0u ? -1 : s0 + (int)(kg & 511u);
+		}
+		if (__ballot(tgt >= 0) == 0) break;                         // (empty elements sort last)
 		swept += band_group(b, P, stage, tgt, jl);
 	}
 	return swept;
 }
-// The callers' side: the batch's arrays and the parameters by value, this wave's scratch as an LDS pointer.
-__device__ __forceinline__ int band_pass(const DevBatch &b, const DevParams &P, int4 *stage, const int s0, const int ce, const int jl, const int g_from, const int g_to)
+// The callers' side: the batch's arrays and the parameters by value, this wave's scratch as an LDS pointer.  shared: a team's part, which
+// reads the slab's published order (band_publish); the wave path orders its slabs itself.
+__device__ __forceinline__ int band_pass(const DevBatch &b, const DevParams &P, int4 *stage, const int s0, const int ce, const int jl, const int g_from, const int g_to, const bool shared)
 {
 	const BandParams bp = { P.bw, P.dq_lim, P.lut_base, P.free_sweep, P.band_slab };
 	return first_lane(band_slab_part((glb_i32_cptr)(const int*)b.raw, (glb_i32_cptr)b.st, (glb_i32_cptr)b.f, (glb_i32_cptr)b.diag, (glb_i32_ptr)b.band_res,
+	                                 shared ? (glb_u16_ptr)b.band_ord : (glb_u16_ptr)nullptr, (glb_i32_ptr)b.band_hdr, b.band_epoch,
 	                                 bp, (lds_i32x4_ptr)stage, s0, ce, jl, g_from, g_to));
+}
+__device__ __forceinline__ void band_publish(const DevBatch &b, const DevParams &P, const int s0, const int ce, const int jl)
+{
+	band_slab_publish((glb_i32_cptr)(const int*)b.raw, (glb_i32_cptr)b.st, (glb_u16_ptr)b.band_ord, (glb_i32_ptr)b.band_hdr, b.band_epoch, P.bw, P.band_slab, s0, ce, jl);
 }
 // A team's wave waits, before a tile's in-tile phase, for every band part of the tile's slab, and a slab's parts are taken by the
 // waves that own its tiles (or pairs).  That is deadlock-free only while those are distinct waves of the team: parts per slab <= team size.
@@ -1889,13 +1970,14 @@ __device__ __forceinline__ bool band_fits_team(const DevParams &P, const int anc
 {
 	return P.band_slab > 0 && P.band_slab / anchors_per_part <= n_waves;
 }
-// Whether a chunk takes the band pass at all: only if its mean window (planner cost = sum of windows + 16 per anchor) is wider than half
-// the lag.  Chunks of narrow windows -- short reads, chain-only stretches -- would pay the diagonals' stores and a look at every slab
-// for sources that are almost never older than the lag.  (Speed only: the results are the same either way.)
+// Whether a chunk takes the band pass at all: only if its mean window (planner cost = sum of windows + 16 per anchor) is wider than
+// band_min_window anchors (256) -- a number of its own, not a path's lag: a lag of 0 must not send every chunk here.  Chunks of narrow
+// windows -- short reads, chain-only stretches -- would pay the diagonals' stores and a look at every slab for sources that are
+// almost never old enough.  (Speed only: the results are the same either way.)
 __device__ __forceinline__ bool band_chunk(const DevBatch &b, const DevParams &P, const int ci, const int cs, const int ce)
 {
 	const long long len = ce - cs;
-	return P.band_slab > 0 && b.band_res && 2 * (b.chunk_cost[ci] - 16 * len) > (long long)P.band_lag * len;
+	return P.band_slab > 0 && b.band_res && b.chunk_cost[ci] - 16 * len > (long long)P.band_min_window * len;
 }
 
 // The band pass's result for the 64 targets from i0 merged into the dense sweep's (threshold form, both): the band's sources are all
@@ -1927,11 +2009,13 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 	int band_groups = 0;
 	for (int i0 = cs; i0 < ce; i0 += 2 * WAVE) {
 		// band pass (band_slab_part): the whole slab at its first pair; the dense sweep starts at jl.  A call: it comes before the pair
-		// is loaded, so that no tile state is live across it (the pair's diagonals are for the band passes of LATER slabs)
-		const int s0 = band ? i0 - (i0 - cs) % P.band_slab : cs, jl = s0 - P.band_lag;
+		// is loaded, so that no tile state is live across it (the pair's diagonals are for the band passes of LATER slabs).  This wave
+		// owns the chunk: every source before s0 is final here, so its lag (band_lag_wave) may be 0 -- the dense sweep then covers
+		// only the slab's own anchors
+		const int s0 = band ? i0 - (i0 - cs) % P.band_slab : cs, jl = s0 - P.band_lag_wave;
 		const bool in_band = band && jl > cs;
 		if (in_band && i0 == s0) {
-			band_groups += band_pass(b, P, stage, s0, ce, jl, 0, P.band_slab / WAVE);
+			band_groups += band_pass(b, P, stage, s0, ce, jl, 0, P.band_slab / WAVE, false);
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // (band_merge reads the results past the CU's cache)
 		}
 		TilePair t = load_pair(b, i0, ce);
@@ -2044,19 +2128,21 @@ __device__ __forceinline__ void coop_chunk(const DevBatch &b, const DevParams &P
 	};
 	// band pass (MODE_LUT; band_slab_part, coop_chunk_pairs): the tiles of a slab take one group each
 	const bool band = MODE == MODE_LUT && band_on && band_fits_team(P, WAVE, n_waves);
-	const int tps = band ? P.band_slab / WAVE : 1, s_first = band ? P.band_lag / P.band_slab + 1 : 0;
+	const int lag = P.band_lag_wg;                                   // (MODE_LUT comes here only as the whole workgroup)
+	const int tps = band ? P.band_slab / WAVE : 1, s_first = band ? lag / P.band_slab + 1 : 0;
 	int band_groups = 0;
 	for (int t = wave; t < n_tiles; t += n_waves) {
 		const int i0 = cs + t * WAVE;
-		const int sl = t / tps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
+		const int sl = t / tps, s0 = cs + sl * P.band_slab, jl = s0 - lag;
 		const bool in_band = band && jl > cs;
 		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
 		// (the band pass is a call: it comes before the tile is loaded, so that no tile state is live across it; the tile's diagonals only have
 		// to be out before the tile is published)
 		if (in_band) {
 			const int part = t - sl * tps;
+			if (part == 0) band_publish(b, P, s0, ce, jl);             // the slab's order, once for all its parts: before the wait, it needs no score
 			wait_done((jl - cs) / WAVE);                               // the band's sources are final
-			band_groups += band_pass(b, P, stage, s0, ce, jl, part, part + 1);
+			band_groups += band_pass(b, P, stage, s0, ce, jl, part, part + 1, true);
 			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 		}
 		const Target T = load_target(b, i0, ce, TRACK);
@@ -2137,19 +2223,21 @@ __device__ __forceinline__ void coop_chunk_pairs(const DevBatch &b, const DevPar
 	// result once every part of its slab has been published.  Parts of slab s may be in flight with those of slab s + 1 (a band pass
 	// waits only for the slabs before jl), never with those of s + 2: they are counted per parity of the slab (sh->part, sh->band)
 	const bool band = band_on && band_fits_team(P, 2 * WAVE, n_waves);
-	const int pps = band ? P.band_slab / (2 * WAVE) : 1, n_pairs = (n_tiles + 1) / 2, s_first = band ? P.band_lag / P.band_slab + 1 : 0;
+	const int lag = n_waves == SMALL_TEAM ? P.band_lag_team4 : P.band_lag_team8;   // a small team has 512 anchors in flight, a big one 1024
+	const int pps = band ? P.band_slab / (2 * WAVE) : 1, n_pairs = (n_tiles + 1) / 2, s_first = band ? lag / P.band_slab + 1 : 0;
 	int band_groups = 0;
 	for (int pr = wave; 2 * pr < n_tiles; pr += n_waves) {
 		const int ta = 2 * pr, i0 = cs + ta * WAVE;              // tile A = tile ta of the chunk, tile B = ta + 1
-		const int sl = pr / pps, s0 = cs + sl * P.band_slab, jl = s0 - P.band_lag;
+		const int sl = pr / pps, s0 = cs + sl * P.band_slab, jl = s0 - lag;
 		const bool in_band = band && jl > cs;
 		int *band_cnt = sl & 1 ? &sh->band : &sh->part;
 		// (the band pass is a call: it comes before the pair is loaded, so that no tile state is live across it; the pair's diagonals only have
 		// to be out before tile A is published)
 		if (in_band) {
 			const int part = pr - sl * pps;
+			if (part == 0) band_publish(b, P, s0, ce, jl);             // the slab's order, once for all its parts: before the wait, it needs no score
 			wait_done((jl - cs) / WAVE);                               // the band's sources are final
-			band_groups += band_pass(b, P, stage, s0, ce, jl, 2 * part, 2 * part + 2);
+			band_groups += band_pass(b, P, stage, s0, ce, jl, 2 * part, 2 * part + 2, true);
 			if (lane == 0) __hip_atomic_fetch_add(band_cnt, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 		}
 		TilePair t = load_pair(b, i0, ce);

@@ -84,8 +84,12 @@ struct Engine {
 		DevBuf skip_mark;                     // k_skip_fill's marks (lchain.c:175 t[]): 4 B per anchor, allocated when first used
 		DevBuf skip_stats;                    // k_skip_fill's counters (SKIP_STAT_WORDS), only with MM2GB_SKIP_STATS=1
 		DevBuf band_diag, band_res;           // k_score's band pass (params.band_slab > 0): x - y per anchor 4 B, its result 8 B, allocated when first used
+		DevBuf band_ord, band_hdr;            // ... and what a team's slab publishes for its other parts: the targets' order 2 B per anchor, a header word per 128 anchors
+		void  *band_hdr_zeroed = nullptr;     // the band_hdr allocation that has been cleared (a grown one is a new, uninitialised buffer)
+		size_t band_hdr_zeroed_bytes = 0;
+		int    band_epoch = 0;                // the last launch's tag in the header words: a word of an earlier launch never reads as published
 		std::vector<DevBuf*> all() { return { &st, &blk_firstcut, &blk_pairs, &blk_clamped, &blk_wmax, &blk_read, &chunk_start, &chunk_end, &chunk_cost,
-		                                      &chunk_track, &order, &long_list, &mid_list, &chunk_pp, &chunk_kk, &chunk_blk, &tile_sums, &tile_base, &bins, &counters, &totals, &flags, &gang_slots, &skip_mark, &skip_stats, &band_diag, &band_res }; }
+		                                      &chunk_track, &order, &long_list, &mid_list, &chunk_pp, &chunk_kk, &chunk_blk, &tile_sums, &tile_base, &bins, &counters, &totals, &flags, &gang_slots, &skip_mark, &skip_stats, &band_diag, &band_res, &band_ord, &band_hdr }; }
 	};
 	WorkSet work[2];
 	DevBuf lut, dbg;

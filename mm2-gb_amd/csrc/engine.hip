@@ -262,7 +262,7 @@ static DevParams make_params(const mm2gb_misc_t &m)
 	P.max_iter = m.max_iter; P.n_seg = m.n_seg; P.is_cdna = m.is_cdna;
 	P.dq_lim = std::min(P.max_dist_x, P.max_dist_y);
 	P.lut_last = P.bw + 1; P.lut_base = LUT_LDS_TOTAL - 4 * (P.lut_last + 1); P.lut_clamp = 1; P.free_sweep = 0;
-	P.band_slab = 0; P.band_lag = 0;
+	P.band_slab = 0; P.band_lag_wave = P.band_lag_team4 = P.band_lag_team8 = P.band_lag_wg = 0; P.band_min_window = 0;
 	P.gap = m.chn_pen_gap; P.skip = m.chn_pen_skip;
 	return P;
 }
@@ -347,21 +347,33 @@ int Engine::configure_score()
 	// beyond a workgroup's LDS (probed in init) the index is not clamped -- a distance beyond bw is an address beyond LDS -- and source
 	// blocks far enough inside a window are swept without any range test (MM2GB_FREE_SWEEP=0 turns that off, for A/B runs).
 	params.lut_last = params.bw + 1; params.lut_base = LUT_LDS_TOTAL - 4 * (params.lut_last + 1); params.lut_clamp = 1; params.free_sweep = 0;
-	params.band_slab = 0; params.band_lag = 0;
+	params.band_slab = 0; params.band_lag_wave = params.band_lag_team4 = params.band_lag_team8 = params.band_lag_wg = 0; params.band_min_window = 0;
 	if (launch.host_mode == SCORE_MODE_LUT && lds_contract_ok && !getenv("MM2GB_LUT_CLAMP")) {
 		params.lut_clamp = 0;
 		const char *v = getenv("MM2GB_FREE_SWEEP");
 		params.free_sweep = !(v && atoi(v) == 0) && params.dq_lim > 2 * params.bw;
 		// sources older than a lag before the target's slab by diagonal band (chain_kernels.hip, band_slab_part): MM2GB_BAND=0 gives the
-		// dense sweep of every window (same results), MM2GB_BAND_SLAB (128, 256, 512) and MM2GB_BAND_LAG (a multiple of 64, at most the slab) the shape
+		// dense sweep of every window (same results), MM2GB_BAND_SLAB (128, 256, 512) the slab.  The lag, a multiple of 64 and at most the
+		// slab, is one per path: MM2GB_BAND_LAG_WAVE, _TEAM4, _TEAM8 and _WG set one each, MM2GB_BAND_LAG sets all four and, as it always
+		// did, the mean window from which a chunk takes the band pass to half of itself (the tests force the band pass at small shapes
+		// with it); without it that window is BAND_MIN_WINDOW whatever the lags are
 		const char *bv = getenv("MM2GB_BAND");
 		if (!(bv && atoi(bv) == 0)) {
-			int slab = 512, lag = 512;
+			int slab = 512;
 			if (const char *e = getenv("MM2GB_BAND_SLAB")) slab = atoi(e);
 			if (slab != 128 && slab != 256 && slab != 512) slab = 512;
-			if (const char *e = getenv("MM2GB_BAND_LAG")) lag = atoi(e);
-			lag = std::min(std::max(lag, 0) & ~63, slab);
-			params.band_slab = slab; params.band_lag = lag;
+			auto lag_of = [&](const char *knob, int dflt) {
+				int lag = dflt;
+				if (const char *e = getenv(knob)) lag = atoi(e);
+				if (const char *e = getenv("MM2GB_BAND_LAG")) lag = atoi(e);
+				return std::min(std::max(lag, 0) & ~63, slab);
+			};
+			params.band_slab = slab;
+			params.band_lag_wave = lag_of("MM2GB_BAND_LAG_WAVE", BAND_LAG_WAVE);
+			params.band_lag_team4 = lag_of("MM2GB_BAND_LAG_TEAM4", BAND_LAG_TEAM4);
+			params.band_lag_team8 = lag_of("MM2GB_BAND_LAG_TEAM8", BAND_LAG_TEAM8);
+			params.band_lag_wg = lag_of("MM2GB_BAND_LAG_WG", BAND_LAG_WG);
+			params.band_min_window = getenv("MM2GB_BAND_LAG") ? params.band_lag_wave / 2 : BAND_MIN_WINDOW;
 		}
 	}
 	(void)n_big;
@@ -576,7 +588,7 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 	b.raw = (const uint4*)d_anchors; b.offsets = d_offsets; b.n = n; b.n_reads = n_reads;
 	b.st = (int32_t*)st.ptr;
 	b.f = d_f; b.p = d_p;
-	b.diag = nullptr; b.band_res = nullptr;
+	b.diag = nullptr; b.band_res = nullptr; b.band_ord = nullptr; b.band_hdr = nullptr; b.band_epoch = 0;
 	b.blk_firstcut = (int32_t*)blk_firstcut.ptr; b.blk_pairs = (int64_t*)blk_pairs.ptr; b.blk_clamped = (int32_t*)blk_clamped.ptr; b.blk_wmax = (int32_t*)blk_wmax.ptr; b.blk_read = (int32_t*)blk_read.ptr;
 	b.n_blocks = (n + PLAN_BLOCK - 1) / PLAN_BLOCK;
 	b.chunk_start = (int32_t*)chunk_start.ptr; b.chunk_end = (int32_t*)chunk_end.ptr; b.chunk_cost = (int64_t*)chunk_cost.ptr;
@@ -618,6 +630,14 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 		if (params.band_slab > 0 && launch.host_mode == SCORE_MODE_LUT) {
 			if (w.band_diag.ensure((size_t)n * sizeof(int32_t)) || w.band_res.ensure((size_t)n * 2 * sizeof(int32_t))) return -1;
 			b.diag = (int32_t*)w.band_diag.ptr; b.band_res = (int32_t*)w.band_res.ptr;
+			// what a team's slab publishes for its other parts: the order 2 B per anchor and a header word per 128 anchors, tagged with the
+			// launch's epoch -- cleared only when the buffer is new or the epoch wraps, so a word of an earlier launch is never "published"
+			if (w.band_ord.ensure((size_t)n * sizeof(uint16_t)) || w.band_hdr.ensure(((size_t)n / 128 + 2) * sizeof(int32_t))) return -1;
+			if (w.band_hdr_zeroed != w.band_hdr.ptr || w.band_hdr_zeroed_bytes != w.band_hdr.bytes || w.band_epoch >= (1 << 30) - 1) {
+				MM2GB_HIP(hipMemsetAsync(w.band_hdr.ptr, 0, w.band_hdr.bytes, stream));
+				w.band_hdr_zeroed = w.band_hdr.ptr; w.band_hdr_zeroed_bytes = w.band_hdr.bytes; w.band_epoch = 0;
+			}
+			b.band_ord = (uint16_t*)w.band_ord.ptr; b.band_hdr = (int32_t*)w.band_hdr.ptr; b.band_epoch = ++w.band_epoch;
 		}
 		launch_score(b, params, cfg_now, stream);
 	}
@@ -1443,6 +1463,13 @@ int mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out)
 {
 	if (!eng || !out) return fail("mm2gb_engine_band_groups: null argument");
 	out[0] = eng->e.last_band_groups[0]; out[1] = eng->e.last_band_groups[1];
+	return 0;
+}
+int mm2gb_engine_band_shape(const mm2gb_engine_t *eng, int *out)
+{
+	if (!eng || !out) return fail("mm2gb_engine_band_shape: null argument");
+	const DevParams &P = eng->e.params;
+	out[0] = P.band_slab; out[1] = P.band_lag_wave; out[2] = P.band_lag_team4; out[3] = P.band_lag_team8; out[4] = P.band_lag_wg; out[5] = P.band_min_window;
 	return 0;
 }
 int mm2gb_engine_skip_stats(mm2gb_engine_t *eng, int64_t *out)
