@@ -480,6 +480,27 @@ int  mm2gb_ksw_extd2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, in
  * kernel time, [0] fill + backtrack, [1] CIGAR packing */
 int  mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2);
 
+/* ---- splice-aware DP, batched: ksw2's ksw_exts2_sse (ksw2_exts2_sse.c), the alignment of a cDNA / RNA read's stretches across
+ *      introns -- one short gap (q, e), one long gap on the target side only (q2, no extension cost) that opens at donor[] and closes at
+ *      acceptor[] -- field for field and CIGAR word for CIGAR word.  Jobs and results are those of the extd2 calls above; the reference's
+ *      function has no band and no end bonus, so a job's w and end_bonus are NOT read, and reach_end is always 0.  Words may carry
+ *      operation 3 (N).  flag: the seven bits above plus the three below; any other bit is refused by name or value.  junc (may be NULL):
+ *      one byte per target residue, indexed like targets (t_off + position), bits 1 / 2 / 4 / 8 = annotated donor / acceptor on the forward
+ *      strand, acceptor / donor on the reverse, each worth junc_bonus.  The signal codes are the literal residues 0..3 = A C G T whatever m is.
+ *      Refused, error text set and nothing run, by both forms: null arguments, m outside 0..5, a residue >= m, qlen * tlen >
+ *      MM2GB_KSW_MAX_CELLS, negative lengths or offsets, e <= 0 (the reference divides by e; checked BEFORE the early return q2 <= q + e),
+ *      q < 0, q2 < 0, q + e > 127, noncan or junc_bonus outside 0..127 (then each of -noncan, -noncan / 2 and 0, with or without
+ *      junc_bonus added, is an int8_t without wrapping).  The reset record and no words: m <= 1, an empty side, q2 <= q + e,
+ *      -min(mat) > 2(q + e).  The host form is the definition; the device form (csrc/ksw_kernels.hip) equals it. ---- */
+#define MM2GB_KSW_SPLICE_FOR   0x100
+#define MM2GB_KSW_SPLICE_REV   0x200
+#define MM2GB_KSW_SPLICE_FLANK 0x400
+typedef struct { int8_t m, mat[25], q, e, q2, noncan, junc_bonus; } mm2gb_ksw_splice_param_t;
+int  mm2gb_ksw_exts2_host(const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                          const uint8_t *junc, int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+int  mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
+                         const uint8_t *targets, const uint8_t *junc, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+
 /* ---- base-level alignment of hits, batched: mm_align_skeleton (align.c:960-1020) for every read of a batch -- which stretches
  *      between and beyond a chain's anchors are aligned, how ends are extended, when a hit is split at a z-drop and when an inversion is
  *      tried, then mm_filter_regs, mm_update_dp_max and mm_hit_sort -- record for record and CIGAR word for CIGAR word.

@@ -569,13 +569,20 @@ def ksw_jobs(pairs, w=-1, zdrop=-1, end_bonus=0, flag=0):
     return jobs, cat(qs), cat(ts)
 
 
-def _ksw_call(fn, head, param, jobs, queries, targets, tail):
+def _ksw_call(fn, head, param, jobs, queries, targets, tail, junc=()):
+    """junc: () for the extd2 calls; for the exts2 calls (None,) or (array indexed like targets,)."""
     jobs = np.ascontiguousarray(jobs, dtype=KSW_JOB_DTYPE)
     queries = np.ascontiguousarray(queries, dtype=np.uint8); targets = np.ascontiguousarray(targets, dtype=np.uint8)
+    junc = tuple(None if x is None else np.ascontiguousarray(x, dtype=np.uint8) for x in junc)
+    for x in junc:
+        if x is not None and len(x) != len(targets):
+            raise Mm2gbError(f"junc has {len(x)} bytes, targets {len(targets)}: it is indexed like targets")
     res = np.zeros(len(jobs), KSW_RES_DTYPE)
     cig, total = C.c_void_p(), C.c_int64(0)
-    fn.argtypes = [C.c_void_p] * len(head) + [C.POINTER(KswParam), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * len(tail) + [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    _check(fn(*head, C.byref(param), len(jobs), jobs.ctypes.data, queries.ctypes.data, targets.ctypes.data, *tail, res.ctypes.data, C.byref(cig), C.byref(total)))
+    fn.argtypes = [C.c_void_p] * len(head) + [C.POINTER(type(param)), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p] * len(junc) + [C.c_int] * len(tail) + \
+                  [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    _check(fn(*head, C.byref(param), len(jobs), jobs.ctypes.data, queries.ctypes.data, targets.ctypes.data, *[None if x is None else x.ctypes.data for x in junc], *tail,
+              res.ctypes.data, C.byref(cig), C.byref(total)))
     try:
         words = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_uint32)), shape=(total.value,)).copy() if total.value else np.zeros(0, np.uint32)
     finally:
@@ -621,6 +628,63 @@ def _engine_ksw_info(self):
 Engine.ksw_extd2 = _engine_ksw_extd2
 Engine.ksw_extd2_batch = _engine_ksw_extd2_batch
 Engine.ksw_info = _engine_ksw_info
+
+
+# ---- splice-aware DP (mm2gb_ksw_exts2_host / _gpu): ksw2's ksw_exts2_sse, batched.  Jobs, records and words as above; w and end_bonus are not
+#      read, reach_end is always 0, and words may carry operation 3 (N). ----
+KSW_SPLICE_FOR, KSW_SPLICE_REV, KSW_SPLICE_FLANK = 0x100, 0x200, 0x400
+
+
+class KswSpliceParam(C.Structure):
+    """mm2gb_ksw_splice_param_t: m, the m x m matrix, the short gap (q, e), the long gap's opening q2, the cost of a non-canonical splice site
+    and the bonus of an annotated one."""
+    _fields_ = [("m", C.c_int8), ("mat", C.c_int8 * 25), ("q", C.c_int8), ("e", C.c_int8), ("q2", C.c_int8), ("noncan", C.c_int8), ("junc_bonus", C.c_int8)]
+
+
+def ksw_splice_param(a=1, b=2, sc_ambi=1, q=2, e=1, q2=32, noncan=9, junc_bonus=9, mat=None, m=5):
+    """The parameters of a batch; the defaults are the `splice` preset's.  mat as in ksw_param."""
+    p = KswSpliceParam()
+    p.m, p.q, p.e, p.q2, p.noncan, p.junc_bonus = int(m), int(q), int(e), int(q2), int(noncan), int(junc_bonus)
+    p.mat[:] = ksw_param(a=a, b=b, sc_ambi=sc_ambi, mat=mat, m=m).mat[:]
+    return p
+
+
+def ksw_splice_jobs(pairs, zdrop=-1, flag=0):
+    """ksw_jobs for the exts2 calls: a pair's dict may also carry `junc`, one byte per target residue (bits 1 / 2 / 4 / 8).  Returns the job
+    records, the two sequence arrays and the annotation array (None when no pair has one; zeros for the pairs without)."""
+    jobs, queries, targets = ksw_jobs(pairs, -1, zdrop, 0, flag)
+    if not any(len(p) > 2 and p[2].get("junc") is not None for p in pairs):
+        return jobs, queries, targets, None
+    junc = np.zeros(len(targets), np.uint8)
+    for p, j in zip(pairs, jobs):
+        if len(p) > 2 and p[2].get("junc") is not None:
+            junc[int(j["t_off"]):int(j["t_off"]) + int(j["tlen"])] = np.asarray(p[2]["junc"], np.uint8).reshape(-1)
+    return jobs, queries, targets, junc
+
+
+def ksw_exts2_host_batch(param, jobs, queries, targets, junc=None, threads=4):
+    """mm2gb_ksw_exts2_host on packed arrays (ksw_splice_jobs): the result records (KSW_RES_DTYPE) and the batch's CIGAR words."""
+    return _ksw_call(lib().mm2gb_ksw_exts2_host, (), param, jobs, queries, targets, (int(threads),), junc=(junc,))
+
+
+def _engine_ksw_exts2_batch(self, param, jobs, queries, targets, junc=None):
+    """mm2gb_ksw_exts2_gpu on packed arrays: as ksw_exts2_host_batch, on the device."""
+    return _ksw_call(lib().mm2gb_ksw_exts2_gpu, (self._h,), param, jobs, queries, targets, (), junc=(junc,))
+
+
+def ksw_exts2_host(pairs, param=None, zdrop=-1, flag=0, threads=4):
+    """The splice-aware DP for every (query, target[, dict of zdrop / flag / junc]) of pairs on host threads -- the definition.  One dict per
+    job, as ksw_extd2_host gives; words len << 4 | op (0 M, 1 I, 2 D, 3 N)."""
+    return _ksw_dicts(*ksw_exts2_host_batch(param or ksw_splice_param(), *ksw_splice_jobs(pairs, zdrop, flag), threads=threads))
+
+
+def _engine_ksw_exts2(self, pairs, param=None, zdrop=-1, flag=0):
+    """ksw_exts2_host's arguments and results, computed on the device (csrc/ksw_kernels.hip)."""
+    return _ksw_dicts(*self.ksw_exts2_batch(param or ksw_splice_param(), *ksw_splice_jobs(pairs, zdrop, flag)))
+
+
+Engine.ksw_exts2 = _engine_ksw_exts2
+Engine.ksw_exts2_batch = _engine_ksw_exts2_batch
 
 
 # ---- base-level alignment of hits (mm2gb_align_regs_host / _gpu): mm_align_skeleton for a batch of reads ----

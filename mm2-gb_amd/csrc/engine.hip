@@ -516,7 +516,7 @@ void Engine::shutdown()
 	for (DevBuf *b : { &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
 	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
-	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack,
+	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack, &kw_junc,
 	                   &al_refs, &al_reads, &al_jobs, &al_slices, &al_list, &al_drop,
 	                   &tx_recs, &tx_words, &tx_slices, &tx_cnt, &tx_run, &tx_bytes, &tx_dest, &tx_tmp, &tx_text,
 	                   &post_out[0].u_off, &post_out[0].a_off, &post_out[0].u_out, &post_out[0].a_out, &post_out[1].u_off, &post_out[1].a_off, &post_out[1].u_out, &post_out[1].a_out })

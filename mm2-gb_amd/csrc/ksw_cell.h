@@ -1,5 +1,6 @@
 // ksw_cell.h -- internal: the dual-affine extension DP's constants, band, cell update, row bookkeeping and backtrack, one definition
 // for the host form (ksw_host.cpp) and the device's (ksw_kernels.hip).  DESIGN 6d says what each piece has to reproduce and why.
+// The splice-aware DP uses the same pieces with a cell, site bytes and a walk start of its own, at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -214,8 +215,10 @@ __host__ __device__ inline bool ksw_walk_from(KswEz &z, int qlen, int tlen, int 
 // The walk back over the direction bytes, P(row r, column) with columns counted from the row's rounded start.  Outside a row's rounded
 // bounds the move is forced (trap 4).  Moves of one kind in a row make one word, handed to out(position, word) when the kind changes; words
 // come out last operation first, and the caller reverses them unless REV_CIGAR is set.  At most qlen + tlen + 2 words; returns their number.
+// min_intron: ksw_backtrack's min_intron_len -- 0 for the dual-affine form; the splice-aware form's long_thres, above 0 of which the long
+// gap state is written N (3) and so is a leftover leading deletion at least that long.
 template <class FP, class FO>
-__host__ __device__ inline int ksw_walk(int qlen, int tlen, int w, int i, int j, FP P, FO out)
+__host__ __device__ inline int ksw_walk(int qlen, int tlen, int w, int min_intron, int i, int j, FP P, FO out)
 {
 	int n = 0, state = 0, run_op = -1;
 	uint32_t run_len = 0;
@@ -237,13 +240,113 @@ __host__ __device__ inline int ksw_walk(int qlen, int tlen, int w, int i, int j,
 		if (state == 0) state = tmp & 7;
 		if (force >= 0) state = force;
 		if (state == 0) { push(0, 1); --i; --j; }
-		else if (state == 1 || state == 3) { push(2, 1); --i; }
+		else if (state == 1 || state == 3) { push(state == 3 && min_intron > 0 ? 3 : 2, 1); --i; }
 		else { push(1, 1); --j; }
 	}
-	if (i >= 0) push(2, i + 1);
+	if (i >= 0) push(min_intron > 0 && i >= min_intron ? 3 : 2, i + 1);
 	if (j >= 0) push(1, j + 1);
 	if (run_op >= 0) out(n++, run_len << 4 | (uint32_t)run_op);
 	return n;
+}
+
+// ---- the splice-aware form (ksw2's ksw_exts2_sse).  It has the short gap (x, y with q, e) and ONE long gap, on the target side
+// only (x2 with q2 and no extension cost), opened at donor[t] and closed at acceptor[t]; no band, no end bonus, no cap at the match score.
+// Its constants are a KswConst with e2 = 0, so that the edge values, the z-drop (no l * e term), the first cell and the wildcard's -e come
+// out of the helpers above unchanged, plus the two splice numbers. ----
+constexpr int KSW_SPLICE_BITS = MM2GB_KSW_SPLICE_FOR | MM2GB_KSW_SPLICE_REV | MM2GB_KSW_SPLICE_FLANK;
+
+struct KswSplice { KswConst k; int noncan, junc_bonus; };
+
+inline KswSplice ksw_derive_splice(const mm2gb_ksw_splice_param_t &p)
+{
+	KswSplice s = {};
+	KswConst &c = s.k;
+	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = 0; c.qe0 = c.q + c.e;
+	s.noncan = p.noncan; s.junc_bonus = p.junc_bonus;
+	for (int i = 0; i < 25; ++i) c.mat[i] = p.mat[i];
+	if (c.m <= 1 || c.q2 <= c.q + c.e) { c.early = 1; return s; }       // the second before anything is divided by e
+	int min_sc = c.mat[1];
+	for (int t = 1; t < c.m * c.m; ++t) min_sc = min_sc < c.mat[t] ? min_sc : c.mat[t];
+	c.early = -min_sc > 2 * (c.q + c.e);
+	c.long_thres = (c.q2 - c.q) / c.e - 1;                              // C's truncating division; e > 0 (ksw_check_splice)
+	if (c.q2 > c.q + c.e + c.long_thres * c.e) ++c.long_thres;
+	c.long_diff = c.long_thres * c.e - (c.q2 - c.q);
+	c.sc_mch = c.mat[0]; c.sc_mis = c.mat[1];
+	c.sc_N = c.mat[c.m * c.m - 1] == 0 ? ksw_i8(-c.e) : c.mat[c.m * c.m - 1];
+	c.ini = ksw_i8(-c.q - c.e); c.ini2 = ksw_i8(-c.q2);
+	c.q8 = ksw_i8(c.q); c.q28 = ksw_i8(c.q2); c.qe8 = ksw_i8(c.q + c.e); c.qe28 = c.q28;
+	return s;
+}
+
+// donor[t] and acceptor[t] of a job (ksw2_exts2_sse.c:120-170, loop bounds as written there): 0 without SPLICE_FOR / SPLICE_REV; with either,
+// -noncan everywhere up to the rounded target length, 0 at a full signal (GTr / yAG, CTr / yAC for the reverse strand; residues are the
+// literal codes 0..3 whatever m is), -noncan / 2 with SPLICE_FLANK or else 0 at a bare GT / AG, and junc_bonus more where junc says so.
+// REV_CIGAR means the target is a reversed left extension: the signals and the junc bits are the mirrored ones.
+// tg(i): the target's residue i, asked only for 0 <= i < tlen; junc: the job's annotation bytes or null.
+template <class FT>
+__host__ __device__ inline void ksw_splice_sites(const KswSplice &s, int flag, FT tg, const uint8_t *junc, int tlen, int t, int8_t *donor, int8_t *acceptor)
+{
+	*donor = *acceptor = 0;
+	if (!(flag & (MM2GB_KSW_SPLICE_FOR | MM2GB_KSW_SPLICE_REV))) return;
+	const bool fwd = (flag & MM2GB_KSW_SPLICE_FOR) != 0, rev = (flag & MM2GB_KSW_SPLICE_REV) != 0, mirror = (flag & MM2GB_KSW_REV_CIGAR) != 0;
+	const int8_t none = ksw_i8(-s.noncan), semi = (flag & MM2GB_KSW_SPLICE_FLANK) ? ksw_i8(-s.noncan / 2) : (int8_t)0;
+	int8_t d = none, a = none;
+	if (t < tlen - 4) {
+		const uint8_t b1 = tg(t + 1), b2 = tg(t + 2), b3 = tg(t + 3), second = mirror ? 0 : 3;
+		int type = (fwd && b1 == 2 && b2 == second) || (rev && b1 == 1 && b2 == second);
+		if (type && (mirror ? (b3 == 1 || b3 == 3) : (b3 == 0 || b3 == 2))) type = 2;
+		if (type) d = type == 2 ? 0 : semi;
+	}
+	if (junc && t < tlen - 1 && ((fwd && (junc[t + 1] & (mirror ? 2 : 1))) || (rev && (junc[t + 1] & (mirror ? 4 : 8))))) d = ksw_i8(d + s.junc_bonus);
+	if (t >= 2 && t < tlen) {
+		const uint8_t b0 = tg(t), b1 = tg(t - 1), b2 = tg(t - 2), before = mirror ? 3 : 0;
+		int type = (fwd && b1 == before && b0 == 2) || (rev && b1 == before && b0 == 1);
+		if (type && (mirror ? (b2 == 0 || b2 == 2) : (b2 == 1 || b2 == 3))) type = 2;
+		if (type) a = type == 2 ? 0 : semi;
+	}
+	if (junc && t < tlen && ((fwd && (junc[t] & (mirror ? 1 : 2))) || (rev && (junc[t] & (mirror ? 8 : 4))))) a = ksw_i8(a + s.junc_bonus);
+	*donor = d; *acceptor = a;
+}
+
+// One cell: as ksw_cell, with a, b and a2 + acceptor the candidates beside the score byte, no cap at the match score, and the long gap going
+// on where a2 beats donor (not 0): x2 = max(a2, donor) - q2.  The SSE2 build's score-only loop stores (a2 > donor ? a2 : 0) - q2 instead;
+// the definition here is the max form for every flag.
+__host__ __device__ inline KswCell ksw_cell_splice(const KswConst &c, bool right, int8_t z, int8_t x1, int8_t v1, int8_t x21, int8_t u, int8_t y, int8_t donor, int8_t acceptor)
+{
+	int8_t a = ksw_i8(x1 + v1), b = ksw_i8(y + u), a2 = ksw_i8(x21 + v1);
+	const int8_t a2a = ksw_i8(a2 + acceptor);
+	uint8_t d;
+	if (!right) {
+		d = a > z ? 1 : 0;  z = a > z ? a : z;
+		if (b > z)   { d = 2; z = b; }
+		if (a2a > z) { d = 3; z = a2a; }
+	} else {
+		d = z > a ? 0 : 1;  z = z > a ? z : a;
+		if (!(z > b))   { d = 2; z = b; }
+		if (!(z > a2a)) { d = 3; z = a2a; }
+	}
+	KswCell o;
+	o.u = ksw_i8(z - v1); o.v = ksw_i8(z - u);
+	const int8_t tmp = ksw_i8(z - c.q8);
+	a = ksw_i8(a - tmp); b = ksw_i8(b - tmp);
+	a2 = ksw_i8(a2 - ksw_i8(z - c.q28));
+	o.x  = ksw_i8((a > 0 ? a : 0) - c.qe8);
+	o.y  = ksw_i8((b > 0 ? b : 0) - c.qe8);
+	o.x2 = ksw_i8((a2 > donor ? a2 : donor) - c.q28);
+	o.y2 = 0;
+	if (!right) d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > donor ? 0x20 : 0);
+	else        d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= donor ? 0x20 : 0);
+	o.d = d;
+	return o;
+}
+
+// where the backtrack starts: as ksw_walk_from without the end bonus's branch (reach_end stays 0)
+__host__ __device__ inline bool ksw_walk_from_splice(const KswEz &z, int qlen, int tlen, int flag, int *i0, int *j0)
+{
+	if (flag & MM2GB_KSW_SCORE_ONLY) return false;
+	if (!z.zdropped && !(flag & MM2GB_KSW_EXTZ_ONLY)) { *i0 = tlen - 1; *j0 = qlen - 1; return true; }
+	if (z.max_t >= 0 && z.max_q >= 0) { *i0 = z.max_t; *j0 = z.max_q; return true; }
+	return false;
 }
 
 } // namespace mm2gb

@@ -1,4 +1,5 @@
-// ksw_host.cpp -- the dual-affine extension DP on host threads (mm2gb_ksw_extd2_host): the definition the device form is held to.
+// ksw_host.cpp -- the dual-affine extension DP (mm2gb_ksw_extd2_host) and the splice-aware one (mm2gb_ksw_exts2_host) on host
+// threads: the definitions the device forms are held to.
 // One job at a time per thread, one cell at a time, over the same arrays the reference's vector code keeps: six difference
 // arrays and the score bytes, rounded out to groups of 16 cells, 32-bit H when the exact maximum is wanted, one row of direction bytes per
 // anti-diagonal.  The arithmetic is ksw_cell.h's, shared with the kernel.
@@ -15,29 +16,54 @@
 
 namespace mm2gb {
 
+namespace {
+
+// what both DPs refuse in a job: flag bits outside known, bad lengths, too many cells, residues >= m
+int check_jobs(const std::string &w, int m, int known, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets)
+{
+	static const struct { int bit; const char *name; } refused[] = { { 0x20, "bit 0x20 (unassigned)" }, { 0x100, "KSW_EZ_SPLICE_FOR" }, { 0x200, "KSW_EZ_SPLICE_REV" }, { 0x400, "KSW_EZ_SPLICE_FLANK" } };
+	for (int64_t j = 0; j < n_jobs; ++j) {
+		const mm2gb_ksw_job_t &b = jobs[j];
+		const std::string at = w + ": job " + std::to_string(j) + ": ";
+		if (b.flag & ~known) {
+			for (const auto &x : refused) if (b.flag & ~known & x.bit) return fail(at + "flag " + x.name + " is not supported");
+			return fail(at + "unknown flag bits " + std::to_string(b.flag & ~known));
+		}
+		if (b.qlen < 0 || b.tlen < 0 || b.q_off < 0 || b.t_off < 0) return fail(at + "negative length or offset");
+		if ((int64_t)b.qlen * b.tlen > MM2GB_KSW_MAX_CELLS) return fail(at + "qlen * tlen = " + std::to_string((int64_t)b.qlen * b.tlen) + " exceeds MM2GB_KSW_MAX_CELLS");
+		if ((b.qlen > 0 && !queries) || (b.tlen > 0 && !targets)) return fail(at + "null sequence array");
+		if (m > 1) {
+			for (int k = 0; k < b.qlen; ++k) if (queries[b.q_off + k] >= m) return fail(at + "query residue >= m at " + std::to_string(k));
+			for (int k = 0; k < b.tlen; ++k) if (targets[b.t_off + k] >= m) return fail(at + "target residue >= m at " + std::to_string(k));
+		}
+	}
+	return 0;
+}
+
+} // namespace
+
 int ksw_check(const char *who, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
               const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	const std::string w = who;
 	if (!param || n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !cigar || !n_cigar_total) return fail(w + ": null argument");
 	if (param->m < 0 || param->m > 5) return fail(w + ": m must be 0..5");
-	static const struct { int bit; const char *name; } refused[] = { { 0x20, "bit 0x20 (unassigned)" }, { 0x100, "KSW_EZ_SPLICE_FOR" }, { 0x200, "KSW_EZ_SPLICE_REV" }, { 0x400, "KSW_EZ_SPLICE_FLANK" } };
-	for (int64_t j = 0; j < n_jobs; ++j) {
-		const mm2gb_ksw_job_t &b = jobs[j];
-		const std::string at = w + ": job " + std::to_string(j) + ": ";
-		if (b.flag & ~KSW_FLAGS_KNOWN) {
-			for (const auto &x : refused) if (b.flag & x.bit) return fail(at + "flag " + x.name + " is not supported");
-			return fail(at + "unknown flag bits " + std::to_string(b.flag & ~KSW_FLAGS_KNOWN));
-		}
-		if (b.qlen < 0 || b.tlen < 0 || b.q_off < 0 || b.t_off < 0) return fail(at + "negative length or offset");
-		if ((int64_t)b.qlen * b.tlen > MM2GB_KSW_MAX_CELLS) return fail(at + "qlen * tlen = " + std::to_string((int64_t)b.qlen * b.tlen) + " exceeds MM2GB_KSW_MAX_CELLS");
-		if ((b.qlen > 0 && !queries) || (b.tlen > 0 && !targets)) return fail(at + "null sequence array");
-		if (param->m > 1) {
-			for (int k = 0; k < b.qlen; ++k) if (queries[b.q_off + k] >= param->m) return fail(at + "query residue >= m at " + std::to_string(k));
-			for (int k = 0; k < b.tlen; ++k) if (targets[b.t_off + k] >= param->m) return fail(at + "target residue >= m at " + std::to_string(k));
-		}
-	}
-	return 0;
+	return check_jobs(w, param->m, KSW_FLAGS_KNOWN, n_jobs, jobs, queries, targets);
+}
+
+// The parameters are refused before anything is looked at that returns early: e <= 0 is an error even where q2 <= q + e.
+int ksw_check_splice(const char *who, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                     const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	const std::string w = who;
+	if (!param || n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !cigar || !n_cigar_total) return fail(w + ": null argument");
+	if (param->m < 0 || param->m > 5) return fail(w + ": m must be 0..5");
+	if (param->e <= 0) return fail(w + ": e must be above 0 (the reference divides by it)");
+	if (param->q < 0 || param->q2 < 0) return fail(w + ": q and q2 must not be negative");
+	if (param->q + param->e > 127) return fail(w + ": q + e exceeds 127");
+	if (param->noncan < 0) return fail(w + ": noncan must be 0..127");
+	if (param->junc_bonus < 0) return fail(w + ": junc_bonus must be 0..127");
+	return check_jobs(w, param->m, KSW_FLAGS_KNOWN | KSW_SPLICE_BITS, n_jobs, jobs, queries, targets);
 }
 
 void ksw_store(const KswEz &z, int n_cigar, mm2gb_ksw_res_t *out)
@@ -50,17 +76,22 @@ namespace {
 
 struct Scratch { std::vector<int8_t> a; std::vector<int32_t> H; std::vector<uint8_t> p; std::vector<uint32_t> cig; };
 
-void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, Scratch &S, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
+// SPLICE: the splice-aware form (sp its two numbers, junc the job's annotation bytes or null); c is then sp->k, the band is none, and y2's
+// array holds donor[] with acceptor[] behind the score bytes
+template <bool SPLICE>
+void one_job(const KswConst &c, const KswSplice *sp, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, const uint8_t *junc, Scratch &S,
+             mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
 {
 	KswEz z;
 	ksw_ez_reset(z);
 	const int qlen = job.qlen, tlen = job.tlen, flag = job.flag;
 	if (c.early || qlen <= 0 || tlen <= 0) { ksw_store(z, 0, out); return; }
-	const int w = ksw_width(qlen, tlen, job.w), T = ksw_round16(tlen), ncol = ksw_ncol16(qlen, tlen, w);
+	const int w = ksw_width(qlen, tlen, SPLICE ? -1 : job.w), T = ksw_round16(tlen), ncol = ksw_ncol16(qlen, tlen, w);
 	const bool with_cigar = !(flag & MM2GB_KSW_SCORE_ONLY), approx = (flag & MM2GB_KSW_APPROX_MAX) != 0, right = (flag & MM2GB_KSW_RIGHT) != 0, generic = (flag & MM2GB_KSW_GENERIC_SC) != 0;
-	S.a.resize((size_t)T * 7);
-	int8_t *u = S.a.data(), *v = u + T, *x = v + T, *y = x + T, *x2 = y + T, *y2 = x2 + T, *s = y2 + T;
+	S.a.resize((size_t)T * 8);
+	int8_t *u = S.a.data(), *v = u + T, *x = v + T, *y = x + T, *x2 = y + T, *y2 = x2 + T, *s = y2 + T, *don = y2, *acc = s + T;
 	memset(u, c.ini, (size_t)T * 4); memset(x2, c.ini2, (size_t)T * 2); memset(s, 0, (size_t)T);
+	if (SPLICE) for (int t = 0; t < T; ++t) ksw_splice_sites(*sp, flag, [&](int i) { return target[i]; }, junc, tlen, t, don + t, acc + t);
 	int32_t *H = nullptr;
 	if (!approx) { S.H.assign((size_t)T, MM2GB_KSW_NEG_INF); H = S.H.data(); }
 	if (with_cigar) S.p.resize((size_t)(qlen + tlen - 1) * ncol);
@@ -74,15 +105,16 @@ void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query
 		int8_t x1 = c.ini, x21 = c.ini2, v1 = c.ini;
 		if (st > 0) { if (st - 1 >= last_st && st - 1 <= last_en) { x1 = x[st - 1]; x21 = x2[st - 1]; v1 = v[st - 1]; } }
 		else v1 = ksw_edge(c, r);
-		if (en >= r) { y[r] = c.ini; y2[r] = c.ini2; u[r] = ksw_edge(c, r); }
+		if (en >= r) { y[r] = c.ini; if (!SPLICE) y2[r] = c.ini2; u[r] = ksw_edge(c, r); }
 		// the score bytes: whole groups of 16 from st0 unless the matrix is looked up, and nothing beyond the array (trap 2)
 		const int s_end = generic ? en0 + 1 : std::min(T, st0 + ((en0 - st0) / 16 + 1) * 16);
 		for (int t = st0; t < s_end; ++t) s[t] = ksw_score(c, c.mat, generic, ksw_target_byte(target, query, qlen, tlen, T, t), ksw_query_byte(query, qlen, r, t));
 		uint8_t *pr = with_cigar ? p + (size_t)r * ncol - st : nullptr;
 		for (int t = st; t <= en; ++t) {
-			const KswCell o = ksw_cell(c, right, s[t], x1, v1, x21, u[t], y[t], y2[t]);
+			const KswCell o = SPLICE ? ksw_cell_splice(c, right, s[t], x1, v1, x21, u[t], y[t], don[t], acc[t]) : ksw_cell(c, right, s[t], x1, v1, x21, u[t], y[t], y2[t]);
 			x1 = x[t]; v1 = v[t]; x21 = x2[t];
-			u[t] = o.u; v[t] = o.v; x[t] = o.x; y[t] = o.y; x2[t] = o.x2; y2[t] = o.y2;
+			u[t] = o.u; v[t] = o.v; x[t] = o.x; y[t] = o.y; x2[t] = o.x2;
+			if (!SPLICE) y2[t] = o.y2;
 			if (pr) pr[t] = o.d;
 		}
 		bool stop;
@@ -101,9 +133,9 @@ void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query
 		last_st = st; last_en = en;
 	}
 	int i0 = 0, j0 = 0, n = 0;
-	if (ksw_walk_from(z, qlen, tlen, job.end_bonus, flag, &i0, &j0)) {
+	if (SPLICE ? ksw_walk_from_splice(z, qlen, tlen, flag, &i0, &j0) : ksw_walk_from(z, qlen, tlen, job.end_bonus, flag, &i0, &j0)) {
 		S.cig.resize((size_t)qlen + tlen + 2);
-		n = ksw_walk(qlen, tlen, w, i0, j0, [&](int r, int col) { return (uint32_t)p[(size_t)r * ncol + col]; }, [&](int k, uint32_t word) { S.cig[(size_t)k] = word; });
+		n = ksw_walk(qlen, tlen, w, SPLICE ? c.long_thres : 0, i0, j0, [&](int r, int col) { return (uint32_t)p[(size_t)r * ncol + col]; }, [&](int k, uint32_t word) { S.cig[(size_t)k] = word; });
 		if (!(flag & MM2GB_KSW_REV_CIGAR)) std::reverse(S.cig.begin(), S.cig.begin() + n);
 		words.insert(words.end(), S.cig.begin(), S.cig.begin() + n);
 	}
@@ -115,7 +147,7 @@ void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query
 void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
 {
 	static thread_local Scratch S;                        // carries only capacity between calls: one_job sizes and writes every array for a job before it reads it
-	one_job(c, job, query, target, S, out, words);
+	one_job<false>(c, nullptr, job, query, target, nullptr, S, out, words);
 }
 
 int ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
@@ -131,11 +163,12 @@ int ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *
 
 using namespace mm2gb;
 
-int mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
-                         int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+namespace {
+
+template <bool SPLICE>
+int host_batch(const KswConst &c, const KswSplice *sp, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, const uint8_t *junc,
+               int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
-	if (ksw_check("mm2gb_ksw_extd2_host", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
-	const KswConst c = ksw_derive(*param);
 	const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(n_threads, 256), n_jobs));
 	// jobs are dealt in runs of 16; a thread keeps the words of its jobs with the job's index, and they are laid out in job order at the end
 	std::vector<std::vector<uint32_t>> words((size_t)nt);
@@ -149,7 +182,7 @@ int mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const m
 			if (lo >= n_jobs) break;
 			for (int64_t j = lo; j < hi; ++j) {
 				who[(size_t)j] = k; where[(size_t)j] = (int64_t)words[(size_t)k].size();
-				one_job(c, jobs[j], queries + jobs[j].q_off, targets + jobs[j].t_off, S, res + j, words[(size_t)k]);
+				one_job<SPLICE>(c, sp, jobs[j], queries + jobs[j].q_off, targets + jobs[j].t_off, junc ? junc + jobs[j].t_off : nullptr, S, res + j, words[(size_t)k]);
 			}
 		}
 	};
@@ -158,4 +191,21 @@ int mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const m
 	for (int64_t j = 0; j < n_jobs; ++j)
 		if (res[j].n_cigar > 0) memcpy(*cigar + res[j].cigar_off, words[(size_t)who[(size_t)j]].data() + where[(size_t)j], (size_t)res[j].n_cigar * 4);
 	return 0;
+}
+
+} // namespace
+
+int mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                         int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	if (ksw_check("mm2gb_ksw_extd2_host", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
+	return host_batch<false>(ksw_derive(*param), nullptr, n_jobs, jobs, queries, targets, nullptr, n_threads, res, cigar, n_cigar_total);
+}
+
+int mm2gb_ksw_exts2_host(const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                         const uint8_t *junc, int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	if (ksw_check_splice("mm2gb_ksw_exts2_host", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
+	const KswSplice sp = ksw_derive_splice(*param);
+	return host_batch<true>(sp.k, &sp, n_jobs, jobs, queries, targets, junc, n_threads, res, cigar, n_cigar_total);
 }
