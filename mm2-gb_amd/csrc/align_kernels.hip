@@ -1,7 +1,7 @@
 // align_kernels.hip -- the device form of the alignment of hits (mm2gb_align_regs_gpu).  Planning, stitching and the per-read steps
 // are align_host.cpp's; this unit is the DP backend of a round.  The batch's residues are uploaded once (one byte per base, the reads' forward
 // strand only); per round k_al_gather writes every job's two stretches from them into the extension DP's input arenas (reverse complement and
-// the left extension's reversal applied on the way), the DP runs on the resident bytes (ksw_extd2_run), k_al_zdrop walks the CIGAR of every
+// the left extension's reversal applied on the way), the DP runs on the resident bytes (ksw_run), k_al_zdrop walks the CIGAR of every
 // first-pass gap fill where words and bytes lie, the host decides mm_test_zdrop's code from the 24 bytes per job that come back, and the
 // fills that need it run again without the approximate maximum on the bytes already gathered.  The host never materialises a stretch.
 #include <algorithm>
@@ -116,7 +116,7 @@ struct DevBackend : AlBackend {
 		uint32_t *cig1 = nullptr, *cig2 = nullptr;
 		int64_t total1 = 0, total2 = 0;
 		struct Free { uint32_t **a, **b; ~Free() { free(*a); free(*b); } } guard{ &cig1, &cig2 };
-		if (ksw_extd2_run(e, c.kc, (int64_t)n, kj.data(), nullptr, nullptr, true, res.data(), &cig1, &total1)) return -1;
+		if (ksw_run(e, c.kc, (int64_t)n, kj.data(), nullptr, nullptr, nullptr, true, res.data(), &cig1, &total1)) return -1;
 		seconds[3] += since(t0);
 		// mm_test_zdrop for the gap fills
 		t0 = clk::now();
@@ -152,7 +152,7 @@ struct DevBackend : AlBackend {
 				kj2[i] = kj[(size_t)again[i]];
 				kj2[i].flag = al_second_flag(x.flag); kj2[i].zdrop = al_second_zdrop(c, x.code);
 			}
-			if (ksw_extd2_run(e, c.kc, (int64_t)again.size(), kj2.data(), nullptr, nullptr, true, res2.data(), &cig2, &total2)) return -1;
+			if (ksw_run(e, c.kc, (int64_t)again.size(), kj2.data(), nullptr, nullptr, nullptr, true, res2.data(), &cig2, &total2)) return -1;
 		}
 		seconds[5] += since(t0);
 		// the round's records and words

@@ -1,6 +1,6 @@
 // ksw_cell.h -- internal: the dual-affine extension DP's constants, band, cell update, row bookkeeping and backtrack, one definition
 // for the host form (ksw_host.cpp) and the device's (ksw_kernels.hip).  DESIGN 6d says what each piece has to reproduce and why.
-// The splice-aware DP uses the same pieces with a cell, site bytes and a walk start of its own, at the end of this file.
+// The splice-aware DP uses the same pieces with a cell and site bytes of its own, at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,31 +12,45 @@ constexpr int KSW_FLAGS_KNOWN = MM2GB_KSW_SCORE_ONLY | MM2GB_KSW_RIGHT | MM2GB_K
                                 MM2GB_KSW_EXTZ_ONLY | MM2GB_KSW_REV_CIGAR;
 
 // What the parameters come to once per batch.  q, e, q2, e2 are the tuple AFTER it has been ordered so that q + e <= q2 + e2;
-// qe0 is q + e BEFORE that (the first cell's H is taken from it: trap 1).
+// qe0 is q + e BEFORE that (the first cell's H is taken from it: trap 1).  splice: the splice-aware form, which has
+// e2 = 0 and the two splice numbers; all three are 0 in the dual-affine form.  They lie behind the bytes: with them in front of mat[] the
+// dual-affine kernels take two more VGPRs and the global-image ones lose a wave of occupancy.
 struct KswConst {
 	int    m, q, e, q2, e2, qe0, long_thres, long_diff, early;
 	int8_t mat[25], sc_mch, sc_mis, sc_N, ini, ini2, q8, q28, qe8, qe28;
+	int    splice, noncan, junc_bonus;
 };
 
 __host__ __device__ inline int8_t ksw_i8(int v) { return (int8_t)(uint8_t)(unsigned)v; }      // wrap to 8 bits (trap 7)
 
-inline KswConst ksw_derive(const mm2gb_ksw_param_t &p)
+// Either parameter record.  The splice-aware form has one long gap without an extension cost: e2 = 0, with which long_thres, long_diff, ini2
+// and qe28 below are ksw_exts2's.  Its own are the second early return, tested before anything is divided by e (e > 0: ksw_check_splice),
+// and the wildcard: -e, not -e2 (trap 10; 6d-b 5).
+template <class Param>
+inline KswConst ksw_derive_as(const Param &p, int e2, bool splice)
 {
 	KswConst c = {};
-	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = p.e2; c.qe0 = c.q + c.e;
+	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = e2; c.qe0 = c.q + c.e; c.splice = splice;
 	for (int i = 0; i < 25; ++i) c.mat[i] = p.mat[i];
-	if (c.m <= 1) { c.early = 1; return c; }
-	if (c.q2 + c.e2 < c.q + c.e) { int t = c.q; c.q = c.q2; c.q2 = t; t = c.e; c.e = c.e2; c.e2 = t; }
+	if (c.m <= 1 || (splice && c.q2 <= c.q + c.e)) { c.early = 1; return c; }
+	if (c.q2 + c.e2 < c.q + c.e) { int t = c.q; c.q = c.q2; c.q2 = t; t = c.e; c.e = c.e2; c.e2 = t; }      // never with splice: q2 > q + e
 	int min_sc = c.mat[1];                                  // the diagonal's first entry is not looked at
 	for (int t = 1; t < c.m * c.m; ++t) min_sc = min_sc < c.mat[t] ? min_sc : c.mat[t];
 	c.early = -min_sc > 2 * (c.q + c.e);                    // no mismatch could ever be seen
-	c.long_thres = c.e != c.e2 ? (c.q2 - c.q) / (c.e - c.e2) - 1 : 0;
+	c.long_thres = c.e != c.e2 ? (c.q2 - c.q) / (c.e - c.e2) - 1 : 0;      // C's truncating division
 	if (c.q2 + c.e2 + c.long_thres * c.e2 > c.q + c.e + c.long_thres * c.e) ++c.long_thres;
 	c.long_diff = c.long_thres * (c.e - c.e2) - (c.q2 - c.q) - c.e2;
 	c.sc_mch = c.mat[0]; c.sc_mis = c.mat[1];
-	c.sc_N = c.mat[c.m * c.m - 1] == 0 ? ksw_i8(-c.e2) : c.mat[c.m * c.m - 1];      // trap 10
+	c.sc_N = c.mat[c.m * c.m - 1] == 0 ? ksw_i8(splice ? -c.e : -c.e2) : c.mat[c.m * c.m - 1];
 	c.ini = ksw_i8(-c.q - c.e); c.ini2 = ksw_i8(-c.q2 - c.e2);
 	c.q8 = ksw_i8(c.q); c.q28 = ksw_i8(c.q2); c.qe8 = ksw_i8(c.q + c.e); c.qe28 = ksw_i8(c.q2 + c.e2);
+	return c;
+}
+inline KswConst ksw_derive(const mm2gb_ksw_param_t &p) { return ksw_derive_as(p, p.e2, false); }
+inline KswConst ksw_derive_splice(const mm2gb_ksw_splice_param_t &p)
+{
+	KswConst c = ksw_derive_as(p, 0, true);
+	c.noncan = p.noncan; c.junc_bonus = p.junc_bonus;
 	return c;
 }
 
@@ -162,6 +176,13 @@ __host__ __device__ inline void ksw_ez_reset(KswEz &z)
 	z.zdropped = 0; z.reach_end = 0;
 }
 
+// a job's record from its state (pad_ / cigar_off: 0; the kernel carries the walk's start in them to k_ksw_walk)
+__host__ __device__ inline void ksw_store(const KswEz &z, int n_cigar, mm2gb_ksw_res_t *out)
+{
+	out->max = z.max; out->zdropped = z.zdropped; out->max_q = z.max_q; out->max_t = z.max_t; out->mqe = z.mqe; out->mqe_t = z.mqe_t;
+	out->mte = z.mte; out->mte_q = z.mte_q; out->score = z.score; out->reach_end = z.reach_end; out->n_cigar = n_cigar; out->pad_ = 0; out->cigar_off = 0;
+}
+
 // a new best, or, diagonally behind the best by more than zdrop + e * (distance off its diagonal), the end of the job
 __host__ __device__ inline bool ksw_zdrop(KswEz &z, int32_t H, int r, int t, int zdrop, int e)
 {
@@ -203,11 +224,12 @@ __host__ __device__ inline bool ksw_row_approx(KswEz &z, const KswConst &c, int 
 }
 
 // Where the backtrack starts once the rows are done; false: no CIGAR.  A dropped job still walks back from its best cell (trap 9).
-__host__ __device__ inline bool ksw_walk_from(KswEz &z, int qlen, int tlen, int end_bonus, int flag, int *i0, int *j0)
+// The splice-aware form has no end bonus and not its branch either (mqe > max can hold there): reach_end stays 0.
+__host__ __device__ inline bool ksw_walk_from(KswEz &z, bool splice, int qlen, int tlen, int end_bonus, int flag, int *i0, int *j0)
 {
 	if (flag & MM2GB_KSW_SCORE_ONLY) return false;
 	if (!z.zdropped && !(flag & MM2GB_KSW_EXTZ_ONLY)) { *i0 = tlen - 1; *j0 = qlen - 1; return true; }
-	if (!z.zdropped && (flag & MM2GB_KSW_EXTZ_ONLY) && z.mqe + end_bonus > z.max) { z.reach_end = 1; *i0 = z.mqe_t; *j0 = qlen - 1; return true; }
+	if (!splice && !z.zdropped && (flag & MM2GB_KSW_EXTZ_ONLY) && z.mqe + end_bonus > z.max) { z.reach_end = 1; *i0 = z.mqe_t; *j0 = qlen - 1; return true; }
 	if (z.max_t >= 0 && z.max_q >= 0) { *i0 = z.max_t; *j0 = z.max_q; return true; }
 	return false;
 }
@@ -251,32 +273,9 @@ __host__ __device__ inline int ksw_walk(int qlen, int tlen, int w, int min_intro
 
 // ---- the splice-aware form (ksw2's ksw_exts2_sse).  It has the short gap (x, y with q, e) and ONE long gap, on the target side
 // only (x2 with q2 and no extension cost), opened at donor[t] and closed at acceptor[t]; no band, no end bonus, no cap at the match score.
-// Its constants are a KswConst with e2 = 0, so that the edge values, the z-drop (no l * e term), the first cell and the wildcard's -e come
-// out of the helpers above unchanged, plus the two splice numbers. ----
+// Its constants (ksw_derive_splice) have e2 = 0, so that the edge values, the z-drop (no l * e term) and the first cell come out of the
+// helpers above unchanged. ----
 constexpr int KSW_SPLICE_BITS = MM2GB_KSW_SPLICE_FOR | MM2GB_KSW_SPLICE_REV | MM2GB_KSW_SPLICE_FLANK;
-
-struct KswSplice { KswConst k; int noncan, junc_bonus; };
-
-inline KswSplice ksw_derive_splice(const mm2gb_ksw_splice_param_t &p)
-{
-	KswSplice s = {};
-	KswConst &c = s.k;
-	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = 0; c.qe0 = c.q + c.e;
-	s.noncan = p.noncan; s.junc_bonus = p.junc_bonus;
-	for (int i = 0; i < 25; ++i) c.mat[i] = p.mat[i];
-	if (c.m <= 1 || c.q2 <= c.q + c.e) { c.early = 1; return s; }       // the second before anything is divided by e
-	int min_sc = c.mat[1];
-	for (int t = 1; t < c.m * c.m; ++t) min_sc = min_sc < c.mat[t] ? min_sc : c.mat[t];
-	c.early = -min_sc > 2 * (c.q + c.e);
-	c.long_thres = (c.q2 - c.q) / c.e - 1;                              // C's truncating division; e > 0 (ksw_check_splice)
-	if (c.q2 > c.q + c.e + c.long_thres * c.e) ++c.long_thres;
-	c.long_diff = c.long_thres * c.e - (c.q2 - c.q);
-	c.sc_mch = c.mat[0]; c.sc_mis = c.mat[1];
-	c.sc_N = c.mat[c.m * c.m - 1] == 0 ? ksw_i8(-c.e) : c.mat[c.m * c.m - 1];
-	c.ini = ksw_i8(-c.q - c.e); c.ini2 = ksw_i8(-c.q2);
-	c.q8 = ksw_i8(c.q); c.q28 = ksw_i8(c.q2); c.qe8 = ksw_i8(c.q + c.e); c.qe28 = c.q28;
-	return s;
-}
 
 // donor[t] and acceptor[t] of a job (ksw2_exts2_sse.c:120-170, loop bounds as written there): 0 without SPLICE_FOR / SPLICE_REV; with either,
 // -noncan everywhere up to the rounded target length, 0 at a full signal (GTr / yAG, CTr / yAC for the reverse strand; residues are the
@@ -284,12 +283,12 @@ inline KswSplice ksw_derive_splice(const mm2gb_ksw_splice_param_t &p)
 // REV_CIGAR means the target is a reversed left extension: the signals and the junc bits are the mirrored ones.
 // tg(i): the target's residue i, asked only for 0 <= i < tlen; junc: the job's annotation bytes or null.
 template <class FT>
-__host__ __device__ inline void ksw_splice_sites(const KswSplice &s, int flag, FT tg, const uint8_t *junc, int tlen, int t, int8_t *donor, int8_t *acceptor)
+__host__ __device__ inline void ksw_splice_sites(const KswConst &c, int flag, FT tg, const uint8_t *junc, int tlen, int t, int8_t *donor, int8_t *acceptor)
 {
 	*donor = *acceptor = 0;
 	if (!(flag & (MM2GB_KSW_SPLICE_FOR | MM2GB_KSW_SPLICE_REV))) return;
 	const bool fwd = (flag & MM2GB_KSW_SPLICE_FOR) != 0, rev = (flag & MM2GB_KSW_SPLICE_REV) != 0, mirror = (flag & MM2GB_KSW_REV_CIGAR) != 0;
-	const int8_t none = ksw_i8(-s.noncan), semi = (flag & MM2GB_KSW_SPLICE_FLANK) ? ksw_i8(-s.noncan / 2) : (int8_t)0;
+	const int8_t none = ksw_i8(-c.noncan), semi = (flag & MM2GB_KSW_SPLICE_FLANK) ? ksw_i8(-c.noncan / 2) : (int8_t)0;
 	int8_t d = none, a = none;
 	if (t < tlen - 4) {
 		const uint8_t b1 = tg(t + 1), b2 = tg(t + 2), b3 = tg(t + 3), second = mirror ? 0 : 3;
@@ -297,14 +296,14 @@ __host__ __device__ inline void ksw_splice_sites(const KswSplice &s, int flag, F
 		if (type && (mirror ? (b3 == 1 || b3 == 3) : (b3 == 0 || b3 == 2))) type = 2;
 		if (type) d = type == 2 ? 0 : semi;
 	}
-	if (junc && t < tlen - 1 && ((fwd && (junc[t + 1] & (mirror ? 2 : 1))) || (rev && (junc[t + 1] & (mirror ? 4 : 8))))) d = ksw_i8(d + s.junc_bonus);
+	if (junc && t < tlen - 1 && ((fwd && (junc[t + 1] & (mirror ? 2 : 1))) || (rev && (junc[t + 1] & (mirror ? 4 : 8))))) d = ksw_i8(d + c.junc_bonus);
 	if (t >= 2 && t < tlen) {
 		const uint8_t b0 = tg(t), b1 = tg(t - 1), b2 = tg(t - 2), before = mirror ? 3 : 0;
 		int type = (fwd && b1 == before && b0 == 2) || (rev && b1 == before && b0 == 1);
 		if (type && (mirror ? (b2 == 0 || b2 == 2) : (b2 == 1 || b2 == 3))) type = 2;
 		if (type) a = type == 2 ? 0 : semi;
 	}
-	if (junc && t < tlen && ((fwd && (junc[t] & (mirror ? 1 : 2))) || (rev && (junc[t] & (mirror ? 8 : 4))))) a = ksw_i8(a + s.junc_bonus);
+	if (junc && t < tlen && ((fwd && (junc[t] & (mirror ? 1 : 2))) || (rev && (junc[t] & (mirror ? 8 : 4))))) a = ksw_i8(a + c.junc_bonus);
 	*donor = d; *acceptor = a;
 }
 
@@ -338,15 +337,6 @@ __host__ __device__ inline KswCell ksw_cell_splice(const KswConst &c, bool right
 	else        d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= donor ? 0x20 : 0);
 	o.d = d;
 	return o;
-}
-
-// where the backtrack starts: as ksw_walk_from without the end bonus's branch (reach_end stays 0)
-__host__ __device__ inline bool ksw_walk_from_splice(const KswEz &z, int qlen, int tlen, int flag, int *i0, int *j0)
-{
-	if (flag & MM2GB_KSW_SCORE_ONLY) return false;
-	if (!z.zdropped && !(flag & MM2GB_KSW_EXTZ_ONLY)) { *i0 = tlen - 1; *j0 = qlen - 1; return true; }
-	if (z.max_t >= 0 && z.max_q >= 0) { *i0 = z.max_t; *j0 = z.max_q; return true; }
-	return false;
 }
 
 } // namespace mm2gb

@@ -40,14 +40,22 @@ int check_jobs(const std::string &w, int m, int known, int64_t n_jobs, const mm2
 	return 0;
 }
 
+// what both parameter records are refused for first: null arguments and m
+template <class Param>
+int check_head(const std::string &w, const Param *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	if (!param || n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !cigar || !n_cigar_total) return fail(w + ": null argument");
+	if (param->m < 0 || param->m > 5) return fail(w + ": m must be 0..5");
+	return 0;
+}
+
 } // namespace
 
 int ksw_check(const char *who, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
               const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	const std::string w = who;
-	if (!param || n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !cigar || !n_cigar_total) return fail(w + ": null argument");
-	if (param->m < 0 || param->m > 5) return fail(w + ": m must be 0..5");
+	if (check_head(w, param, n_jobs, jobs, res, cigar, n_cigar_total)) return -1;
 	return check_jobs(w, param->m, KSW_FLAGS_KNOWN, n_jobs, jobs, queries, targets);
 }
 
@@ -56,8 +64,7 @@ int ksw_check_splice(const char *who, const mm2gb_ksw_splice_param_t *param, int
                      const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	const std::string w = who;
-	if (!param || n_jobs < 0 || (n_jobs > 0 && (!jobs || !res)) || !cigar || !n_cigar_total) return fail(w + ": null argument");
-	if (param->m < 0 || param->m > 5) return fail(w + ": m must be 0..5");
+	if (check_head(w, param, n_jobs, jobs, res, cigar, n_cigar_total)) return -1;
 	if (param->e <= 0) return fail(w + ": e must be above 0 (the reference divides by it)");
 	if (param->q < 0 || param->q2 < 0) return fail(w + ": q and q2 must not be negative");
 	if (param->q + param->e > 127) return fail(w + ": q + e exceeds 127");
@@ -66,20 +73,14 @@ int ksw_check_splice(const char *who, const mm2gb_ksw_splice_param_t *param, int
 	return check_jobs(w, param->m, KSW_FLAGS_KNOWN | KSW_SPLICE_BITS, n_jobs, jobs, queries, targets);
 }
 
-void ksw_store(const KswEz &z, int n_cigar, mm2gb_ksw_res_t *out)
-{
-	out->max = z.max; out->zdropped = z.zdropped; out->max_q = z.max_q; out->max_t = z.max_t; out->mqe = z.mqe; out->mqe_t = z.mqe_t;
-	out->mte = z.mte; out->mte_q = z.mte_q; out->score = z.score; out->reach_end = z.reach_end; out->n_cigar = n_cigar; out->pad_ = 0; out->cigar_off = 0;
-}
-
 namespace {
 
 struct Scratch { std::vector<int8_t> a; std::vector<int32_t> H; std::vector<uint8_t> p; std::vector<uint32_t> cig; };
 
-// SPLICE: the splice-aware form (sp its two numbers, junc the job's annotation bytes or null); c is then sp->k, the band is none, and y2's
-// array holds donor[] with acceptor[] behind the score bytes
+// SPLICE: the splice-aware form (c.splice; junc the job's annotation bytes or null): the band is none, and y2's array holds donor[] with
+// acceptor[] behind the score bytes
 template <bool SPLICE>
-void one_job(const KswConst &c, const KswSplice *sp, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, const uint8_t *junc, Scratch &S,
+void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, const uint8_t *junc, Scratch &S,
              mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
 {
 	KswEz z;
@@ -91,7 +92,7 @@ void one_job(const KswConst &c, const KswSplice *sp, const mm2gb_ksw_job_t &job,
 	S.a.resize((size_t)T * 8);
 	int8_t *u = S.a.data(), *v = u + T, *x = v + T, *y = x + T, *x2 = y + T, *y2 = x2 + T, *s = y2 + T, *don = y2, *acc = s + T;
 	memset(u, c.ini, (size_t)T * 4); memset(x2, c.ini2, (size_t)T * 2); memset(s, 0, (size_t)T);
-	if (SPLICE) for (int t = 0; t < T; ++t) ksw_splice_sites(*sp, flag, [&](int i) { return target[i]; }, junc, tlen, t, don + t, acc + t);
+	if (SPLICE) for (int t = 0; t < T; ++t) ksw_splice_sites(c, flag, [&](int i) { return target[i]; }, junc, tlen, t, don + t, acc + t);
 	int32_t *H = nullptr;
 	if (!approx) { S.H.assign((size_t)T, MM2GB_KSW_NEG_INF); H = S.H.data(); }
 	if (with_cigar) S.p.resize((size_t)(qlen + tlen - 1) * ncol);
@@ -133,7 +134,7 @@ void one_job(const KswConst &c, const KswSplice *sp, const mm2gb_ksw_job_t &job,
 		last_st = st; last_en = en;
 	}
 	int i0 = 0, j0 = 0, n = 0;
-	if (SPLICE ? ksw_walk_from_splice(z, qlen, tlen, flag, &i0, &j0) : ksw_walk_from(z, qlen, tlen, job.end_bonus, flag, &i0, &j0)) {
+	if (ksw_walk_from(z, SPLICE, qlen, tlen, job.end_bonus, flag, &i0, &j0)) {
 		S.cig.resize((size_t)qlen + tlen + 2);
 		n = ksw_walk(qlen, tlen, w, SPLICE ? c.long_thres : 0, i0, j0, [&](int r, int col) { return (uint32_t)p[(size_t)r * ncol + col]; }, [&](int k, uint32_t word) { S.cig[(size_t)k] = word; });
 		if (!(flag & MM2GB_KSW_REV_CIGAR)) std::reverse(S.cig.begin(), S.cig.begin() + n);
@@ -147,7 +148,7 @@ void one_job(const KswConst &c, const KswSplice *sp, const mm2gb_ksw_job_t &job,
 void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
 {
 	static thread_local Scratch S;                        // carries only capacity between calls: one_job sizes and writes every array for a job before it reads it
-	one_job<false>(c, nullptr, job, query, target, nullptr, S, out, words);
+	one_job<false>(c, job, query, target, nullptr, S, out, words);
 }
 
 int ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
@@ -165,8 +166,7 @@ using namespace mm2gb;
 
 namespace {
 
-template <bool SPLICE>
-int host_batch(const KswConst &c, const KswSplice *sp, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, const uint8_t *junc,
+int host_batch(const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, const uint8_t *junc,
                int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(n_threads, 256), n_jobs));
@@ -182,7 +182,7 @@ int host_batch(const KswConst &c, const KswSplice *sp, int64_t n_jobs, const mm2
 			if (lo >= n_jobs) break;
 			for (int64_t j = lo; j < hi; ++j) {
 				who[(size_t)j] = k; where[(size_t)j] = (int64_t)words[(size_t)k].size();
-				one_job<SPLICE>(c, sp, jobs[j], queries + jobs[j].q_off, targets + jobs[j].t_off, junc ? junc + jobs[j].t_off : nullptr, S, res + j, words[(size_t)k]);
+				(c.splice ? one_job<true> : one_job<false>)(c, jobs[j], queries + jobs[j].q_off, targets + jobs[j].t_off, junc ? junc + jobs[j].t_off : nullptr, S, res + j, words[(size_t)k]);
 			}
 		}
 	};
@@ -199,13 +199,12 @@ int mm2gb_ksw_extd2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const m
                          int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	if (ksw_check("mm2gb_ksw_extd2_host", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
-	return host_batch<false>(ksw_derive(*param), nullptr, n_jobs, jobs, queries, targets, nullptr, n_threads, res, cigar, n_cigar_total);
+	return host_batch(ksw_derive(*param), n_jobs, jobs, queries, targets, nullptr, n_threads, res, cigar, n_cigar_total);
 }
 
 int mm2gb_ksw_exts2_host(const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
                          const uint8_t *junc, int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	if (ksw_check_splice("mm2gb_ksw_exts2_host", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
-	const KswSplice sp = ksw_derive_splice(*param);
-	return host_batch<true>(sp.k, &sp, n_jobs, jobs, queries, targets, junc, n_threads, res, cigar, n_cigar_total);
+	return host_batch(ksw_derive_splice(*param), n_jobs, jobs, queries, targets, junc, n_threads, res, cigar, n_cigar_total);
 }

@@ -10,15 +10,15 @@ int  ksw_check(const char *who, const mm2gb_ksw_param_t *param, int64_t n_jobs, 
                const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
 int  ksw_check_splice(const char *who, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
                       const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);        // ... and of mm2gb_ksw_exts2_*
-void ksw_store(const KswEz &z, int n_cigar, mm2gb_ksw_res_t *out);
-// cigar_off of every job from its n_cigar, and the batch's word array (malloc'd, NULL when empty)
 // one job on the calling thread (the body of mm2gb_ksw_extd2_host; the thread keeps its scratch): the record, and the job's words appended
 void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words);
+// cigar_off of every job from its n_cigar, and the batch's word array (malloc'd, NULL when empty)
 int  ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
 
-// the device form's planning and launches (ksw_kernels.hip); resident: the sequences already lie in the engine's arenas
+// the device forms' planning and launches (ksw_kernels.hip), c.splice choosing the DP; junc: the splice-aware form's annotation bytes, indexed
+// like targets, or null; resident: the sequences already lie in the engine's arenas
 struct Engine;
-int  ksw_extd2_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, bool resident,
-                   mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+int  ksw_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, const uint8_t *junc, bool resident,
+             mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
 
 } // namespace mm2gb

@@ -1,5 +1,5 @@
 // ksw_kernels.hip -- the dual-affine extension DP on the device (mm2gb_ksw_extd2_gpu) and the splice-aware one
-// (mm2gb_ksw_exts2_gpu), which has the same shape: k_ksw_exts2 beside k_ksw_extd2, one planner, one walk, one pack.
+// (mm2gb_ksw_exts2_gpu), which has the same shape: one fill kernel in two forms (k_ksw's SPLICE), one planner, one walk, one pack.
 // One workgroup per job, taken from a cost-ordered list.  The anti-diagonals are walked in order; the cells of a diagonal's band (rounded out
 // to groups of 16, as the definition in ksw_host.cpp has them) are dealt to the workgroup's threads by position: cell t belongs to thread
 // t mod NT for the whole job, so every array a cell reads only from itself (u, y, y2, the score byte, H) needs no barrier, and the three it
@@ -27,17 +27,23 @@ constexpr int KSW_LDS_STEP[4] = { 8 * 1024, 32 * 1024, 64 * 1024, KSW_LDS_MAX };
 
 struct KswDevJob { int64_t q_off, t_off, slab_off, cig_off; int32_t qlen, tlen, w, zdrop, end_bonus, flag, idx, ncol; };
 
-// bytes of a job's state image: H when the exact maximum is wanted, u v x x2 twice, y y2 and the score bytes, target and query
-__host__ __device__ inline int64_t ksw_image_bytes(int qlen, int tlen, int flag)
+// bytes of a job's state image: H when the exact maximum is wanted, u v x x2 twice, y, y2 (the splice-aware form: donor and acceptor) and
+// the score bytes, target and query
+inline int64_t ksw_image_bytes(bool splice, int qlen, int tlen, int flag)
 {
 	const int64_t T = ksw_round16(tlen);
-	return ((flag & MM2GB_KSW_APPROX_MAX) ? 0 : 4 * T) + 11 * T + T + ksw_round16(qlen);
+	return ((flag & MM2GB_KSW_APPROX_MAX) ? 0 : 4 * T) + (splice ? 12 : 11) * T + T + ksw_round16(qlen);
 }
 
-template <int NT, bool IN_LDS>
-__global__ __launch_bounds__(NT) void k_ksw_extd2(const KswConst c, const KswDevJob *__restrict__ jobs, int lo, int hi, int *counter,
-                                                  const uint8_t *__restrict__ queries, const uint8_t *__restrict__ targets, uint8_t *slab,
-                                                  uint8_t *gimg, int64_t gimg_stride, mm2gb_ksw_res_t *res)
+// The fill.  SPLICE: the splice-aware DP, the same walk over the anti-diagonals with ksw_cell_splice as the cell and donor[] / acceptor[] where
+// y2 is.  It has no band (job.w is the longer side, so ksw_band binds nowhere and no row is empty: that exit is left out), a row is at most
+// min(qlen, tlen) cells wide, and the image is proportional to the TARGET: a read's stretch across an intron of tens of kilobases has a
+// narrow row over a long image, which then lives in global memory.  donor[] / acceptor[] are filled from the staged target, every thread
+// the positions it owns, so the barrier after staging is the only one they need.  junc: their annotation bytes, or null (SPLICE only).
+template <int NT, bool IN_LDS, bool SPLICE>
+__global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *__restrict__ jobs, int lo, int hi, int *counter,
+                                            const uint8_t *__restrict__ queries, const uint8_t *__restrict__ targets, const uint8_t *__restrict__ junc, uint8_t *slab,
+                                            uint8_t *gimg, int64_t gimg_stride, mm2gb_ksw_res_t *res)
 {
 	extern __shared__ __align__(16) uint8_t smem[];
 	__shared__ uint64_t part[2][NT / 64];
@@ -56,17 +62,26 @@ __global__ __launch_bounds__(NT) void k_ksw_extd2(const KswConst c, const KswDev
 		const int qlen = job.qlen, tlen = job.tlen, flag = job.flag, w = job.w, ncol = job.ncol, T = ksw_round16(tlen);
 		const bool with_cigar = !(flag & MM2GB_KSW_SCORE_ONLY), approx = (flag & MM2GB_KSW_APPROX_MAX) != 0, right = (flag & MM2GB_KSW_RIGHT) != 0, generic = (flag & MM2GB_KSW_GENERIC_SC) != 0;
 		int32_t *H = (int32_t*)img;
-		int8_t *u = (int8_t*)img + (approx ? 0 : 4 * T), *v = u + 2 * T, *x = v + 2 * T, *x2 = x + 2 * T, *y = x2 + 2 * T, *y2 = y + T, *s = y2 + T;
+		int8_t *u = (int8_t*)img + (approx ? 0 : 4 * T), *v = u + 2 * T, *x = v + 2 * T, *x2 = x + 2 * T, *y = x2 + 2 * T;
+		int8_t *y2 = y + T, *don = y + T, *acc = don + T, *s = (SPLICE ? acc : y2) + T;      // y2, or donor and acceptor
 		uint8_t *tg = (uint8_t*)(s + T), *qy = tg + T;
 		for (int t = tid; t < T; t += NT) {
 			u[t] = u[T + t] = v[t] = v[T + t] = x[t] = x[T + t] = y[t] = c.ini;
-			x2[t] = x2[T + t] = y2[t] = c.ini2;
+			if constexpr (SPLICE) x2[t] = x2[T + t] = c.ini2; else x2[t] = x2[T + t] = y2[t] = c.ini2;
 			s[t] = 0;
 			if (!approx) H[t] = MM2GB_KSW_NEG_INF;
 			if (t < tlen) tg[t] = targets[job.t_off + t];
 		}
 		for (int t = tid; t < qlen; t += NT) qy[t] = queries[job.q_off + t];
 		__syncthreads();
+		if constexpr (SPLICE) {
+			const uint8_t *jn = junc ? junc + job.t_off : nullptr;
+			for (int t = tid; t < T; t += NT) {
+				int8_t d, a;
+				ksw_splice_sites(c, flag, [&](int i) { return tg[i]; }, jn, tlen, t, &d, &a);
+				don[t] = d; acc[t] = a;
+			}
+		}
 		uint8_t *p = slab + job.slab_off;
 		KswEz z;
 		ksw_ez_reset(z);
@@ -74,20 +89,24 @@ __global__ __launch_bounds__(NT) void k_ksw_extd2(const KswConst c, const KswDev
 		for (int r = 0; r < qlen + tlen - 1; ++r) {
 			int st0, en0;
 			ksw_band(r, qlen, tlen, w, &st0, &en0);
-			if (st0 > en0) { z.zdropped = 1; break; }
+			if constexpr (!SPLICE) if (st0 > en0) { z.zdropped = 1; break; }      // without a band no row is empty
 			const int st = st0 / 16 * 16, en = (en0 + 16) / 16 * 16 - 1, cur = (r & 1) * T, nxt = T - cur;
 			int8_t bx1 = c.ini, bx21 = c.ini2, bv1 = c.ini;
 			if (st > 0) { if (st - 1 >= last_st && st - 1 <= last_en) { bx1 = x[cur + st - 1]; bx21 = x2[cur + st - 1]; bv1 = v[cur + st - 1]; } }
 			else bv1 = ksw_edge(c, r);
-			if (en >= r && (r & (NT - 1)) == tid) { y[r] = c.ini; y2[r] = c.ini2; u[cur + r] = ksw_edge(c, r); }
+			if (en >= r && (r & (NT - 1)) == tid) { y[r] = c.ini; if constexpr (!SPLICE) y2[r] = c.ini2; u[cur + r] = ksw_edge(c, r); }
 			const int s_end = generic ? en0 + 1 : min(T, st0 + ((en0 - st0) / 16 + 1) * 16);
 			for (int t = st0 + ((tid - st0) & (NT - 1)); t < s_end; t += NT)
 				s[t] = ksw_score(c, s_mat, generic, ksw_target_byte((const uint8_t*)tg, (const uint8_t*)qy, qlen, tlen, T, t), ksw_query_byte((const uint8_t*)qy, qlen, r, t));
 			uint8_t *pr = p + (int64_t)r * ncol - st;
 			for (int t = st + ((tid - st) & (NT - 1)); t <= en; t += NT) {
 				const bool first = t == st;
-				const KswCell o = ksw_cell(c, right, s[t], first ? bx1 : x[cur + t - 1], first ? bv1 : v[cur + t - 1], first ? bx21 : x2[cur + t - 1], u[cur + t], y[t], y2[t]);
-				u[nxt + t] = o.u; v[nxt + t] = o.v; x[nxt + t] = o.x; x2[nxt + t] = o.x2; y[t] = o.y; y2[t] = o.y2;
+				const int8_t x1 = first ? bx1 : x[cur + t - 1], v1 = first ? bv1 : v[cur + t - 1], x21 = first ? bx21 : x2[cur + t - 1];
+				KswCell o;
+				if constexpr (SPLICE) o = ksw_cell_splice(c, right, s[t], x1, v1, x21, u[cur + t], y[t], don[t], acc[t]);
+				else o = ksw_cell(c, right, s[t], x1, v1, x21, u[cur + t], y[t], y2[t]);
+				u[nxt + t] = o.u; v[nxt + t] = o.v; x[nxt + t] = o.x; x2[nxt + t] = o.x2; y[t] = o.y;
+				if constexpr (!SPLICE) y2[t] = o.y2;
 				if (with_cigar && t - st < ncol) pr[t] = o.d;
 			}
 			bool stop;
@@ -119,122 +138,11 @@ __global__ __launch_bounds__(NT) void k_ksw_extd2(const KswConst c, const KswDev
 		}
 		// the record, and where the walk back starts (k_ksw_walk takes it from pad_ / cigar_off and clears them)
 		int i0 = 0, j0 = 0;
-		const bool walk = ksw_walk_from(z, qlen, tlen, job.end_bonus, flag, &i0, &j0);
+		const bool walk = ksw_walk_from(z, SPLICE, qlen, tlen, job.end_bonus, flag, &i0, &j0);
 		if (tid == 0) {
 			mm2gb_ksw_res_t o;
-			o.max = z.max; o.zdropped = z.zdropped; o.max_q = z.max_q; o.max_t = z.max_t; o.mqe = z.mqe; o.mqe_t = z.mqe_t; o.mte = z.mte; o.mte_q = z.mte_q;
-			o.score = z.score; o.reach_end = z.reach_end; o.n_cigar = 0; o.pad_ = walk; o.cigar_off = walk ? (int64_t)i0 << 32 | (uint32_t)j0 : 0;
-			res[job.idx] = o;
-		}
-	}
-}
-
-// bytes of a splice-aware job's image: H when the exact maximum is wanted, u v x x2 twice, y, donor, acceptor and the score bytes, target and query
-__host__ __device__ inline int64_t ksw_image_bytes_splice(int qlen, int tlen, int flag)
-{
-	const int64_t T = ksw_round16(tlen);
-	return ((flag & MM2GB_KSW_APPROX_MAX) ? 0 : 4 * T) + 12 * T + T + ksw_round16(qlen);
-}
-
-// The splice-aware DP: k_ksw_extd2's walk over the anti-diagonals with ksw_cell_splice as the cell.  There is no band (job.w is the longer side,
-// so ksw_band binds nowhere), a row is at most min(qlen, tlen) cells wide, and the image is proportional to the TARGET: a read's stretch
-// across an intron of tens of kilobases has a narrow row over a long image, which then lives in global memory.  donor[] / acceptor[] are
-// filled from the staged target, every thread the positions it owns, so the barrier after staging is the only one they need.
-template <int NT, bool IN_LDS>
-__global__ __launch_bounds__(NT) void k_ksw_exts2(const KswSplice sp, const KswDevJob *__restrict__ jobs, int lo, int hi, int *counter,
-                                                  const uint8_t *__restrict__ queries, const uint8_t *__restrict__ targets, const uint8_t *__restrict__ junc, uint8_t *slab,
-                                                  uint8_t *gimg, int64_t gimg_stride, mm2gb_ksw_res_t *res)
-{
-	extern __shared__ __align__(16) uint8_t smem[];
-	__shared__ uint64_t part[2][NT / 64];
-	__shared__ int s_job;
-	__shared__ int8_t s_mat[25];
-	const KswConst &c = sp.k;
-	const int tid = threadIdx.x;
-	if (tid < 25) s_mat[tid] = c.mat[tid];                  // visible after the loop's first barrier
-	uint8_t *img;
-	if constexpr (IN_LDS) img = smem; else img = gimg + (int64_t)blockIdx.x * gimg_stride;
-	for (;;) {
-		__syncthreads();                                    // the last job's image and s_job are done with
-		if (tid == 0) s_job = lo + atomicAdd(counter, 1);
-		__syncthreads();
-		if (s_job >= hi) break;
-		const KswDevJob job = jobs[s_job];
-		const int qlen = job.qlen, tlen = job.tlen, flag = job.flag, w = job.w, ncol = job.ncol, T = ksw_round16(tlen);
-		const bool with_cigar = !(flag & MM2GB_KSW_SCORE_ONLY), approx = (flag & MM2GB_KSW_APPROX_MAX) != 0, right = (flag & MM2GB_KSW_RIGHT) != 0, generic = (flag & MM2GB_KSW_GENERIC_SC) != 0;
-		int32_t *H = (int32_t*)img;
-		int8_t *u = (int8_t*)img + (approx ? 0 : 4 * T), *v = u + 2 * T, *x = v + 2 * T, *x2 = x + 2 * T, *y = x2 + 2 * T, *don = y + T, *acc = don + T, *s = acc + T;
-		uint8_t *tg = (uint8_t*)(s + T), *qy = tg + T;
-		for (int t = tid; t < T; t += NT) {
-			u[t] = u[T + t] = v[t] = v[T + t] = x[t] = x[T + t] = y[t] = c.ini;
-			x2[t] = x2[T + t] = c.ini2;
-			s[t] = 0;
-			if (!approx) H[t] = MM2GB_KSW_NEG_INF;
-			if (t < tlen) tg[t] = targets[job.t_off + t];
-		}
-		for (int t = tid; t < qlen; t += NT) qy[t] = queries[job.q_off + t];
-		__syncthreads();
-		const uint8_t *jn = junc ? junc + job.t_off : nullptr;
-		for (int t = tid; t < T; t += NT) {
-			int8_t d, a;
-			ksw_splice_sites(sp, flag, [&](int i) { return tg[i]; }, jn, tlen, t, &d, &a);
-			don[t] = d; acc[t] = a;
-		}
-		uint8_t *p = slab + job.slab_off;
-		KswEz z;
-		ksw_ez_reset(z);
-		int32_t H0 = 0; int H0_t = 0, last_st = -1, last_en = -1;
-		for (int r = 0; r < qlen + tlen - 1; ++r) {
-			int st0, en0;
-			ksw_band(r, qlen, tlen, w, &st0, &en0);
-			const int st = st0 / 16 * 16, en = (en0 + 16) / 16 * 16 - 1, cur = (r & 1) * T, nxt = T - cur;
-			int8_t bx1 = c.ini, bx21 = c.ini2, bv1 = c.ini;
-			if (st > 0) { if (st - 1 >= last_st && st - 1 <= last_en) { bx1 = x[cur + st - 1]; bx21 = x2[cur + st - 1]; bv1 = v[cur + st - 1]; } }
-			else bv1 = ksw_edge(c, r);
-			if (en >= r && (r & (NT - 1)) == tid) { y[r] = c.ini; u[cur + r] = ksw_edge(c, r); }
-			const int s_end = generic ? en0 + 1 : min(T, st0 + ((en0 - st0) / 16 + 1) * 16);
-			for (int t = st0 + ((tid - st0) & (NT - 1)); t < s_end; t += NT)
-				s[t] = ksw_score(c, s_mat, generic, ksw_target_byte((const uint8_t*)tg, (const uint8_t*)qy, qlen, tlen, T, t), ksw_query_byte((const uint8_t*)qy, qlen, r, t));
-			uint8_t *pr = p + (int64_t)r * ncol - st;
-			for (int t = st + ((tid - st) & (NT - 1)); t <= en; t += NT) {
-				const bool first = t == st;
-				const KswCell o = ksw_cell_splice(c, right, s[t], first ? bx1 : x[cur + t - 1], first ? bv1 : v[cur + t - 1], first ? bx21 : x2[cur + t - 1], u[cur + t], y[t], don[t], acc[t]);
-				u[nxt + t] = o.u; v[nxt + t] = o.v; x[nxt + t] = o.x; x2[nxt + t] = o.x2; y[t] = o.y;
-				if (with_cigar && t - st < ncol) pr[t] = o.d;
-			}
-			bool stop;
-			if (!approx) {
-				int32_t Hl = 0;
-				if (r > 0 && en0 > 0 && (en0 & (NT - 1)) == tid) Hl = H[en0 - 1];      // before its owner moves it on
-				__syncthreads();
-				uint64_t key = 0;
-				for (int t = st0 + ((tid - st0) & (NT - 1)); t <= en0; t += NT) {
-					int32_t h;
-					if (t == en0) h = r == 0 ? v[nxt] - c.qe0 : en0 > 0 ? Hl + u[nxt + en0] : H[en0] + v[nxt + en0];
-					else h = H[t] + v[nxt + t];
-					H[t] = h;
-					const uint64_t k = ksw_max_key(h, t, st0, en0);
-					key = k > key ? k : key;
-				}
-				for (int d = 32; d; d >>= 1) { const uint64_t o = __shfl_xor((unsigned long long)key, d, 64); key = o > key ? o : key; }
-				if ((tid & 63) == 0) part[r & 1][tid >> 6] = key;
-				__syncthreads();
-				key = part[r & 1][0];
-				for (int k = 1; k < NT / 64; ++k) key = part[r & 1][k] > key ? part[r & 1][k] : key;
-				stop = ksw_row_exact(z, c, qlen, tlen, job.zdrop, r, st0, en0, en, ksw_key_H(key), ksw_key_t(key, st0, en0), H[en0], H[st0]);
-			} else {
-				__syncthreads();
-				stop = ksw_row_approx(z, c, qlen, tlen, job.zdrop, flag, r, st0, en0, H0, H0_t, [=](int t) { return (int32_t)v[nxt + t]; }, [=](int t) { return (int32_t)u[nxt + t]; });
-			}
-			if (stop) break;
-			last_st = st; last_en = en;
-		}
-		int i0 = 0, j0 = 0;
-		const bool walk = ksw_walk_from_splice(z, qlen, tlen, flag, &i0, &j0);
-		if (tid == 0) {
-			mm2gb_ksw_res_t o;
-			o.max = z.max; o.zdropped = z.zdropped; o.max_q = z.max_q; o.max_t = z.max_t; o.mqe = z.mqe; o.mqe_t = z.mqe_t; o.mte = z.mte; o.mte_q = z.mte_q;
-			o.score = z.score; o.reach_end = z.reach_end; o.n_cigar = 0; o.pad_ = walk; o.cigar_off = walk ? (int64_t)i0 << 32 | (uint32_t)j0 : 0;
+			ksw_store(z, 0, &o);
+			o.pad_ = walk; o.cigar_off = walk ? (int64_t)i0 << 32 | (uint32_t)j0 : 0;
 			res[job.idx] = o;
 		}
 	}
@@ -280,31 +188,30 @@ int64_t slab_budget()
 	return (int64_t)(mb > 0 ? mb : 4096) << 20;
 }
 
-// sp: the splice-aware kernel (junc: its annotation bytes in kw_junc, or none)
-template <int NT, bool IN_LDS>
-int launch_one(Engine &e, const KswConst &c, const KswSplice *sp, bool junc, const Launch &L, int k, int grid)
+using Fill = void (*)(KswConst, const KswDevJob*, int, int, int*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, int64_t, mm2gb_ksw_res_t*);
+template <bool IN_LDS, bool SPLICE>
+constexpr Fill FILL[3] = { k_ksw<KSW_NT[0], IN_LDS, SPLICE>, k_ksw<KSW_NT[1], IN_LDS, SPLICE>, k_ksw<KSW_NT[2], IN_LDS, SPLICE> };
+
+// launch k of a call: the fill for its classes and c.splice (junc: its annotation bytes are in kw_junc)
+int launch_one(Engine &e, const KswConst &c, bool junc, const Launch &L, int k, int grid)
 {
-	if (sp) {
-		if (IN_LDS) MM2GB_HIP(hipFuncSetAttribute((const void*)k_ksw_exts2<NT, IN_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-		hipLaunchKernelGGL((k_ksw_exts2<NT, IN_LDS>), dim3(grid), dim3(NT), IN_LDS ? (size_t)L.lds : 0, e.stream, *sp, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, (int*)e.kw_cnt.ptr + k,
-		                   (const uint8_t*)e.kw_q.ptr, (const uint8_t*)e.kw_t.ptr, junc ? (const uint8_t*)e.kw_junc.ptr : nullptr, (uint8_t*)e.kw_slab.ptr, (uint8_t*)e.kw_img.ptr, L.img,
-		                   (mm2gb_ksw_res_t*)e.kw_res.ptr);
-	} else {
-		if (IN_LDS) MM2GB_HIP(hipFuncSetAttribute((const void*)k_ksw_extd2<NT, IN_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-		hipLaunchKernelGGL((k_ksw_extd2<NT, IN_LDS>), dim3(grid), dim3(NT), IN_LDS ? (size_t)L.lds : 0, e.stream, c, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, (int*)e.kw_cnt.ptr + k,
-		                   (const uint8_t*)e.kw_q.ptr, (const uint8_t*)e.kw_t.ptr, (uint8_t*)e.kw_slab.ptr, (uint8_t*)e.kw_img.ptr, L.img, (mm2gb_ksw_res_t*)e.kw_res.ptr);
-	}
+	const bool in_lds = L.lds_class < 4;
+	const Fill fill = in_lds ? (c.splice ? FILL<true, true> : FILL<true, false>)[L.nt_class] : (c.splice ? FILL<false, true> : FILL<false, false>)[L.nt_class];
+	if (in_lds) MM2GB_HIP(hipFuncSetAttribute((const void*)fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+	hipLaunchKernelGGL(fill, dim3(grid), dim3(KSW_NT[L.nt_class]), in_lds ? (size_t)L.lds : 0, e.stream, c, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, (int*)e.kw_cnt.ptr + k,
+	                   (const uint8_t*)e.kw_q.ptr, (const uint8_t*)e.kw_t.ptr, junc ? (const uint8_t*)e.kw_junc.ptr : nullptr, (uint8_t*)e.kw_slab.ptr, (uint8_t*)e.kw_img.ptr, L.img,
+	                   (mm2gb_ksw_res_t*)e.kw_res.ptr);
 	MM2GB_HIP(hipGetLastError());
 	return 0;
 }
 
 } // namespace
 
-// The planning and the launches behind mm2gb_ksw_extd2_gpu and, with sp (and junc, indexed like targets, or null), mm2gb_ksw_exts2_gpu.  resident: the jobs' sequences already lie in kw_q / kw_t at their q_off / t_off
+// The planning and the launches behind mm2gb_ksw_extd2_gpu and, with c.splice (and junc, indexed like targets, or null), mm2gb_ksw_exts2_gpu.  resident: the jobs' sequences already lie in kw_q / kw_t at their q_off / t_off
 // (the alignment call's gather kernel put them there, align_kernels.hip) and nothing is uploaded.  Either way the records (n_cigar set) stay in
 // kw_res, the packed words in kw_pack and their offsets in kw_off until the engine's next call.
-static int ksw_run(Engine &e, const KswConst &c, const KswSplice *sp, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
-                   const uint8_t *junc, bool resident, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+int ksw_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, const uint8_t *junc, bool resident,
+            mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
 	if (n_jobs >= ((int64_t)1 << 31)) return fail("mm2gb_ksw_extd2_gpu / mm2gb_ksw_exts2_gpu: a batch is limited to 2^31 jobs");
 	e.kw_ms[0] = e.kw_ms[1] = 0;
@@ -320,10 +227,10 @@ static int ksw_run(Engine &e, const KswConst &c, const KswSplice *sp, int64_t n_
 		ksw_store(reset, 0, res + j);
 		if (c.early || b.qlen <= 0 || b.tlen <= 0) continue;
 		Plan P;
-		const int w = ksw_width(b.qlen, b.tlen, sp ? -1 : b.w), ncol = ksw_ncol16(b.qlen, b.tlen, w);
+		const int w = ksw_width(b.qlen, b.tlen, c.splice ? -1 : b.w), ncol = ksw_ncol16(b.qlen, b.tlen, w);
 		const bool with_cigar = !(b.flag & MM2GB_KSW_SCORE_ONLY);
 		P.d = { b.q_off, b.t_off, 0, cig_words, b.qlen, b.tlen, w, b.zdrop, b.end_bonus, b.flag, (int32_t)j, ncol };
-		P.img = sp ? ksw_image_bytes_splice(b.qlen, b.tlen, b.flag) : ksw_image_bytes(b.qlen, b.tlen, b.flag);
+		P.img = ksw_image_bytes(c.splice, b.qlen, b.tlen, b.flag);
 		P.slab = with_cigar ? ((int64_t)(b.qlen + b.tlen - 1) * ncol + 15) / 16 * 16 : 0;
 		P.cost = (int64_t)(b.qlen + b.tlen - 1) * ((ncol + KSW_NT[2] - 1) / KSW_NT[2]);
 		const int nt_class = ncol <= KSW_BAND[0] ? 0 : ncol <= KSW_BAND[1] ? 1 : 2;
@@ -374,15 +281,10 @@ static int ksw_run(Engine &e, const KswConst &c, const KswSplice *sp, int64_t n_
 	for (size_t k = 0; k < launches.size(); ++k) {
 		const Launch &L = launches[k];
 		const int nt = KSW_NT[L.nt_class], n = L.hi - L.lo;
-		const bool in_lds = L.lds_class < 4;
-		const int per_cu = in_lds ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min(2048 / nt, 8), (160 * 1024) / (L.lds + 1024))) : 2;
-		const int grid = std::min(n, e.n_cu * per_cu);
-		int rc;
-		if (in_lds) rc = L.nt_class == 0 ? launch_one<KSW_NT[0], true>(e, c, sp, junc != nullptr, L, (int)k, grid) : L.nt_class == 1 ? launch_one<KSW_NT[1], true>(e, c, sp, junc != nullptr, L, (int)k, grid) : launch_one<KSW_NT[2], true>(e, c, sp, junc != nullptr, L, (int)k, grid);
-		else        rc = L.nt_class == 0 ? launch_one<KSW_NT[0], false>(e, c, sp, junc != nullptr, L, (int)k, grid) : L.nt_class == 1 ? launch_one<KSW_NT[1], false>(e, c, sp, junc != nullptr, L, (int)k, grid) : launch_one<KSW_NT[2], false>(e, c, sp, junc != nullptr, L, (int)k, grid);
-		if (rc) return -1;
+		const int per_cu = L.lds_class < 4 ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min(2048 / nt, 8), (160 * 1024) / (L.lds + 1024))) : 2;
+		if (launch_one(e, c, junc != nullptr, L, (int)k, std::min(n, e.n_cu * per_cu))) return -1;
 		if (L.slab > 0) {
-			hipLaunchKernelGGL(k_ksw_walk, dim3((n + 63) / 64), dim3(64), 0, e.stream, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, sp ? c.long_thres : 0, (const uint8_t*)e.kw_slab.ptr, (uint32_t*)e.kw_cig.ptr,
+			hipLaunchKernelGGL(k_ksw_walk, dim3((n + 63) / 64), dim3(64), 0, e.stream, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, c.splice ? c.long_thres : 0, (const uint8_t*)e.kw_slab.ptr, (uint32_t*)e.kw_cig.ptr,
 			                   (mm2gb_ksw_res_t*)e.kw_res.ptr);
 			MM2GB_HIP(hipGetLastError());
 		}
@@ -416,44 +318,28 @@ static int ksw_run(Engine &e, const KswConst &c, const KswSplice *sp, int64_t n_
 	return 0;
 }
 
-int ksw_extd2_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, bool resident,
-                  mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
-{
-	return ksw_run(e, c, nullptr, n_jobs, jobs, queries, targets, nullptr, resident, res, cigar, n_cigar_total);
-}
-
-int ksw_extd2_gpu(Engine &e, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
-                  mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
-{
-	if (ksw_check("mm2gb_ksw_extd2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
-	return ksw_extd2_run(e, ksw_derive(*param), n_jobs, jobs, queries, targets, false, res, cigar, n_cigar_total);
-}
-
-int ksw_exts2_gpu(Engine &e, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
-                  const uint8_t *junc, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
-{
-	if (ksw_check_splice("mm2gb_ksw_exts2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
-	const KswSplice sp = ksw_derive_splice(*param);
-	return ksw_run(e, sp.k, &sp, n_jobs, jobs, queries, targets, junc, false, res, cigar, n_cigar_total);
-}
-
 } // namespace mm2gb
 
-int mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
-                        const uint8_t *targets, const uint8_t *junc, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
-{
-	return eng ? mm2gb::ksw_exts2_gpu(eng->e, param, n_jobs, jobs, queries, targets, junc, res, cigar, n_cigar_total) : mm2gb::fail("mm2gb: null engine");
-}
+using namespace mm2gb;
 
 int mm2gb_ksw_extd2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
                         const uint8_t *targets, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
 {
-	return eng ? mm2gb::ksw_extd2_gpu(eng->e, param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total) : mm2gb::fail("mm2gb: null engine");
+	if (!eng) return fail("mm2gb: null engine");
+	if (ksw_check("mm2gb_ksw_extd2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
+	return ksw_run(eng->e, ksw_derive(*param), n_jobs, jobs, queries, targets, nullptr, false, res, cigar, n_cigar_total);
+}
+
+int mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
+                        const uint8_t *targets, const uint8_t *junc, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	if (!eng) return fail("mm2gb: null engine");
+	if (ksw_check_splice("mm2gb_ksw_exts2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
+	return ksw_run(eng->e, ksw_derive_splice(*param), n_jobs, jobs, queries, targets, junc, false, res, cigar, n_cigar_total);
 }
 
 int mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2)
 {
-	using namespace mm2gb;
 	if (consts6) { consts6[0] = KSW_NT[0]; consts6[1] = KSW_NT[1]; consts6[2] = KSW_NT[2]; consts6[3] = KSW_BAND[0]; consts6[4] = KSW_BAND[1]; consts6[5] = KSW_LDS_MAX; }
 	if (ms2) { if (!eng) return fail("mm2gb: null engine"); ms2[0] = eng->e.kw_ms[0]; ms2[1] = eng->e.kw_ms[1]; }
 	return 0;

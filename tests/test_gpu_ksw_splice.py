@@ -137,6 +137,47 @@ def test_arenas_are_reused(eng):
     kc.assert_same(first, mm.ksw_exts2_host_batch(p, *small), "the small batch", small[0])
 
 
+def test_both_forms_take_turns_on_one_engine(eng):
+    """The two DPs are one kernel body and share the engine's arenas: a dual-affine batch, a splice-aware one, and both again on the same
+    engine.  Each batch has about 40 jobs over the three workgroup sizes (rows of at most 64, at most 256 and more cells), both maxima, and
+    a job whose image lives in global memory: 10 000 x 10 000 at w = 50 for the dual-affine form (16 T + Q bytes; the 10 240 x 10 240 pair
+    this was first written down with is 1.05 x 10^8 cells and refused by the cell limit, which the test asserts, so it is the largest
+    square under the limit), a 300-base query on a 12 800-base target for the splice-aware one (13 T alone is beyond LDS).  Every run
+    equals the host form, and a repeat is its first run byte for byte."""
+    info = eng.ksw_info()
+    rng = np.random.default_rng(28)
+    pd, ps = mm.ksw_param(), mm.ksw_splice_param()
+    sizes = (30, 200, 420)                                                    # min(qlen, tlen): rows of 48, 224 and 448 cells
+    dual, splice = [], []
+    for k in range(39):
+        n, flag = sizes[k % 3], (0, A, X | R | V, A | D | X, R, A | V)[k // 3 % 6]
+        q, t = kc.make_pair(rng, 5, n + int(rng.integers(0, 40)), n, err=0.1)
+        dual.append((q, t, dict(w=(-1, n, 500)[k // 3 % 3], zdrop=(200, -1)[k % 2], end_bonus=5, flag=flag)))
+        q, t, junc = sc.make_intron_pair(rng, 5, n // 2, n - n // 2, int(rng.integers(20, 400)), sc.MOTIFS[k % 4], 0.05)
+        splice.append((exactly(q, n), t, dict(zdrop=(200, -1)[k % 2], flag=flag | (FOR, FOR | REV | FLANK)[k // 3 % 2], junc=junc)))
+    big = kc.make_pair(rng, 5, 10000, 10000, err=0.05)
+    dual.append(big + (dict(w=50, flag=0),))
+    for flag in (FOR, FOR | A):
+        q, t, junc = sc.make_intron_pair(rng, 5, 150, 150, 12800 - 300, sc.MOTIFS[1], 0.03)
+        splice.append((exactly(q, 300), t, dict(flag=flag, junc=junc)))
+    assert 16 * 10000 + 10000 > info["lds_max"] and 13 * 12800 > info["lds_max"]
+    with pytest.raises(mm.Mm2gbError, match="MM2GB_KSW_MAX_CELLS"):
+        eng.ksw_extd2([(np.zeros(10240, np.uint8), np.zeros(10240, np.uint8))], w=50)
+    dual, splice = mm.ksw_jobs(dual), mm.ksw_splice_jobs(splice)
+    for jobs in (dual[0], splice[0]):                                         # the three classes, and both maxima
+        rows = np.minimum(jobs["qlen"], jobs["tlen"])
+        rows = ((np.where(jobs["w"] >= 0, np.minimum(rows, jobs["w"] + 1), rows) + 15) // 16 + 1) * 16
+        assert (rows <= info["band"][0]).any() and ((rows > info["band"][0]) & (rows <= info["band"][1])).any() and (rows > info["band"][1]).any()
+        assert (jobs["flag"] & A).any() and not (jobs["flag"] & A).all()
+    want_d, want_s = mm.ksw_extd2_host_batch(pd, *dual, threads=16), mm.ksw_exts2_host_batch(ps, *splice, threads=16)
+    runs = [eng.ksw_extd2_batch(pd, *dual), eng.ksw_exts2_batch(ps, *splice), eng.ksw_extd2_batch(pd, *dual), eng.ksw_exts2_batch(ps, *splice)]
+    for k, got in enumerate(runs):
+        kc.assert_same(got, (want_d, want_s)[k % 2], ("dual-affine", "splice-aware")[k % 2] + (" batch", " batch again")[k // 2], (dual, splice)[k % 2][0])
+    for first, again in ((runs[0], runs[2]), (runs[1], runs[3])):
+        assert first[0].tobytes() == again[0].tobytes() and first[1].tobytes() == again[1].tobytes()
+    assert sc.has_N(*runs[1]).sum() >= 10 and runs[0][0]["n_cigar"][-1] > 0
+
+
 def test_several_launches(eng):
     """A slab budget of 1 MiB cuts a batch whose direction bytes need more into several launches; the answers do not change."""
     rng = np.random.default_rng(27)
