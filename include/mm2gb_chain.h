@@ -479,6 +479,9 @@ int  mm2gb_ksw_extd2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, in
  * two classes, [5] the largest state image (bytes) kept in LDS -- a larger one lives in global memory; ms2 (optional): the last call's
  * kernel time, [0] fill + backtrack, [1] CIGAR packing */
 int  mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2);
+/* jobs2: the DP jobs the engine has launched since it was made (by either form of the DP, through any call) with their state image
+ * [0] in LDS, [1] in global memory (the class of a job whose image, proportional to its target, does not fit) */
+int  mm2gb_ksw_gpu_class_jobs(mm2gb_engine_t *eng, int64_t *jobs2);
 
 /* ---- splice-aware DP, batched: ksw2's ksw_exts2_sse (ksw2_exts2_sse.c), the alignment of a cDNA / RNA read's stretches across
  *      introns -- one short gap (q, e), one long gap on the target side only (q2, no extension cost) that opens at donor[] and closes at
@@ -552,6 +555,42 @@ int  mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int
                           const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out);
 void mm2gb_align_out_free(mm2gb_align_out_t *out);
 
+/* ---- spliced alignment of hits, batched: mm_align_skeleton under MM_F_SPLICE -- the end filter of
+ *      mm_fix_bad_ends_splice, every stretch through ksw_exts2 (above), no inversions, and with MM_F_SPLICE_FOR and MM_F_SPLICE_REV both
+ *      set every chain aligned once per transcript strand, the larger dp_score kept (trans_strand 1 / 2; 3 on a tie, where the trial
+ *      (qlen + dp_score) & 1 is kept).  A second set of calls on the records of the calls above, which keep refusing MM_F_SPLICE.
+ *      mm2gb_align_splice_opt_init sets options.c's values for "splice", "cdna" (the same) or "splice:hq", with ONE departure: the preset's
+ *      max_sw_mat = 0 (no limit) is MM2GB_KSW_MAX_CELLS here, mm_mapopt_init's own default.  max_sw_mat outside 1 .. MM2GB_KSW_MAX_CELLS is
+ *      refused as above and a stretch over it gives the reset record with zdropped = 1 (mm_align_pair's rule); the reference equals these
+ *      calls when it runs with the same value (--cap-sw-mem=100000000 after -x splice).
+ *      Flags honoured: MM_F_SPLICE_FOR alone, MM_F_SPLICE_REV alone (one trial, align.c:997-1000), both, MM_F_SPLICE_FLANK, MM_F_NO_END_FLT,
+ *      MM_F_FOR_ONLY, MM_F_REV_ONLY; FOR or REV implies SPLICE (options.c:70-71).  Junction annotation is absent (no --junc-bed), which
+ *      equals the zero bytes mm_idx_bed_junc gives without one.
+ *      Refused by name, error text set, nothing run and *out zeroed: a flag word without MM_F_SPLICE, MM_F_SR, MM_F_QSTRAND, MM_F_EQX;
+ *      e <= 0; an index with MM2GB_I_HPC; gap penalties, noncan or junc_bonus that mm2gb_ksw_exts2_* refuses; and what the calls above
+ *      refuse about max_sw_mat, records, anchors and segments.  splice_counts (may be NULL): the paths met, see MM2GB_SPL_N_*; the
+ *      MM2GB_ALN_N_* counts in *out are those of the trials kept, except jobs, cells and cells_discarded, which count every trial.
+ *      The host form is the definition; the device form equals it: the two trials of a chain are two DP jobs on the same gathered bytes. ---- */
+#define MM2GB_F_SPLICE_FOR   0x100LL
+#define MM2GB_F_SPLICE_REV   0x200LL
+#define MM2GB_F_SPLICE_FLANK 0x40000LL
+typedef struct { mm2gb_align_opt_t base; int32_t noncan, junc_bonus, anchor_ext_len, anchor_ext_shift; } mm2gb_align_splice_opt_t;
+/* trial_*: which trial a chain's record came from (for = trial 0); end_flt_*: an anchor dropped at the head / tail, or the probe run and the
+ * anchor kept; *_intron: an N in the words of a left extension, a right extension, a gap fill (trials kept); tail_other_strand: a split-off
+ * tail whose trans_strand differs from the record before it; n_seam_merged: two N words merged where two stretches meet;
+ * noncanonical_intron: an N of a finished record whose ends are neither GT..AG nor CT..AC; single_trial: chains aligned once */
+enum { MM2GB_SPL_N_TRIAL_FOR_WON, MM2GB_SPL_N_TRIAL_REV_WON, MM2GB_SPL_N_TRIAL_TIE_KEPT_0, MM2GB_SPL_N_TRIAL_TIE_KEPT_1, MM2GB_SPL_N_END_FLT_HEAD, MM2GB_SPL_N_END_FLT_TAIL,
+       MM2GB_SPL_N_END_FLT_PROBE_KEPT, MM2GB_SPL_N_LEFT_EXT_INTRON, MM2GB_SPL_N_RIGHT_EXT_INTRON, MM2GB_SPL_N_FILL_INTRON, MM2GB_SPL_N_FILL_TWO_PASS, MM2GB_SPL_N_SPLIT,
+       MM2GB_SPL_N_TAIL_OTHER_STRAND, MM2GB_SPL_N_N_SEAM_MERGED, MM2GB_SPL_N_NONCANONICAL_INTRON, MM2GB_SPL_N_SINGLE_TRIAL, MM2GB_SPL_N_REV_CHAIN, MM2GB_SPL_N_OVER_SW_MAT,
+       MM2GB_SPL_N_COUNTS };
+int  mm2gb_align_splice_opt_init(mm2gb_align_splice_opt_t *opt, const char *preset);
+int  mm2gb_align_regs_splice_host(const mm2gb_align_splice_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                                  int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts);
+int  mm2gb_align_regs_splice_gpu(mm2gb_engine_t *eng, const mm2gb_align_splice_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
+                                 const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off,
+                                 const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out, int64_t *splice_counts);
+
 /* ---- the text of a PAF line's alignment tags, batched: for record i the bytes text[text_off[i] .. text_off[i+1]) are what
  *      mm_write_paf3 appends after rl:i (format.c:322-329): "\tcg:Z:" and "%d%c" per CIGAR word with MM2GB_TEXT_CG, then "\tcs:Z:..." with
  *      MM2GB_TEXT_CS (the long form, =ACGT instead of :n, with MM2GB_TEXT_CS_LONG as well) or "\tMD:Z:..." with MM2GB_TEXT_MD (write_cs_core,
@@ -576,6 +615,16 @@ int  mm2gb_aln_text_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char
  * call's seconds: [0] residues to the device (0 where they were resident), [1] the host's pass over the words (checks, word starts, slices),
  * [2] words and slices up, kernels, [3] the text back */
 int  mm2gb_aln_text_gpu_info(mm2gb_engine_t *eng, int64_t *consts2, double *s4);
+/* The same two calls for records of the spliced alignment calls: operation 3 (N) is accepted beside M, I and D.  cg:Z: the letter N.  cs:Z, short
+ * and long: "~", the intron's first two target bases in lower case, its length, its last two (format.c:179-184); a run of matches is closed
+ * before it as before any event.  MD:Z: the target moves on, nothing is printed and the run stays open (format.c:212-213).  Refused as
+ * above, and an N word shorter than 2 (format.c:180 asserts it).  The device form takes an N word as ONE column. */
+int  mm2gb_aln_text_splice_host(int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                                const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
+                                int n_threads, int64_t **text_off, char **text);
+int  mm2gb_aln_text_splice_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                               const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
+                               int64_t **text_off, char **text);
 
 /* ---- the mapper with base-level alignment (minimap2 -c, --cs, --MD; csrc/mapper.cpp): mm2gb_map_reads / mm2gb_map_reads_stream with a
  *      mm2gb_map_aln_t.  After mm_filter_strand_retained the batch's surviving records go through mm2gb_align_regs_* in one call (map.c:342-352;
@@ -596,6 +645,27 @@ int  mm2gb_map_reads_aln(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, co
 int  mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
                                 int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs,
                                 const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra /* 3, optional; summed over chunks */);
+
+/* ---- the mapper for spliced reads (minimap2 -x splice -c, --cs, --MD): the two calls above with a mm2gb_map_splice_t.  The stages are the
+ *      same but for: is_cdna = 1 in the chaining DP (map.c:419, 695; max_dist_x = max_gap_ref as always), no re-chaining stage (map.c:698),
+ *      the spliced alignment and text calls, and "ts:A:+" / "ts:A:-" after nn:i for trans_strand 1 / 2 (nothing for 0 and 3; format.c:281-282).
+ *      mm2gb_map_opt_init_splice: mm2gb_map_opt_init, then the preset's bw = bw_long = max_gap_ref = 200000 and max_gap = 2000.  The index is
+ *      built with k = 15, w = 5.  The calls always align; junction annotation is not taken.  Equal to
+ *      minimap2 -x splice --cap-sw-mem=100000000 --max-chain-skip=2147483647 (the max_sw_mat departure of mm2gb_align_splice_opt_init). ---- */
+typedef struct {
+	const char *const *ref_seqs;      /* the reference sequences as text, in the index's order */
+	mm2gb_align_splice_opt_t opt;
+	int32_t what;                     /* MM2GB_TEXT_* */
+	int32_t align_on_device;          /* as in mm2gb_map_aln_t */
+	int32_t text_on_device;
+} mm2gb_map_splice_t;
+void mm2gb_map_opt_init_splice(mm2gb_map_opt_t *opt);
+int  mm2gb_map_reads_splice(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                            const mm2gb_map_opt_t *opt, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                            char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra /* 3, optional */);
+int  mm2gb_map_reads_stream_splice(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                   int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                   const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra /* 3, optional; summed over chunks */);
 
 #ifdef __cplusplus
 }

@@ -89,7 +89,9 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free",
                 "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split",
                 "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag",
-                "mm2gb_align_opt_init", "mm2gb_align_regs_host", "mm2gb_align_regs_gpu", "mm2gb_align_out_free"]
+                "mm2gb_align_opt_init", "mm2gb_align_regs_host", "mm2gb_align_regs_gpu", "mm2gb_align_out_free",
+                "mm2gb_align_splice_opt_init", "mm2gb_align_regs_splice_host", "mm2gb_align_regs_splice_gpu", "mm2gb_aln_text_splice_host", "mm2gb_aln_text_splice_gpu",
+                "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -627,7 +629,17 @@ def _engine_ksw_info(self):
 
 Engine.ksw_extd2 = _engine_ksw_extd2
 Engine.ksw_extd2_batch = _engine_ksw_extd2_batch
+def _engine_ksw_class_jobs(self):
+    """mm2gb_ksw_gpu_class_jobs: the DP jobs launched on this engine so far with their image (in LDS, in global memory)."""
+    c = (C.c_int64 * 2)()
+    fn = lib().mm2gb_ksw_gpu_class_jobs
+    fn.argtypes = [C.c_void_p, C.c_void_p]
+    _check(fn(self._h, c))
+    return int(c[0]), int(c[1])
+
+
 Engine.ksw_info = _engine_ksw_info
+Engine.ksw_class_jobs = _engine_ksw_class_jobs
 
 
 # ---- splice-aware DP (mm2gb_ksw_exts2_host / _gpu): ksw2's ksw_exts2_sse, batched.  Jobs, records and words as above; w and end_bonus are not
@@ -725,7 +737,7 @@ def cigar_string(words):
     return "".join(f"{int(w) >> 4}{'MIDNSHP=XB'[int(w) & 0xf]}" for w in words)
 
 
-def _align_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail):
+def _align_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail, opt_type=None, after=()):
     """reads: list of bytes; regs / anchors: one REG_DTYPE array / (n,2) uint64 array per read.  Returns per read (regs, aln, words) with
     aln.cigar_off counted within the read's words, and dict(counts=..., seconds=...)."""
     refs = [bytes(s) for s in refs]; reads = [bytes(s) for s in reads]
@@ -737,10 +749,10 @@ def _align_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail):
     reg_all = np.ascontiguousarray(np.concatenate([np.asarray(x, REG_DTYPE) for x in regs]) if R else np.zeros(0, REG_DTYPE), dtype=REG_DTYPE)
     a_all = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint64).reshape(-1, 2) for x in anchors]) if R else np.zeros((0, 2), np.uint64), dtype=np.uint64)
     out = _AlignOut()
-    fn.argtypes = [C.c_void_p] * len(head) + [C.POINTER(AlignOpt), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * len(tail) + [C.POINTER(_AlignOut)]
+    fn.argtypes = [C.c_void_p] * len(head) + [C.POINTER(opt_type or AlignOpt), C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * len(tail) + [C.POINTER(_AlignOut)] + [C.c_void_p] * len(after)
     _check(fn(*head, C.byref(opt), int(k), I_HPC if hpc else 0, len(refs), ref_arr, ref_len.ctypes.data, R, read_arr, read_len.ctypes.data,
-              reg_off.ctypes.data, reg_all.ctypes.data, a_off.ctypes.data, a_all.ctypes.data, *tail, C.byref(out)))
+              reg_off.ctypes.data, reg_all.ctypes.data, a_off.ctypes.data, a_all.ctypes.data, *tail, C.byref(out), *[C.addressof(x) for x in after]))
     try:
         off = _take(out.reg_off, R + 1, np.int64)
         rg = _take(out.regs, out.n_regs, REG_DTYPE); al = _take(out.aln, out.n_regs, ALN_DTYPE); words = _take(out.cigar, out.n_cigar, np.uint32)
@@ -770,6 +782,57 @@ def _engine_align_regs(self, opt, k, hpc, refs, reads, regs, anchors):
 
 
 Engine.align_regs = _engine_align_regs
+
+
+# ---- spliced alignment of hits (mm2gb_align_regs_splice_host / _gpu): mm_align_skeleton under MM_F_SPLICE; the calls above keep refusing it ----
+F_SPLICE_FOR, F_SPLICE_REV, F_SPLICE_FLANK = 0x100, 0x200, 0x40000
+SPLICE_COUNTS = ("trial_for_won", "trial_rev_won", "trial_tie_kept_0", "trial_tie_kept_1", "end_flt_head", "end_flt_tail", "end_flt_probe_kept", "left_ext_intron",
+                 "right_ext_intron", "fill_intron", "fill_two_pass", "split", "tail_other_strand", "n_seam_merged", "noncanonical_intron", "single_trial", "rev_chain",
+                 "over_sw_mat")
+
+
+class AlignSpliceOpt(C.Structure):
+    """mm2gb_align_splice_opt_t: mm2gb_align_opt_t and the four numbers only the spliced form reads."""
+    _fields_ = [("base", AlignOpt)] + [(k, C.c_int32) for k in "noncan junc_bonus anchor_ext_len anchor_ext_shift".split()]
+
+
+def align_splice_opt(preset="splice", **kw):
+    """mm2gb_align_splice_opt_init for "splice", "cdna" or "splice:hq", then keyword overrides (a field of either record by its name)."""
+    o = AlignSpliceOpt()
+    fn = lib().mm2gb_align_splice_opt_init
+    fn.argtypes = [C.POINTER(AlignSpliceOpt), C.c_char_p]
+    _check(fn(C.byref(o), preset.encode()))
+    own = {k for k, _ in AlignSpliceOpt._fields_[1:]}
+    for k, v in kw.items():
+        if k in own:
+            setattr(o, k, v)
+        elif hasattr(o.base, k):
+            setattr(o.base, k, v)
+        else:
+            raise Mm2gbError(f"mm2gb_align_splice_opt_t has no field {k!r}")
+    return o
+
+
+def _align_splice_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail):
+    if not isinstance(opt, AlignSpliceOpt):
+        raise Mm2gbError("the spliced alignment calls take an AlignSpliceOpt (align_splice_opt())")
+    sc = (C.c_int64 * len(SPLICE_COUNTS))()
+    res, info = _align_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail, opt_type=AlignSpliceOpt, after=(sc,))
+    info["splice_counts"] = dict(zip(SPLICE_COUNTS, (int(x) for x in sc)))
+    return res, info
+
+
+def align_regs_splice_host(opt, k, hpc, refs, reads, regs, anchors, threads=4):
+    """mm2gb_align_regs_splice_host: align_regs_host's arguments and results for spliced reads, with info["splice_counts"] (the paths met)."""
+    return _align_splice_call(lib().mm2gb_align_regs_splice_host, (), opt, k, hpc, refs, reads, regs, anchors, (int(threads),))
+
+
+def _engine_align_regs_splice(self, opt, k, hpc, refs, reads, regs, anchors):
+    """mm2gb_align_regs_splice_gpu: align_regs_splice_host's arguments and results, the DP and its sequences on the device."""
+    return _align_splice_call(lib().mm2gb_align_regs_splice_gpu, (self._h,), opt, k, hpc, refs, reads, regs, anchors, ())
+
+
+Engine.align_regs_splice = _engine_align_regs_splice
 
 
 # ---- the text of a PAF line's alignment tags (mm2gb_aln_text_host / _gpu): cg:Z, cs:Z, MD:Z for a batch of records ----
@@ -834,7 +897,18 @@ def _engine_aln_text_info(self):
     return dict(slice=int(c[0]), wg=int(c[1]), s_upload=s[0], s_prepare=s[1], s_kernels=s[2], s_back=s[3])
 
 
+def aln_text_splice_host(what, refs, reads, regs, read_of_reg, aln, cigar, threads=4):
+    """mm2gb_aln_text_splice_host: aln_text_host for records of the spliced alignment calls: N words are taken (cg:Z `N`, cs:Z `~gt123ag`, MD:Z nothing)."""
+    return _aln_text_call(lib().mm2gb_aln_text_splice_host, (), what, refs, reads, regs, read_of_reg, aln, cigar, (int(threads),))
+
+
+def _engine_aln_text_splice(self, what, refs, reads, regs, read_of_reg, aln, cigar):
+    """mm2gb_aln_text_splice_gpu: aln_text_splice_host's arguments and results, every column on the device; an N word is one column."""
+    return _aln_text_call(lib().mm2gb_aln_text_splice_gpu, (self._h,), what, refs, reads, regs, read_of_reg, aln, cigar, ())
+
+
 Engine.aln_text = _engine_aln_text
+Engine.aln_text_splice = _engine_aln_text_splice
 Engine.aln_text_info = _engine_aln_text_info
 
 
@@ -1045,10 +1119,13 @@ I_HPC = 0x1    # MM2GB_I_HPC
 
 def preset(name):
     """The index and seeding parameters of a minimap2 preset, as keywords for SeedIndex (k, w, hpc) and map_reads (k).  "map-pb" (alias
-    "map10k"): -H -k19 (options.c:102-103), w = 10.  No other preset: their mapping options are not the mapper's."""
+    "map10k"): -H -k19 (options.c:102-103), w = 10.  "splice" / "cdna" / "splice:hq": -k15 -w5 (options.c:152); their alignment options are
+    align_splice_opt's.  No other preset: their mapping options are not the mapper's."""
     if name in ("map-pb", "map10k"):
         return dict(k=19, w=10, hpc=True)
-    raise Mm2gbError(f"preset {name!r} is not supported (map-pb / map10k only)")
+    if name in ("splice", "cdna", "splice:hq"):
+        return dict(k=15, w=5, hpc=False)
+    raise Mm2gbError(f"preset {name!r} is not supported (map-pb / map10k, splice / cdna / splice:hq)")
 
 
 def sketch(seq, w=10, k=15, rid=0, hpc=False):
@@ -1273,6 +1350,35 @@ def map_align(refs, preset="map-ont", cigar=True, cs=None, md=False, align_on_de
     return a
 
 
+class MapSplice(C.Structure):
+    """mm2gb_map_splice_t: what mm2gb_map_reads_splice needs beside the mapping options (make one with map_splice)."""
+    _fields_ = [("ref_seqs", C.POINTER(C.c_char_p)), ("opt", AlignSpliceOpt), ("what", C.c_int32), ("align_on_device", C.c_int32), ("text_on_device", C.c_int32)]
+
+
+def map_splice(refs, preset="splice", cigar=True, cs=None, md=False, align_on_device=0, text_on_device=0, **align_opt_fields):
+    """Spliced base-level alignment for map_reads / map_reads_stream (their align= argument; minimap2 -x splice -c): map_align's arguments with
+    preset "splice", "cdna" or "splice:hq" (align_splice_opt).  Use opt=map_opt_splice() and an index built with **preset("splice")."""
+    if cs not in (None, "short", "long"):
+        raise Mm2gbError('map_splice: cs is None, "short" or "long"')
+    a = MapSplice()
+    a._refs = [bytes(s) for s in refs]
+    a._arr = (C.c_char_p * max(len(a._refs), 1))(*a._refs)
+    a.ref_seqs = C.cast(a._arr, C.POINTER(C.c_char_p))
+    a.opt = align_splice_opt(preset, **align_opt_fields)
+    a.what = (TEXT_CG if cigar else 0) | (TEXT_CS if cs else 0) | (TEXT_CS_LONG if cs == "long" else 0) | (TEXT_MD if md else 0)
+    a.align_on_device, a.text_on_device = int(align_on_device), int(text_on_device)
+    return a
+
+
+def map_opt_splice(**kw):
+    """mm2gb_map_opt_init_splice (the `splice` presets' mapping fields: bw = bw_long = max_gap_ref = 200000, max_gap = 2000), then keyword overrides."""
+    o = MapOpt()
+    lib().mm2gb_map_opt_init_splice(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
 def _check_align_refs(align, ref_names):
     if len(align._refs) != len(ref_names):
         raise Mm2gbError("map_reads: align holds another number of reference sequences than ref_names")
@@ -1284,12 +1390,13 @@ def _stats_with_extra(st, extra):
 
 def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
     """mm2gb_map_reads: reads = list of (name, sequence bytes); returns (PAF text, stats dict).  index: a SeedIndex of the references.
-    align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln); the stats then hold s_align, s_post_align and s_text as well."""
+    align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln) or a map_splice(...) for spliced reads (mm2gb_map_reads_splice); the stats then hold s_align, s_post_align and s_text as well."""
     L = lib()
     head = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
     tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
     L.mm2gb_map_reads.argtypes = head + tail
     L.mm2gb_map_reads_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
+    L.mm2gb_map_reads_splice.argtypes = head + [C.POINTER(MapSplice)] + tail + [C.c_void_p]
     opt = opt or map_opt()
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
     names = (C.c_char_p * len(reads))(*[n.encode() for n, _ in reads])
@@ -1303,7 +1410,7 @@ def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
         _check(L.mm2gb_map_reads(*first, *rest))
     else:
         _check_align_refs(align, ref_names)
-        _check(L.mm2gb_map_reads_aln(*first, C.byref(align), *rest, extra))
+        _check((L.mm2gb_map_reads_splice if isinstance(align, MapSplice) else L.mm2gb_map_reads_aln)(*first, C.byref(align), *rest, extra))
     text = C.string_at(out, n.value).decode()
     L.mm2gb_free(out)
     return text, st.as_dict() if align is None else _stats_with_extra(st, extra)
@@ -1348,6 +1455,7 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
     tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
     L.mm2gb_map_reads_stream.argtypes = head + tail
     L.mm2gb_map_reads_stream_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
+    L.mm2gb_map_reads_stream_splice.argtypes = head + [C.POINTER(MapSplice)] + tail + [C.c_void_p]
     opt = opt or map_opt()
     hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
@@ -1362,7 +1470,7 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
         _check(L.mm2gb_map_reads_stream(*first, *rest))
     else:
         _check_align_refs(align, ref_names)
-        _check(L.mm2gb_map_reads_stream_aln(*first, C.byref(align), *rest, extra))
+        _check((L.mm2gb_map_reads_stream_splice if isinstance(align, MapSplice) else L.mm2gb_map_reads_stream_aln)(*first, C.byref(align), *rest, extra))
     text = C.string_at(out, n.value).decode()
     L.mm2gb_free(out)
     return text, st.as_dict() if align is None else _stats_with_extra(st, extra)

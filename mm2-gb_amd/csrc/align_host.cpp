@@ -32,12 +32,12 @@ inline int32_t ay(const mm2gb_anchor_t &a) { return (int32_t)a.y; }
 inline int32_t aspan(const mm2gb_anchor_t &a) { return (int32_t)(a.y >> 32 & 0xff); }
 
 struct Fill { int32_t rs, qs, re, qe, i, run; };
-struct Plan { int32_t as1, cnt1, rid, rev, rs, qs, re, qe, rs0, qs0, re0, qe0, left, right; std::vector<Fill> fills; };
+struct Plan { int32_t as1, cnt1, rid, rev, rs, qs, re, qe, rs0, qs0, re0, qe0, left, right, n_runs, trials; std::vector<Fill> fills; };      // n_runs: its jobs; trials: 2 when they lie in the round twice
 enum { ST_DONE, ST_FRESH, ST_PENDING, ST_INV_FRESH, ST_INV_PENDING };
 struct Reg {
 	mm2gb_reg_t r;
 	bool has_p = false;
-	int32_t dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0;
+	int32_t dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0, trans_strand = 0;
 	std::vector<uint32_t> cig;
 	int state = ST_FRESH, plan = -1;
 	AlRun inv;                       // an inversion's alignment job, and where its coordinates start from
@@ -52,6 +52,7 @@ struct Read {
 	std::vector<AlRun> runs;         // this round's jobs; first_run: where they begin in the round's array
 	int64_t first_run = 0;
 	int64_t cnt[MM2GB_ALN_N_COUNTS] = {};
+	int64_t scnt[MM2GB_SPL_N_COUNTS] = {};      // the spliced form's
 };
 
 inline uint8_t read_base(const AlCtx &c, int64_t read, int strand, int p)
@@ -129,6 +130,45 @@ void fix_bad_ends(const mm2gb_reg_t &r, const mm2gb_anchor_t *a, int bw, int min
 		l += mn;
 		m += mn < q_span ? mn : q_span;
 		if (l >= bw << 1 || (m >= min_match && m >= bw) || m >= r.mlen >> 1) break;
+	}
+}
+
+int ll_i16(const AlCtx &c, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int gapo, int gape, int *qe, int *te);
+
+// ---- mm_seed_ext_score (align.c:526-551): the anchor's span widened by anchor_ext_len on both sides, the query on the anchor's strand ----
+int seed_ext_score(const AlCtx &c, const Read &R, const mm2gb_anchor_t &a)
+{
+	const int32_t q_span = aspan(a), rid = (int32_t)(a.x << 1 >> 33), ext = c.anchor_ext_len, strand = (int32_t)(a.x >> 63);
+	const int32_t ref_len = (int32_t)(c.ref_at[(size_t)rid + 1] - c.ref_at[(size_t)rid]);
+	int32_t re = ax(a) + 1, rs = re - q_span, qe = ay(a) + 1, qs = qe - q_span;
+	rs = rs - ext > 0 ? rs - ext : 0;
+	qs = qs - ext > 0 ? qs - ext : 0;
+	re = re + ext < ref_len ? re + ext : ref_len;
+	qe = qe + ext < R.qlen ? qe + ext : R.qlen;
+	std::vector<uint8_t> q((size_t)std::max(qe - qs, 0)), t((size_t)std::max(re - rs, 0));
+	for (int k = 0; k < qe - qs; ++k) q[(size_t)k] = read_base(c, R.id, strand, qs + k);
+	for (int k = 0; k < re - rs; ++k) t[(size_t)k] = c.refs[(size_t)(c.ref_at[(size_t)rid] + rs + k)];
+	int q_off, t_off;
+	return ll_i16(c, (int)q.size(), q.data(), (int)t.size(), t.data(), c.opt.q, c.opt.e, &q_off, &t_off);
+}
+
+// ---- mm_fix_bad_ends_splice (align.c:553-571): an end anchor shorter than ln(distance to its neighbour) + anchor_ext_shift is probed and, where
+//      the probe's score / a is below that too, left out.  Reads positions, spans and sequences; no seed flag, no DP result ----
+void fix_bad_ends_splice(const AlCtx &c, Read &R, const mm2gb_reg_t &r, const mm2gb_anchor_t *a, int32_t *as, int32_t *cnt)
+{
+	*as = r.as; *cnt = r.cnt;
+	if (r.cnt < 3) return;
+	double log_gap = log(ax(a[r.as + 1]) - ax(a[r.as]));
+	if (aspan(a[r.as]) < log_gap + c.anchor_ext_shift) {
+		const int score = seed_ext_score(c, R, a[r.as]);
+		if ((double)score / c.mat[0] < log_gap + c.anchor_ext_shift) { ++*as; --*cnt; ++R.scnt[MM2GB_SPL_N_END_FLT_HEAD]; }
+		else ++R.scnt[MM2GB_SPL_N_END_FLT_PROBE_KEPT];
+	}
+	log_gap = log(ax(a[r.as + r.cnt - 1]) - ax(a[r.as + r.cnt - 2]));
+	if (aspan(a[r.as + r.cnt - 1]) < log_gap + c.anchor_ext_shift) {
+		const int score = seed_ext_score(c, R, a[r.as + r.cnt - 1]);
+		if ((double)score / c.mat[0] < log_gap + c.anchor_ext_shift) { --*cnt; ++R.scnt[MM2GB_SPL_N_END_FLT_TAIL]; }
+		else ++R.scnt[MM2GB_SPL_N_END_FLT_PROBE_KEPT];
 	}
 }
 
@@ -234,11 +274,25 @@ inline AlRun make_run(const AlCtx &c, const Read &R, int rid, int rev, int q0, i
 	memset(&x, 0, sizeof x);
 	x.j.q_at = c.read_at[(size_t)R.id]; x.j.t_at = c.ref_at[(size_t)rid];
 	x.j.qn = R.qlen; x.j.tn = (int32_t)(c.ref_at[(size_t)rid + 1] - c.ref_at[(size_t)rid]); x.j.q0 = q0; x.j.qlen = qlen; x.j.t0 = t0; x.j.tlen = tlen; x.j.rev = rev; x.j.flip = flip; x.j.kind = kind;
-	x.w = w; x.zdrop = zdrop; x.end_bonus = end_bonus; x.flag = flag;
+	x.w = w; x.zdrop = zdrop; x.end_bonus = end_bonus; x.flag = flag;      // twin = 0 by the memset
 	return x;
 }
 
-// ---- the first half of mm_align1 (align.c:573-700 and the coordinates of 700-803): a chain's job list.  false: the chain has no anchors ----
+// ---- the DP's splice bits of a trial (align.c:612-616): splice_flag holds MM_F_SPLICE_FOR and / or _REV, which swap on a reverse-strand chain ----
+inline int splice_bits(const AlCtx &c, int64_t splice_flag, int rev)
+{
+	int x = 0;
+	if (splice_flag & MM2GB_F_SPLICE_FOR) x |= rev ? MM2GB_KSW_SPLICE_REV : MM2GB_KSW_SPLICE_FOR;
+	if (splice_flag & MM2GB_F_SPLICE_REV) x |= rev ? MM2GB_KSW_SPLICE_FOR : MM2GB_KSW_SPLICE_REV;
+	if (c.opt.flag & MM2GB_F_SPLICE_FLANK) x |= MM2GB_KSW_SPLICE_FLANK;
+	return x;
+}
+inline bool two_trials(const AlCtx &c) { return c.splice && (c.opt.flag & MM2GB_F_SPLICE_FOR) && (c.opt.flag & MM2GB_F_SPLICE_REV); }
+
+// ---- the first half of mm_align1 (align.c:573-700 and the coordinates of 700-803): a chain's job list.  false: the chain has no anchors.
+//      Spliced form: the plan reads anchors' positions and spans and the sequences alone (the seed flags the filters SET are read by the job
+//      loop below, and both trials would set the same ones), so a chain is planned once and its jobs entered once per trial with that trial's
+//      splice bits, the second copy marked as the first's twin ----
 bool plan_chain(const AlCtx &c, Read &R, const Reg &g, Plan &P, std::vector<int> &K)
 {
 	const mm2gb_align_opt_t &o = c.opt;
@@ -247,8 +301,9 @@ bool plan_chain(const AlCtx &c, Read &R, const Reg &g, Plan &P, std::vector<int>
 	mm2gb_anchor_t *a = R.a.data();
 	const int32_t rid = (int32_t)(a[r.as].x << 1 >> 33), rev = (int32_t)(a[r.as].x >> 63), ref_len = (int32_t)(c.ref_at[(size_t)rid + 1] - c.ref_at[(size_t)rid]), qlen = R.qlen;
 	int32_t as1, cnt1, rs, qs, re, qe, rs0, qs0, re0, qe0, rs1, qs1, re1, qe1, i, l;
-	if (!(o.flag & MM2GB_F_NO_END_FLT)) fix_bad_ends(r, a, o.bw, o.min_chain_score * 2, &as1, &cnt1);
-	else { as1 = r.as; cnt1 = r.cnt; }
+	if (o.flag & MM2GB_F_NO_END_FLT) { as1 = r.as; cnt1 = r.cnt; }
+	else if (c.splice) fix_bad_ends_splice(c, R, r, a, &as1, &cnt1);
+	else fix_bad_ends(r, a, o.bw, o.min_chain_score * 2, &as1, &cnt1);
 	filter_bad_seeds(as1, cnt1, a, 10, 40, o.max_gap >> 1, 10, K);
 	filter_bad_seeds_alt(as1, cnt1, a, 30, o.max_gap >> 1, K);
 	adjust_minier(c, R, a[as1], &rs, &qs);
@@ -314,8 +369,9 @@ bool plan_chain(const AlCtx &c, Read &R, const Reg &g, Plan &P, std::vector<int>
 	P.as1 = as1; P.cnt1 = cnt1; P.rid = rid; P.rev = rev; P.rs = rs; P.qs = qs; P.re = re; P.qe = qe; P.rs0 = rs0; P.qs0 = qs0; P.re0 = re0; P.qe0 = qe0;
 	P.left = P.right = -1;
 	P.fills.clear();
-	if (rev) ++R.cnt[MM2GB_ALN_N_REV_CHAIN];
+	if (rev) { ++R.cnt[MM2GB_ALN_N_REV_CHAIN]; ++R.scnt[MM2GB_SPL_N_REV_CHAIN]; }
 	// the jobs
+	const int first = (int)R.runs.size();
 	if (qs > 0 && rs > 0) {
 		P.left = (int)R.runs.size();
 		if (rs0 == 0) ++R.cnt[MM2GB_ALN_N_LEFT_AT_0];
@@ -336,6 +392,16 @@ bool plan_chain(const AlCtx &c, Read &R, const Reg &g, Plan &P, std::vector<int>
 	if (qe < qe0 && re < re0) {
 		P.right = (int)R.runs.size();
 		R.runs.push_back(make_run(c, R, rid, rev, qe, qe0 - qe, re, re0 - re, 0, 2, c.bw, o.zdrop, o.end_bonus, MM2GB_KSW_EXTZ_ONLY));
+	}
+	P.n_runs = (int)R.runs.size() - first; P.trials = 1;
+	if (c.splice) {
+		P.trials = two_trials(c) ? 2 : 1;
+		if (P.trials == 1) ++R.scnt[MM2GB_SPL_N_SINGLE_TRIAL];
+		const int bits0 = splice_bits(c, P.trials == 2 ? MM2GB_F_SPLICE_FOR : o.flag, rev), bits1 = splice_bits(c, MM2GB_F_SPLICE_REV, rev);
+		for (int k = 0; k < P.n_runs; ++k) {
+			if (P.trials == 2) { AlRun x = R.runs[(size_t)(first + k)]; x.flag |= bits1; x.twin = P.n_runs; R.runs.push_back(x); }      // lands at first + n_runs + k
+			R.runs[(size_t)(first + k)].flag |= bits0;
+		}
 	}
 	return true;
 }
@@ -556,12 +622,36 @@ void append_cigar(Read &R, Reg &g, const AlRun &x, const uint32_t *pool)
 		g.cig.back() += w[0] >> 4 << 4;
 		g.cig.insert(g.cig.end(), w + 1, w + n);
 		++R.cnt[MM2GB_ALN_N_SEAM_MERGED];
+		if ((w[0] & 0xf) == 3) ++R.scnt[MM2GB_SPL_N_N_SEAM_MERGED];
 	} else g.cig.insert(g.cig.end(), w, w + n);
 }
 
 inline int64_t run_cells(const AlRun &x) { return (int64_t)std::max(x.j.qlen, 0) * std::max(x.j.tlen, 0) * (x.code ? 2 : 1); }
 
-// ---- the second half of mm_align1 (align.c:712-822): a chain's results stitched into its record; true: tail holds what a z-drop split off ----
+inline bool has_intron(const AlRun &x, const uint32_t *pool)
+{
+	for (int k = 0; k < x.res.n_cigar; ++k) if ((pool[x.res.cigar_off + k] & 0xf) == 3) return true;
+	return false;
+}
+
+// the N words of a finished record whose ends on the target are neither GT..AG nor CT..AC (information: MM2GB_SPL_N_NONCANONICAL_INTRON)
+template <class FT>
+int count_noncanonical(const Reg &g, FT T)
+{
+	int n = 0, toff = 0;
+	for (uint32_t w : g.cig) {
+		const int op = (int)(w & 0xf), len = (int)(w >> 4);
+		if (op == 3 && len >= 4) {
+			const int d0 = T(toff), d1 = T(toff + 1), a0 = T(toff + len - 2), a1 = T(toff + len - 1);
+			if (!((d0 == 2 && d1 == 3 && a0 == 0 && a1 == 2) || (d0 == 1 && d1 == 3 && a0 == 0 && a1 == 1))) ++n;
+		}
+		if (op == 0 || op == 2 || op == 3) toff += len;
+	}
+	return n;
+}
+
+// ---- the second half of mm_align1 (align.c:712-822): a chain's results stitched into its record; true: tail holds what a z-drop split off.
+//      ru: the jobs of the trial that is stitched (the plan's indices count from there) ----
 bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *ru, const uint32_t *pool, Reg &tail)
 {
 	const mm2gb_align_opt_t &o = c.opt;
@@ -574,6 +664,7 @@ bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *r
 		rs1 = P.rs - (x.res.reach_end ? x.res.mqe_t + 1 : x.res.max_t + 1);
 		qs1 = P.qs - (x.res.reach_end ? P.qs - P.qs0 : x.res.max_q + 1);
 		++R.cnt[x.res.reach_end ? MM2GB_ALN_N_LEFT_END : MM2GB_ALN_N_LEFT_SHORT];
+		if (c.splice && has_intron(x, pool)) ++R.scnt[MM2GB_SPL_N_LEFT_EXT_INTRON];
 	} else { rs1 = P.rs; qs1 = P.qs; }
 	re1 = P.rs; qe1 = P.qs;
 	size_t used = 0;
@@ -583,7 +674,8 @@ bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *r
 		re1 = f.re; qe1 = f.qe;
 		++R.cnt[x.code ? MM2GB_ALN_N_FILL_TWO_PASS : MM2GB_ALN_N_FILL_ONE_PASS];
 		if (x.code == 2) ++R.cnt[MM2GB_ALN_N_INV_PROBE_HIT];
-		if (al_too_big(c, x.j)) ++R.cnt[MM2GB_ALN_N_OVER_SW_MAT];
+		if (al_too_big(c, x.j)) { ++R.cnt[MM2GB_ALN_N_OVER_SW_MAT]; ++R.scnt[MM2GB_SPL_N_OVER_SW_MAT]; }
+		if (c.splice) { if (x.code) ++R.scnt[MM2GB_SPL_N_FILL_TWO_PASS]; if (has_intron(x, pool)) ++R.scnt[MM2GB_SPL_N_FILL_INTRON]; }
 		append_cigar(R, g, x, pool);
 		if (x.res.zdropped) {
 			int j;
@@ -598,7 +690,7 @@ bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *r
 			if (P.cnt1 - (j + 1) >= o.min_cnt && split_reg(g.r, tail.r, P.as1 + j + 1 - g.r.as, R.qlen, a)) {
 				split = true;
 				if (x.code == 2) tail.r.flags |= RF_SPLIT_INV;
-				++R.cnt[MM2GB_ALN_N_SPLIT];
+				++R.cnt[MM2GB_ALN_N_SPLIT]; ++R.scnt[MM2GB_SPL_N_SPLIT];
 			} else ++R.cnt[MM2GB_ALN_N_SPLIT_REFUSED];
 			break;
 		} else g.dp_score += x.res.score;
@@ -609,6 +701,7 @@ bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *r
 		re1 = P.re + (x.res.reach_end ? x.res.mqe_t + 1 : x.res.max_t + 1);
 		qe1 = P.qe + (x.res.reach_end ? P.qe0 - P.qe : x.res.max_q + 1);
 		++R.cnt[x.res.reach_end ? MM2GB_ALN_N_RIGHT_END : MM2GB_ALN_N_RIGHT_SHORT];
+		if (c.splice && has_intron(x, pool)) ++R.scnt[MM2GB_SPL_N_RIGHT_EXT_INTRON];
 	}
 	if (dropped) {            // what ran behind the drop was speculation
 		for (size_t k = used; k < P.fills.size(); ++k) R.cnt[MM2GB_ALN_N_CELLS_DISCARDED] += run_cells(ru[P.fills[k].run]);
@@ -621,8 +714,42 @@ bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *r
 		const int strand = (g.r.flags & RF_REV) != 0;
 		const int64_t t_at = c.ref_at[(size_t)P.rid];
 		update_extra(c, R, g, [&](int k) { return (int)read_base(c, R.id, strand, qs1 + k); }, [&](int k) { return (int)c.refs[(size_t)(t_at + rs1 + k)]; });
+		if (c.splice) R.scnt[MM2GB_SPL_N_NONCANONICAL_INTRON] += count_noncanonical(g, [&](int k) { return (int)c.refs[(size_t)(t_at + g.r.rs + k)]; });
 	}
 	return split;
+}
+
+// ---- a chain of the spliced form (align.c:980-1001): one trial, or both stitched from the same input record and the larger dp_score kept
+//      (a tie: trial (qlen + dp_score) & 1); the loser's record, tail and counts are dropped.  trans_strand is set HERE, after mm_align1: the
+//      flip to the read's strand at align.c:820-821 tests a field that is still 0 and never fires, and so a reverse-strand chain keeps 1 / 2
+//      as the trial says.  The cells behind a drop in the trial dropped count as discarded too ----
+bool stitch_trials(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *ru, const uint32_t *pool, Reg &tail)
+{
+	if (P.trials == 1) {
+		const bool split = stitch_chain(c, R, g, P, ru, pool, tail);
+		g.trans_strand = (c.opt.flag & MM2GB_F_SPLICE_FOR) ? 1 : 2;
+		return split;
+	}
+	Reg s[2] = { g, g }, s2[2];
+	bool split[2];
+	int64_t cnt0[MM2GB_ALN_N_COUNTS], scnt0[MM2GB_SPL_N_COUNTS], cnt[2][MM2GB_ALN_N_COUNTS], scnt[2][MM2GB_SPL_N_COUNTS];
+	memcpy(cnt0, R.cnt, sizeof cnt0); memcpy(scnt0, R.scnt, sizeof scnt0);
+	for (int t = 0; t < 2; ++t) {
+		memcpy(R.cnt, cnt0, sizeof cnt0); memcpy(R.scnt, scnt0, sizeof scnt0);
+		split[t] = stitch_chain(c, R, s[t], P, ru + (size_t)t * P.n_runs, pool, s2[t]);
+		memcpy(cnt[t], R.cnt, sizeof cnt0); memcpy(scnt[t], R.scnt, sizeof scnt0);
+	}
+	int which, trans_strand;
+	if (s[0].dp_score > s[1].dp_score) { which = 0; trans_strand = 1; }
+	else if (s[0].dp_score < s[1].dp_score) { which = 1; trans_strand = 2; }
+	else { trans_strand = 3; which = (R.qlen + s[0].dp_score) & 1; }
+	memcpy(R.cnt, cnt[which], sizeof cnt0); memcpy(R.scnt, scnt[which], sizeof scnt0);
+	R.cnt[MM2GB_ALN_N_CELLS_DISCARDED] += cnt[!which][MM2GB_ALN_N_CELLS_DISCARDED] - cnt0[MM2GB_ALN_N_CELLS_DISCARDED];
+	++R.scnt[trans_strand == 1 ? MM2GB_SPL_N_TRIAL_FOR_WON : trans_strand == 2 ? MM2GB_SPL_N_TRIAL_REV_WON : which ? MM2GB_SPL_N_TRIAL_TIE_KEPT_1 : MM2GB_SPL_N_TRIAL_TIE_KEPT_0];
+	g = std::move(s[which]);
+	g.trans_strand = trans_strand;
+	if (split[which]) tail = std::move(s2[which]);
+	return split[which];
 }
 
 // ---- mm_align1_inv's end (align.c:860-879): false: no words came back, the record is dropped ----
@@ -773,8 +900,10 @@ int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, int nt, doub
 			for (size_t i = 0; i < R.regs.size(); ++i) {
 				if (R.regs[i].state == ST_PENDING) {
 					Reg tail;
-					const bool split = stitch_chain(c, R, R.regs[i], R.plans[(size_t)R.regs[i].plan], ru, pool.data(), tail);
+					const Plan &P = R.plans[(size_t)R.regs[i].plan];
+					const bool split = c.splice ? stitch_trials(c, R, R.regs[i], P, ru, pool.data(), tail) : stitch_chain(c, R, R.regs[i], P, ru, pool.data(), tail);
 					R.regs[i].state = ST_DONE;
+					if (c.splice && i > 0 && (R.regs[i].r.flags & RF_SPLIT2) && R.regs[i].trans_strand != R.regs[i - 1].trans_strand) ++R.scnt[MM2GB_SPL_N_TAIL_OTHER_STRAND];
 					if (split) R.regs.insert(R.regs.begin() + (ptrdiff_t)i + 1, std::move(tail));          // mm_insert_reg: next round's chain
 					if (i > 0 && (R.regs[i].r.flags & RF_SPLIT_INV) && !(c.opt.flag & MM2GB_F_NO_INV)) {
 						Reg inv;
@@ -839,7 +968,7 @@ int al_zdrop_code(const AlCtx &c, const AlJob &j, const AlDrop &d)
 {
 	const mm2gb_align_opt_t &o = c.opt;
 	const int q_len = d.q_to - d.q_from, t_len = d.t_to - d.t_from;
-	if (!(o.flag & (MM2GB_F_FOR_ONLY | MM2GB_F_REV_ONLY)) && d.max_zdrop > o.zdrop_inv && q_len < o.max_gap && t_len < o.max_gap) {
+	if (!(o.flag & (MM2GB_F_SPLICE | MM2GB_F_FOR_ONLY | MM2GB_F_REV_ONLY)) && d.max_zdrop > o.zdrop_inv && q_len < o.max_gap && t_len < o.max_gap) {
 		std::vector<uint8_t> q2((size_t)std::max(q_len, 0)), ts((size_t)std::max(t_len, 0));
 		for (int i = 0; i < q_len; ++i) { const uint8_t x = al_query(c.reads.data(), j, d.q_to - i - 1); q2[(size_t)i] = x >= 4 ? 4 : 3 - x; }
 		for (int i = 0; i < t_len; ++i) ts[(size_t)i] = al_target(c.refs.data(), j, d.t_from + i);
@@ -861,19 +990,36 @@ void pack_residues(int32_t n_ref, const char *const *ref_seqs, const int32_t *re
 	for_each_on_threads((size_t)n_reads, nt, 1, [&](size_t i) { for (int32_t p = 0; p < read_lens[i]; ++p) reads[(size_t)(read_at[i] + p)] = nt4(read_seqs[i][p]); });
 }
 
-int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                   int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out)
+                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts)
 {
 	const std::string who = who_;
 	if (!out) return fail(who + ": null argument");
 	memset(out, 0, sizeof *out);
+	if (splice_counts) memset(splice_counts, 0, MM2GB_SPL_N_COUNTS * 8);
+	mm2gb_align_opt_t opt_own;
+	const mm2gb_align_opt_t *opt = opt_;
+	if (spl && opt_) {            // options.c:70-71: either strand flag implies MM_F_SPLICE
+		opt_own = *opt_;
+		if (opt_own.flag & (MM2GB_F_SPLICE_FOR | MM2GB_F_SPLICE_REV)) opt_own.flag |= MM2GB_F_SPLICE;
+		opt = &opt_own;
+	}
 	if (!opt || n_reads < 0 || n_ref < 0 || (n_ref > 0 && (!ref_seqs || !ref_lens)) || (n_reads > 0 && (!read_seqs || !read_lens || !reg_off || !anchor_off))) return fail(who + ": null argument");
 	static const struct { int64_t bit; const char *name; } refused[] = { { MM2GB_F_SPLICE, "MM_F_SPLICE" }, { MM2GB_F_SR, "MM_F_SR" }, { MM2GB_F_QSTRAND, "MM_F_QSTRAND" }, { MM2GB_F_EQX, "MM_F_EQX" } };
-	for (const auto &x : refused) if (opt->flag & x.bit) return fail(who + ": " + x.name + " is not supported");
-	if (opt->q == opt->q2 && opt->e == opt->e2) return fail(who + ": q == q2 && e == e2 selects ksw_extz2_sse, which is not supported");
+	for (const auto &x : refused) if ((opt->flag & x.bit) && !(spl && x.bit == MM2GB_F_SPLICE)) return fail(who + ": " + x.name + " is not supported");
+	mm2gb_ksw_splice_param_t sp;
+	if (spl) {
+		if (!(opt->flag & MM2GB_F_SPLICE)) return fail(who + ": the flag word lacks MM_F_SPLICE (the calls without _splice align unspliced reads)");
+		if (idx_flag & MM2GB_I_HPC) return fail(who + ": an index with MM2GB_I_HPC is not supported");
+		if (opt->e <= 0) return fail(who + ": e must be above 0 (the reference divides by it)");
+		if (opt->q <= 0 || opt->q2 < 0 || opt->q > 127 || opt->q2 > 127 || spl->noncan < 0 || spl->noncan > 127 || spl->junc_bonus < 0 || spl->junc_bonus > 127)
+			return fail(who + ": q must be 1..127 and q2, noncan and junc_bonus 0..127");
+		if (spl->anchor_ext_len < 0) return fail(who + ": anchor_ext_len must not be negative");
+	}
+	if (!spl && opt->q == opt->q2 && opt->e == opt->e2) return fail(who + ": q == q2 && e == e2 selects ksw_extz2_sse, which is not supported");
 	if (opt->max_sw_mat <= 0 || opt->max_sw_mat > MM2GB_KSW_MAX_CELLS) return fail(who + ": max_sw_mat must be in 1 .. MM2GB_KSW_MAX_CELLS");
-	if (opt->e <= 0 || opt->q <= 0 || opt->q + opt->e + opt->q2 + opt->e2 > 127) return fail(who + ": gap penalties out of range");
+	if (opt->e <= 0 || opt->q <= 0 || (spl ? opt->q + opt->e : opt->q + opt->e + opt->q2 + opt->e2) > 127) return fail(who + ": gap penalties out of range");
 	for (int64_t r = 0; r < n_reads; ++r) {
 		const int64_t na = anchor_off[r + 1] - anchor_off[r];
 		if (na < 0 || reg_off[r + 1] < reg_off[r] || read_lens[r] < 0) return fail(who + ": read " + std::to_string(r) + ": offsets not ascending");
@@ -897,9 +1043,15 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx
 	c.bw = (int)(opt->bw * 1.5 + 1.); c.bw_long = (int)(opt->bw_long * 1.5 + 1.);
 	if (c.bw_long < c.bw) c.bw_long = c.bw;
 	for (int i = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) c.mat[i * 5 + j] = (int8_t)al_score(c.a, c.b, c.ambi, i, j);
-	mm2gb_ksw_param_t kp;
-	kp.m = 5; memcpy(kp.mat, c.mat, 25); kp.q = (int8_t)opt->q; kp.e = (int8_t)opt->e; kp.q2 = (int8_t)opt->q2; kp.e2 = (int8_t)opt->e2;
-	c.kc = ksw_derive(kp);
+	if (spl) {
+		sp.m = 5; memcpy(sp.mat, c.mat, 25); sp.q = (int8_t)opt->q; sp.e = (int8_t)opt->e; sp.q2 = (int8_t)opt->q2; sp.noncan = (int8_t)spl->noncan; sp.junc_bonus = (int8_t)spl->junc_bonus;
+		c.kc = ksw_derive_splice(sp);
+		c.splice = true; c.noncan = spl->noncan; c.junc_bonus = spl->junc_bonus; c.anchor_ext_len = spl->anchor_ext_len; c.anchor_ext_shift = spl->anchor_ext_shift;
+	} else {
+		mm2gb_ksw_param_t kp;
+		kp.m = 5; memcpy(kp.mat, c.mat, 25); kp.q = (int8_t)opt->q; kp.e = (int8_t)opt->e; kp.q2 = (int8_t)opt->q2; kp.e2 = (int8_t)opt->e2;
+		c.kc = ksw_derive(kp);
+	}
 	c.n_ref = n_ref; c.n_reads = n_reads;
 	const int nt = std::min(n_threads, 256);
 	pack_residues(n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, nt, c.ref_at, c.read_at, c.refs, c.reads);
@@ -945,7 +1097,7 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx
 			memset(&p, 0, sizeof p);
 			p.cigar_off = -1;
 			if (!g.has_p) continue;
-			p.dp_score = g.dp_score; p.dp_max = g.dp_max; p.dp_max2 = g.dp_max2; p.n_ambi = g.n_ambi; p.n_cigar = (int32_t)g.cig.size(); p.cigar_off = nc;
+			p.dp_score = g.dp_score; p.dp_max = g.dp_max; p.dp_max2 = g.dp_max2; p.n_ambi = g.n_ambi; p.trans_strand = g.trans_strand; p.n_cigar = (int32_t)g.cig.size(); p.cigar_off = nc;
 			if (!g.cig.empty()) memcpy(out->cigar + nc, g.cig.data(), g.cig.size() * 4);
 			nc += (int64_t)g.cig.size();
 		}
@@ -953,6 +1105,7 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt, int k, int idx
 			if (k2 == MM2GB_ALN_N_ROUNDS) out->counts[k2] = std::max<int64_t>(out->counts[k2], R[(size_t)r].rounds);
 			else out->counts[k2] += R[(size_t)r].cnt[k2];
 		}
+		if (splice_counts) for (int k2 = 0; k2 < MM2GB_SPL_N_COUNTS; ++k2) splice_counts[k2] += R[(size_t)r].scnt[k2];
 	}
 	out->reg_off[n_reads] = nr;
 	out->n_regs = n_regs; out->n_cigar = n_cigar;
@@ -977,18 +1130,53 @@ int mm2gb_align_opt_init(mm2gb_align_opt_t *opt, const char *preset)
 	return 0;
 }
 
-int mm2gb_align_regs_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
-                          int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                          const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out)
+int mm2gb_align_splice_opt_init(mm2gb_align_splice_opt_t *opt, const char *preset)
+{
+	if (!opt || !preset) return fail("mm2gb_align_splice_opt_init: null argument");
+	const bool hq = !strcmp(preset, "splice:hq");
+	if (strcmp(preset, "splice") != 0 && strcmp(preset, "cdna") != 0 && !hq) return fail(std::string("mm2gb_align_splice_opt_init: preset ") + preset + " is not supported (splice, cdna, splice:hq)");
+	memset(opt, 0, sizeof *opt);            // options.c:14-66, then 151-162
+	mm2gb_align_opt_t &o = opt->base;
+	o.flag = MM2GB_F_SPLICE | MM2GB_F_SPLICE_FOR | MM2GB_F_SPLICE_REV | MM2GB_F_SPLICE_FLANK;
+	o.min_cnt = 3; o.min_chain_score = 40; o.max_gap = 2000; o.bw = o.bw_long = 200000;
+	o.a = 1; o.b = 2; o.q = 2; o.e = 1; o.q2 = 32; o.e2 = 0; o.sc_ambi = 1;
+	opt->noncan = 9; opt->junc_bonus = 9;
+	if (hq) { opt->junc_bonus = 5; o.b = 4; o.q = 6; o.q2 = 24; }
+	o.zdrop = 200; o.zdrop_inv = 100; o.end_bonus = -1;
+	o.min_dp_max = 80; o.min_ksw_len = 200;            // mm_mapopt_init's min_chain_score * a with ITS a = 2; the preset does not touch it
+	opt->anchor_ext_len = 20; opt->anchor_ext_shift = 6;
+	o.max_clip_ratio = 1.0f; o.max_sw_mat = MM2GB_KSW_MAX_CELLS;            // the departure: the preset's 0 means no limit
+	o.rank_min_len = 500; o.rank_frac = 0.9f;
+	return 0;
+}
+
+int mm2gb::al_align_regs_host(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
+                              const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts)
 {
 	// MM2GB_ALIGN_ROUNDS=batch (read at every call): the device form's schedule -- every read in one sequence of rounds, planning and stitching on
 	// n_threads threads -- with the host DP behind it; the same bytes come out.  For checking that schedule where there is no device.
 	const char *mode = getenv("MM2GB_ALIGN_ROUNDS");
 	if (mode && !strcmp(mode, "batch")) {
 		HostBackend be;
-		return al_align_regs("mm2gb_align_regs_host", opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, &be, out);
+		return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, &be, out, splice_counts);
 	}
-	return al_align_regs("mm2gb_align_regs_host", opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, nullptr, out);
+	return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, nullptr, out, splice_counts);
+}
+
+int mm2gb_align_regs_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                          int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                          const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out)
+{
+	return al_align_regs_host("mm2gb_align_regs_host", opt, nullptr, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, out, nullptr);
+}
+
+int mm2gb_align_regs_splice_host(const mm2gb_align_splice_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                                 int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                                 const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts)
+{
+	if (!opt) { if (out) memset(out, 0, sizeof *out); return fail("mm2gb_align_regs_splice_host: null argument"); }
+	return al_align_regs_host("mm2gb_align_regs_splice_host", &opt->base, opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, out, splice_counts);
 }
 
 void mm2gb_align_out_free(mm2gb_align_out_t *out)

@@ -77,7 +77,7 @@ struct DevBackend : AlBackend {
 	{
 		if (!uploaded && upload(c)) return -1;
 		const size_t n = runs.size();
-		if (n >= ((size_t)1 << 31)) return fail("mm2gb_align_regs_gpu: a round is limited to 2^31 jobs");
+		if (n >= ((size_t)1 << 31)) return fail("mm2gb_align_regs: a round is limited to 2^31 jobs");
 		// where every job's bytes go, and the slices that write them; a stretch over max_sw_mat is neither gathered nor run
 		auto t0 = clk::now();
 		std::vector<AlDevJob> dev(n);
@@ -92,10 +92,11 @@ struct DevBackend : AlBackend {
 			dev[k].j = x.j;
 			if (big[k] || dev[k].j.qlen < 0 || dev[k].j.tlen < 0) dev[k].j.qlen = dev[k].j.tlen = 0;
 			if (dev[k].j.qlen == 0 || dev[k].j.tlen == 0) dev[k].j.qlen = dev[k].j.tlen = 0;            // the DP returns at once: nothing to gather
-			dev[k].q_off = q_total; dev[k].t_off = t_total;
-			q_total += (dev[k].j.qlen + 15) / 16 * 16; t_total += (dev[k].j.tlen + 15) / 16 * 16;
+			const bool twin = x.twin > 0 && (size_t)x.twin <= k;          // a chain's second trial: the first one's bytes, nothing gathered
+			if (twin) { dev[k].q_off = dev[k - (size_t)x.twin].q_off; dev[k].t_off = dev[k - (size_t)x.twin].t_off; }
+			else { dev[k].q_off = q_total; dev[k].t_off = t_total; q_total += (dev[k].j.qlen + 15) / 16 * 16; t_total += (dev[k].j.tlen + 15) / 16 * 16; }
 			kj[k] = { dev[k].q_off, dev[k].t_off, dev[k].j.qlen, dev[k].j.tlen, x.w, x.zdrop, x.end_bonus, x.flag };
-			for (int s = 0; s < std::max(dev[k].j.qlen, dev[k].j.tlen); s += AL_SLICE) slices.push_back({ (int32_t)k, s });
+			for (int s = 0; !twin && s < std::max(dev[k].j.qlen, dev[k].j.tlen); s += AL_SLICE) slices.push_back({ (int32_t)k, s });
 		}
 		MM2GB_HIP(hipSetDevice(e.device));
 		MM2GB_HIP(hipStreamSynchronize(e.stream));
@@ -188,6 +189,19 @@ int mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int 
 	if (!eng) { if (out) memset(out, 0, sizeof *out); return fail("mm2gb: null engine"); }
 	eng->e.al_resident[0] = eng->e.al_resident[1] = -1;          // until this call's backend has uploaded its batch
 	DevBackend be(eng->e);
-	return al_align_regs("mm2gb_align_regs_gpu", opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors,
-	                     std::min(usable_cpus(), 16), &be, out);
+	return al_align_regs("mm2gb_align_regs_gpu", opt, nullptr, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors,
+	                     std::min(usable_cpus(), 16), &be, out, nullptr);
+}
+
+// the spliced form: the same backend; the context's constants select the splice-aware fill, a job's flag word carries its trial's
+// strand bits, and a second trial names the first as its twin
+int mm2gb_align_regs_splice_gpu(mm2gb_engine_t *eng, const mm2gb_align_splice_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
+                                const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off,
+                                const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out, int64_t *splice_counts)
+{
+	if (!eng || !opt) { if (out) memset(out, 0, sizeof *out); return fail(!eng ? "mm2gb: null engine" : "mm2gb_align_regs_splice_gpu: null argument"); }
+	eng->e.al_resident[0] = eng->e.al_resident[1] = -1;
+	DevBackend be(eng->e);
+	return al_align_regs("mm2gb_align_regs_splice_gpu", &opt->base, opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors,
+	                     std::min(usable_cpus(), 16), &be, out, splice_counts);
 }

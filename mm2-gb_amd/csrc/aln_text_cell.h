@@ -10,6 +10,9 @@
 //   cs long    no run lengths: a match prints its base, with "=" in front where the column before it in the word is no match.
 //   MD         match: counts; mismatch and the first column of a D word: event, the length prints as "%d", zero too; insertions and the
 //              other columns of a D word neither.  At the record's end a length prints only when positive.
+// The spliced calls (mm2gb_aln_text_splice_*) know a fourth word, N (an intron): ONE column whatever its length, which advances the target
+// by the word's length.  cs, short and long: an event (short form) whose own bytes are "~", the intron's first two target bases, its
+// length, its last two (format.c:179-184; tx_intron_*).  MD: neither event nor count nor bytes (format.c:212-213).  tx_col is not asked.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,7 +82,18 @@ template <class Put> __host__ __device__ inline void tx_put_word(uint32_t w, int
 	const int d = tx_digits(w >> 4);
 	uint32_t v = w >> 4;
 	for (int i = d - 1; i >= 0; --i) { P(p + i, (char)('0' + v % 10)); v /= 10; }
-	P(p + d, "MID"[w & 0xf]);
+	P(p + d, "MIDN"[w & 0xf]);
+}
+// an N word's own bytes in cs:Z: t0 t1 / t2 t3 the first and the last two target residues of the intron (len >= 2: they may be the same two)
+__host__ __device__ inline int tx_intron_bytes(uint32_t len) { return 5 + tx_digits(len); }
+template <class Put> __host__ __device__ inline void tx_put_intron(uint32_t len, int t0, int t1, int t2, int t3, int64_t p, Put P)
+{
+	const char *lo = "acgtn";
+	const int d = tx_digits(len);
+	P(p, '~'); P(p + 1, lo[t0]); P(p + 2, lo[t1]);
+	uint32_t v = len;
+	for (int i = d - 1; i >= 0; --i) { P(p + 3 + i, (char)('0' + v % 10)); v /= 10; }
+	P(p + 3 + d, lo[t2]); P(p + 4 + d, lo[t3]);
 }
 
 // the query residue of column position k of a record: forward reads[q_at + k]; reverse strand: the complement of reads[q_at - k], q_at the

@@ -20,7 +20,7 @@ constexpr uint32_t RF_REV = 1u << 10;          // mm_reg1_t's bit-field word (mi
 constexpr int WHAT_ALL = MM2GB_TEXT_CG | MM2GB_TEXT_CS | MM2GB_TEXT_CS_LONG | MM2GB_TEXT_MD;
 }
 
-int tx_prepare(const std::string &who, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
+int tx_prepare(bool splice, const std::string &who, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
                const int64_t *read_at, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
                int slice, TxPlan &plan)
 {
@@ -44,10 +44,12 @@ int tx_prepare(const std::string &who, int what, int32_t n_ref, const int32_t *r
 		int64_t col = 0, q = 0, t = 0;
 		for (int32_t k = 0; k < aln[i].n_cigar; ++k) {
 			const uint32_t w = cigar[aln[i].cigar_off + k], op = w & 0xf, len = w >> 4;
-			if (op > 2) return fail(rec + ": CIGAR operation " + std::string(1, "MIDNSHP=XB??????"[op]) + " is not supported (M, I and D are)");
+			if (op > (splice ? 3u : 2u)) return fail(rec + ": CIGAR operation " + std::string(1, "MIDNSHP=XB??????"[op]) + " is not supported (" + (splice ? "M, I, D and N are)" : "M, I and D are)"));
 			if (len == 0) return fail(rec + ": a CIGAR word of length 0");
+			if (op == 3 && len < 2) return fail(rec + ": an N word shorter than 2 (format.c:180 asserts it)");
 			plan.words.push_back({ (int32_t)col, (int32_t)q, (int32_t)t, w });
-			col += len; if (op != 2) q += len; if (op != 1) t += len;
+			if (op == 3) { col += 1; t += len; plan.introns = true; }          // an intron is one column
+			else { col += len; if (op != 2) q += len; if (op != 1) t += len; }
 			if (col > INT32_MAX) return fail(rec + ": more than 2^31 columns");
 		}
 		if (q != g.qe - g.qs || t != g.re - g.rs) return fail(rec + ": its CIGAR words do not sum to qe - qs and re - rs");
@@ -93,6 +95,14 @@ template <class FT, class FQ> void tx_walk(const TxPlan &p, const TxRec &x, FT T
 	for (int32_t k = 0; k < x.n_words; ++k) {
 		const int op = (int)(W[k].w & 0xf), len = (int)(W[k].w >> 4);
 		bool prev = false;
+		if (op == 3) {          // an intron: one column, its own bytes in cs, nothing in MD
+			if (p.mode == TX_MD) continue;
+			if (p.mode == TX_CS) close(false);
+			const size_t at = s.size();
+			s.resize(at + (size_t)tx_intron_bytes((uint32_t)len));
+			tx_put_intron((uint32_t)len, T(W[k].t), T(W[k].t + 1), T(W[k].t + len - 2), T(W[k].t + len - 1), (int64_t)at, put);
+			continue;
+		}
 		for (int j = 0; j < len; ++j) {
 			const int t = op != 1 ? T(W[k].t + j) : 0, q = op != 2 ? Q(W[k].q + j) : 0;
 			const TxCol c = tx_col(p.mode, op, j == 0, t, q, prev);
@@ -111,16 +121,18 @@ template <class FT, class FQ> void tx_walk(const TxPlan &p, const TxRec &x, FT T
 
 using namespace mm2gb;
 
-int mm2gb_aln_text_host(int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens,
-                        int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar, int n_threads,
-                        int64_t **text_off, char **text)
+namespace {
+
+int aln_text_host_any(bool splice, const char *who_, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                      const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar, int n_threads,
+                      int64_t **text_off, char **text)
 {
-	const std::string who = "mm2gb_aln_text_host";
+	const std::string who = who_;
 	if (!text_off || !text) return fail(who + ": null argument");
 	*text_off = nullptr; *text = nullptr;
 	if ((n_ref > 0 && !ref_seqs) || (n_reads > 0 && !read_seqs)) return fail(who + ": null argument");
 	TxPlan p;
-	if (tx_prepare(who, what, n_ref, ref_lens, nullptr, n_reads, read_lens, nullptr, n_regs, regs, read_of_reg, aln, cigar, 0, p)) return -1;
+	if (tx_prepare(splice, who, what, n_ref, ref_lens, nullptr, n_reads, read_lens, nullptr, n_regs, regs, read_of_reg, aln, cigar, 0, p)) return -1;
 	const size_t n = p.recs.size();
 	std::vector<std::string> out(n);
 	auto one = [&](size_t i) {
@@ -143,4 +155,20 @@ int mm2gb_aln_text_host(int what, int32_t n_ref, const char *const *ref_seqs, co
 	for (int64_t i = 0; i < n_regs; ++i) if (k < n && p.reg_of[k] == i) { memcpy(buf + off[i], out[k].data(), out[k].size()); ++k; }
 	*text_off = off; *text = buf;
 	return 0;
+}
+
+} // namespace
+
+int mm2gb_aln_text_host(int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens,
+                        int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar, int n_threads,
+                        int64_t **text_off, char **text)
+{
+	return aln_text_host_any(false, "mm2gb_aln_text_host", what, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, n_regs, regs, read_of_reg, aln, cigar, n_threads, text_off, text);
+}
+
+int mm2gb_aln_text_splice_host(int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens,
+                               int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar, int n_threads,
+                               int64_t **text_off, char **text)
+{
+	return aln_text_host_any(true, "mm2gb_aln_text_splice_host", what, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, n_regs, regs, read_of_reg, aln, cigar, n_threads, text_off, text);
 }

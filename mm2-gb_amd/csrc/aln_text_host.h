@@ -21,7 +21,7 @@ struct TxSlice { int32_t rec, kind, start, n, w_first, n_w; };
 
 struct TxPlan {
 	int mode = TX_CS;
-	bool cg = false, tag = false;
+	bool cg = false, tag = false, introns = false;      // introns: some word is an N
 	std::vector<TxRec> recs;
 	std::vector<int64_t> reg_of;          // recs[i] is record reg_of[i] of the call
 	std::vector<TxWord> words;
@@ -29,13 +29,13 @@ struct TxPlan {
 };
 
 // checks the call (every refusal of mm2gb_aln_text_*) and lays the batch out; ref_at / read_at: n + 1 each, where a sequence's residues begin;
-// slice: columns (words) per slice, 0: no slices wanted (the host form)
-int tx_prepare(const std::string &who, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
+// slice: columns (words) per slice, 0: no slices wanted (the host form); splice: the spliced calls, which take N words (one column each)
+int tx_prepare(bool splice, const std::string &who, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
                const int64_t *read_at, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
                int slice, TxPlan &plan);
 
 // the device form on residues resident in e.al_refs / e.al_reads (one byte per base, laid out by ref_at / read_at as AlCtx has them)
-int aln_text_resident(Engine &e, const char *who, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
+int aln_text_resident(Engine &e, bool splice, const char *who, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
                       const int64_t *read_at, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
                       int64_t **text_off, char **text);
 

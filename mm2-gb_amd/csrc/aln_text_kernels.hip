@@ -10,6 +10,9 @@
 //   write  (k_tx_pass<true>)  the same computation with the open run at the cut known; every column stores its bytes at their final place, the
 //          event that closes a run the whole number.
 // No atomics, no scratch, every byte stored once.
+// The spliced calls (SPLICE): an N word is ONE column (tx_prepare counts it so, and its target position moves on by the word's length), so a cut
+// falls before or after it, never inside; the column is an event in cs:Z with own bytes of its own length (tx_intron_*), nothing in MD:Z.
+// The carry step sees events and counts only and is the same.  A batch of the spliced calls without an N word runs the plain instantiation.
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>
 #include <algorithm>
@@ -42,7 +45,7 @@ __device__ __forceinline__ int wave_sum_incl(int v)
 	return v + (row == 0 ? 0 : row == 1 ? t0 : row == 2 ? t1 : t2);
 }
 
-template <bool WRITE>
+template <bool WRITE, bool SPLICE>
 __global__ __launch_bounds__(TX_WG) void k_tx_pass(int mode, int n_slices, const TxRec *__restrict__ recs, const TxSlice *__restrict__ slices, const TxWord *__restrict__ words,
                                                    const uint8_t *__restrict__ refs, const uint8_t *__restrict__ reads, TxCnt *__restrict__ cnt,
                                                    const int32_t *__restrict__ run_in, const int64_t *__restrict__ dest, char *__restrict__ text)
@@ -88,16 +91,26 @@ __global__ __launch_bounds__(TX_WG) void k_tx_pass(int mode, int n_slices, const
 		const int k = base + tid, p = it & 1;
 		TxCol col;
 		col.ev = col.m = col.n_own = 0; col.own[0] = col.own[1] = col.own[2] = 0;
+		uint32_t intron = 0;                                     // SPLICE: the length of the N word this column is, and its first and last two target residues
+		int i0 = 0, i1 = 0, i2 = 0, i3 = 0;
 		if (k < sl.n) {
 			const int c = sl.start + k;
 			int lo = 0, hi = sl.n_w - 1;                             // the last word that starts at or before c
 			while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s_col[mid] <= c) lo = mid; else hi = mid - 1; }
 			const TxWord w = W[sl.w_first + lo];
 			const int op = (int)(w.w & 0xf), j = c - w.col;
-			const int t = op != 1 ? refs[rc.t_at + w.t + j] : 0, q = op != 2 ? tx_query(reads, rc.q_at, rc.rev, w.q + j) : 0;
-			bool prev = false;
-			if (mode == TX_CS_LONG && op == 0 && j > 0) prev = refs[rc.t_at + w.t + j - 1] == tx_query(reads, rc.q_at, rc.rev, w.q + j - 1);
-			col = tx_col(mode, op, j == 0, t, q, prev);
+			if (SPLICE && op == 3) {
+				if (mode != TX_MD) {
+					const int64_t at = rc.t_at + w.t;
+					intron = w.w >> 4; col.ev = mode == TX_CS;
+					i0 = refs[at]; i1 = refs[at + 1]; i2 = refs[at + intron - 2]; i3 = refs[at + intron - 1];
+				}
+			} else {
+				const int t = op != 1 ? refs[rc.t_at + w.t + j] : 0, q = op != 2 ? tx_query(reads, rc.q_at, rc.rev, w.q + j) : 0;
+				bool prev = false;
+				if (mode == TX_CS_LONG && op == 0 && j > 0) prev = refs[rc.t_at + w.t + j - 1] == tx_query(reads, rc.q_at, rc.rev, w.q + j - 1);
+				col = tx_col(mode, op, j == 0, t, q, prev);
+			}
 		}
 		// the run before this column: the matches since the last event below it in the wave, or else since the wave began plus what was open there
 		const int m = col.m, upto_m = wave_sum_incl(m), before_m = upto_m - m;
@@ -117,7 +130,7 @@ __global__ __launch_bounds__(TX_WG) void k_tx_pass(int mode, int n_slices, const
 		const bool first_ev = !WRITE && col.ev && below < 0 && !any_here;
 		if (first_ev) s_lead = len;
 		const int nb = col.ev && !first_ev ? tx_len_bytes(mode, false, len) : 0;
-		const int b = nb + col.n_own, upto = wave_sum_incl(b);
+		const int b = nb + col.n_own + (SPLICE && intron ? tx_intron_bytes(intron) : 0), upto = wave_sum_incl(b);
 		if (lane == 63) s_by[p][wv] = upto;
 		__syncthreads();
 		int off = 0, all = 0;
@@ -129,6 +142,7 @@ __global__ __launch_bounds__(TX_WG) void k_tx_pass(int mode, int n_slices, const
 			if (col.n_own > 0) put(at, col.own[0]);
 			if (col.n_own > 1) put(at + 1, col.own[1]);
 			if (col.n_own > 2) put(at + 2, col.own[2]);
+			if (SPLICE && intron) tx_put_intron(intron, i0, i1, i2, i3, at, put);
 		}
 		pos += all; total += all; run = run_next; any = any_next;
 	}
@@ -165,7 +179,7 @@ using clk = std::chrono::steady_clock;
 inline double since(clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); }
 }
 
-int aln_text_resident(Engine &e, const char *who_, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
+int aln_text_resident(Engine &e, bool splice, const char *who_, int what, int32_t n_ref, const int32_t *ref_lens, const int64_t *ref_at, int64_t n_reads, const int32_t *read_lens,
                       const int64_t *read_at, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
                       int64_t **text_off, char **text)
 {
@@ -175,7 +189,7 @@ int aln_text_resident(Engine &e, const char *who_, int what, int32_t n_ref, cons
 	TxPlan p;
 	auto t0 = clk::now();
 	e.tx_s[0] = e.tx_s[1] = e.tx_s[2] = e.tx_s[3] = 0;
-	if (tx_prepare(who, what, n_ref, ref_lens, ref_at, n_reads, read_lens, read_at, n_regs, regs, read_of_reg, aln, cigar, TX_SLICE, p)) return -1;
+	if (tx_prepare(splice, who, what, n_ref, ref_lens, ref_at, n_reads, read_lens, read_at, n_regs, regs, read_of_reg, aln, cigar, TX_SLICE, p)) return -1;
 	e.tx_s[1] = since(t0);
 	t0 = clk::now();
 	const size_t n_recs = p.recs.size(), n_sl = p.slices.size();
@@ -195,7 +209,7 @@ int aln_text_resident(Engine &e, const char *who_, int what, int32_t n_ref, cons
 		MM2GB_HIP(hipMemcpyAsync(e.tx_slices.ptr, p.slices.data(), n_sl * sizeof(TxSlice), hipMemcpyHostToDevice, e.stream));
 		const TxRec *d_recs = (const TxRec*)e.tx_recs.ptr; const TxSlice *d_sl = (const TxSlice*)e.tx_slices.ptr; const TxWord *d_words = (const TxWord*)e.tx_words.ptr;
 		const uint8_t *d_refs = (const uint8_t*)e.al_refs.ptr, *d_reads = (const uint8_t*)e.al_reads.ptr;
-		hipLaunchKernelGGL(k_tx_pass<false>, dim3((unsigned)n_sl), dim3(TX_WG), 0, e.stream, p.mode, (int)n_sl, d_recs, d_sl, d_words, d_refs, d_reads, (TxCnt*)e.tx_cnt.ptr,
+		hipLaunchKernelGGL((p.introns ? k_tx_pass<false, true> : k_tx_pass<false, false>), dim3((unsigned)n_sl), dim3(TX_WG), 0, e.stream, p.mode, (int)n_sl, d_recs, d_sl, d_words, d_refs, d_reads, (TxCnt*)e.tx_cnt.ptr,
 		                   (const int32_t*)nullptr, (const int64_t*)nullptr, (char*)nullptr);
 		MM2GB_HIP(hipGetLastError());
 		hipLaunchKernelGGL(k_tx_carry, dim3((unsigned)((n_recs + 63) / 64)), dim3(64), 0, e.stream, p.mode, (int)n_recs, (int)n_sl, d_recs, (const TxCnt*)e.tx_cnt.ptr, (int32_t*)e.tx_run.ptr,
@@ -211,7 +225,7 @@ int aln_text_resident(Engine &e, const char *who_, int what, int32_t n_ref, cons
 	guard.b = buf;
 	if (total > 0) {
 		if (e.tx_text.ensure((size_t)total)) return -1;
-		hipLaunchKernelGGL(k_tx_pass<true>, dim3((unsigned)n_sl), dim3(TX_WG), 0, e.stream, p.mode, (int)n_sl, (const TxRec*)e.tx_recs.ptr, (const TxSlice*)e.tx_slices.ptr,
+		hipLaunchKernelGGL((p.introns ? k_tx_pass<true, true> : k_tx_pass<true, false>), dim3((unsigned)n_sl), dim3(TX_WG), 0, e.stream, p.mode, (int)n_sl, (const TxRec*)e.tx_recs.ptr, (const TxSlice*)e.tx_slices.ptr,
 		                   (const TxWord*)e.tx_words.ptr, (const uint8_t*)e.al_refs.ptr, (const uint8_t*)e.al_reads.ptr, (TxCnt*)nullptr, (const int32_t*)e.tx_run.ptr,
 		                   (const int64_t*)e.tx_dest.ptr, (char*)e.tx_text.ptr);
 		MM2GB_HIP(hipGetLastError());
@@ -236,11 +250,13 @@ int aln_text_resident(Engine &e, const char *who_, int what, int32_t n_ref, cons
 
 using namespace mm2gb;
 
-int mm2gb_aln_text_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
-                       const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
-                       int64_t **text_off, char **text)
+namespace {
+
+int aln_text_gpu_any(bool splice, const char *who_, mm2gb_engine_t *eng, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads,
+                     const char *const *read_seqs, const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln,
+                     const uint32_t *cigar, int64_t **text_off, char **text)
 {
-	const std::string who = "mm2gb_aln_text_gpu";
+	const std::string who = who_;
 	if (!eng) return fail("mm2gb: null engine");
 	if (!text_off || !text || n_ref < 0 || n_reads < 0 || (n_ref > 0 && (!ref_seqs || !ref_lens)) || (n_reads > 0 && (!read_seqs || !read_lens))) return fail(who + ": null argument");
 	*text_off = nullptr; *text = nullptr;
@@ -259,9 +275,25 @@ int mm2gb_aln_text_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char 
 	MM2GB_HIP(hipStreamSynchronize(e.stream));
 	e.al_resident[0] = (int64_t)refs.size(); e.al_resident[1] = (int64_t)reads.size();
 	const double s_up = since(t0);
-	const int rc = aln_text_resident(e, "mm2gb_aln_text_gpu", what, n_ref, ref_lens, ref_at.data(), n_reads, read_lens, read_at.data(), n_regs, regs, read_of_reg, aln, cigar, text_off, text);
+	const int rc = aln_text_resident(e, splice, who_, what, n_ref, ref_lens, ref_at.data(), n_reads, read_lens, read_at.data(), n_regs, regs, read_of_reg, aln, cigar, text_off, text);
 	e.tx_s[0] = s_up;
 	return rc;
+}
+
+} // namespace
+
+int mm2gb_aln_text_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                       const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
+                       int64_t **text_off, char **text)
+{
+	return aln_text_gpu_any(false, "mm2gb_aln_text_gpu", eng, what, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, n_regs, regs, read_of_reg, aln, cigar, text_off, text);
+}
+
+int mm2gb_aln_text_splice_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                              const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
+                              int64_t **text_off, char **text)
+{
+	return aln_text_gpu_any(true, "mm2gb_aln_text_splice_gpu", eng, what, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, n_regs, regs, read_of_reg, aln, cigar, text_off, text);
 }
 
 int mm2gb_aln_text_gpu_info(mm2gb_engine_t *eng, int64_t *consts2, double *s4)

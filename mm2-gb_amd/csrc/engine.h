@@ -104,6 +104,7 @@ struct Engine {
 	// of one launch, every job's CIGAR words before and after packing, state images too large for LDS, the launches' job counters, the words' offsets
 	// kw_junc: the splice-aware DP's annotation bytes, laid out like kw_t (mm2gb_ksw_exts2_gpu)
 	DevBuf kw_jobs, kw_q, kw_t, kw_res, kw_slab, kw_cig, kw_img, kw_cnt, kw_off, kw_pack, kw_junc;
+	int64_t kw_class_jobs[2] = { 0, 0 };   // since the engine was made: DP jobs launched with their image in LDS / in global memory
 	double kw_ms[2] = { 0, 0 };            // of the last call: fill + backtrack kernels, packing kernel
 	// the alignment of hits (align_kernels.hip; mm2gb_align_regs_gpu): the batch's resident residues (references, reads), a round's job
 	// descriptors, gather slices, the list of gap fills to test and the test's results

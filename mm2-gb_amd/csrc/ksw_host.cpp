@@ -148,7 +148,7 @@ void one_job(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query
 void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words)
 {
 	static thread_local Scratch S;                        // carries only capacity between calls: one_job sizes and writes every array for a job before it reads it
-	one_job<false>(c, job, query, target, nullptr, S, out, words);
+	(c.splice ? one_job<true> : one_job<false>)(c, job, query, target, nullptr, S, out, words);
 }
 
 int ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)

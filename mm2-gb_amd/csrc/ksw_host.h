@@ -10,7 +10,7 @@ int  ksw_check(const char *who, const mm2gb_ksw_param_t *param, int64_t n_jobs, 
                const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
 int  ksw_check_splice(const char *who, const mm2gb_ksw_splice_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
                       const mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);        // ... and of mm2gb_ksw_exts2_*
-// one job on the calling thread (the body of mm2gb_ksw_extd2_host; the thread keeps its scratch): the record, and the job's words appended
+// one job on the calling thread (the body of mm2gb_ksw_extd2_host or, with c.splice, of mm2gb_ksw_exts2_host without annotation; the thread keeps its scratch): the record, and the job's words appended
 void ksw_one_host(const KswConst &c, const mm2gb_ksw_job_t &job, const uint8_t *query, const uint8_t *target, mm2gb_ksw_res_t *out, std::vector<uint32_t> &words);
 // cigar_off of every job from its n_cigar, and the batch's word array (malloc'd, NULL when empty)
 int  ksw_gather(int64_t n_jobs, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);

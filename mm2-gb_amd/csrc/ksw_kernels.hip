@@ -283,6 +283,7 @@ int ksw_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t 
 		const int nt = KSW_NT[L.nt_class], n = L.hi - L.lo;
 		const int per_cu = L.lds_class < 4 ? (int)std::max<int64_t>(1, std::min<int64_t>(std::min(2048 / nt, 8), (160 * 1024) / (L.lds + 1024))) : 2;
 		if (launch_one(e, c, junc != nullptr, L, (int)k, std::min(n, e.n_cu * per_cu))) return -1;
+		e.kw_class_jobs[L.lds_class < 4 ? 0 : 1] += n;
 		if (L.slab > 0) {
 			hipLaunchKernelGGL(k_ksw_walk, dim3((n + 63) / 64), dim3(64), 0, e.stream, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, c.splice ? c.long_thres : 0, (const uint8_t*)e.kw_slab.ptr, (uint32_t*)e.kw_cig.ptr,
 			                   (mm2gb_ksw_res_t*)e.kw_res.ptr);
@@ -336,6 +337,13 @@ int mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *par
 	if (!eng) return fail("mm2gb: null engine");
 	if (ksw_check_splice("mm2gb_ksw_exts2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
 	return ksw_run(eng->e, ksw_derive_splice(*param), n_jobs, jobs, queries, targets, junc, false, res, cigar, n_cigar_total);
+}
+
+int mm2gb_ksw_gpu_class_jobs(mm2gb_engine_t *eng, int64_t *jobs2)
+{
+	if (!eng || !jobs2) return fail("mm2gb_ksw_gpu_class_jobs: null argument");
+	jobs2[0] = eng->e.kw_class_jobs[0]; jobs2[1] = eng->e.kw_class_jobs[1];
+	return 0;
 }
 
 int mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2)

@@ -11,8 +11,10 @@
 //   mm2gb_align_regs_* in one call (map.c:342-352), 6b then per read mm_set_parent, mm_select_sub and mm_set_mapq in their forms with an
 //   alignment, 6c and the PAF line gets NM/ms/AS/nn/de and cg:Z / cs:Z / MD:Z (the text of the whole batch from one mm2gb_aln_text_* call).
 //
-// Not reproduced: more than one query segment, spliced and short-read alignment, --eqx, SAM output, ALT contigs, the heap variant of
-// seed collection, --qstrand, multi-part indexes.
+//   With a mm2gb_map_splice_t (mm2gb_map_reads_splice; minimap2 -x splice -c): the same stages with is_cdna = 1 in the chaining DP
+//   (map.c:419, 695), no re-chaining stage (map.c:698 leaves MM_F_SPLICE out), the spliced alignment and text calls in 6a / 6c, and ts:A in the line.
+// Not reproduced: more than one query segment, spliced mapping without base-level alignment, short-read alignment, junction annotation, --eqx,
+// SAM output, ALT contigs, the heap variant of seed collection, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -302,6 +304,7 @@ struct MapCall {
 	mm2gb_engine_t *eng; const mm2gb_index_t *ix; int k; const char *const *ref_names; const int32_t *ref_lens; int32_t n_ref;
 	const mm2gb_map_opt_t *opt; int32_t n_reads; const char *const *names; const char *const *seqs; const int32_t *lens;
 	char **paf_out; int64_t *paf_len; mm2gb_map_stats_t *stats; const mm2gb_map_aln_t *aln; double *s_extra;
+	const mm2gb_align_splice_opt_t *spl = nullptr;       // the spliced calls: their alignment options (aln then holds the rest of the mm2gb_map_splice_t)
 };
 
 // what the stages of one batch share
@@ -431,7 +434,7 @@ int chain(Batch &B)
 	const mm2gb_map_opt_t &opt = B.opt;
 	mm2gb_misc_t &misc = B.misc;
 	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = opt.max_gap; misc.max_dist_x = opt.max_gap_ref > 0 ? opt.max_gap_ref : opt.max_gap;
-	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
+	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = B.c.spl ? 1 : 0; misc.n_seg = 1;
 	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * B.c.k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * B.c.k);
 	if (mm2gb_engine_set_misc(eng, &misc)) return -1;
 	mm2gb_chains_t &ch = B.ch_own.c;
@@ -668,6 +671,11 @@ int align_kept(Batch &B, Aligned &A)
 	const MapCall &c = B.c;
 	const int idx_flag = mm2gb_index_flag(c.ix);
 	if (idx_flag < 0) return -1;
+	if (c.spl)
+		return B.aln->align_on_device < 0 ? mm2gb_align_regs_splice_host(c.spl, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(),
+		                                                                 B.ca, B.nt, &A.o, nullptr)
+		                                  : mm2gb_align_regs_splice_gpu(c.eng, c.spl, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(),
+		                                                                B.ca, &A.o, nullptr);
 	return B.aln->align_on_device < 0 ? mm2gb_align_regs_host(&B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca,
 	                                                          B.nt, &A.o)
 	                                  : mm2gb_align_regs_gpu(c.eng, &B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca, &A.o);
@@ -706,16 +714,17 @@ int tag_text(Batch &B, Aligned &A)
 			treg[j] = A.o.regs[A.kept[r][i].aln]; taln[j] = A.o.aln[A.kept[r][i].aln]; tread[j] = (int32_t)r;
 		}
 	if (aln->text_on_device <= 0)                         // text_on_device 0: the host form (profiles/aln_text_rate.json)
-		return mm2gb_aln_text_host(aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, B.nt, &A.tx_off, &A.tx);
+		return (c.spl ? mm2gb_aln_text_splice_host : mm2gb_aln_text_host)(aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar,
+		                                                                  B.nt, &A.tx_off, &A.tx);
 	std::vector<int64_t> ref_at((size_t)c.n_ref + 1, 0), read_at(R + 1, 0);
 	for (int32_t i = 0; i < c.n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + c.ref_lens[i];
 	for (size_t i = 0; i < R; ++i) read_at[i + 1] = read_at[i] + c.lens[i];
 	// the alignment call's device backend says what it left resident (engine.h: al_resident): this batch's residues, or nothing
 	Engine &e = c.eng->e;
 	if (aln->align_on_device >= 0 && e.al_resident[0] == ref_at.back() && e.al_resident[1] == read_at.back())
-		return aln_text_resident(e, "mm2gb_map_reads_aln", aln->what, c.n_ref, c.ref_lens, ref_at.data(), c.n_reads, c.lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
+		return aln_text_resident(e, c.spl != nullptr, c.spl ? "mm2gb_map_reads_splice" : "mm2gb_map_reads_aln", aln->what, c.n_ref, c.ref_lens, ref_at.data(), c.n_reads, c.lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
 		                         A.o.cigar, &A.tx_off, &A.tx);
-	return mm2gb_aln_text_gpu(c.eng, aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, &A.tx_off, &A.tx);
+	return (c.spl ? mm2gb_aln_text_splice_gpu : mm2gb_aln_text_gpu)(c.eng, aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, &A.tx_off, &A.tx);
 }
 
 // ... then the lines
@@ -782,7 +791,8 @@ int map_reads_body(const MapCall &c)
 	if (chain(B)) return -1;                                                                          // 3
 	lap(B.st.s_chain);
 	stage("mm2gb:map_rechain");
-	if (rechain(B)) return -1;                                                                        // 4
+	if (c.spl) B.st.n_chains = B.u_off[B.R];                                                          // 4 (map.c:698: not under MM_F_SPLICE)
+	else if (rechain(B)) return -1;
 	lap(B.st.s_rechain);
 	stage("mm2gb:map_hit_records");
 	if (hit_records(B)) return -1;                                                                    // 5
@@ -1004,6 +1014,51 @@ int mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, co
 	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_stream_aln: ") + why);
 	double s3[3] = { 0, 0, 0 };
 	const int rc = stream_body(engines, n_engines, chunk_bases, { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 });
+	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
+	return rc;
+}
+
+// options.c:151-155 on top of mm_mapopt_init: the mapping fields of the `splice` presets
+void mm2gb_map_opt_init_splice(mm2gb_map_opt_t *o)
+{
+	mm2gb_map_opt_init(o);
+	o->bw = o->bw_long = o->max_gap_ref = 200000; o->max_gap = 2000;
+}
+
+namespace {
+// the mm2gb_map_aln_t the shared stages read, from a mm2gb_map_splice_t; nullptr, or why it cannot be used
+const char *splice_as_aln(const mm2gb_map_splice_t *s, mm2gb_map_aln_t &a)
+{
+	if (!s) return "null argument";
+	a.ref_seqs = s->ref_seqs; a.opt = s->opt.base; a.what = s->what; a.align_on_device = s->align_on_device; a.text_on_device = s->text_on_device;
+	return bad_aln(&a);
+}
+}
+
+int mm2gb_map_reads_splice(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                           const mm2gb_map_opt_t *opt_in, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                           char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
+{
+	mm2gb_map_aln_t aln;
+	if (const char *why = splice_as_aln(spl, aln)) return fail(std::string("mm2gb_map_reads_splice: ") + why);
+	double s3[3] = { 0, 0, 0 };
+	MapCall c = { eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, &aln, s3 };
+	c.spl = &spl->opt;
+	const int rc = map_reads_try(c);
+	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
+	return rc;
+}
+
+int mm2gb_map_reads_stream_splice(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                  int32_t n_ref, const mm2gb_map_opt_t *opt_in, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                  const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
+{
+	mm2gb_map_aln_t aln;
+	if (const char *why = splice_as_aln(spl, aln)) return fail(std::string("mm2gb_map_reads_stream_splice: ") + why);
+	double s3[3] = { 0, 0, 0 };
+	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, &aln, s3 };
+	c.spl = &spl->opt;
+	const int rc = stream_body(engines, n_engines, chunk_bases, c);
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
 }
