@@ -92,6 +92,12 @@ int  mm2gb_engine_set_misc(mm2gb_engine_t *eng, const mm2gb_misc_t *misc);
  * 1 the skip-limited walk.  Stats keep their meaning (n_pairs: the sum of window sizes, not the candidates met). */
 int  mm2gb_engine_set_chain_skip(mm2gb_engine_t *eng, int keep);
 int  mm2gb_engine_last_score_form(const mm2gb_engine_t *eng);
+/* Which build of the exhaustive score kernel did the work of the engine's last micro-batch: 0 the penalty table in LDS, 1 per-pair float
+ * penalties, 2 every branch of comput_sc (cDNA, several segments).  It is the host's choice for the current parameters combined with what
+ * the range pass found in the anchors, exactly as the kernel combines them: a segment id anywhere in the micro-batch gives 2, a query
+ * position too large for the table turns 0 into 1.  Waits for the engine and reads the micro-batch's flag word back; scoring calls carry
+ * no cost for it.  Where the skip-limited walk ran (mm2gb_engine_last_score_form == 1) it is the build the exhaustive kernel would have run. */
+int  mm2gb_engine_last_score_mode(mm2gb_engine_t *eng);
 /* measurement aid: groups of 64 targets that k_score's band pass (far predecessors by diagonal band; MM2GB_BAND, MM2GB_BAND_SLAB,
  * MM2GB_BAND_LAG when the engine is made) swept in the engine's calls since its stats were last reset: out[0] the wave path, out[1] the teams */
 int  mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out);

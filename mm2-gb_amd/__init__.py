@@ -85,7 +85,7 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_batcher_create", "mm2gb_batcher_add", "mm2gb_batcher_feed", "mm2gb_batcher_flush", "mm2gb_batcher_stats", "mm2gb_batcher_destroy",
                 "mm2gb_plan_batches", "mm2gb_rmq_chain_gpu", "mm2gb_lchain_rmq", "mm2gb_lchain_rmq_counts",
                 "mm2gb_sort_seeds_gpu", "mm2gb_gen_regs_gpu", "mm2gb_collect_seeds_gpu",
-                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_band_groups", "mm2gb_engine_band_shape", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
+                "mm2gb_sketch", "mm2gb_index_build", "mm2gb_index_destroy", "mm2gb_index_size", "mm2gb_index_mid_occ", "mm2gb_collect_matches", "mm2gb_matches_free", "mm2gb_map_opt_init", "mm2gb_map_reads", "mm2gb_engine_release_host_scratch", "mm2gb_rmq_chain_host", "mm2gb_rmq_chain_host_tied", "mm2gb_rmq_chain", "mm2gb_engine_set_rmq_kernel", "mm2gb_engine_set_rmq_team_reads", "mm2gb_engine_set_chain_skip", "mm2gb_engine_last_score_form", "mm2gb_engine_last_score_mode", "mm2gb_engine_band_groups", "mm2gb_engine_band_shape", "mm2gb_collect_seeds_host", "mm2gb_map_reads_multi", "mm2gb_map_reads_stream",
                 "mm2gb_sketch_gpu", "mm2gb_index_to_device", "mm2gb_collect_matches_gpu", "mm2gb_match_batch_free",
                 "mm2gb_index_build_gpu", "mm2gb_index_mid_occ_gpu", "mm2gb_index_view", "mm2gb_index_fetch_device", "mm2gb_index_build_split",
                 "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag",
@@ -118,6 +118,7 @@ def lib():
         L.mm2gb_engine_reserve.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
         L.mm2gb_engine_set_chain_skip.argtypes = [C.c_void_p, C.c_int]
         L.mm2gb_engine_last_score_form.argtypes = [C.c_void_p]
+        L.mm2gb_engine_last_score_mode.argtypes = [C.c_void_p]
         L.mm2gb_engine_band_groups.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.mm2gb_score_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.mm2gb_score_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -304,6 +305,14 @@ class Engine:
     def last_score_form(self):
         """Form of the DP the last call ran: 0 exhaustive (k_score), 1 the skip-limited walk (k_skip_fill)."""
         return int(lib().mm2gb_engine_last_score_form(self._h))
+
+    def last_score_mode(self):
+        """Build of k_score that did the work of the last call's last micro-batch: 0 penalty table (LUT), 1 per-pair float penalties (FAST),
+        2 every branch of comput_sc (GENERAL): the host's choice for the parameters combined with the device's flag word.  Waits for the engine."""
+        m = int(lib().mm2gb_engine_last_score_mode(self._h))
+        if m < 0:
+            raise Mm2gbError(lib().mm2gb_last_error().decode())
+        return m
 
     def band_groups(self):
         """Groups of 64 targets k_score's band pass swept in the last call: (wave path, team paths)."""

@@ -156,6 +156,7 @@ struct Engine {
 	bool chain_skip = false;        // the DP keeps misc.max_skip (k_skip_fill) where the limit can be reached; false: exhaustive (k_score), the default.  MM2GB_CHAIN_SKIP=keep at creation
 	int64_t last_band_groups[2] = { 0, 0 };   // groups of targets k_score's band pass swept in the wave path / the team paths, since the last reset of the stats
 	int  last_score_form = 0;       // form of the DP the last enqueued micro-batch ran: 0 exhaustive (k_score), 1 the skip-limited walk (k_skip_fill)
+	int  last_score_set = 0, last_score_host_mode = 0;   // work set (whose flag word the device combined with it) and launch.host_mode of the last enqueued micro-batch (mm2gb_engine_last_score_mode)
 	bool skip_stats = false;        // MM2GB_SKIP_STATS=1: k_skip_fill counts rounds, targets and its slowest chunk (mm2gb_engine_skip_stats; profiles/skip_rate.py)
 	int  last_skip_set = 0;         // work set of the last micro-batch the walk ran on
 

@@ -620,6 +620,7 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 	// window holds at most max_iter of them, so at max_skip >= max_iter the exhaustive kernel gives the same f/p
 	const bool walk = chain_skip && misc.max_skip < misc.max_iter;
 	last_score_form = walk ? 1 : 0;
+	last_score_set = set; last_score_host_mode = launch.host_mode;
 	if (n > 0 && walk) {
 		if (w.skip_mark.ensure((size_t)n * sizeof(int32_t))) return -1;
 		if (skip_stats && w.skip_stats.ensure(SKIP_STAT_WORDS * sizeof(unsigned long long))) return -1;
@@ -1459,6 +1460,18 @@ int mm2gb_engine_device(const mm2gb_engine_t *eng) { return eng ? eng->e.device 
 int mm2gb_engine_set_rmq_team_reads(mm2gb_engine_t *eng, int n) { if (!eng || n < 0) return fail("mm2gb_engine_set_rmq_team_reads: bad argument"); eng->e.rmq_team_reads = n; return 0; }
 int mm2gb_engine_set_chain_skip(mm2gb_engine_t *eng, int keep) { if (!eng || keep < 0 || keep > 1) return fail("mm2gb_engine_set_chain_skip: bad argument"); eng->e.chain_skip = keep == 1; return 0; }
 int mm2gb_engine_last_score_form(const mm2gb_engine_t *eng) { return eng ? eng->e.last_score_form : -1; }
+int mm2gb_engine_last_score_mode(mm2gb_engine_t *eng)
+{
+	if (!eng) return -1;
+	Engine &e = eng->e;
+	if (!e.work[e.last_score_set].flags.ptr) return fail("mm2gb_engine_last_score_mode: engine not initialised");
+	if (e.sync()) return -1;
+	unsigned fl = 0;
+	MM2GB_HIP(hipMemcpy(&fl, e.work[e.last_score_set].flags.ptr, sizeof fl, hipMemcpyDeviceToHost));
+	// k_score's own choice (chain_kernels.hip): a segment id takes every build to GENERAL, an inexact table takes LUT to FAST
+	const int host_mode = e.last_score_host_mode;
+	return (fl & FLAG_ANY_SEGID) ? SCORE_MODE_GENERAL : (host_mode == SCORE_MODE_LUT && (fl & FLAG_NO_LUT)) ? SCORE_MODE_FAST : host_mode;
+}
 int mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out)
 {
 	if (!eng || !out) return fail("mm2gb_engine_band_groups: null argument");

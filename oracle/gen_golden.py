@@ -9,7 +9,7 @@ What is recorded (data only -- inputs and expected outputs, no reference source 
     mg_lchain_dp in-process, same arrays.
   * data/*.fa              : the reference's test FASTA files (its only test data).
 
-Run:  make -C oracle all && python oracle/gen_golden.py
+Run:  make -C oracle all && python oracle/gen_golden.py [synthetic case ...]
 """
 import json
 import os
@@ -65,8 +65,11 @@ def real_pairs():
             print(f"real {name} {tag}: {len(recs)} chaining calls, {sum(len(r['a']) for r in recs)} anchors, {paf.count(chr(10))} PAF lines")
 
 
-def synth_cases():
+def synth_cases(only=()):
     P = orc.default_param
+    splice = dict(sc.SPLICE_KW)
+    spl = sc.spliced(60, 5, noise_n=3000)
+    jumps = sc.jump_chain([5116, 5117, 5118, 5119, 5120, 5121], 9)
     cases = {
         "noise": (sc.noise(4000, 1, n_rid=2, span=200000), P()),
         "read_like": (sc.read_like(20000, 11), P()),
@@ -85,8 +88,18 @@ def synth_cases():
         "iter64": (sc.read_like(8000, 16), P(max_iter=64)),
         "single": (sc.noise(1, 17), P()),
         "pair": (sc.colinear(2, 18), P(min_cnt=1, min_sc=1)),
+        # the per-pair score builds: the splice preset (bw = max_dist_x = 200 000, max_dist_y stays 2 000), the X-drop off on chains it would
+        # cut, the last bw with a penalty table and the first without, three segments
+        "spliced": (spl, P(**splice)),
+        "spliced_iter200": (spl, P(max_iter=200, **splice)),
+        "qins": (sc.qins_chain(150, 7), P(is_cdna=1, bw=100, pen_gap=np.float32(1.0), min_cnt=2, min_sc=15)),
+        "jump_bw5118": (jumps, P(bw=5118, max_dist_x=8000, max_dist_y=8000)),
+        "jump_bw5119": (jumps, P(bw=5119, max_dist_x=8000, max_dist_y=8000)),
+        "three_seg": (sc.with_segments(sc.colinear(600, 44, r0=50_000, q0=10, max_gap=9), 3, 45), P(n_seg=3)),
     }
     for name, (a, prm) in cases.items():
+        if only and name not in only:
+            continue
         r = orc.ref_lchain_dp(a, prm)
         save_case(os.path.join(GOLD, f"synth_{name}.npz"), a, prm, r["f"], r["p"], r["u"], r["a_out"], extra=dict(source="tests/synth_cases.py"))
         print(f"synth {name}: {len(a)} anchors, {len(r['u'])} chains")
@@ -96,5 +109,7 @@ if __name__ == "__main__":
     if not orc.ref_available():
         sys.exit("reference build missing: run `make -C oracle all` in a container that has /root/reference")
     os.makedirs(GOLD, exist_ok=True)
-    real_pairs()
-    synth_cases()
+    only = set(sys.argv[1:])                 # names of synthetic cases: record these alone, leave every other file as it is
+    if not only:
+        real_pairs()
+    synth_cases(only)

@@ -1,5 +1,5 @@
-"""Soak tool (not collected by pytest): python tests/fuzz_soak.py SEED [SEED ...] [--iters N] [--teams] [--post] [--big N] [--huge N]
-Runs tests/synth_cases.fuzz_case batches through the HIP path and the oracle; the first batch that differs is written
+"""Soak tool (not collected by pytest): python tests/fuzz_soak.py SEED [SEED ...] [--iters N] [--general] [--teams] [--post] [--big N] [--huge N]
+Runs tests/synth_cases.fuzz_case batches (--general: fuzz_case_general, the per-pair score builds) through the HIP path and the oracle; the first batch that differs is written
 to gpurun_out/fuzz_fail_<seed>_<iteration>.npz (anchors, offsets, GPU f/p, parameters) and the exit code is 1.
 --teams adds three engines whose planner thresholds send every chunk that fits the LDS ring to the big (8/16-wave) teams and to
 the 4-wave teams (normally reserved for long chunks), and one that sends every chunk of two strips or more to a gang of workgroups, so the cooperative
@@ -15,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("seeds", type=int, nargs="+")
 ap.add_argument("--iters", type=int, default=200)
 ap.add_argument("--teams", action="store_true")
+ap.add_argument("--general", action="store_true", help="batches from synth_cases.fuzz_case_general: cDNA, segments, segment ids under a table launch, bw beyond the table, pen_skip")
 ap.add_argument("--post", action="store_true", help="also the device post-pass (mm2gb_chain_gpu): chains and compacted anchors against the host post-pass of the same scores")
 ap.add_argument("--big", type=int, default=0, help="per seed, also this many batches of bench-like reads (10-100 kb, ~1-2 M anchors) with random parameters")
 ap.add_argument("--huge", type=int, default=0, help="per seed, also this many batches of >= 20 M anchors (30-300 kb reads): the size at which team modes, gangs and the planner's "
@@ -37,8 +38,6 @@ def make_engine(env):
 def post_differs(eng, a, off, prm, what):
     """mm2gb_chain_gpu (scores + device post-pass) against mm2gb_chain_host (same scores, host post-pass); True and a dump if they differ."""
     global failed
-    if prm.n_seg > 1 and False:
-        return False
     dev, _ = eng.chain_gpu(a, off)
     host, _ = eng.chain(a, off, threads=8)
     for r in range(len(off) - 1):
@@ -65,7 +64,7 @@ gang_chunks = 0
 for seed in args.seeds:
     rng = np.random.default_rng(seed)
     for it in range(args.iters):
-        a, off, kw = sc.fuzz_case(rng)
+        a, off, kw = sc.fuzz_case_general(rng, it) if args.general else sc.fuzz_case(rng)
         prm = orc.default_param(**kw)
         fo, po, pairs = orc.chain_fill_many(a, off, prm, threads=4)
         po_rel = np.concatenate([rel(po[off[r]:off[r + 1]]) for r in range(len(off) - 1)]) if len(a) else np.zeros(0, np.int32)

@@ -38,6 +38,32 @@ def test_multi_segment():
     _same(sc.two_segments(600, 42), orc.default_param(n_seg=2, is_cdna=1))
 
 
+def test_inputs_of_the_per_pair_score_builds():
+    """What tests/test_gpu_score_builds.py holds the GPU to the oracle on: the splice preset on a transcript-like read (also with windows
+    cut by max_iter), the X-drop off on chains it would cut, the last bw with a penalty table and the first without, three segments."""
+    spl = sc.spliced(60, 5, noise_n=3000)
+    _same(spl, orc.default_param(**sc.SPLICE_KW))
+    _same(spl, orc.default_param(max_iter=200, **sc.SPLICE_KW))
+    _same(sc.sort_by_x(np.concatenate([sc.repeat_block(3000, 71, xwin=150_000, ywin=1800), sc.spliced(30, 72, r0=2_000_000, q0=5_000)])), orc.default_param(max_iter=100, **sc.SPLICE_KW))
+    _same(sc.qins_chain(150, 7), orc.default_param(is_cdna=1, bw=100, pen_gap=np.float32(1.0), min_cnt=2, min_sc=15))
+    jumps = sc.jump_chain([5116, 5117, 5118, 5119, 5120, 5121], 9)
+    for bw in (5117, 5118, 5119, 5120):
+        _same(jumps, orc.default_param(bw=bw, max_dist_x=8000, max_dist_y=8000))
+    three = sc.with_segments(sc.colinear(600, 44, r0=50_000, q0=10, max_gap=9), 3, 45)
+    for kw in (dict(n_seg=3), dict(n_seg=3, is_cdna=1), dict(n_seg=1), dict(n_seg=2, **dict(sc.SPLICE_KW, is_cdna=0))):
+        _same(three, orc.default_param(**kw))
+    _same(sc.with_segments(spl, 2, 46, share=0.5), orc.default_param(n_seg=2, **sc.SPLICE_KW))
+
+
+def test_fuzz_case_general_oracle_vs_reference():
+    """Ten batches of fuzz_case_general (every parameter class at least once), read by read: f, p, chains and compacted anchors."""
+    rng = np.random.default_rng(411)
+    for it in range(10):
+        a, off, kw = sc.fuzz_case_general(rng, it)
+        for r in range(len(off) - 1):
+            _same(a[off[r]:off[r + 1]], orc.default_param(**kw))
+
+
 @pytest.mark.parametrize("n", [0, 1, 2, 63, 64, 65, 66, 300, 5000, 70000])
 def test_radix_sort_order_matches(n):
     """ksort.h:98-151 is unstable; equal keys must come out in the reference's order."""
