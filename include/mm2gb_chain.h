@@ -352,7 +352,7 @@ int  mm2gb_index_build_split(const mm2gb_index_t *ix, double *ms5);
  *      max-chain-skip = infinity (the GPU path's contract) unless max_chain_skip is set below INT32_MAX.  paf: malloc'd text, one line per
  *      hit in read order (free with mm2gb_free). ---- */
 typedef struct {
-	int64_t flag;              /* MM_F_FOR_ONLY | MM_F_REV_ONLY only */
+	int64_t flag;              /* MM_F_FOR_ONLY | MM_F_REV_ONLY | MM_F_RMQ only (the spliced calls refuse MM_F_RMQ, options.c:173) */
 	int32_t seed, mid_occ, min_mid_occ, max_mid_occ, max_max_occ, occ_dist;
 	float   mid_occ_frac, q_occ_frac;
 	int32_t min_cnt, min_chain_score, bw, bw_long, max_gap, max_gap_ref, max_chain_iter;
@@ -367,6 +367,13 @@ typedef struct {
 } mm2gb_map_opt_t;
 typedef struct { int64_t n_reads, n_mapped, n_anchors, n_chains, n_rechained, n_rmq_tied; double s_seed, s_anchors, s_chain, s_rechain, s_regs, s_post; } mm2gb_map_stats_t;   /* s_*: seconds per stage */
 void mm2gb_map_opt_init(mm2gb_map_opt_t *opt);
+/* mm2gb_map_opt_init, then the mapping fields a preset sets (options.c:95-131): "map-ont" and "map-pb" nothing; "map-hifi" / "map-ccs" max_gap = 10000,
+ * min_mid_occ = 50, max_mid_occ = 500; "asm5" / "asm10" / "asm20" those and bw = 1000, bw_long = 100000, best_n = 50, flag |= MM_F_RMQ.  max_chain_skip stays
+ * what mm2gb_map_opt_init sets.  The index is the caller's: k = 19, w = 19 (asm20: w = 10) for the new names.  Another name: -1 and the error text.
+ * MM_F_RMQ (minimap2 --rmq=yes): stage 3 is not the chaining DP; every read's sorted anchors go through mg_lchain_rmq's fill with bw (map.c:690-692;
+ * max_gap_ref and max_chain_iter play no part), in the form rechain_on_device selects, ties redone by the host form, then re-chaining with bw_long as always. */
+#define MM2GB_F_RMQ 0x80000000LL
+int  mm2gb_map_opt_init_preset(mm2gb_map_opt_t *opt, const char *preset);
 int  mm2gb_map_reads(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
                      const mm2gb_map_opt_t *opt, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                      char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats);
@@ -513,7 +520,8 @@ int  mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *pa
 /* ---- base-level alignment of hits, batched: mm_align_skeleton (align.c:960-1020) for every read of a batch -- which stretches
  *      between and beyond a chain's anchors are aligned, how ends are extended, when a hit is split at a z-drop and when an inversion is
  *      tried, then mm_filter_regs, mm_update_dp_max and mm_hit_sort -- record for record and CIGAR word for CIGAR word.
- *      Options: the fields of mm_mapopt_t those functions read; mm2gb_align_opt_init sets options.c's values for "map-ont" or "map-pb".
+ *      Options: the fields of mm_mapopt_t those functions read; mm2gb_align_opt_init sets options.c's values for "map-ont", "map-pb",
+ *      "map-hifi" (= "map-ccs"), "asm5", "asm10" or "asm20".
  *      Input per read: the sequence as text, the hit records as map.c has them when it calls align_regs (regs[reg_off[r] .. reg_off[r+1]),
  *      `as` counted within the read's anchors) and the read's anchors, not yet squeezed (mm_squeeze_a is part of the call).  k and
  *      idx_flag (MM2GB_I_HPC) are the index's, for mm_adjust_minier.  Reference sequences as text.
@@ -531,6 +539,8 @@ int  mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *pa
 #define MM2GB_F_NO_END_FLT  0x10000000LL
 #define MM2GB_F_QSTRAND     0x100000000LL
 #define MM2GB_F_NO_INV      0x200000000LL
+/* flag: mm_mapopt_t's one flag word.  mm2gb_align_opt_init leaves the asm presets' MM2GB_F_RMQ (0x80000000) in it, as mm_set_opt does; the alignment
+ * calls ignore that bit, but the spliced option set must not carry it into a mapping call (the _splice mapper calls refuse MM_F_RMQ). */
 typedef struct {
 	int64_t flag, max_sw_mat;
 	int32_t a, b, q, e, q2, e2, sc_ambi, zdrop, zdrop_inv, end_bonus;

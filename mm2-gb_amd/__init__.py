@@ -91,7 +91,7 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag",
                 "mm2gb_align_opt_init", "mm2gb_align_regs_host", "mm2gb_align_regs_gpu", "mm2gb_align_out_free",
                 "mm2gb_align_splice_opt_init", "mm2gb_align_regs_splice_host", "mm2gb_align_regs_splice_gpu", "mm2gb_aln_text_splice_host", "mm2gb_aln_text_splice_gpu",
-                "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice"]
+                "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice", "mm2gb_map_opt_init_preset"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -729,7 +729,7 @@ class _AlignOut(C.Structure):
 
 
 def align_opt(preset="map-ont", **kw):
-    """mm2gb_align_opt_init for "map-ont" or "map-pb", then keyword overrides."""
+    """mm2gb_align_opt_init for "map-ont", "map-pb", "map-hifi" / "map-ccs", "asm5", "asm10" or "asm20", then keyword overrides."""
     o = AlignOpt()
     fn = lib().mm2gb_align_opt_init
     fn.argtypes = [C.POINTER(AlignOpt), C.c_char_p]
@@ -1129,12 +1129,17 @@ I_HPC = 0x1    # MM2GB_I_HPC
 def preset(name):
     """The index and seeding parameters of a minimap2 preset, as keywords for SeedIndex (k, w, hpc) and map_reads (k).  "map-pb" (alias
     "map10k"): -H -k19 (options.c:102-103), w = 10.  "splice" / "cdna" / "splice:hq": -k15 -w5 (options.c:152); their alignment options are
-    align_splice_opt's.  No other preset: their mapping options are not the mapper's."""
+    align_splice_opt's.  "map-hifi" / "map-ccs", "asm5", "asm10": -k19 -w19; "asm20": -k19 -w10 (options.c:110-131); their mapping options are
+    map_opt_preset's, their alignment options align_opt's.  No other preset: their mapping options are not the mapper's."""
     if name in ("map-pb", "map10k"):
         return dict(k=19, w=10, hpc=True)
+    if name in ("map-hifi", "map-ccs", "asm5", "asm10"):
+        return dict(k=19, w=19, hpc=False)
+    if name == "asm20":
+        return dict(k=19, w=10, hpc=False)
     if name in ("splice", "cdna", "splice:hq"):
         return dict(k=15, w=5, hpc=False)
-    raise Mm2gbError(f"preset {name!r} is not supported (map-pb / map10k, splice / cdna / splice:hq)")
+    raise Mm2gbError(f"preset {name!r} is not supported (map-pb / map10k, splice / cdna / splice:hq, map-hifi / map-ccs, asm5, asm10, asm20)")
 
 
 def sketch(seq, w=10, k=15, rid=0, hpc=False):
@@ -1337,6 +1342,23 @@ def map_opt(**kw):
     return o
 
 
+F_RMQ = 0x80000000      # MM2GB_F_RMQ (MM_F_RMQ): mg_lchain_rmq as the first chainer; what the asm presets set
+
+
+def map_opt_preset(name, **kw):
+    """mm2gb_map_opt_init_preset: the mapping fields of "map-ont", "map-pb", "map-hifi" / "map-ccs", "asm5", "asm10" or "asm20" (the asm presets set
+    F_RMQ, bw = 1000, bw_long = 100000, best_n = 50), then keyword overrides.  Use an index built with **preset(name) and align=map_align(refs, preset=name)."""
+    o = MapOpt()
+    fn = lib().mm2gb_map_opt_init_preset
+    fn.argtypes = [C.POINTER(MapOpt), C.c_char_p]
+    _check(fn(C.byref(o), name.encode()))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise Mm2gbError(f"mm2gb_map_opt_t has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
 class MapAln(C.Structure):
     """mm2gb_map_aln_t: what mm2gb_map_reads_aln needs beside the mapping options (make one with map_align)."""
     _fields_ = [("ref_seqs", C.POINTER(C.c_char_p)), ("opt", AlignOpt), ("what", C.c_int32), ("align_on_device", C.c_int32), ("text_on_device", C.c_int32)]
@@ -1344,7 +1366,7 @@ class MapAln(C.Structure):
 
 def map_align(refs, preset="map-ont", cigar=True, cs=None, md=False, align_on_device=0, text_on_device=0, **align_opt_fields):
     """Base-level alignment for map_reads / map_reads_stream (their align= argument; minimap2 -c): refs: the reference sequences as bytes, in the
-    index's order; preset: "map-ont" or "map-pb" (align_opt), keyword overrides for its fields; cigar: cg:Z; cs: None, "short" or "long"
+    index's order; preset: any name align_opt takes, keyword overrides for its fields; cigar: cg:Z; cs: None, "short" or "long"
     (--cs, --cs=long); md: MD:Z (--MD; it is written instead of cs when both are asked for, as by minimap2).  align_on_device / text_on_device:
     1 the device form, -1 host threads, 0 the default (alignment on the device; text on host threads)."""
     if cs not in (None, "short", "long"):

@@ -1116,15 +1116,38 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_a
 
 using namespace mm2gb;
 
+namespace mm2gb {
+// options.c:95-131 on top of mm_mapopt_init's a=2 b=4 q=4 e=2 q2=24 e2=1, zdrop 400 / 200, min_dp_max = 40 * 2, max_gap 5000, bw 500 / 20000,
+// min_mid_occ 10, max_mid_occ 1000000, best_n 5.  map-pb changes the index alone (options.c:102-103); MM_F_RMQ is 0x80000000
+static const PresetRow preset_table[] = {
+	//  name        a  b   q   e  q2  e2  zdrop inv  min_dp_max max_gap bw    bw_long  flag         min/max_mid_occ best_n
+	{ "map-ont",    2, 4,  4,  2, 24, 1,  400,  200, 80,        5000,   500,  20000,   0,           10, 1000000,    5 },
+	{ "map-pb",     2, 4,  4,  2, 24, 1,  400,  200, 80,        5000,   500,  20000,   0,           10, 1000000,    5 },
+	{ "map-hifi",   1, 4,  6,  2, 26, 1,  400,  200, 200,       10000,  500,  20000,   0,           50, 500,        5 },
+	{ "map-ccs",    1, 4,  6,  2, 26, 1,  400,  200, 200,       10000,  500,  20000,   0,           50, 500,        5 },
+	{ "asm5",       1, 19, 39, 3, 81, 1,  200,  200, 200,       10000,  1000, 100000,  0x80000000LL, 50, 500,       50 },
+	{ "asm10",      1, 9,  16, 2, 41, 1,  200,  200, 200,       10000,  1000, 100000,  0x80000000LL, 50, 500,       50 },
+	{ "asm20",      1, 4,  6,  2, 26, 1,  200,  200, 200,       10000,  1000, 100000,  0x80000000LL, 50, 500,       50 },
+};
+const char *const preset_names = "map-ont, map-pb, map-hifi, map-ccs, asm5, asm10, asm20";
+const PresetRow *preset_row(const char *name)
+{
+	for (const PresetRow &r : preset_table) if (!strcmp(r.name, name)) return &r;
+	return nullptr;
+}
+}
+
 int mm2gb_align_opt_init(mm2gb_align_opt_t *opt, const char *preset)
 {
 	if (!opt || !preset) return fail("mm2gb_align_opt_init: null argument");
-	if (strcmp(preset, "map-ont") != 0 && strcmp(preset, "map-pb") != 0) return fail(std::string("mm2gb_align_opt_init: preset ") + preset + " is not supported (map-ont, map-pb)");
-	memset(opt, 0, sizeof *opt);            // options.c:14-66; map-pb changes the index alone (options.c:102-103)
-	opt->min_cnt = 3; opt->min_chain_score = 40; opt->bw = 500; opt->bw_long = 20000; opt->max_gap = 5000;
-	opt->a = 2; opt->b = 4; opt->q = 4; opt->e = 2; opt->q2 = 24; opt->e2 = 1; opt->sc_ambi = 1;
-	opt->zdrop = 400; opt->zdrop_inv = 200; opt->end_bonus = -1;
-	opt->min_dp_max = opt->min_chain_score * opt->a; opt->min_ksw_len = 200;
+	const PresetRow *p = preset_row(preset);
+	if (!p) return fail(std::string("mm2gb_align_opt_init: preset ") + preset + " is not supported (" + preset_names + ")");
+	memset(opt, 0, sizeof *opt);            // options.c:14-66, then the preset's row
+	opt->flag = p->map_flag;                // (mm_mapopt_t has one flag word: the asm presets' MM_F_RMQ stands here too; the alignment calls do not look at it)
+	opt->min_cnt = 3; opt->min_chain_score = 40; opt->bw = p->bw; opt->bw_long = p->bw_long; opt->max_gap = p->max_gap;
+	opt->a = p->a; opt->b = p->b; opt->q = p->q; opt->e = p->e; opt->q2 = p->q2; opt->e2 = p->e2; opt->sc_ambi = 1;
+	opt->zdrop = p->zdrop; opt->zdrop_inv = p->zdrop_inv; opt->end_bonus = -1;
+	opt->min_dp_max = p->min_dp_max; opt->min_ksw_len = 200;
 	opt->max_clip_ratio = 1.0f; opt->max_sw_mat = 100000000;
 	opt->rank_min_len = 500; opt->rank_frac = 0.9f;
 	return 0;

@@ -20,6 +20,17 @@ struct AlCtx {
 	std::vector<uint8_t> refs, reads;          // one residue per base (seq_nt4_table); reads as given, the reverse strand is computed
 };
 
+// What a long-read or assembly preset sets on top of mm_mapopt_init (options.c:95-131): one row per name, read by mm2gb_align_opt_init
+// (the scores, drops, min_dp_max, max_gap and the two bands) and by mm2gb_map_opt_init_preset (max_gap, the bands, flag, the mid_occ bounds, best_n)
+struct PresetRow {
+	const char *name;
+	int32_t a, b, q, e, q2, e2, zdrop, zdrop_inv, min_dp_max, max_gap, bw, bw_long;
+	int64_t map_flag;
+	int32_t min_mid_occ, max_mid_occ, best_n;
+};
+const PresetRow *preset_row(const char *name);     // nullptr: not a name of the table
+extern const char *const preset_names;             // the table's names, for error texts
+
 // a base as text -> its residue
 inline uint8_t nt4(char ch)
 {

@@ -13,8 +13,13 @@
 //
 //   With a mm2gb_map_splice_t (mm2gb_map_reads_splice; minimap2 -x splice -c): the same stages with is_cdna = 1 in the chaining DP
 //   (map.c:419, 695), no re-chaining stage (map.c:698 leaves MM_F_SPLICE out), the spliced alignment and text calls in 6a / 6c, and ts:A in the line.
-// Not reproduced: more than one query segment, spliced mapping without base-level alignment, short-read alignment, junction annotation, --eqx,
-// SAM output, ALT contigs, the heap variant of seed collection, --qstrand, multi-part indexes.
+//
+//   With MM_F_RMQ in the options' flag (the asm5 / asm10 / asm20 presets, mm2gb_map_opt_init_preset; minimap2 --rmq=yes): stage 3 is not the chaining
+//   DP -- every read's sorted anchors go through mg_lchain_rmq's fill with bw (map.c:690-692), the same call as stage 4's with bw_long (device and host
+//   threads as rechain_on_device says, ties redone by the host form).  Stage 4 follows as always.  The spliced calls refuse the flag (options.c:173).
+// Not reproduced: more than one query segment, spliced mapping without base-level alignment, short-read alignment (sr), the all-against-all presets
+// (ava-ont, ava-pb: MM_F_ALL_CHAINS, NO_DIAG, NO_DUAL, NO_LJOIN), junction annotation, --eqx, SAM output, ALT contigs, the heap variant of seed
+// collection, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -324,6 +329,8 @@ struct Batch {
 	BigBuf<mm2gb_anchor_t> &anchors;                     // the engine's
 	// the current chains, read where they lie: the chaining call's (ch_own) until re-chaining splices new ones into the engine's arrays
 	ChainsOwner ch_own;
+	BigBuf<uint64_t> first_u;                            // under MM_F_RMQ: the first chainer's result instead (splice)
+	BigBuf<mm2gb_anchor_t> first_a;
 	std::vector<int64_t> u_off, c_off;
 	const uint64_t *u = nullptr;
 	const mm2gb_anchor_t *ca = nullptr;
@@ -391,13 +398,15 @@ int seed_on_device(Batch &B)
 // 2. anchors, sorted: from the matches resident on the device, or from the host's matches -- on the device for large batches
 //    (mm2gb_collect_seeds_gpu: matches up, anchors down, one wave sorts a read); below that the host threads are quicker: the largest
 //    read's sort alone is hundreds of milliseconds for one wave, milliseconds for a core
+int64_t seed_flag(const Batch &B) { return B.opt.flag & ~(int64_t)MM2GB_F_RMQ; }       // the strand bits: all that seed collection looks at
+
 int collect_anchors(Batch &B, bool dev_seed)
 {
 	const size_t R = B.R;
 	mm2gb_engine_t *eng = B.c.eng;
 	if (dev_seed) {
 		B.anchors.resize((size_t)std::max<int64_t>(B.dev_hits, 1));
-		return B.c.eng->e.collect_seeds_resident(B.opt.flag, B.c.n_reads, B.dev_seeds, B.dev_hits, B.a_off.data(), B.anchors.data()) ? -1 : 0;
+		return B.c.eng->e.collect_seeds_resident(seed_flag(B), B.c.n_reads, B.dev_seeds, B.dev_hits, B.a_off.data(), B.anchors.data()) ? -1 : 0;
 	}
 	const std::vector<mm2gb_matches_t> &mt = B.mt;
 	std::vector<int64_t> seed_off(R + 1, 0);
@@ -420,9 +429,9 @@ int collect_anchors(Batch &B, bool dev_seed)
 	});
 	B.anchors.resize((size_t)std::max<int64_t>(n_hits, 1));
 	const bool seeds_on_device = B.opt.seeds_on_device > 0 || (B.opt.seeds_on_device == 0 && n_hits >= 400000000);
-	return seeds_on_device ? mm2gb_collect_seeds_gpu(eng, B.opt.flag, B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
+	return seeds_on_device ? mm2gb_collect_seeds_gpu(eng, seed_flag(B), B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
 	                                                 B.a_off.data(), B.anchors.data())
-	                       : mm2gb_collect_seeds_host(B.opt.flag, B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
+	                       : mm2gb_collect_seeds_host(seed_flag(B), B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
 	                                                  B.nt, B.a_off.data(), B.anchors.data());
 }
 
@@ -437,6 +446,7 @@ int chain(Batch &B)
 	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = B.c.spl ? 1 : 0; misc.n_seg = 1;
 	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * B.c.k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * B.c.k);
 	if (mm2gb_engine_set_misc(eng, &misc)) return -1;
+	if (opt.flag & MM2GB_F_RMQ) return 0;                // (mg_lchain_rmq instead, map.c:690-692: first_chain below, which shares stage 4's fill)
 	mm2gb_chains_t &ch = B.ch_own.c;
 	struct ChainSkipMode {                               // the engine's own mode comes back on every way out of the chaining call
 		bool &mode; const bool before;
@@ -506,23 +516,24 @@ struct Refill {
 // threads, at the same time, the few whose windows are so dense that one wave would still be on them long after the rest of the
 // batch is done, and afterwards the reads the kernel reported a tie for (where the reference's answer follows from the shape of
 // its tree; the host form keeps that tree's rules).  rechain_on_device = 1: every read on the device first; -1: host threads only.
-int rechain_fill(Batch &B, const std::vector<int64_t> &ro, const mm2gb_anchor_t *ra, bool verbose, Refill &F)
+// Both callers: stage 4 with bw_long on the chained anchors, sorted again, and under MM_F_RMQ stage 3 with bw on a read's raw sorted anchors
+// (map.c:690-692 and 705-706 differ in that argument alone).  stage: its name in the MM2GB_DEBUG_PHASES line
+int rmq_fill(Batch &B, int32_t bw, const char *stage, const int64_t *ro, size_t n, const mm2gb_anchor_t *ra, bool verbose, Refill &F)
 {
 	const mm2gb_map_opt_t &opt = B.opt;
-	const mm2gb_rmq_param_t rp = { opt.max_gap, opt.rmq_inner_dist, opt.bw_long, opt.max_chain_skip, opt.rmq_size_cap, opt.min_cnt, opt.min_chain_score, B.misc.chn_pen_gap, B.misc.chn_pen_skip };
-	const size_t n = ro.size() - 1;
+	const mm2gb_rmq_param_t rp = { opt.max_gap, opt.rmq_inner_dist, bw, opt.max_chain_skip, opt.rmq_size_cap, opt.min_cnt, opt.min_chain_score, B.misc.chn_pen_gap, B.misc.chn_pen_skip };
 	if (opt.rechain_on_device == 0) {
 		std::vector<int32_t> where(n, 0);
 		mm2gb_rmq_deal_t deal = {};
-		if (rmq_chain_parts(B.c.eng, &rp, (int64_t)n, ro.data(), ra, B.nt, F.parts, where.data(), &deal)) return -1;
+		if (rmq_chain_parts(B.c.eng, &rp, (int64_t)n, ro, ra, B.nt, F.parts, where.data(), &deal)) return -1;
 		for (size_t q = 0; q < n; ++q) { F.tied[q] = where[q] == 2; F.side[q] = (unsigned char)(2 + F.parts.which[q]); F.slot[q] = F.parts.slot[q]; }
-		if (verbose) fprintf(stderr, "[mm2gb] re-chaining deal: %lld reads on the device, %d of them a whole workgroup's (%.3f s, estimated %.3f), %lld on host threads by cost (%.3f s, estimated %.3f), %lld redone after a tie (%.3f s)\n",
-		                     (long long)deal.n_device, (int)deal.n_team, deal.device_s, deal.est_device_s, (long long)deal.n_host_cost, deal.host_s, deal.est_host_s, (long long)deal.n_host_tie, deal.tie_s);
+		if (verbose) fprintf(stderr, "[mm2gb] %s deal: %lld reads on the device, %d of them a whole workgroup's (%.3f s, estimated %.3f), %lld on host threads by cost (%.3f s, estimated %.3f), %lld redone after a tie (%.3f s)\n",
+		                     stage, (long long)deal.n_device, (int)deal.n_team, deal.device_s, deal.est_device_s, (long long)deal.n_host_cost, deal.host_s, deal.est_host_s, (long long)deal.n_host_tie, deal.tie_s);
 		return 0;
 	}
 	for (size_t q = 0; q < n; ++q) F.slot[q] = (int64_t)q;
-	if (opt.rechain_on_device < 0) return mm2gb_rmq_chain_host(&rp, (int64_t)n, ro.data(), ra, B.nt, &F.rc.c, F.tied.data());
-	if (mm2gb_rmq_chain_gpu(B.c.eng, &rp, (int64_t)n, ro.data(), ra, &F.rc.c, F.tied.data(), nullptr)) return -1;
+	if (opt.rechain_on_device < 0) return mm2gb_rmq_chain_host(&rp, (int64_t)n, ro, ra, B.nt, &F.rc.c, F.tied.data());
+	if (mm2gb_rmq_chain_gpu(B.c.eng, &rp, (int64_t)n, ro, ra, &F.rc.c, F.tied.data(), nullptr)) return -1;
 	std::vector<int64_t> to(1, 0);                       // the tied reads, again on host threads
 	std::vector<mm2gb_anchor_t> ta;
 	for (size_t q = 0; q < n; ++q)
@@ -535,11 +546,14 @@ int rechain_fill(Batch &B, const std::vector<int64_t> &ro, const mm2gb_anchor_t 
 }
 
 // the batch's chains with the re-chained reads' new ones in place, in the engine's arrays (touched pages); the chaining call's result goes
-void splice(Batch &B, const std::vector<int32_t> &redo, const Refill &F)
+// (first: stage 3 under MM_F_RMQ -- there are no chains yet, a read outside `redo` has none, and the result goes to the batch's own arrays, which
+// stage 4's splice then reads while it fills the engine's)
+void splice(Batch &B, const std::vector<int32_t> &redo, const Refill &F, bool first = false)
 {
 	const size_t R = B.R;
 	std::vector<int64_t> nu_off(R + 1, 0), nc_off(R + 1, 0);
 	std::vector<int> which(R, -1);
+	if (first) { B.u_off.assign(R + 1, 0); B.c_off.assign(R + 1, 0); }
 	for (size_t q = 0; q < redo.size(); ++q) { which[(size_t)redo[q]] = (int)q; if (F.tied[q]) ++B.st.n_rmq_tied; }
 	for (size_t r = 0; r < R; ++r) {
 		const int q = which[r];
@@ -549,9 +563,9 @@ void splice(Batch &B, const std::vector<int32_t> &redo, const Refill &F)
 		nu_off[r + 1] = nu_off[r] + (from.u_off[qq + 1] - from.u_off[qq]);
 		nc_off[r + 1] = nc_off[r] + (from.a_off[qq + 1] - from.a_off[qq]);
 	}
-	BigBuf<uint64_t> &nu = host_scratch(B.c.eng).nu;
-	BigBuf<mm2gb_anchor_t> &nc = host_scratch(B.c.eng).nc;
-	nu.resize((size_t)nu_off[R]); nc.resize((size_t)nc_off[R]);
+	BigBuf<uint64_t> &nu = first ? B.first_u : host_scratch(B.c.eng).nu;
+	BigBuf<mm2gb_anchor_t> &nc = first ? B.first_a : host_scratch(B.c.eng).nc;
+	nu.resize((size_t)std::max<int64_t>(nu_off[R], 1)); nc.resize((size_t)std::max<int64_t>(nc_off[R], 1));
 	uint64_t *const nu_ptr = nu.data();
 	mm2gb_anchor_t *const nc_ptr = nc.data();
 	// (a batch's kept anchors are a gigabyte: the copies go to all host threads)
@@ -568,6 +582,32 @@ void splice(Batch &B, const std::vector<int32_t> &redo, const Refill &F)
 	mm2gb_chains_free(&B.ch_own.c);
 }
 
+// 3 under MM_F_RMQ (map.c:690-692): every read that has anchors through the same fill with bw, its raw sorted anchors where stage 2 left them
+// (a read's anchors are contiguous there: the offsets of the picked reads' begins and ends are stage 2's own); the chains land where the chaining
+// call's would.  A read without anchors has no chains; a batch without any is not sent.  The reads go in batch order, not largest first as
+// rechain_pick sends them: the default form deals by cost itself (rmq_chain_parts), but with rechain_on_device = 1 or -1 a large contig at the
+// end of a batch sets the length of the call
+int first_chain(Batch &B)
+{
+	using clk = std::chrono::steady_clock;
+	const auto t0 = clk::now();
+	std::vector<int32_t> redo;
+	for (size_t r = 0; r < B.R; ++r) if (B.a_off[r + 1] > B.a_off[r]) redo.push_back((int32_t)r);
+	Refill F(redo.size());
+	if (!redo.empty()) {
+		// (the reads in between are empty, so the picked reads' anchors are end to end already: no gather)
+		std::vector<int64_t> ro(redo.size() + 1, 0);
+		for (size_t q = 0; q < redo.size(); ++q) ro[q + 1] = B.a_off[(size_t)redo[q] + 1] - B.a_off[(size_t)redo[0]];
+		const bool verbose = getenv("MM2GB_DEBUG_PHASES") != nullptr;
+		if (rmq_fill(B, B.opt.bw, "first chaining", ro.data(), redo.size(), B.anchors.data() + B.a_off[(size_t)redo[0]], verbose, F)) return -1;
+		const auto t_filled = clk::now();
+		splice(B, redo, F, true);
+		if (verbose) fprintf(stderr, "[mm2gb] first chaining (MM_F_RMQ) %zu reads (%lld redone on the host after a tie), %lld anchors: fill %.3f s, splice %.3f s\n", redo.size(), (long long)B.st.n_rmq_tied,
+		                     (long long)ro.back(), std::chrono::duration<double>(t_filled - t0).count(), std::chrono::duration<double>(clk::now() - t_filled).count());
+	} else splice(B, redo, F, true);
+	return 0;
+}
+
 int rechain(Batch &B)
 {
 	using clk = std::chrono::steady_clock;
@@ -577,14 +617,15 @@ int rechain(Batch &B)
 	std::vector<int64_t> ro;
 	rechain_pick(B, redo, ro);
 	B.st.n_rechained = (int64_t)redo.size();
+	const int64_t tied_before = B.st.n_rmq_tied;         // (under MM_F_RMQ the first chaining stage's ties are in the count already)
 	if (!redo.empty()) {
 		const auto t_sorted = clk::now();
 		const bool verbose = getenv("MM2GB_DEBUG_PHASES") != nullptr;
 		Refill F(redo.size());
-		if (rechain_fill(B, ro, host_scratch(B.c.eng).ra.data(), verbose, F)) return -1;
+		if (rmq_fill(B, B.opt.bw_long, "re-chaining", ro.data(), redo.size(), host_scratch(B.c.eng).ra.data(), verbose, F)) return -1;
 		const auto t_filled = clk::now();
 		splice(B, redo, F);
-		if (verbose) fprintf(stderr, "[mm2gb] re-chaining %zu reads (%lld redone on the host after a tie), %lld anchors: sort %.3f s, fill %.3f s, splice %.3f s\n", redo.size(), (long long)B.st.n_rmq_tied, (long long)ro.back(),
+		if (verbose) fprintf(stderr, "[mm2gb] re-chaining %zu reads (%lld redone on the host after a tie), %lld anchors: sort %.3f s, fill %.3f s, splice %.3f s\n", redo.size(), (long long)(B.st.n_rmq_tied - tied_before), (long long)ro.back(),
 		                     seconds(t_rechain, t_sorted), seconds(t_sorted, t_filled), seconds(t_filled, clk::now()));
 	}
 	B.st.n_chains = B.u_off[B.R];
@@ -762,7 +803,8 @@ int map_reads_body(const MapCall &c)
 	if (!c.eng || !c.ix || !c.opt || !c.paf_out || !c.paf_len || c.n_reads < 0 || c.n_ref <= 0 || !c.ref_names || !c.ref_lens || (c.n_reads > 0 && (!c.names || !c.seqs || !c.lens)))
 		return fail("mm2gb_map_reads: null argument");
 	mm2gb_map_opt_t opt = *c.opt;
-	if (opt.flag & ~(int64_t)(0x100000 | 0x200000)) return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported");
+	if (opt.flag & ~(int64_t)(0x100000 | 0x200000 | MM2GB_F_RMQ)) return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported");
+	if (c.spl && (opt.flag & MM2GB_F_RMQ)) return fail("mm2gb_map_reads_splice: MM_F_RMQ does not work with MM_F_SPLICE (options.c:173)");
 	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(c.ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);   // options.c:78-84
 	if (opt.bw_long < opt.bw) opt.bw_long = opt.bw;
 	if (opt.host_threads <= 0) opt.host_threads = std::min(32, usable_cpus());
@@ -788,7 +830,7 @@ int map_reads_body(const MapCall &c)
 	B.st.n_anchors = B.a_off[B.R];
 	lap(B.st.s_anchors);
 	stage("mm2gb:map_chain");
-	if (chain(B)) return -1;                                                                          // 3
+	if (chain(B) || ((opt.flag & MM2GB_F_RMQ) && first_chain(B))) return -1;                          // 3
 	lap(B.st.s_chain);
 	stage("mm2gb:map_rechain");
 	if (c.spl) B.st.n_chains = B.u_off[B.R];                                                          // 4 (map.c:698: not under MM_F_SPLICE)
@@ -940,6 +982,17 @@ void mm2gb_map_opt_init(mm2gb_map_opt_t *o)       // mm_mapopt_init (options.c:1
 	o->mask_level = 0.5f; o->mask_len = INT32_MAX; o->pri_ratio = 0.8f; o->best_n = 5;
 	o->host_threads = 0;           // 0: as many as the process may use, at most 32
 	o->max_chain_skip = INT32_MAX; // (mm_mapopt_init: 25) the GPU path's contract is max-chain-skip = infinity; a finite value is kept on request
+}
+
+int mm2gb_map_opt_init_preset(mm2gb_map_opt_t *o, const char *preset)       // options.c:95-131: the mapping fields of the table's row (align_host.cpp)
+{
+	if (!o || !preset) return fail("mm2gb_map_opt_init_preset: null argument");
+	const PresetRow *p = preset_row(preset);
+	if (!p) return fail(std::string("mm2gb_map_opt_init_preset: preset ") + preset + " is not supported (" + preset_names + ")");
+	mm2gb_map_opt_init(o);
+	o->bw = p->bw; o->bw_long = p->bw_long; o->max_gap = p->max_gap; o->flag |= p->map_flag;
+	o->min_mid_occ = p->min_mid_occ; o->max_mid_occ = p->max_mid_occ; o->best_n = p->best_n;
+	return 0;
 }
 
 int mm2gb_engine_release_host_scratch(mm2gb_engine_t *eng)
