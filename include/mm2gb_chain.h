@@ -496,6 +496,18 @@ int  mm2gb_ksw_gpu_info(mm2gb_engine_t *eng, int64_t *consts6, double *ms2);
  * [0] in LDS, [1] in global memory (the class of a job whose image, proportional to its target, does not fit) */
 int  mm2gb_ksw_gpu_class_jobs(mm2gb_engine_t *eng, int64_t *jobs2);
 
+/* ---- single-affine DP, batched: ksw2's ksw_extz2_sse (ksw2_extz2_sse.c, its SSE2 build), the DP mm_align_pair runs when
+ *      q == q2 && e == e2 (align.c:331) -- one gap cost, the same band, z-drop, end bonus and flags -- field for field and CIGAR word for
+ *      CIGAR word.  Jobs, results, flags and word array are those of the extd2 calls above.  Of the parameter record only m, mat, q and e
+ *      are read; q2 and e2 are IGNORED.  Refused, error text set and nothing run, by both forms: what the extd2 calls refuse (the splice
+ *      flag bits by name), q <= 0, e <= 0, 2(q + e) > 127 (options.c:205, 215), and with m == 1 a residue other than 0.  The reset record
+ *      and no words: m <= 0, an empty side, -min(mat) > 2(q + e), the minimum taken from mat[1] on whatever m is.  m == 1 is NOT an early
+ *      return here.  The host form is the definition; the device form (csrc/ksw_kernels.hip, the same fill kernel in a third form) equals it. ---- */
+int  mm2gb_ksw_extz2_host(const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets,
+                          int n_threads, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+int  mm2gb_ksw_extz2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
+                         const uint8_t *targets, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total);
+
 /* ---- splice-aware DP, batched: ksw2's ksw_exts2_sse (ksw2_exts2_sse.c), the alignment of a cDNA / RNA read's stretches across
  *      introns -- one short gap (q, e), one long gap on the target side only (q2, no extension cost) that opens at donor[] and closes at
  *      acceptor[] -- field for field and CIGAR word for CIGAR word.  Jobs and results are those of the extd2 calls above; the reference's
@@ -528,9 +540,13 @@ int  mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *pa
  *      Output (malloc'd, free with mm2gb_align_out_free): the records after the call with their own reg_off, one mm2gb_aln_t per record
  *      (mm_extra_t without the words; cigar_off = -1 and zeros for a record without one) and the batch's CIGAR words.
  *      Refused, with the error text set, nothing run and *out zeroed: MM_F_SPLICE, MM_F_SR, MM_F_QSTRAND, MM_F_EQX; q == q2 && e == e2
- *      (that path is ksw_extz2_sse); max_sw_mat <= 0 or above MM2GB_KSW_MAX_CELLS; a record whose as + cnt leaves its read's anchors;
- *      multi-segment reads (a record marked seg_split or an anchor of a segment other than 0).
- *      The host form is the definition; the device form (csrc/align_kernels.hip) equals it.  counts (information): see MM2GB_ALN_N_* . ---- */
+ *      (that path is ksw_extz2_sse: the _extz pair below takes it); max_sw_mat <= 0 or above MM2GB_KSW_MAX_CELLS; a record whose as + cnt
+ *      leaves its read's anchors; multi-segment reads (a record marked seg_split or an anchor of a segment other than 0).
+ *      The host form is the definition; the device form (csrc/align_kernels.hip) equals it.  counts (information): see MM2GB_ALN_N_* .
+ *      mm2gb_align_regs_extz_host / _gpu: the same call for an option set with q == q2 && e == e2 (minimap2 -O4 -E2: one number to -O
+ *      and one to -E; main.c:304-309), where mm_align_pair runs ksw_extz2_sse (align.c:331) -- every stretch goes through the
+ *      single-affine DP above, and nothing else differs: the region arithmetic, mm_update_extra's gap score and the inversion test read
+ *      q and e.  They refuse q != q2 || e != e2 (that is the pair without _extz), 2(q + e) > 127, and whatever the pair above refuses. ---- */
 #define MM2GB_F_SPLICE      0x080LL
 #define MM2GB_F_SR          0x1000LL
 #define MM2GB_F_FOR_ONLY    0x100000LL
@@ -569,6 +585,12 @@ int  mm2gb_align_regs_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, in
 int  mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                           int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
                           const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out);
+int  mm2gb_align_regs_extz_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                                int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                                const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out);
+int  mm2gb_align_regs_extz_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                               int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                               const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out);
 void mm2gb_align_out_free(mm2gb_align_out_t *out);
 
 /* ---- spliced alignment of hits, batched: mm_align_skeleton under MM_F_SPLICE -- the end filter of
@@ -644,7 +666,8 @@ int  mm2gb_aln_text_splice_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, con
 
 /* ---- the mapper with base-level alignment (minimap2 -c, --cs, --MD; csrc/mapper.cpp): mm2gb_map_reads / mm2gb_map_reads_stream with a
  *      mm2gb_map_aln_t.  After mm_filter_strand_retained the batch's surviving records go through mm2gb_align_regs_* in one call (map.c:342-352;
- *      k and the HPC flag are the index's; what that call refuses fails the mapping call with the same text), then per read mm_set_parent,
+ *      k and the HPC flag are the index's; what that call refuses fails the mapping call with the same text; with opt.q == opt.q2 &&
+ *      opt.e == opt.e2 -- minimap2 -O4 -E2 -- the call is mm2gb_align_regs_extz_*, the single-affine DP), then per read mm_set_parent,
  *      mm_select_sub and mm_set_mapq in their forms with an alignment, and every PAF line is format.c:274-329's: columns 10 and 11 from the
  *      alignment, NM ms AS nn tp cm s1 s2 de zd rl, then the text mm2gb_aln_text_* gives for `what` (one call for the batch's lines).
  *      s_extra (optional): seconds for the alignment call, the steps after it and the text; stats->s_post holds the rest of the host's share. ---- */

@@ -91,7 +91,8 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_sketch_flag", "mm2gb_sketch_gpu_flag", "mm2gb_index_build_flag", "mm2gb_index_build_gpu_flag", "mm2gb_index_flag",
                 "mm2gb_align_opt_init", "mm2gb_align_regs_host", "mm2gb_align_regs_gpu", "mm2gb_align_out_free",
                 "mm2gb_align_splice_opt_init", "mm2gb_align_regs_splice_host", "mm2gb_align_regs_splice_gpu", "mm2gb_aln_text_splice_host", "mm2gb_aln_text_splice_gpu",
-                "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice", "mm2gb_map_opt_init_preset"]
+                "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice", "mm2gb_map_opt_init_preset",
+                "mm2gb_ksw_extz2_host", "mm2gb_ksw_extz2_gpu", "mm2gb_align_regs_extz_host", "mm2gb_align_regs_extz_gpu"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -638,6 +639,33 @@ def _engine_ksw_info(self):
 
 Engine.ksw_extd2 = _engine_ksw_extd2
 Engine.ksw_extd2_batch = _engine_ksw_extd2_batch
+
+
+# ---- single-affine DP (mm2gb_ksw_extz2_host / _gpu): ksw2's ksw_extz2_sse, what mm_align_pair runs at q == q2 && e == e2.  The calls mirror
+#      the extd2 ones; of the parameters only m, mat, q and e are read ----
+def ksw_extz2_host_batch(param, jobs, queries, targets, threads=4):
+    """mm2gb_ksw_extz2_host on packed arrays (ksw_jobs): the result records (KSW_RES_DTYPE) and the batch's CIGAR words."""
+    return _ksw_call(lib().mm2gb_ksw_extz2_host, (), param, jobs, queries, targets, (int(threads),))
+
+
+def _engine_ksw_extz2_batch(self, param, jobs, queries, targets):
+    """mm2gb_ksw_extz2_gpu on packed arrays: as ksw_extz2_host_batch, on the device."""
+    return _ksw_call(lib().mm2gb_ksw_extz2_gpu, (self._h,), param, jobs, queries, targets, ())
+
+
+def ksw_extz2_host(pairs, param=None, w=-1, zdrop=-1, end_bonus=0, flag=0, threads=4):
+    """The single-affine extension DP for every (query, target) of pairs on host threads -- the definition.  Arguments and results are
+    ksw_extd2_host's; param's q2 and e2 are not read."""
+    return _ksw_dicts(*ksw_extz2_host_batch(param or ksw_param(), *ksw_jobs(pairs, w, zdrop, end_bonus, flag), threads=threads))
+
+
+def _engine_ksw_extz2(self, pairs, param=None, w=-1, zdrop=-1, end_bonus=0, flag=0):
+    """ksw_extz2_host's arguments and results, computed on the device (csrc/ksw_kernels.hip)."""
+    return _ksw_dicts(*self.ksw_extz2_batch(param or ksw_param(), *ksw_jobs(pairs, w, zdrop, end_bonus, flag)))
+
+
+Engine.ksw_extz2 = _engine_ksw_extz2
+Engine.ksw_extz2_batch = _engine_ksw_extz2_batch
 def _engine_ksw_class_jobs(self):
     """mm2gb_ksw_gpu_class_jobs: the DP jobs launched on this engine so far with their image (in LDS, in global memory)."""
     c = (C.c_int64 * 2)()
@@ -791,6 +819,21 @@ def _engine_align_regs(self, opt, k, hpc, refs, reads, regs, anchors):
 
 
 Engine.align_regs = _engine_align_regs
+
+
+# ---- the same calls for q == q2 && e == e2 (minimap2 -O4 -E2), where every stretch goes through the single-affine DP (ksw_extz2) ----
+def align_regs_extz_host(opt, k, hpc, refs, reads, regs, anchors, threads=4):
+    """mm2gb_align_regs_extz_host: align_regs_host's arguments and results for an option set with q == q2 and e == e2
+    (align_opt("map-ont", q2=4, e2=2)), which align_regs_host refuses -- the definition."""
+    return _align_call(lib().mm2gb_align_regs_extz_host, (), opt, k, hpc, refs, reads, regs, anchors, (int(threads),))
+
+
+def _engine_align_regs_extz(self, opt, k, hpc, refs, reads, regs, anchors):
+    """mm2gb_align_regs_extz_gpu: align_regs_extz_host's arguments and results, the DP and its sequences on the device."""
+    return _align_call(lib().mm2gb_align_regs_extz_gpu, (self._h,), opt, k, hpc, refs, reads, regs, anchors, ())
+
+
+Engine.align_regs_extz = _engine_align_regs_extz
 
 
 # ---- spliced alignment of hits (mm2gb_align_regs_splice_host / _gpu): mm_align_skeleton under MM_F_SPLICE; the calls above keep refusing it ----

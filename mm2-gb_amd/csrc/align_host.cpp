@@ -992,7 +992,7 @@ void pack_residues(int32_t n_ref, const char *const *ref_seqs, const int32_t *re
 
 int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                   int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts)
+                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts, bool single)
 {
 	const std::string who = who_;
 	if (!out) return fail(who + ": null argument");
@@ -1017,9 +1017,11 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_a
 			return fail(who + ": q must be 1..127 and q2, noncan and junc_bonus 0..127");
 		if (spl->anchor_ext_len < 0) return fail(who + ": anchor_ext_len must not be negative");
 	}
-	if (!spl && opt->q == opt->q2 && opt->e == opt->e2) return fail(who + ": q == q2 && e == e2 selects ksw_extz2_sse, which is not supported");
+	if (!spl && !single && opt->q == opt->q2 && opt->e == opt->e2) return fail(who + ": q == q2 && e == e2 selects ksw_extz2_sse, which is not supported");
+	if (single && (opt->q != opt->q2 || opt->e != opt->e2))
+		return fail(who + ": q != q2 || e != e2 selects ksw_extd2_sse: that is mm2gb_align_regs_host / mm2gb_align_regs_gpu");
 	if (opt->max_sw_mat <= 0 || opt->max_sw_mat > MM2GB_KSW_MAX_CELLS) return fail(who + ": max_sw_mat must be in 1 .. MM2GB_KSW_MAX_CELLS");
-	if (opt->e <= 0 || opt->q <= 0 || (spl ? opt->q + opt->e : opt->q + opt->e + opt->q2 + opt->e2) > 127) return fail(who + ": gap penalties out of range");
+	if (opt->e <= 0 || opt->q <= 0 || (spl ? opt->q + opt->e : opt->q + opt->e + opt->q2 + opt->e2) > 127) return fail(who + ": gap penalties out of range");      // single: 2(q + e)
 	for (int64_t r = 0; r < n_reads; ++r) {
 		const int64_t na = anchor_off[r + 1] - anchor_off[r];
 		if (na < 0 || reg_off[r + 1] < reg_off[r] || read_lens[r] < 0) return fail(who + ": read " + std::to_string(r) + ": offsets not ascending");
@@ -1050,7 +1052,7 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_a
 	} else {
 		mm2gb_ksw_param_t kp;
 		kp.m = 5; memcpy(kp.mat, c.mat, 25); kp.q = (int8_t)opt->q; kp.e = (int8_t)opt->e; kp.q2 = (int8_t)opt->q2; kp.e2 = (int8_t)opt->e2;
-		c.kc = ksw_derive(kp);
+		c.kc = single ? ksw_derive_single(kp) : ksw_derive(kp);          // align.c:331; nothing else of the call reads q2 or e2
 	}
 	c.n_ref = n_ref; c.n_reads = n_reads;
 	const int nt = std::min(n_threads, 256);
@@ -1175,16 +1177,16 @@ int mm2gb_align_splice_opt_init(mm2gb_align_splice_opt_t *opt, const char *prese
 
 int mm2gb::al_align_regs_host(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
                               const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts)
+                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts, bool single)
 {
 	// MM2GB_ALIGN_ROUNDS=batch (read at every call): the device form's schedule -- every read in one sequence of rounds, planning and stitching on
 	// n_threads threads -- with the host DP behind it; the same bytes come out.  For checking that schedule where there is no device.
 	const char *mode = getenv("MM2GB_ALIGN_ROUNDS");
 	if (mode && !strcmp(mode, "batch")) {
 		HostBackend be;
-		return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, &be, out, splice_counts);
+		return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, &be, out, splice_counts, single);
 	}
-	return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, nullptr, out, splice_counts);
+	return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, nullptr, out, splice_counts, single);
 }
 
 int mm2gb_align_regs_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
@@ -1200,6 +1202,13 @@ int mm2gb_align_regs_splice_host(const mm2gb_align_splice_opt_t *opt, int k, int
 {
 	if (!opt) { if (out) memset(out, 0, sizeof *out); return fail("mm2gb_align_regs_splice_host: null argument"); }
 	return al_align_regs_host("mm2gb_align_regs_splice_host", &opt->base, opt, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, out, splice_counts);
+}
+
+int mm2gb_align_regs_extz_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                               int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                               const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out)
+{
+	return al_align_regs_host("mm2gb_align_regs_extz_host", opt, nullptr, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, out, nullptr, true);
 }
 
 void mm2gb_align_out_free(mm2gb_align_out_t *out)

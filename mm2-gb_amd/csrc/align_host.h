@@ -69,13 +69,14 @@ inline int al_second_zdrop(const AlCtx &ctx, int code) { return code == 2 ? ctx.
 int  al_zdrop_code(const AlCtx &ctx, const AlJob &j, const AlDrop &d);
 
 // the call behind the public forms: whole_batch: every read in one sequence of rounds (the device form) instead of read by read on n_threads
-// threads (the host form).  spl: the spliced calls' options (opt is then &spl->base) with splice_counts (or null); null: the calls that refuse splice
+// threads (the host form).  spl: the spliced calls' options (opt is then &spl->base) with splice_counts (or null); null: the calls that refuse splice.
+// single: the _extz calls, which take q == q2 && e == e2 and nothing else, and run the single-affine DP
 int  al_align_regs(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                    int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                   const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts);
+                   const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts, bool single = false);
 // MM2GB_ALIGN_ROUNDS=batch (read at every call): the host forms run the device form's schedule with the host DP behind it
 int  al_align_regs_host(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
                         const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                        const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts);
+                        const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts, bool single = false);
 
 } // namespace mm2gb

@@ -193,6 +193,18 @@ int mm2gb_align_regs_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int 
 	                     std::min(usable_cpus(), 16), &be, out, nullptr);
 }
 
+// q == q2 && e == e2: the same backend; the context's constants select the single-affine fill
+int mm2gb_align_regs_extz_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                              int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out)
+{
+	if (!eng) { if (out) memset(out, 0, sizeof *out); return fail("mm2gb: null engine"); }
+	eng->e.al_resident[0] = eng->e.al_resident[1] = -1;
+	DevBackend be(eng->e);
+	return al_align_regs("mm2gb_align_regs_extz_gpu", opt, nullptr, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors,
+	                     std::min(usable_cpus(), 16), &be, out, nullptr, true);
+}
+
 // the spliced form: the same backend; the context's constants select the splice-aware fill, a job's flag word carries its trial's
 // strand bits, and a second trial names the first as its twin
 int mm2gb_align_regs_splice_gpu(mm2gb_engine_t *eng, const mm2gb_align_splice_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,

@@ -1,6 +1,7 @@
 // ksw_cell.h -- internal: the dual-affine extension DP's constants, band, cell update, row bookkeeping and backtrack, one definition
 // for the host form (ksw_host.cpp) and the device's (ksw_kernels.hip).  DESIGN 6d says what each piece has to reproduce and why.
-// The splice-aware DP uses the same pieces with a cell and site bytes of its own, at the end of this file.
+// The splice-aware DP uses the same pieces with a cell and site bytes of its own, and so does the single-affine DP
+// (DESIGN 6d-c), whose bytes live in another domain; both at the end of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,13 +13,16 @@ constexpr int KSW_FLAGS_KNOWN = MM2GB_KSW_SCORE_ONLY | MM2GB_KSW_RIGHT | MM2GB_K
                                 MM2GB_KSW_EXTZ_ONLY | MM2GB_KSW_REV_CIGAR;
 
 // What the parameters come to once per batch.  q, e, q2, e2 are the tuple AFTER it has been ordered so that q + e <= q2 + e2;
-// qe0 is q + e BEFORE that (the first cell's H is taken from it: trap 1).  splice: the splice-aware form, which has
-// e2 = 0 and the two splice numbers; all three are 0 in the dual-affine form.  They lie behind the bytes: with them in front of mat[] the
-// dual-affine kernels take two more VGPRs and the global-image ones lose a wave of occupancy.
+// qe0 is q + e BEFORE that (the first cell's H is taken from it: trap 1).  form: which DP.  The splice-aware form has
+// e2 = 0 and the two splice numbers; the single-affine form has e2 = e, ini = ini2 = 0 and the two bytes of its shifted
+// domain, shift = 2(q + e) and cap = mat[0] + shift, both wrapped.  What only one form reads is 0 in the others.  All of it lies behind the
+// bytes: with them in front of mat[] the dual-affine kernels take two more VGPRs and the global-image ones lose a wave of occupancy.
+enum { KSW_DUAL = 0, KSW_SPLICE = 1, KSW_SINGLE = 2 };
 struct KswConst {
 	int    m, q, e, q2, e2, qe0, long_thres, long_diff, early;
 	int8_t mat[25], sc_mch, sc_mis, sc_N, ini, ini2, q8, q28, qe8, qe28;
-	int    splice, noncan, junc_bonus;
+	int    form, noncan, junc_bonus;
+	int8_t shift, cap;
 };
 
 __host__ __device__ inline int8_t ksw_i8(int v) { return (int8_t)(uint8_t)(unsigned)v; }      // wrap to 8 bits (trap 7)
@@ -30,7 +34,7 @@ template <class Param>
 inline KswConst ksw_derive_as(const Param &p, int e2, bool splice)
 {
 	KswConst c = {};
-	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = e2; c.qe0 = c.q + c.e; c.splice = splice;
+	c.m = p.m; c.q = p.q; c.e = p.e; c.q2 = p.q2; c.e2 = e2; c.qe0 = c.q + c.e; c.form = splice ? KSW_SPLICE : KSW_DUAL;
 	for (int i = 0; i < 25; ++i) c.mat[i] = p.mat[i];
 	if (c.m <= 1 || (splice && c.q2 <= c.q + c.e)) { c.early = 1; return c; }
 	if (c.q2 + c.e2 < c.q + c.e) { int t = c.q; c.q = c.q2; c.q2 = t; t = c.e; c.e = c.e2; c.e2 = t; }      // never with splice: q2 > q + e
@@ -51,6 +55,23 @@ inline KswConst ksw_derive_splice(const mm2gb_ksw_splice_param_t &p)
 {
 	KswConst c = ksw_derive_as(p, 0, true);
 	c.noncan = p.noncan; c.junc_bonus = p.junc_bonus;
+	return c;
+}
+// The single-affine form reads m, mat, q and e.  Nothing is ordered and there is no long gap; m == 1 is no early return, the minimum starts
+// from mat[1] whatever m is, and the wildcard is -e (6d-c 6, 7).  e2 = e is what the z-drop reads.
+inline KswConst ksw_derive_single(const mm2gb_ksw_param_t &p)
+{
+	KswConst c = {};
+	c.form = KSW_SINGLE;
+	c.m = p.m; c.q = c.q2 = p.q; c.e = c.e2 = p.e; c.qe0 = c.q + c.e;
+	for (int i = 0; i < 25; ++i) c.mat[i] = p.mat[i];
+	if (c.m <= 0) { c.early = 1; return c; }
+	int min_sc = c.mat[1];
+	for (int t = 1; t < c.m * c.m; ++t) min_sc = min_sc < c.mat[t] ? min_sc : c.mat[t];
+	c.early = -min_sc > 2 * (c.q + c.e);
+	c.sc_mch = c.mat[0]; c.sc_mis = c.mat[1];
+	c.sc_N = c.mat[c.m * c.m - 1] == 0 ? ksw_i8(-c.e) : c.mat[c.m * c.m - 1];
+	c.q8 = ksw_i8(c.q); c.shift = ksw_i8(2 * (c.q + c.e)); c.cap = ksw_i8(c.mat[0] + 2 * (c.q + c.e));
 	return c;
 }
 
@@ -79,10 +100,20 @@ __host__ __device__ inline void ksw_band(int r, int qlen, int tlen, int w, int *
 	*st0 = st; *en0 = en;
 }
 
-// u of the cell on the first column / v left of the first row, at anti-diagonal r: the long gap takes over at long_thres
+// u of the cell on the first column / v left of the first row, at anti-diagonal r: the long gap takes over at long_thres.  The
+// single-affine form's is q with nothing subtracted (6d-c 5).
+template <int FORM = KSW_DUAL>
 __host__ __device__ inline int8_t ksw_edge(const KswConst &c, int r)
 {
+	if (FORM == KSW_SINGLE) return r == 0 ? (int8_t)0 : c.q8;
 	return r == 0 ? c.ini : r < c.long_thres ? ksw_i8(-c.e) : r == c.long_thres ? ksw_i8(c.long_diff) : ksw_i8(-c.e2);
+}
+// what a row's bookkeeping adds to H for a difference byte b (a row's u or v): the byte itself, signed; in the single-affine form the
+// byte read as unsigned, less q + e (6d-c 1)
+template <int FORM>
+__host__ __device__ inline int32_t ksw_diff(const KswConst &c, int8_t b)
+{
+	return FORM == KSW_SINGLE ? (int32_t)(uint8_t)b - c.qe0 : (int32_t)b;
 }
 
 // The byte the score pass finds at target position t.  The pass works in groups of 16 from st0, so it reads up to 15 positions past the
@@ -205,8 +236,9 @@ __host__ __device__ inline bool ksw_row_exact(KswEz &z, const KswConst &c, int q
 	return false;
 }
 
-// After a row in approximate mode: one cell's H is followed down or right, whichever difference is larger.  V(t) / U(t): this row's v, u.
-template <class FV, class FU>
+// After a row in approximate mode: one cell's H is followed down or right, whichever difference is larger.  V(t) / U(t): what this row's
+// v, u add to H (ksw_diff).  The single-affine form does not test the drop at the first cell (6d-c 10).
+template <int FORM = KSW_DUAL, class FV, class FU>
 __host__ __device__ inline bool ksw_row_approx(KswEz &z, const KswConst &c, int qlen, int tlen, int zdrop, int flag, int r, int st0, int en0,
                                                int32_t &H0, int &H0_t, FV V, FU U)
 {
@@ -218,7 +250,7 @@ __host__ __device__ inline bool ksw_row_approx(KswEz &z, const KswConst &c, int 
 		} else if (H0_t >= st0 && H0_t <= en0) H0 += V(H0_t);
 		else { ++H0_t; H0 += U(H0_t); }
 	} else { H0 = V(0) - c.qe0; H0_t = 0; }
-	if ((flag & MM2GB_KSW_APPROX_DROP) && ksw_zdrop(z, H0, r, H0_t, zdrop, c.e2)) return true;
+	if ((flag & MM2GB_KSW_APPROX_DROP) && (FORM != KSW_SINGLE || r > 0) && ksw_zdrop(z, H0, r, H0_t, zdrop, c.e2)) return true;
 	if (r == qlen + tlen - 2 && en0 == tlen - 1) z.score = H0;
 	return false;
 }
@@ -335,6 +367,40 @@ __host__ __device__ inline KswCell ksw_cell_splice(const KswConst &c, bool right
 	o.y2 = 0;
 	if (!right) d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > donor ? 0x20 : 0);
 	else        d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= donor ? 0x20 : 0);
+	o.d = d;
+	return o;
+}
+
+// ---- the single-affine form (ksw2's ksw_extz2_sse in its SSE2 build).  One gap cost, and the bytes in a domain of their own:
+// non-negative and shifted, z = s + 2(q + e) capped at mat[0] + 2(q + e), x and y clamped at 0 with nothing subtracted, every array 0 at the
+// start.  Sums and differences wrap, maximum and minimum are unsigned, and the compares that choose d and clamp are signed: that mix is the
+// reference's, and it decides the cells outside the band that flow into real ones when the band moves. ----
+
+// The first cell of a row takes x1 / v1 from a signed byte that the reference widens to 32 bits before it goes into the vector, so a byte
+// with its top bit set fills the next three lanes too: the left neighbours of cells st + 1 .. st + 3 read as 0xff (6d-c 9).  Only v can
+// have that bit (x is clamped to 0..127), and only where the cap is above 127.  first: the row's boundary v1; k: the cell's distance from
+// st; b: the neighbour's v as stored.
+__host__ __device__ inline int8_t ksw_smear(int8_t first, int k, int8_t b) { return first < 0 && k >= 1 && k <= 3 ? (int8_t)-1 : b; }
+
+// One cell: s the score byte, x1 / v1 the left neighbour's x, v, and the cell's own u, y.  d: bits 0-1 which candidate won, 0x08 / 0x10
+// whether each gap state goes on.  The three code paths of the reference (score only, left, right) compute the same bytes; only d differs.
+__host__ __device__ inline KswCell ksw_cell_single(const KswConst &c, bool right, int8_t s, int8_t x1, int8_t v1, int8_t u, int8_t y)
+{
+	uint8_t z = (uint8_t)(s + c.shift), a = (uint8_t)(x1 + v1), b = (uint8_t)(y + u);
+	uint8_t d = right ? ((int8_t)z > (int8_t)a ? 0 : 1) : ((int8_t)a > (int8_t)z ? 1 : 0);      // on the unclamped z
+	z = (int8_t)z > 0 ? z : 0;
+	z = z > a ? z : a;
+	if (right ? !((int8_t)z > (int8_t)b) : (int8_t)b > (int8_t)z) d = 2;
+	z = z > b ? z : b;
+	z = z < (uint8_t)c.cap ? z : (uint8_t)c.cap;
+	KswCell o;
+	o.u = ksw_i8(z - (uint8_t)v1); o.v = ksw_i8(z - (uint8_t)u);
+	z = (uint8_t)(z - c.q8);
+	const int8_t a8 = ksw_i8(a - z), b8 = ksw_i8(b - z);
+	o.x = a8 > 0 ? a8 : 0; o.y = b8 > 0 ? b8 : 0;
+	o.x2 = o.y2 = 0;
+	if (!right) d |= (a8 > 0 ? 0x08 : 0) | (b8 > 0 ? 0x10 : 0);
+	else        d |= (a8 >= 0 ? 0x08 : 0) | (b8 >= 0 ? 0x10 : 0);
 	o.d = d;
 	return o;
 }

@@ -1,5 +1,6 @@
-// ksw_kernels.hip -- the dual-affine extension DP on the device (mm2gb_ksw_extd2_gpu) and the splice-aware one
-// (mm2gb_ksw_exts2_gpu), which has the same shape: one fill kernel in two forms (k_ksw's SPLICE), one planner, one walk, one pack.
+// ksw_kernels.hip -- the dual-affine extension DP on the device (mm2gb_ksw_extd2_gpu), the splice-aware one
+// (mm2gb_ksw_exts2_gpu) and the single-affine one (mm2gb_ksw_extz2_gpu), which have the same shape: one fill kernel
+// in three forms (k_ksw's FORM), one planner, one walk, one pack.
 // One workgroup per job, taken from a cost-ordered list.  The anti-diagonals are walked in order; the cells of a diagonal's band (rounded out
 // to groups of 16, as the definition in ksw_host.cpp has them) are dealt to the workgroup's threads by position: cell t belongs to thread
 // t mod NT for the whole job, so every array a cell reads only from itself (u, y, y2, the score byte, H) needs no barrier, and the three it
@@ -28,11 +29,11 @@ constexpr int KSW_LDS_STEP[4] = { 8 * 1024, 32 * 1024, 64 * 1024, KSW_LDS_MAX };
 struct KswDevJob { int64_t q_off, t_off, slab_off, cig_off; int32_t qlen, tlen, w, zdrop, end_bonus, flag, idx, ncol; };
 
 // bytes of a job's state image: H when the exact maximum is wanted, u v x x2 twice, y, y2 (the splice-aware form: donor and acceptor) and
-// the score bytes, target and query
-inline int64_t ksw_image_bytes(bool splice, int qlen, int tlen, int flag)
+// the score bytes, target and query.  The single-affine form has neither x2 nor y2: 8 bytes a position where the dual-affine form has 11.
+inline int64_t ksw_image_bytes(int form, int qlen, int tlen, int flag)
 {
 	const int64_t T = ksw_round16(tlen);
-	return ((flag & MM2GB_KSW_APPROX_MAX) ? 0 : 4 * T) + (splice ? 12 : 11) * T + T + ksw_round16(qlen);
+	return ((flag & MM2GB_KSW_APPROX_MAX) ? 0 : 4 * T) + (form == KSW_SPLICE ? 12 : form == KSW_SINGLE ? 8 : 11) * T + T + ksw_round16(qlen);
 }
 
 // The fill.  SPLICE: the splice-aware DP, the same walk over the anti-diagonals with ksw_cell_splice as the cell and donor[] / acceptor[] where
@@ -40,7 +41,9 @@ inline int64_t ksw_image_bytes(bool splice, int qlen, int tlen, int flag)
 // min(qlen, tlen) cells wide, and the image is proportional to the TARGET: a read's stretch across an intron of tens of kilobases has a
 // narrow row over a long image, which then lives in global memory.  donor[] / acceptor[] are filled from the staged target, every thread
 // the positions it owns, so the barrier after staging is the only one they need.  junc: their annotation bytes, or null (SPLICE only).
-template <int NT, bool IN_LDS, bool SPLICE>
+// SINGLE: the single-affine DP, ksw_cell_single as the cell over u, v, x (twice each), y and the score bytes alone, all zero at the start
+// (its c.ini); a row's first v1 reaches three cells further (ksw_smear), and H takes its differences through ksw_diff.
+template <int NT, bool IN_LDS, int FORM>
 __global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *__restrict__ jobs, int lo, int hi, int *counter,
                                             const uint8_t *__restrict__ queries, const uint8_t *__restrict__ targets, const uint8_t *__restrict__ junc, uint8_t *slab,
                                             uint8_t *gimg, int64_t gimg_stride, mm2gb_ksw_res_t *res)
@@ -49,6 +52,7 @@ __global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *_
 	__shared__ uint64_t part[2][NT / 64];
 	__shared__ int s_job;
 	__shared__ int8_t s_mat[25];
+	constexpr bool SPLICE = FORM == KSW_SPLICE, SINGLE = FORM == KSW_SINGLE;
 	const int tid = threadIdx.x;
 	if (tid < 25) s_mat[tid] = c.mat[tid];                  // visible after the loop's first barrier
 	uint8_t *img;
@@ -62,12 +66,12 @@ __global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *_
 		const int qlen = job.qlen, tlen = job.tlen, flag = job.flag, w = job.w, ncol = job.ncol, T = ksw_round16(tlen);
 		const bool with_cigar = !(flag & MM2GB_KSW_SCORE_ONLY), approx = (flag & MM2GB_KSW_APPROX_MAX) != 0, right = (flag & MM2GB_KSW_RIGHT) != 0, generic = (flag & MM2GB_KSW_GENERIC_SC) != 0;
 		int32_t *H = (int32_t*)img;
-		int8_t *u = (int8_t*)img + (approx ? 0 : 4 * T), *v = u + 2 * T, *x = v + 2 * T, *x2 = x + 2 * T, *y = x2 + 2 * T;
-		int8_t *y2 = y + T, *don = y + T, *acc = don + T, *s = (SPLICE ? acc : y2) + T;      // y2, or donor and acceptor
+		int8_t *u = (int8_t*)img + (approx ? 0 : 4 * T), *v = u + 2 * T, *x = v + 2 * T, *x2 = x + (SINGLE ? 0 : 2 * T), *y = x2 + 2 * T;
+		int8_t *y2 = y + T, *don = y + T, *acc = don + T, *s = SINGLE ? y + T : (SPLICE ? acc : y2) + T;      // y2, or donor and acceptor, or neither
 		uint8_t *tg = (uint8_t*)(s + T), *qy = tg + T;
 		for (int t = tid; t < T; t += NT) {
 			u[t] = u[T + t] = v[t] = v[T + t] = x[t] = x[T + t] = y[t] = c.ini;
-			if constexpr (SPLICE) x2[t] = x2[T + t] = c.ini2; else x2[t] = x2[T + t] = y2[t] = c.ini2;
+			if constexpr (SPLICE) x2[t] = x2[T + t] = c.ini2; else if constexpr (!SINGLE) x2[t] = x2[T + t] = y2[t] = c.ini2;
 			s[t] = 0;
 			if (!approx) H[t] = MM2GB_KSW_NEG_INF;
 			if (t < tlen) tg[t] = targets[job.t_off + t];
@@ -92,21 +96,27 @@ __global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *_
 			if constexpr (!SPLICE) if (st0 > en0) { z.zdropped = 1; break; }      // without a band no row is empty
 			const int st = st0 / 16 * 16, en = (en0 + 16) / 16 * 16 - 1, cur = (r & 1) * T, nxt = T - cur;
 			int8_t bx1 = c.ini, bx21 = c.ini2, bv1 = c.ini;
-			if (st > 0) { if (st - 1 >= last_st && st - 1 <= last_en) { bx1 = x[cur + st - 1]; bx21 = x2[cur + st - 1]; bv1 = v[cur + st - 1]; } }
-			else bv1 = ksw_edge(c, r);
-			if (en >= r && (r & (NT - 1)) == tid) { y[r] = c.ini; if constexpr (!SPLICE) y2[r] = c.ini2; u[cur + r] = ksw_edge(c, r); }
+			if (st > 0) { if (st - 1 >= last_st && st - 1 <= last_en) { bx1 = x[cur + st - 1]; if constexpr (!SINGLE) bx21 = x2[cur + st - 1]; bv1 = v[cur + st - 1]; } }
+			else bv1 = ksw_edge<FORM>(c, r);
+			if (en >= r && (r & (NT - 1)) == tid) { y[r] = c.ini; if constexpr (FORM == KSW_DUAL) y2[r] = c.ini2; u[cur + r] = ksw_edge<FORM>(c, r); }
 			const int s_end = generic ? en0 + 1 : min(T, st0 + ((en0 - st0) / 16 + 1) * 16);
 			for (int t = st0 + ((tid - st0) & (NT - 1)); t < s_end; t += NT)
 				s[t] = ksw_score(c, s_mat, generic, ksw_target_byte((const uint8_t*)tg, (const uint8_t*)qy, qlen, tlen, T, t), ksw_query_byte((const uint8_t*)qy, qlen, r, t));
 			uint8_t *pr = p + (int64_t)r * ncol - st;
 			for (int t = st + ((tid - st) & (NT - 1)); t <= en; t += NT) {
 				const bool first = t == st;
-				const int8_t x1 = first ? bx1 : x[cur + t - 1], v1 = first ? bv1 : v[cur + t - 1], x21 = first ? bx21 : x2[cur + t - 1];
 				KswCell o;
-				if constexpr (SPLICE) o = ksw_cell_splice(c, right, s[t], x1, v1, x21, u[cur + t], y[t], don[t], acc[t]);
-				else o = ksw_cell(c, right, s[t], x1, v1, x21, u[cur + t], y[t], y2[t]);
-				u[nxt + t] = o.u; v[nxt + t] = o.v; x[nxt + t] = o.x; x2[nxt + t] = o.x2; y[t] = o.y;
-				if constexpr (!SPLICE) y2[t] = o.y2;
+				if constexpr (SINGLE) {
+					const int8_t x1 = first ? bx1 : x[cur + t - 1], v1 = first ? bv1 : ksw_smear(bv1, t - st, v[cur + t - 1]);
+					o = ksw_cell_single(c, right, s[t], x1, v1, u[cur + t], y[t]);
+				} else {
+					const int8_t x1 = first ? bx1 : x[cur + t - 1], v1 = first ? bv1 : v[cur + t - 1], x21 = first ? bx21 : x2[cur + t - 1];
+					if constexpr (SPLICE) o = ksw_cell_splice(c, right, s[t], x1, v1, x21, u[cur + t], y[t], don[t], acc[t]);
+					else o = ksw_cell(c, right, s[t], x1, v1, x21, u[cur + t], y[t], y2[t]);
+				}
+				u[nxt + t] = o.u; v[nxt + t] = o.v; x[nxt + t] = o.x; y[t] = o.y;
+				if constexpr (!SINGLE) x2[nxt + t] = o.x2;
+				if constexpr (FORM == KSW_DUAL) y2[t] = o.y2;
 				if (with_cigar && t - st < ncol) pr[t] = o.d;
 			}
 			bool stop;
@@ -117,8 +127,8 @@ __global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *_
 				uint64_t key = 0;
 				for (int t = st0 + ((tid - st0) & (NT - 1)); t <= en0; t += NT) {
 					int32_t h;
-					if (t == en0) h = r == 0 ? v[nxt] - c.qe0 : en0 > 0 ? Hl + u[nxt + en0] : H[en0] + v[nxt + en0];
-					else h = H[t] + v[nxt + t];
+					if (t == en0) h = r == 0 ? ksw_diff<FORM>(c, v[nxt]) - c.qe0 : en0 > 0 ? Hl + ksw_diff<FORM>(c, u[nxt + en0]) : H[en0] + ksw_diff<FORM>(c, v[nxt + en0]);
+					else h = H[t] + ksw_diff<FORM>(c, v[nxt + t]);
 					H[t] = h;
 					const uint64_t k = ksw_max_key(h, t, st0, en0);
 					key = k > key ? k : key;
@@ -131,7 +141,7 @@ __global__ __launch_bounds__(NT) void k_ksw(const KswConst c, const KswDevJob *_
 				stop = ksw_row_exact(z, c, qlen, tlen, job.zdrop, r, st0, en0, en, ksw_key_H(key), ksw_key_t(key, st0, en0), H[en0], H[st0]);
 			} else {
 				__syncthreads();
-				stop = ksw_row_approx(z, c, qlen, tlen, job.zdrop, flag, r, st0, en0, H0, H0_t, [=](int t) { return (int32_t)v[nxt + t]; }, [=](int t) { return (int32_t)u[nxt + t]; });
+				stop = ksw_row_approx<FORM>(z, c, qlen, tlen, job.zdrop, flag, r, st0, en0, H0, H0_t, [=](int t) { return ksw_diff<FORM>(c, v[nxt + t]); }, [=](int t) { return ksw_diff<FORM>(c, u[nxt + t]); });
 			}
 			if (stop) break;
 			last_st = st; last_en = en;
@@ -189,14 +199,16 @@ int64_t slab_budget()
 }
 
 using Fill = void (*)(KswConst, const KswDevJob*, int, int, int*, const uint8_t*, const uint8_t*, const uint8_t*, uint8_t*, uint8_t*, int64_t, mm2gb_ksw_res_t*);
-template <bool IN_LDS, bool SPLICE>
-constexpr Fill FILL[3] = { k_ksw<KSW_NT[0], IN_LDS, SPLICE>, k_ksw<KSW_NT[1], IN_LDS, SPLICE>, k_ksw<KSW_NT[2], IN_LDS, SPLICE> };
+template <bool IN_LDS, int FORM>
+constexpr Fill FILL[3] = { k_ksw<KSW_NT[0], IN_LDS, FORM>, k_ksw<KSW_NT[1], IN_LDS, FORM>, k_ksw<KSW_NT[2], IN_LDS, FORM> };
+template <bool IN_LDS>
+inline Fill fill_of(int form, int nt_class) { return (form == KSW_SPLICE ? FILL<IN_LDS, KSW_SPLICE> : form == KSW_SINGLE ? FILL<IN_LDS, KSW_SINGLE> : FILL<IN_LDS, KSW_DUAL>)[nt_class]; }
 
-// launch k of a call: the fill for its classes and c.splice (junc: its annotation bytes are in kw_junc)
+// launch k of a call: the fill for its classes and c.form (junc: its annotation bytes are in kw_junc)
 int launch_one(Engine &e, const KswConst &c, bool junc, const Launch &L, int k, int grid)
 {
 	const bool in_lds = L.lds_class < 4;
-	const Fill fill = in_lds ? (c.splice ? FILL<true, true> : FILL<true, false>)[L.nt_class] : (c.splice ? FILL<false, true> : FILL<false, false>)[L.nt_class];
+	const Fill fill = in_lds ? fill_of<true>(c.form, L.nt_class) : fill_of<false>(c.form, L.nt_class);
 	if (in_lds) MM2GB_HIP(hipFuncSetAttribute((const void*)fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
 	hipLaunchKernelGGL(fill, dim3(grid), dim3(KSW_NT[L.nt_class]), in_lds ? (size_t)L.lds : 0, e.stream, c, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, (int*)e.kw_cnt.ptr + k,
 	                   (const uint8_t*)e.kw_q.ptr, (const uint8_t*)e.kw_t.ptr, junc ? (const uint8_t*)e.kw_junc.ptr : nullptr, (uint8_t*)e.kw_slab.ptr, (uint8_t*)e.kw_img.ptr, L.img,
@@ -207,7 +219,7 @@ int launch_one(Engine &e, const KswConst &c, bool junc, const Launch &L, int k, 
 
 } // namespace
 
-// The planning and the launches behind mm2gb_ksw_extd2_gpu and, with c.splice (and junc, indexed like targets, or null), mm2gb_ksw_exts2_gpu.  resident: the jobs' sequences already lie in kw_q / kw_t at their q_off / t_off
+// The planning and the launches behind mm2gb_ksw_extd2_gpu and, by c.form, mm2gb_ksw_exts2_gpu (with junc, indexed like targets, or null) and mm2gb_ksw_extz2_gpu.  resident: the jobs' sequences already lie in kw_q / kw_t at their q_off / t_off
 // (the alignment call's gather kernel put them there, align_kernels.hip) and nothing is uploaded.  Either way the records (n_cigar set) stay in
 // kw_res, the packed words in kw_pack and their offsets in kw_off until the engine's next call.
 int ksw_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries, const uint8_t *targets, const uint8_t *junc, bool resident,
@@ -227,10 +239,10 @@ int ksw_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t 
 		ksw_store(reset, 0, res + j);
 		if (c.early || b.qlen <= 0 || b.tlen <= 0) continue;
 		Plan P;
-		const int w = ksw_width(b.qlen, b.tlen, c.splice ? -1 : b.w), ncol = ksw_ncol16(b.qlen, b.tlen, w);
+		const int w = ksw_width(b.qlen, b.tlen, c.form == KSW_SPLICE ? -1 : b.w), ncol = ksw_ncol16(b.qlen, b.tlen, w);
 		const bool with_cigar = !(b.flag & MM2GB_KSW_SCORE_ONLY);
 		P.d = { b.q_off, b.t_off, 0, cig_words, b.qlen, b.tlen, w, b.zdrop, b.end_bonus, b.flag, (int32_t)j, ncol };
-		P.img = ksw_image_bytes(c.splice, b.qlen, b.tlen, b.flag);
+		P.img = ksw_image_bytes(c.form, b.qlen, b.tlen, b.flag);
 		P.slab = with_cigar ? ((int64_t)(b.qlen + b.tlen - 1) * ncol + 15) / 16 * 16 : 0;
 		P.cost = (int64_t)(b.qlen + b.tlen - 1) * ((ncol + KSW_NT[2] - 1) / KSW_NT[2]);
 		const int nt_class = ncol <= KSW_BAND[0] ? 0 : ncol <= KSW_BAND[1] ? 1 : 2;
@@ -285,7 +297,7 @@ int ksw_run(Engine &e, const KswConst &c, int64_t n_jobs, const mm2gb_ksw_job_t 
 		if (launch_one(e, c, junc != nullptr, L, (int)k, std::min(n, e.n_cu * per_cu))) return -1;
 		e.kw_class_jobs[L.lds_class < 4 ? 0 : 1] += n;
 		if (L.slab > 0) {
-			hipLaunchKernelGGL(k_ksw_walk, dim3((n + 63) / 64), dim3(64), 0, e.stream, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, c.splice ? c.long_thres : 0, (const uint8_t*)e.kw_slab.ptr, (uint32_t*)e.kw_cig.ptr,
+			hipLaunchKernelGGL(k_ksw_walk, dim3((n + 63) / 64), dim3(64), 0, e.stream, (const KswDevJob*)e.kw_jobs.ptr, L.lo, L.hi, c.form == KSW_SPLICE ? c.long_thres : 0, (const uint8_t*)e.kw_slab.ptr, (uint32_t*)e.kw_cig.ptr,
 			                   (mm2gb_ksw_res_t*)e.kw_res.ptr);
 			MM2GB_HIP(hipGetLastError());
 		}
@@ -337,6 +349,14 @@ int mm2gb_ksw_exts2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_splice_param_t *par
 	if (!eng) return fail("mm2gb: null engine");
 	if (ksw_check_splice("mm2gb_ksw_exts2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
 	return ksw_run(eng->e, ksw_derive_splice(*param), n_jobs, jobs, queries, targets, junc, false, res, cigar, n_cigar_total);
+}
+
+int mm2gb_ksw_extz2_gpu(mm2gb_engine_t *eng, const mm2gb_ksw_param_t *param, int64_t n_jobs, const mm2gb_ksw_job_t *jobs, const uint8_t *queries,
+                        const uint8_t *targets, mm2gb_ksw_res_t *res, uint32_t **cigar, int64_t *n_cigar_total)
+{
+	if (!eng) return fail("mm2gb: null engine");
+	if (ksw_check_single("mm2gb_ksw_extz2_gpu", param, n_jobs, jobs, queries, targets, res, cigar, n_cigar_total)) return -1;
+	return ksw_run(eng->e, ksw_derive_single(*param), n_jobs, jobs, queries, targets, nullptr, false, res, cigar, n_cigar_total);
 }
 
 int mm2gb_ksw_gpu_class_jobs(mm2gb_engine_t *eng, int64_t *jobs2)

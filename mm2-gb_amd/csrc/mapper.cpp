@@ -717,9 +717,12 @@ int align_kept(Batch &B, Aligned &A)
 		                                                                 B.ca, B.nt, &A.o, nullptr)
 		                                  : mm2gb_align_regs_splice_gpu(c.eng, c.spl, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(),
 		                                                                B.ca, &A.o, nullptr);
-	return B.aln->align_on_device < 0 ? mm2gb_align_regs_host(&B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca,
-	                                                          B.nt, &A.o)
-	                                  : mm2gb_align_regs_gpu(c.eng, &B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca, &A.o);
+	// q == q2 && e == e2 (minimap2 -O4 -E2): mm_align_pair runs ksw_extz2_sse (align.c:331), the _extz pair
+	const bool single = B.aln->opt.q == B.aln->opt.q2 && B.aln->opt.e == B.aln->opt.e2;
+	return B.aln->align_on_device < 0 ? (single ? mm2gb_align_regs_extz_host : mm2gb_align_regs_host)(&B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(),
+	                                                                                                  A.rin.data(), B.c_off.data(), B.ca, B.nt, &A.o)
+	                                  : (single ? mm2gb_align_regs_extz_gpu : mm2gb_align_regs_gpu)(c.eng, &B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(),
+	                                                                                                A.rin.data(), B.c_off.data(), B.ca, &A.o);
 }
 
 // 6b. per read: primary / secondary, which secondaries stay and the mapping quality, all with the alignment (map.c:347-348, 758)
