@@ -352,7 +352,8 @@ int  mm2gb_index_build_split(const mm2gb_index_t *ix, double *ms5);
  *      max-chain-skip = infinity (the GPU path's contract) unless max_chain_skip is set below INT32_MAX.  paf: malloc'd text, one line per
  *      hit in read order (free with mm2gb_free). ---- */
 typedef struct {
-	int64_t flag;              /* MM_F_FOR_ONLY | MM_F_REV_ONLY | MM_F_RMQ only (the spliced calls refuse MM_F_RMQ, options.c:173) */
+	int64_t flag;              /* MM_F_FOR_ONLY | MM_F_REV_ONLY | MM_F_RMQ (the spliced calls refuse it, options.c:173) | MM_F_NO_LJOIN, and in the calls without base-level
+	                            * alignment MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_ALL_CHAINS (read overlap: below, mm2gb_map_opt_init_ava) */
 	int32_t seed, mid_occ, min_mid_occ, max_mid_occ, max_max_occ, occ_dist;
 	float   mid_occ_frac, q_occ_frac;
 	int32_t min_cnt, min_chain_score, bw, bw_long, max_gap, max_gap_ref, max_chain_iter;
@@ -363,7 +364,10 @@ typedef struct {
 	int32_t seeds_on_device;   /* matches -> sorted anchors: 1 on the device, -1 on host threads, 0 by batch size */
 	int32_t rechain_on_device; /* mg_lchain_rmq's fill: 0 (default) mm2gb_rmq_chain -- device and host threads at the same time, reads dealt by cost, ties redone on the host; 1 every read on the device first (ties redone on host threads); -1 host threads only */
 	int32_t max_chain_skip;    /* mm_mapopt_t::max_chain_skip; INT32_MAX (the default here): chaining and re-chaining exhaustive.  Below it both keep the limit */
-	int32_t seeding_on_device; /* 1: sketch, look-up and match selection on the device (mm2gb_collect_matches_gpu's kernels), anchors from the resident matches; 0 (default), -1: on host threads */
+	int32_t seeding_on_device; /* 1: sketch, look-up and match selection on the device (mm2gb_collect_matches_gpu's kernels), anchors from the resident matches; 0 (default), -1: on host threads.
+	                            * 2 (MM2GB_SEEDING_RESIDENT): as 1, and in the calls without base-level alignment, where the options have neither a re-chaining stage (MM_F_NO_LJOIN, or
+	                            * bw_long <= bw) nor MM_F_RMQ, the resident path: anchors, chains and kept anchors never leave the device -- hit records and the divergence walk's counts
+	                            * come down.  Where the options do not allow it, and for a batch with more anchors than one chaining micro-batch holds, 2 is 1 */
 } mm2gb_map_opt_t;
 typedef struct { int64_t n_reads, n_mapped, n_anchors, n_chains, n_rechained, n_rmq_tied; double s_seed, s_anchors, s_chain, s_rechain, s_regs, s_post; } mm2gb_map_stats_t;   /* s_*: seconds per stage */
 void mm2gb_map_opt_init(mm2gb_map_opt_t *opt);
@@ -374,6 +378,31 @@ void mm2gb_map_opt_init(mm2gb_map_opt_t *opt);
  * max_gap_ref and max_chain_iter play no part), in the form rechain_on_device selects, ties redone by the host form, then re-chaining with bw_long as always. */
 #define MM2GB_F_RMQ 0x80000000LL
 int  mm2gb_map_opt_init_preset(mm2gb_map_opt_t *opt, const char *preset);
+/* Read against read (minimap2 -x ava-ont / ava-pb, or -X on any option set): seeding and chaining and nothing else.
+ *   MM2GB_F_NO_DIAG     a read's hits on a sequence of its own name and length: those on the diagonal are dropped, the others of the same strand carry MM_SEED_SELF (map.c:212-215)
+ *   MM2GB_F_NO_DUAL     hits on a sequence whose name is smaller than the read's are dropped: every pair is reported once (map.c:216)
+ *   MM2GB_F_NO_LJOIN    no re-chaining stage (map.c:698); honoured by every mapping call
+ *   MM2GB_F_ALL_CHAINS  every chain is reported: no primary / secondary decision, no secondaries dropped (map.c:335); every line is tp:A:S with mapping quality 0
+ * Names compare as strcmp does (bytes as unsigned char); the calls with base-level alignment refuse NO_DIAG, NO_DUAL and ALL_CHAINS by name.
+ * mm2gb_map_opt_init_ava: mm2gb_map_opt_init, then options.c:96-109 for "ava-ont" (the four bits, min_chain_score = 100, pri_ratio = 0, occ_dist = 0, bw = bw_long = 2000; index k = 15,
+ * w = 5) or "ava-pb" (the same with bw_long = bw = 500; index k = 19, w = 5, MM2GB_I_HPC); max_chain_skip stays what mm2gb_map_opt_init sets.  Another name: -1 and the error text. */
+#define MM2GB_SEEDING_RESIDENT 2
+#define MM2GB_F_NO_DIAG    0x001LL
+#define MM2GB_F_NO_DUAL    0x002LL
+#define MM2GB_F_NO_LJOIN   0x400LL
+#define MM2GB_F_ALL_CHAINS 0x800000LL
+int  mm2gb_map_opt_init_ava(mm2gb_map_opt_t *opt, const char *preset);
+/* mm_est_err's walk (esterr.c:30-61) for every hit record of a batch, on host threads (the definition) and on the device (est_err_kernels.hip; equal results):
+ * read r owns regs[reg_off[r] .. reg_off[r+1]) -- looked at: as (an index into the read's anchors, which begin at anchor_off[r]), cnt, rid, qs, rs, re and the rev bit --
+ * and the minimizer positions mini_pos[mini_off[r] .. mini_off[r+1]) (mm2gb_matches_t::mini_pos).  out[j]: n_match and n_tot after both end increments (esterr.c:60-61), or
+ * n_tot = -1 where the walk does not start (no anchors, no minimizers, or the first anchor's position is no minimizer's: esterr.c:36, 45-51) and div stays -1.
+ * sum_k[r]: esterr.c:37-38.  The pow of esterr.c:62 stays on the host in both forms: mm2gb_est_err_div(n_match, n_tot, sum_k, n_mini) finishes it. */
+typedef struct { int32_t n_match, n_tot; } mm2gb_est_err_t;
+int  mm2gb_est_err_host(int64_t n_reads, const int64_t *reg_off, const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, const int32_t *qlen,
+                        const int64_t *mini_off, const uint64_t *mini_pos, int32_t n_ref, const int32_t *ref_len, int n_threads, mm2gb_est_err_t *out, uint64_t *sum_k);
+int  mm2gb_est_err_gpu(mm2gb_engine_t *eng, int64_t n_reads, const int64_t *reg_off, const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, const int32_t *qlen,
+                       const int64_t *mini_off, const uint64_t *mini_pos, int32_t n_ref, const int32_t *ref_len, mm2gb_est_err_t *out, uint64_t *sum_k);
+float mm2gb_est_err_div(int32_t n_match, int32_t n_tot, uint64_t sum_k, int32_t n_mini);
 int  mm2gb_map_reads(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
                      const mm2gb_map_opt_t *opt, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                      char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats);

@@ -1402,6 +1402,101 @@ def map_opt_preset(name, **kw):
     return o
 
 
+# read against read (minimap2 -X = the four together; main.c:176-178): MM2GB_F_NO_DIAG, _NO_DUAL, _NO_LJOIN, _ALL_CHAINS
+F_NO_DIAG, F_NO_DUAL, F_NO_LJOIN, F_ALL_CHAINS = 0x001, 0x002, 0x400, 0x800000
+SEEDING_RESIDENT = 2    # MM2GB_SEEDING_RESIDENT: seeding_on_device's value for the resident path (anchors and chains never leave the device)
+
+
+def map_opt_ava(name, **kw):
+    """mm2gb_map_opt_init_ava: the mapping fields of "ava-ont" or "ava-pb" (options.c:96-109: the four read-overlap bits, min_chain_score = 100, pri_ratio = 0,
+    occ_dist = 0; ava-ont bw = bw_long = 2000, ava-pb bw_long = bw), then keyword overrides.  Use an index built with **preset_ava(name), and no align=."""
+    o = MapOpt()
+    fn = lib().mm2gb_map_opt_init_ava
+    fn.argtypes = [C.POINTER(MapOpt), C.c_char_p]
+    _check(fn(C.byref(o), name.encode()))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise Mm2gbError(f"mm2gb_map_opt_t has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def preset_ava(name):
+    """The index parameters of the read-overlap presets, as keywords for SeedIndex and map_reads: "ava-ont" -k15 -w5, "ava-pb" -Hk19 -w5 (options.c:96-109)."""
+    if name == "ava-ont":
+        return dict(k=15, w=5, hpc=False)
+    if name == "ava-pb":
+        return dict(k=19, w=5, hpc=True)
+    raise Mm2gbError(f"preset_ava: {name!r} is not supported (ava-ont, ava-pb)")
+
+
+class EstErr(C.Structure):
+    _fields_ = [("n_match", C.c_int32), ("n_tot", C.c_int32)]
+
+
+def _est_err_call(fn, head, reads, ref_len, tail):
+    """The arguments of mm2gb_est_err_host / _gpu from reads: a list of dicts with hits (list of dicts: as, cnt, rid, qs, rs, re, rev), anchors ((n,2) uint64), qlen,
+    mini_pos (uint64).  Returns the offsets, the result arrays, the call's arguments before and after the form's own, and the arrays to keep alive."""
+    R = len(reads)
+    reg_off, a_off, m_off = (np.zeros(R + 1, dtype=np.int64) for _ in range(3))
+    for r, rd in enumerate(reads):
+        reg_off[r + 1] = reg_off[r] + len(rd["hits"])
+        a_off[r + 1] = a_off[r] + len(rd["anchors"])
+        m_off[r + 1] = m_off[r] + len(rd["mini_pos"])
+    regs = np.zeros(max(int(reg_off[R]), 1), dtype=REG_DTYPE)
+    j = 0
+    for rd in reads:
+        for h in rd["hits"]:
+            for k in ("cnt", "rid", "qs", "rs", "re"):
+                regs[j][k] = h[k]
+            regs[j]["as_"] = h["as"]
+            regs[j]["flags"] = (1 << 10) if h.get("rev") else 0
+            j += 1
+    anchors = np.ascontiguousarray(np.concatenate([np.asarray(rd["anchors"], dtype=np.uint64).reshape(-1, 2) for rd in reads] + [np.zeros((1, 2), dtype=np.uint64)]))
+    mini = np.ascontiguousarray(np.concatenate([np.asarray(rd["mini_pos"], dtype=np.uint64).reshape(-1) for rd in reads] + [np.zeros(1, dtype=np.uint64)]))
+    qlen = np.ascontiguousarray([rd["qlen"] for rd in reads] + [0], dtype=np.int32)
+    rl = np.ascontiguousarray(ref_len, dtype=np.int32)
+    out = np.zeros((max(int(reg_off[R]), 1), 2), dtype=np.int32)
+    sum_k = np.zeros(R + 1, dtype=np.uint64)
+    fn.argtypes = head + [C.c_int64] + [C.c_void_p] * 7 + [C.c_int32, C.c_void_p] + tail + [C.c_void_p, C.c_void_p]
+    return reg_off, m_off, out, sum_k, (R, reg_off.ctypes.data, regs.ctypes.data, a_off.ctypes.data, anchors.ctypes.data, qlen.ctypes.data, m_off.ctypes.data, mini.ctypes.data,
+                                        len(rl), rl.ctypes.data), (out.ctypes.data, sum_k.ctypes.data), (regs, anchors, mini, qlen, rl, a_off)
+
+
+def _est_err_result(reg_off, m_off, out, sum_k):
+    """Per read a dict with n_match, n_tot (int32 arrays, one entry per hit; n_tot = -1: the walk did not start), sum_k and div (float32: mm2gb_est_err_div on them)."""
+    L = lib()
+    L.mm2gb_est_err_div.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_int32]
+    L.mm2gb_est_err_div.restype = C.c_float
+    res = []
+    for r in range(len(reg_off) - 1):
+        o = out[reg_off[r]:reg_off[r + 1]]
+        n_mini = int(m_off[r + 1] - m_off[r])
+        div = np.asarray([L.mm2gb_est_err_div(int(a), int(b), int(sum_k[r]), n_mini) for a, b in o], dtype=np.float32)
+        res.append(dict(n_match=o[:, 0].copy(), n_tot=o[:, 1].copy(), sum_k=int(sum_k[r]), div=div))
+    return res
+
+
+def est_err_host(reads, ref_len, threads=4):
+    """mm2gb_est_err_host: mm_est_err's walk (esterr.c:30-61) on host threads; reads as _est_err_call takes them, ref_len per reference sequence; result as
+    _est_err_result gives it."""
+    fn = lib().mm2gb_est_err_host
+    reg_off, m_off, out, sum_k, first, last, keep = _est_err_call(fn, [], reads, ref_len, [C.c_int])
+    _check(fn(*first, int(threads), *last))
+    return _est_err_result(reg_off, m_off, out, sum_k)
+
+
+def _engine_est_err(self, reads, ref_len):
+    """mm2gb_est_err_gpu: the same on the device (k_est_err)."""
+    fn = lib().mm2gb_est_err_gpu
+    reg_off, m_off, out, sum_k, first, last, keep = _est_err_call(fn, [C.c_void_p], reads, ref_len, [])
+    _check(fn(self._h, *first, *last))
+    return _est_err_result(reg_off, m_off, out, sum_k)
+
+
+Engine.est_err = _engine_est_err
+
+
 class MapAln(C.Structure):
     """mm2gb_map_aln_t: what mm2gb_map_reads_aln needs beside the mapping options (make one with map_align)."""
     _fields_ = [("ref_seqs", C.POINTER(C.c_char_p)), ("opt", AlignOpt), ("what", C.c_int32), ("align_on_device", C.c_int32), ("text_on_device", C.c_int32)]

@@ -100,6 +100,9 @@ struct Engine {
 	// sequence bytes -> matches on the device (seed_kernels.hip; mm2gb_sketch_gpu, mm2gb_collect_matches_gpu): the sequences, their offsets and
 	// ids, the minimizers with their reads and offsets, one arena for the work arrays of either stage, what the host's mapq / divergence code wants
 	DevBuf sk_seqs, sk_seq_off, sk_rid, sk_mini, sk_mini_read, sk_mini_off, sk_work, sd_src_first, sd_mini_pos, sd_rep_len;
+	// mm_est_err's walk (est_err_kernels.hip; mm2gb_est_err_gpu and the mapper's resident path): the call's arrays as the host gives them (the resident path reads
+	// the engine's own instead: reg_out, post_out[0], sd_qlen, sd_seed_off, sd_mini_pos), the reads' hashes of the resident path's hit records, scratch, results
+	DevBuf ee_reg_off, ee_a_off, ee_a, ee_qlen, ee_mini_off, ee_mini, ee_ref_len, ee_hash, ee_reg_read, ee_literal, ee_out, ee_sum_k;
 	// the extension DP (ksw_kernels.hip; mm2gb_ksw_extd2_gpu): job records, both sequence arrays, result records, the direction bytes of the jobs
 	// of one launch, every job's CIGAR words before and after packing, state images too large for LDS, the launches' job counters, the words' offsets
 	// kw_junc: the splice-aware DP's annotation bytes, laid out like kw_t (mm2gb_ksw_exts2_gpu)
@@ -197,8 +200,17 @@ struct Engine {
 	int  sketch_device(int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini);
 	// mm_collect_matches for a batch, left in sd_seeds / sd_seed_off / sd_hit_off / sd_hits (+ sd_qlen, sd_mini_pos, sd_rep_len)
 	int  collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits);
-	// launch_collect_seeds on what collect_matches_device left (no name tests, no reference lengths: the flags the mapper takes)
-	int  collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, int64_t *anchor_off, mm2gb_anchor_t *anchors);
+	// launch_collect_seeds on what collect_matches_device left; q_rank / ref_rank / ref_len as for collect_seeds (null: no name tests).  anchors null: the anchors
+	// stay in sd_out / sd_a_off and only the offsets come down (the mapper's resident path)
+	int  collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank,
+	                            int64_t *anchor_off, mm2gb_anchor_t *anchors);
+	// the mapper's resident path on what collect_seeds_resident left: chaining DP, backtrack and compaction on device pointers -- the chains stay in
+	// post_out[0]; only their totals come down ...
+	int  resident_chain(int64_t n_reads, int64_t n_anchors, int64_t *n_chains, int64_t *n_kept);
+	// ... then k_gen_regs and k_est_err on them: hit records, their offsets, the walk's counts and sum_k come down
+	int  resident_regs(int64_t n_reads, int64_t n_chains, const uint32_t *hash, int32_t n_ref, const int32_t *ref_len, int64_t *u_off, mm2gb_reg_t *regs, mm2gb_est_err_t *est, uint64_t *sum_k);
+	int  est_err(int64_t n_reads, const int64_t *reg_off, const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, const int32_t *qlen,
+	             const int64_t *mini_off, const uint64_t *mini_pos, int32_t n_ref, const int32_t *ref_len, mm2gb_est_err_t *out, uint64_t *sum_k);
 	int  sort_seeds(int64_t n_reads, const int64_t *offsets, mm2gb_anchor_t *anchors);
 	int  gen_regs(int64_t n_reads, const mm2gb_chains_t *chains, const int32_t *qlen, const uint32_t *hash, int is_qstrand, mm2gb_reg_t *regs);
 	int  record_outputs_done(hipEvent_t ev);   // fires when every D2H enqueued so far has landed

@@ -14,6 +14,7 @@
 #include <vector>
 #include <string>
 #include "engine.h"
+#include "est_err.h"
 #include "host_chain.h"
 
 namespace mm2gb {
@@ -516,6 +517,7 @@ void Engine::shutdown()
 	for (DevBuf *b : { &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
 	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
+	                   &ee_reg_off, &ee_a_off, &ee_a, &ee_qlen, &ee_mini_off, &ee_mini, &ee_ref_len, &ee_hash, &ee_reg_read, &ee_literal, &ee_out, &ee_sum_k,
 	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack, &kw_junc,
 	                   &al_refs, &al_reads, &al_jobs, &al_slices, &al_list, &al_drop,
 	                   &tx_recs, &tx_words, &tx_slices, &tx_cnt, &tx_run, &tx_bytes, &tx_dest, &tx_tmp, &tx_text,
@@ -1201,16 +1203,28 @@ int Engine::collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_
 	return 0;
 }
 
-int Engine::collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, int64_t *anchor_off, mm2gb_anchor_t *anchors)
+int Engine::collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank,
+                                   int64_t *anchor_off, mm2gb_anchor_t *anchors)
 {
+	constexpr int64_t F_NO_DIAG = 0x001, F_NO_DUAL = 0x002;
 	anchor_off[0] = 0;
 	if (n_hits == 0) { for (int64_t r = 0; r < n_reads; ++r) anchor_off[r + 1] = 0; return 0; }
 	if (n_hits >= ((int64_t)1 << 31)) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 hits");
-	const size_t nr = (size_t)n_reads, ns = (size_t)std::max<int64_t>(n_seeds, 1), nh = (size_t)n_hits;
+	const bool names = (opt_flag & (F_NO_DIAG | F_NO_DUAL)) != 0 && q_rank != nullptr;
+	if (names && (!ref_rank || !ref_len || n_ref <= 0)) return fail("mm2gb_map_reads: NO_DIAG / NO_DUAL need the references' ranks and lengths");
+	const size_t nr = (size_t)n_reads, ns = (size_t)std::max<int64_t>(n_seeds, 1), nh = (size_t)n_hits, nf = (size_t)std::max<int32_t>(n_ref, 1);
 	if (sd_seed_read.ensure(ns * 4) || sd_tmp.ensure(nh * 16) || sd_n_kept.ensure(nr * 4) || sd_a_off.ensure((nr + 1) * 8) || sd_out.ensure(nh * 16)) return -1;
+	if (names) {
+		// (the hits are the index's own: every one names a sequence below n_ref)
+		if (sd_q_rank.ensure(nr * 4) || sd_ref_len.ensure(nf * 4) || sd_ref_rank.ensure(nf * 4)) return -1;
+		MM2GB_HIP(hipMemcpyAsync(sd_q_rank.ptr, q_rank, nr * 4, hipMemcpyHostToDevice, stream));
+		MM2GB_HIP(hipMemcpyAsync(sd_ref_len.ptr, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, stream));
+		MM2GB_HIP(hipMemcpyAsync(sd_ref_rank.ptr, ref_rank, (size_t)n_ref * 4, hipMemcpyHostToDevice, stream));
+	}
 	SeedBatch sb;
 	sb.seeds = (const SeedRecord*)sd_seeds.ptr; sb.seed_off = (const int64_t*)sd_seed_off.ptr; sb.hit_off = (const int64_t*)sd_hit_off.ptr;
-	sb.hits = (const unsigned long long*)sd_hits.ptr; sb.qlen = (const int32_t*)sd_qlen.ptr; sb.q_rank = nullptr; sb.ref_len = nullptr; sb.ref_rank = nullptr;
+	sb.hits = (const unsigned long long*)sd_hits.ptr; sb.qlen = (const int32_t*)sd_qlen.ptr; sb.q_rank = names ? (const int32_t*)sd_q_rank.ptr : nullptr;
+	sb.ref_len = names ? (const int32_t*)sd_ref_len.ptr : nullptr; sb.ref_rank = names ? (const int32_t*)sd_ref_rank.ptr : nullptr;
 	sb.n_reads = n_reads; sb.n_seeds = n_seeds; sb.n_hits = n_hits; sb.flag = (long long)opt_flag;
 	sb.seed_read = (int32_t*)sd_seed_read.ptr; sb.tmp = (ulonglong2*)sd_tmp.ptr; sb.n_kept = (int32_t*)sd_n_kept.ptr;
 	sb.anchor_off = (int64_t*)sd_a_off.ptr; sb.out = (ulonglong2*)sd_out.ptr; sb.grid_waves = n_cu * 32;
@@ -1218,7 +1232,97 @@ int Engine::collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_
 	MM2GB_HIP(hipGetLastError());
 	MM2GB_HIP(hipMemcpyAsync(anchor_off, sd_a_off.ptr, (nr + 1) * 8, hipMemcpyDeviceToHost, stream));
 	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (!anchors) return 0;
 	if (anchor_off[n_reads] > 0) { MM2GB_HIP(hipMemcpyAsync(anchors, sd_out.ptr, (size_t)anchor_off[n_reads] * 16, hipMemcpyDeviceToHost, s_out)); MM2GB_HIP(hipStreamSynchronize(s_out)); }
+	return 0;
+}
+
+// The resident path's chaining: chain_gpu without its copies -- the anchors and offsets are where collect_seeds_resident left them, the chains stay in post_out[0].
+int Engine::resident_chain(int64_t n_reads, int64_t n, int64_t *n_chains, int64_t *n_kept)
+{
+	*n_chains = *n_kept = 0;
+	if (n_reads <= 0 || n <= 0) return 0;
+	MM2GB_HIP(hipSetDevice(device));
+	if (begin_call()) return -1;
+	IoSet &s = io[io_seq++ & 1];
+	for (hipStream_t q : { s_in, work[0].stream, work[1].stream, s_out }) MM2GB_HIP(hipStreamSynchronize(q));
+	if (s.f.ensure((size_t)n * 4) || s.p.ensure((size_t)n * 4)) return -1;
+	const int64_t *d_off = (const int64_t*)sd_a_off.ptr;
+	const mm2gb_anchor_t *d_a = (const mm2gb_anchor_t*)sd_out.ptr;
+	if (enqueue(n_reads, d_off, d_a, n, (int32_t*)s.f.ptr, (int32_t*)s.p.ptr)) return -1;
+	if (enqueue_post(n_reads, d_off, d_a, n, (const int32_t*)s.f.ptr, (const int32_t*)s.p.ptr)) return -1;
+	s.used = false;
+	if (sync()) return -1;
+	*n_chains = h_post_totals[0]; *n_kept = h_post_totals[1];
+	return 0;
+}
+
+// The resident path's hit records and divergence walk, on the chains resident_chain left (n_chains of them: its total).
+int Engine::resident_regs(int64_t n_reads, int64_t n_u, const uint32_t *hash, int32_t n_ref, const int32_t *ref_len, int64_t *u_off, mm2gb_reg_t *regs, mm2gb_est_err_t *est, uint64_t *sum_k)
+{
+	static_assert(sizeof(RegRecord) == sizeof(mm2gb_reg_t) && sizeof(mm2gb_est_err_t) == sizeof(int2), "record layouts");
+	if (n_reads <= 0) return 0;
+	MM2GB_HIP(hipSetDevice(device));
+	const size_t nr = (size_t)n_reads, nu = (size_t)std::max<int64_t>(n_u, 1);
+	if (reg_out.ensure(nu * sizeof(RegRecord)) || ee_hash.ensure(nr * 4) || ee_ref_len.ensure((size_t)std::max(n_ref, 1) * 4) || ee_reg_read.ensure(nu * 4) || ee_literal.ensure(nr * 4) ||
+	    ee_out.ensure(nu * 8) || ee_sum_k.ensure(nr * 8)) return -1;
+	MM2GB_HIP(hipMemcpyAsync(ee_hash.ptr, hash, nr * 4, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(ee_ref_len.ptr, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, stream));
+	if (n_u > 0) {
+		RegBatch rb;
+		rb.u_off = (const int64_t*)post_uoff.ptr; rb.a_off = (const int64_t*)post_aoff.ptr; rb.u = (const unsigned long long*)post_uout.ptr; rb.a = (const uint4*)post_aout.ptr;
+		rb.qlen = (const int32_t*)sd_qlen.ptr; rb.hash = (const uint32_t*)ee_hash.ptr; rb.n_reads = n_reads;
+		rb.z = (ulonglong2*)post_heads.ptr; rb.regs = (RegRecord*)reg_out.ptr; rb.cursor = nullptr; rb.is_qstrand = 0; rb.grid_waves = n_cu * 32;
+		launch_gen_regs(rb, stream);
+		MM2GB_HIP(hipGetLastError());
+	}
+	EstErrBatch eb;
+	eb.reg_off = (const int64_t*)post_uoff.ptr; eb.regs = (const RegRecord*)reg_out.ptr; eb.a_off = (const int64_t*)post_aoff.ptr; eb.a = (const uint4*)post_aout.ptr;
+	eb.qlen = (const int32_t*)sd_qlen.ptr; eb.mini_off = (const int64_t*)sd_seed_off.ptr; eb.mini_pos = (const unsigned long long*)sd_mini_pos.ptr; eb.ref_len = (const int32_t*)ee_ref_len.ptr;
+	eb.n_reads = n_reads; eb.n_regs = n_u; eb.reg_read = (int32_t*)ee_reg_read.ptr; eb.read_literal = (int32_t*)ee_literal.ptr; eb.out = (int2*)ee_out.ptr;
+	eb.sum_k = (unsigned long long*)ee_sum_k.ptr; eb.grid_waves = n_cu * 32;
+	launch_est_err(eb, stream);
+	MM2GB_HIP(hipGetLastError());
+	MM2GB_HIP(hipMemcpyAsync(u_off, post_uoff.ptr, (nr + 1) * 8, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipMemcpyAsync(sum_k, ee_sum_k.ptr, nr * 8, hipMemcpyDeviceToHost, stream));
+	if (n_u > 0) {
+		MM2GB_HIP(hipMemcpyAsync(regs, reg_out.ptr, (size_t)n_u * sizeof(RegRecord), hipMemcpyDeviceToHost, stream));
+		MM2GB_HIP(hipMemcpyAsync(est, ee_out.ptr, (size_t)n_u * 8, hipMemcpyDeviceToHost, stream));
+	}
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	return 0;
+}
+
+// mm_est_err's walk for a batch the host holds (arguments checked by the caller: est_err_check).
+int Engine::est_err(int64_t n_reads, const int64_t *reg_off, const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, const int32_t *qlen,
+                    const int64_t *mini_off, const uint64_t *mini_pos, int32_t n_ref, const int32_t *ref_len, mm2gb_est_err_t *out, uint64_t *sum_k)
+{
+	if (n_reads <= 0) return 0;
+	const int64_t n_u = reg_off[n_reads], n_a = anchor_off[n_reads], n_m = mini_off[n_reads];
+	MM2GB_HIP(hipSetDevice(device));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	const size_t nr = (size_t)n_reads, nu = (size_t)std::max<int64_t>(n_u, 1);
+	if (ee_reg_off.ensure((nr + 1) * 8) || reg_out.ensure(nu * sizeof(RegRecord)) || ee_a_off.ensure((nr + 1) * 8) || ee_a.ensure((size_t)std::max<int64_t>(n_a, 1) * 16) || ee_qlen.ensure(nr * 4) ||
+	    ee_mini_off.ensure((nr + 1) * 8) || ee_mini.ensure((size_t)std::max<int64_t>(n_m, 1) * 8) || ee_ref_len.ensure((size_t)std::max(n_ref, 1) * 4) || ee_reg_read.ensure(nu * 4) ||
+	    ee_literal.ensure(nr * 4) || ee_out.ensure(nu * 8) || ee_sum_k.ensure(nr * 8)) return -1;
+	MM2GB_HIP(hipMemcpyAsync(ee_reg_off.ptr, reg_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(ee_a_off.ptr, anchor_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(ee_mini_off.ptr, mini_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(ee_qlen.ptr, qlen, nr * 4, hipMemcpyHostToDevice, stream));
+	if (n_u > 0) MM2GB_HIP(hipMemcpyAsync(reg_out.ptr, regs, (size_t)n_u * sizeof(RegRecord), hipMemcpyHostToDevice, stream));
+	if (n_a > 0) MM2GB_HIP(hipMemcpyAsync(ee_a.ptr, anchors, (size_t)n_a * 16, hipMemcpyHostToDevice, stream));
+	if (n_m > 0) MM2GB_HIP(hipMemcpyAsync(ee_mini.ptr, mini_pos, (size_t)n_m * 8, hipMemcpyHostToDevice, stream));
+	if (n_ref > 0 && ref_len) MM2GB_HIP(hipMemcpyAsync(ee_ref_len.ptr, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, stream));
+	EstErrBatch eb;
+	eb.reg_off = (const int64_t*)ee_reg_off.ptr; eb.regs = (const RegRecord*)reg_out.ptr; eb.a_off = (const int64_t*)ee_a_off.ptr; eb.a = (const uint4*)ee_a.ptr;
+	eb.qlen = (const int32_t*)ee_qlen.ptr; eb.mini_off = (const int64_t*)ee_mini_off.ptr; eb.mini_pos = (const unsigned long long*)ee_mini.ptr; eb.ref_len = (const int32_t*)ee_ref_len.ptr;
+	eb.n_reads = n_reads; eb.n_regs = n_u; eb.reg_read = (int32_t*)ee_reg_read.ptr; eb.read_literal = (int32_t*)ee_literal.ptr; eb.out = (int2*)ee_out.ptr;
+	eb.sum_k = (unsigned long long*)ee_sum_k.ptr; eb.grid_waves = n_cu * 32;
+	launch_est_err(eb, stream);
+	MM2GB_HIP(hipGetLastError());
+	MM2GB_HIP(hipMemcpyAsync(sum_k, ee_sum_k.ptr, nr * 8, hipMemcpyDeviceToHost, stream));
+	if (n_u > 0) MM2GB_HIP(hipMemcpyAsync(out, ee_out.ptr, (size_t)n_u * 8, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipStreamSynchronize(stream));
 	return 0;
 }
 
@@ -1702,6 +1806,14 @@ int mm2gb_gen_regs_gpu(mm2gb_engine_t *eng, int64_t n_reads, const mm2gb_chains_
                        int is_qstrand, mm2gb_reg_t *regs)
 {
 	return eng ? eng->e.gen_regs(n_reads, chains, qlen, hash, is_qstrand, regs) : fail("mm2gb: null engine");
+}
+
+int mm2gb_est_err_gpu(mm2gb_engine_t *eng, int64_t n_reads, const int64_t *reg_off, const mm2gb_reg_t *regs, const int64_t *anchor_off, const mm2gb_anchor_t *anchors, const int32_t *qlen,
+                      const int64_t *mini_off, const uint64_t *mini_pos, int32_t n_ref, const int32_t *ref_len, mm2gb_est_err_t *out, uint64_t *sum_k)
+{
+	if (!eng) return fail("mm2gb: null engine");
+	if (est_err_check("mm2gb_est_err_gpu", n_reads, reg_off, regs, anchor_off, anchors, qlen, mini_off, mini_pos, n_ref, ref_len, out, sum_k)) return -1;
+	return eng->e.est_err(n_reads, reg_off, regs, anchor_off, anchors, qlen, mini_off, mini_pos, n_ref, ref_len, out, sum_k);
 }
 
 int mm2gb_post_device(mm2gb_engine_t *eng, int64_t n_reads, const int64_t *d_offsets, const mm2gb_anchor_t *d_anchors, int64_t n_anchors,

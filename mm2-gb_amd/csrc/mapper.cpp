@@ -17,9 +17,17 @@
 //   With MM_F_RMQ in the options' flag (the asm5 / asm10 / asm20 presets, mm2gb_map_opt_init_preset; minimap2 --rmq=yes): stage 3 is not the chaining
 //   DP -- every read's sorted anchors go through mg_lchain_rmq's fill with bw (map.c:690-692), the same call as stage 4's with bw_long (device and host
 //   threads as rechain_on_device says, ties redone by the host form).  Stage 4 follows as always.  The spliced calls refuse the flag (options.c:173).
-// Not reproduced: more than one query segment, spliced mapping without base-level alignment, short-read alignment (sr), the all-against-all presets
-// (ava-ont, ava-pb: MM_F_ALL_CHAINS, NO_DIAG, NO_DUAL, NO_LJOIN), junction annotation, --eqx, SAM output, ALT contigs, the heap variant of seed
-// collection, --qstrand, multi-part indexes.
+//
+//   Read against read (mm2gb_map_opt_init_ava, or the four bits of minimap2 -X on any option set; the calls without base-level alignment only): with
+//   MM_F_NO_DIAG / MM_F_NO_DUAL step 2's name tests run (map.c:208-219) on the names' ranks in strcmp order over reads and references together (name_ranks, once
+//   per call); MM_F_NO_LJOIN leaves stage 4 out (map.c:698); MM_F_ALL_CHAINS leaves mm_set_parent / mm_select_sub out of stage 6 (map.c:335), so every
+//   record keeps parent = MM_PARENT_UNSET: mapping quality 0 (hit.c:436, 463), tp:A:S and no s2 (format.c:301-304).
+//
+//   The resident path (seeding_on_device = 2, no re-chaining stage, no MM_F_RMQ, no alignment; chain_resident, hit_records_resident): steps 2, 3 and 5 run on
+//   device pointers and mm_est_err's walk runs there too (est_err_kernels.hip), so no anchor crosses the link in either direction: what comes down is the
+//   offsets, the hit records, the walk's counts, sum_k and rep_len.
+// Not reproduced: more than one query segment, spliced mapping without base-level alignment, short-read alignment (sr), read overlap with base-level
+// alignment, junction annotation, --eqx, SAM output, ALT contigs, the heap variant of seed collection, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -36,6 +44,7 @@
 #include "host_chain.h"
 #include "align_host.h"
 #include "aln_text_host.h"
+#include "est_err.h"
 #include "trace.h"
 
 namespace mm2gb {
@@ -52,6 +61,7 @@ struct Hit {                                   // mm_reg1_t without the alignmen
 	int split = 0, dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0, trans_strand = 0, n_cigar = 0;
 	uint32_t flags = 0;                        // mm_reg1_t's bit-field word as the record carries it between the calls
 	int64_t aln = -1;                          // its place in the alignment call's result
+	int src = -1;                              // the resident path: its place among the read's hit records as the device made them (where its walk's counts are)
 };
 
 enum { PARENT_UNSET = -1, PARENT_TMP_PRI = -2 };   // mmpriv.h:13-14
@@ -157,38 +167,25 @@ void select_sub(float pri_ratio, int min_diff, int best_n, bool check_strand, in
 	if (k != n) { r.resize(k); sync_hits(r); }
 }
 
-// esterr.c:9-64
-int forward_qpos(int qlen, const mm2gb_anchor_t &a)
-{
-	const int x = (int32_t)a.y, span = (int)(a.y >> 32 & 0xff);
-	return a.x >> 63 ? qlen - 1 - (x + 1 - span) : x;
-}
+void reg_from(const struct Hit &h, mm2gb_reg_t &g);
 
+// esterr.c:30-64: the walk is est_err.cpp's (the definition of the device form); the pow of esterr.c:62 is finished here
 void estimate_divergence(int qlen, const std::vector<int32_t> &ref_len, std::vector<Hit> &r, const mm2gb_anchor_t *a, int n_mini, const uint64_t *mini_pos)
 {
-	if (n_mini == 0) return;
+	if (n_mini == 0 || r.empty()) return;
+	std::vector<mm2gb_reg_t> g(r.size());
+	std::vector<mm2gb_est_err_t> e(r.size());
 	uint64_t sum_k = 0;
-	for (int i = 0; i < n_mini; ++i) sum_k += mini_pos[i] >> 32 & 0xff;
-	const float avg_k = (float)sum_k / n_mini;
-	for (Hit &h : r) {
-		h.div = -1.0f;
-		if (h.cnt == 0) continue;
-		auto anchor = [&](int k) -> const mm2gb_anchor_t & { return h.rev ? a[h.as + h.cnt - 1 - k] : a[h.as + k]; };   // in query order
-		const int x0 = forward_qpos(qlen, anchor(0));
-		int lo = 0, hi = n_mini - 1, st = -1;
-		while (lo <= hi) {
-			const int mid = (int)(((uint64_t)lo + (uint64_t)hi) >> 1), y = (int32_t)mini_pos[mid];
-			if (y < x0) lo = mid + 1; else if (y > x0) hi = mid - 1; else { st = mid; break; }
-		}
-		if (st < 0) continue;
-		int en = st, n_match = 1;
-		for (int k = 1, j = st + 1; j < n_mini && k < h.cnt; ++j)
-			if (forward_qpos(qlen, anchor(k)) == (int32_t)mini_pos[j]) { ++k; en = j; ++n_match; }
-		int n_tot = en - st + 1;
-		if (h.qs > avg_k && h.rs > avg_k) ++n_tot;
-		if (qlen - h.qs > avg_k && ref_len[(size_t)h.rid] - h.re > avg_k) ++n_tot;
-		h.div = n_match >= n_tot ? 0.0f : (float)(1.0 - pow((double)n_match / n_tot, 1.0 / avg_k));
-	}
+	for (size_t i = 0; i < r.size(); ++i) reg_from(r[i], g[i]);
+	est_err_read(qlen, (int64_t)r.size(), g.data(), a, n_mini, mini_pos, ref_len.data(), e.data(), &sum_k);
+	for (size_t i = 0; i < r.size(); ++i) r[i].div = mm2gb_est_err_div(e[i].n_match, e[i].n_tot, sum_k, n_mini);
+}
+
+// the same from the counts the device's walk left (the resident path): e, the counts of the read's records as the device made them
+void divergence_from_counts(std::vector<Hit> &r, const mm2gb_est_err_t *e, uint64_t sum_k, int n_mini)
+{
+	if (n_mini == 0) return;
+	for (Hit &h : r) h.div = mm2gb_est_err_div(e[h.src].n_match, e[h.src].n_tot, sum_k, n_mini);
 }
 
 // hit.c:297-309
@@ -304,12 +301,29 @@ void reg_from(const Hit &h, mm2gb_reg_t &g)
 	g.flags = h.flags | (h.strand_retained ? 1u << 26 : 0u);
 }
 
+// MM_F_NO_DIAG / MM_F_NO_DUAL (map.c:211): the names of reads and references in one strcmp order (bytes as unsigned char), equal names equal ranks.  A read without
+// a name has rank -1, below and unequal to every reference's: no test drops a hit of its (map.c:208 tests qname first)
+void name_ranks(int32_t n_reads, const char *const *names, int32_t n_ref, const char *const *ref_names, std::vector<int32_t> &q_rank, std::vector<int32_t> &ref_rank)
+{
+	std::vector<std::pair<const char*, int32_t>> all;     // (name, index: reads first)
+	for (int32_t r = 0; r < n_reads; ++r) if (names[r]) all.emplace_back(names[r], r);
+	for (int32_t i = 0; i < n_ref; ++i) all.emplace_back(ref_names[i] ? ref_names[i] : "", n_reads + i);
+	std::sort(all.begin(), all.end(), [](const std::pair<const char*, int32_t> &u, const std::pair<const char*, int32_t> &v) { return strcmp(u.first, v.first) < 0; });
+	q_rank.assign((size_t)n_reads, -1); ref_rank.assign((size_t)n_ref, 0);
+	int32_t rank = 0;
+	for (size_t i = 0; i < all.size(); ++i) {
+		if (i > 0 && strcmp(all[i - 1].first, all[i].first) != 0) ++rank;
+		(all[i].second < n_reads ? q_rank[(size_t)all[i].second] : ref_rank[(size_t)(all[i].second - n_reads)]) = rank;
+	}
+}
+
 // the arguments of a mapping call (eng: the one engine of mm2gb_map_reads, unused by the stream)
 struct MapCall {
 	mm2gb_engine_t *eng; const mm2gb_index_t *ix; int k; const char *const *ref_names; const int32_t *ref_lens; int32_t n_ref;
 	const mm2gb_map_opt_t *opt; int32_t n_reads; const char *const *names; const char *const *seqs; const int32_t *lens;
 	char **paf_out; int64_t *paf_len; mm2gb_map_stats_t *stats; const mm2gb_map_aln_t *aln; double *s_extra;
 	const mm2gb_align_splice_opt_t *spl = nullptr;       // the spliced calls: their alignment options (aln then holds the rest of the mm2gb_map_splice_t)
+	const int32_t *q_rank = nullptr, *ref_rank = nullptr; // MM_F_NO_DIAG / MM_F_NO_DUAL: the names' ranks where the caller has them already (the stream: once for all chunks)
 };
 
 // what the stages of one batch share
@@ -335,6 +349,12 @@ struct Batch {
 	const uint64_t *u = nullptr;
 	const mm2gb_anchor_t *ca = nullptr;
 	std::vector<mm2gb_reg_t> regs;
+	std::vector<int32_t> own_q_rank, own_ref_rank;       // MM_F_NO_DIAG / MM_F_NO_DUAL: the names' ranks, where the call did not bring them
+	const int32_t *q_rank = nullptr, *ref_rank = nullptr;
+	bool resident = false;                               // the resident path runs: no anchor, chain or kept anchor on the host (u, ca, a_off's anchors stay unset)
+	std::vector<mm2gb_est_err_t> est;                    // ... the walk's counts per hit record and sum_k per read instead
+	std::vector<uint64_t> sum_k;
+	int64_t link[2] = { 0, 0 };                          // seeded on the device: bytes the stages copied to the device / back (the MM2GB_DEBUG_PHASES line; profiles/ava_rate.py)
 	std::vector<std::string> lines;
 	mm2gb_map_stats_t st = {};
 	double *const s_extra;
@@ -363,6 +383,14 @@ int seed_on_host(Batch &B)
 
 // 1. on the device (seeding_on_device = 1): the reads go up as bytes, sketch / look-up / match selection run as kernels (seed_kernels.hip) and leave
 //    the arrays step 2's kernels read where they are; what comes down is what the host's mapq and divergence code wants (rep_len, mini_pos)
+// what one chaining micro-batch of the engine holds (Engine::chain_gpu slices a larger batch, and a sliced batch's chains do not lie end to end on the device)
+int64_t resident_max_anchors()
+{
+	int64_t slice = 64 * 1000 * 1000;
+	if (const char *v = getenv("MM2GB_CHAIN_SLICE_ANCHORS")) slice = std::max<int64_t>(1, atoll(v));
+	return slice + slice / 2;
+}
+
 int seed_on_device(Batch &B)
 {
 	const size_t R = B.R;
@@ -380,14 +408,19 @@ int seed_on_device(Batch &B)
 	if (e.collect_matches_device(view, B.so, B.c.n_reads, seq_off.data(), bases, &B.dev_seeds, &B.dev_hits)) return -1;
 	std::vector<int64_t> seed_off(R + 1, 0);
 	std::vector<int32_t> rep(R, 0);
-	std::vector<uint64_t> mini_pos((size_t)B.dev_seeds + 1);
+	// (the resident path walks the minimizer positions where they are: only their number per read comes down)
+	B.resident = B.resident && B.dev_hits > 0 && B.dev_hits <= resident_max_anchors();
+	std::vector<uint64_t> mini_pos(B.resident ? 1 : (size_t)B.dev_seeds + 1);
 	if (hipMemcpy(seed_off.data(), e.sd_seed_off.ptr, (R + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rep.data(), e.sd_rep_len.ptr, R * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-	    (B.dev_seeds > 0 && hipMemcpy(mini_pos.data(), e.sd_mini_pos.ptr, (size_t)B.dev_seeds * 8, hipMemcpyDeviceToHost) != hipSuccess))
+	    (!B.resident && B.dev_seeds > 0 && hipMemcpy(mini_pos.data(), e.sd_mini_pos.ptr, (size_t)B.dev_seeds * 8, hipMemcpyDeviceToHost) != hipSuccess))
 		return fail("mm2gb_map_reads: the device's matches could not be copied back");
+	B.link[0] += seq_off[R] + (int64_t)(R + 1) * 8;
+	B.link[1] += (int64_t)((R + 1) * 8 + R * 4) + (B.resident ? 0 : B.dev_seeds * 8);
 	for (size_t r = 0; r < R; ++r) {
 		const int64_t n = seed_off[r + 1] - seed_off[r];
 		mm2gb_matches_t &m = B.mt[r];
 		m.rep_len = rep[r]; m.n_seeds = m.n_mini_pos = (int32_t)n;
+		if (B.resident) continue;
 		m.mini_pos = (uint64_t*)malloc(((size_t)n + 1) * 8);
 		if (!m.mini_pos) return fail("mm2gb_map_reads: out of memory");
 		if (n > 0) memcpy(m.mini_pos, mini_pos.data() + seed_off[r], (size_t)n * 8);
@@ -405,8 +438,9 @@ int collect_anchors(Batch &B, bool dev_seed)
 	const size_t R = B.R;
 	mm2gb_engine_t *eng = B.c.eng;
 	if (dev_seed) {
-		B.anchors.resize((size_t)std::max<int64_t>(B.dev_hits, 1));
-		return B.c.eng->e.collect_seeds_resident(seed_flag(B), B.c.n_reads, B.dev_seeds, B.dev_hits, B.a_off.data(), B.anchors.data()) ? -1 : 0;
+		if (!B.resident) B.anchors.resize((size_t)std::max<int64_t>(B.dev_hits, 1));
+		return B.c.eng->e.collect_seeds_resident(seed_flag(B), B.c.n_reads, B.dev_seeds, B.dev_hits, B.q_rank, B.c.n_ref, B.ref_len.data(), B.ref_rank, B.a_off.data(),
+		                                         B.resident ? nullptr : B.anchors.data()) ? -1 : 0;
 	}
 	const std::vector<mm2gb_matches_t> &mt = B.mt;
 	std::vector<int64_t> seed_off(R + 1, 0);
@@ -429,9 +463,9 @@ int collect_anchors(Batch &B, bool dev_seed)
 	});
 	B.anchors.resize((size_t)std::max<int64_t>(n_hits, 1));
 	const bool seeds_on_device = B.opt.seeds_on_device > 0 || (B.opt.seeds_on_device == 0 && n_hits >= 400000000);
-	return seeds_on_device ? mm2gb_collect_seeds_gpu(eng, seed_flag(B), B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
+	return seeds_on_device ? mm2gb_collect_seeds_gpu(eng, seed_flag(B), B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), B.q_rank, B.c.n_ref, B.q_rank ? B.ref_len.data() : nullptr, B.ref_rank,
 	                                                 B.a_off.data(), B.anchors.data())
-	                       : mm2gb_collect_seeds_host(seed_flag(B), B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), nullptr, B.c.n_ref, nullptr, nullptr,
+	                       : mm2gb_collect_seeds_host(seed_flag(B), B.c.n_reads, seed_off.data(), seeds.data(), hit_off.data(), hits.data(), B.qlen.data(), B.q_rank, B.c.n_ref, B.q_rank ? B.ref_len.data() : nullptr, B.ref_rank,
 	                                                  B.nt, B.a_off.data(), B.anchors.data());
 }
 
@@ -472,7 +506,7 @@ void rechain_pick(Batch &B, std::vector<int32_t> &redo, std::vector<int64_t> &ro
 {
 	const std::vector<int64_t> &u_off = B.u_off, &c_off = B.c_off;
 	const int32_t *lens = B.c.lens;
-	if (B.opt.bw_long > B.opt.bw) {
+	if (B.opt.bw_long > B.opt.bw && !(B.opt.flag & MM2GB_F_NO_LJOIN)) {                      // map.c:698
 		for (size_t r = 0; r < B.R; ++r) {
 			if (u_off[r + 1] - u_off[r] <= 1) continue;
 			const mm2gb_anchor_t *a = B.ca + c_off[r];
@@ -646,6 +680,46 @@ int hit_records(Batch &B)
 	return mm2gb_gen_regs_gpu(B.c.eng, B.c.n_reads, &view, B.qlen.data(), hash.data(), 0, B.regs.data());
 }
 
+// 3 and 5 of the resident path (seeding_on_device = 2): the anchors are where step 2 left them on the device, the engine chains them there with the mode chain() sets,
+// and hit records and the walk's counts are all that comes down
+int chain_resident(Batch &B)
+{
+	mm2gb_engine_t *eng = B.c.eng;
+	const mm2gb_map_opt_t &opt = B.opt;
+	mm2gb_misc_t &misc = B.misc;
+	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = opt.max_gap; misc.max_dist_x = opt.max_gap_ref > 0 ? opt.max_gap_ref : opt.max_gap;
+	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
+	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * B.c.k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * B.c.k);
+	if (mm2gb_engine_set_misc(eng, &misc)) return -1;
+	const bool before = eng->e.chain_skip;
+	eng->e.chain_skip = opt.max_chain_skip != INT32_MAX;
+	int64_t n_kept = 0;
+	const int rc = eng->e.resident_chain(B.c.n_reads, B.a_off[B.R], &B.st.n_chains, &n_kept);
+	eng->e.chain_skip = before;
+	B.link[1] += (int64_t)(B.R + 1) * 8 + 16;            // step 2's offsets, the chains' totals
+	if (B.q_rank) B.link[0] += (int64_t)B.R * 4 + (int64_t)B.c.n_ref * 8;
+	return rc;
+}
+
+int hit_records_resident(Batch &B)
+{
+	const size_t R = B.R, n_u = (size_t)B.st.n_chains;
+	std::vector<uint32_t> hash(R);
+	for (size_t r = 0; r < R; ++r) {
+		uint32_t h = B.c.names[r] ? name_hash(B.c.names[r]) : 0;
+		h ^= wang((uint32_t)B.c.lens[r]) + wang((uint32_t)B.opt.seed);
+		hash[r] = wang(h);
+	}
+	B.u_off.assign(R + 1, 0);
+	B.regs.resize(std::max<size_t>(n_u, 1)); B.est.resize(std::max<size_t>(n_u, 1)); B.sum_k.assign(R, 0);
+	if (n_u == 0) return 0;                               // (no chain in the batch: no line either)
+	if (B.c.eng->e.resident_regs(B.c.n_reads, B.st.n_chains, hash.data(), B.c.n_ref, B.ref_len.data(), B.u_off.data(), B.regs.data(), B.est.data(), B.sum_k.data())) return -1;
+	if (B.u_off[R] != B.st.n_chains) return fail("mm2gb_map_reads: the resident chains' offsets do not add up to their total");
+	B.link[0] += (int64_t)R * 4 + (int64_t)B.c.n_ref * 4;
+	B.link[1] += (int64_t)(R + 1) * 8 + (int64_t)R * 8 + (int64_t)n_u * (int64_t)(sizeof(mm2gb_reg_t) + sizeof(mm2gb_est_err_t));
+	return 0;
+}
+
 // ---- 6. per read on the host ----
 
 // the hits of a read up to mm_filter_strand_retained (map.c:749-752)
@@ -653,11 +727,14 @@ void chain_hits(const Batch &B, size_t r, std::vector<Hit> &hs)
 {
 	const mm2gb_map_opt_t &opt = B.opt;
 	hs.clear();
-	for (int64_t j = B.u_off[r]; j < B.u_off[r + 1]; ++j) hs.push_back(hit_from(B.regs[(size_t)j]));
+	for (int64_t j = B.u_off[r]; j < B.u_off[r + 1]; ++j) { hs.push_back(hit_from(B.regs[(size_t)j])); hs.back().src = (int)(j - B.u_off[r]); }
 	if (hs.empty()) return;
-	set_parent(opt.mask_level, opt.mask_len, hs, false);                                              // map.c:336
-	select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);              // map.c:337
-	estimate_divergence(B.c.lens[r], B.ref_len, hs, B.ca + B.c_off[r], B.mt[r].n_mini_pos, B.mt[r].mini_pos);   // map.c:751
+	if (!(opt.flag & MM2GB_F_ALL_CHAINS)) {                                                           // map.c:335
+		set_parent(opt.mask_level, opt.mask_len, hs, false);                                          // map.c:336
+		select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);          // map.c:337
+	}
+	if (B.resident) divergence_from_counts(hs, B.est.data() + B.u_off[r], B.sum_k[r], B.mt[r].n_mini_pos);
+	else estimate_divergence(B.c.lens[r], B.ref_len, hs, B.ca + B.c_off[r], B.mt[r].n_mini_pos, B.mt[r].mini_pos);   // map.c:751
 	filter_strand_retained(hs);                                                                       // map.c:752
 }
 
@@ -803,10 +880,20 @@ int emit_paf(Batch &B)
 
 int map_reads_body(const MapCall &c)
 {
-	if (!c.eng || !c.ix || !c.opt || !c.paf_out || !c.paf_len || c.n_reads < 0 || c.n_ref <= 0 || !c.ref_names || !c.ref_lens || (c.n_reads > 0 && (!c.names || !c.seqs || !c.lens)))
-		return fail("mm2gb_map_reads: null argument");
+	if (!c.opt) return fail("mm2gb_map_reads: null argument");
 	mm2gb_map_opt_t opt = *c.opt;
-	if (opt.flag & ~(int64_t)(0x100000 | 0x200000 | MM2GB_F_RMQ)) return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported");
+	// (what the options rule out is said before anything else is looked at)
+	constexpr int64_t overlap_bits = MM2GB_F_NO_DIAG | MM2GB_F_NO_DUAL | MM2GB_F_ALL_CHAINS;
+	if (opt.flag & ~(int64_t)(0x100000 | 0x200000 | MM2GB_F_RMQ | MM2GB_F_NO_LJOIN | overlap_bits))
+		return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported, MM_F_RMQ, MM_F_NO_LJOIN and read overlap's MM_F_NO_DIAG, MM_F_NO_DUAL and MM_F_ALL_CHAINS beside them");
+	if ((opt.flag & MM2GB_F_RMQ) && (opt.flag & overlap_bits))         // (read overlap goes through the chaining DP: no fixture has it with mg_lchain_rmq as the first chainer)
+		return fail("mm2gb_map_reads: beside MM_F_RMQ only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported, and MM_F_NO_LJOIN: not MM_F_NO_DIAG, MM_F_NO_DUAL or MM_F_ALL_CHAINS");
+	if (c.aln && (opt.flag & overlap_bits)) {
+		const char *bit = opt.flag & MM2GB_F_ALL_CHAINS ? "MM_F_ALL_CHAINS" : opt.flag & MM2GB_F_NO_DIAG ? "MM_F_NO_DIAG" : "MM_F_NO_DUAL";
+		return fail(std::string(c.spl ? "mm2gb_map_reads_splice: " : "mm2gb_map_reads_aln: ") + bit + " is not supported with base-level alignment (read overlap runs without it)");
+	}
+	if (!c.eng || !c.ix || !c.paf_out || !c.paf_len || c.n_reads < 0 || c.n_ref <= 0 || !c.ref_names || !c.ref_lens || (c.n_reads > 0 && (!c.names || !c.seqs || !c.lens)))
+		return fail("mm2gb_map_reads: null argument");
 	if (c.spl && (opt.flag & MM2GB_F_RMQ)) return fail("mm2gb_map_reads_splice: MM_F_RMQ does not work with MM_F_SPLICE (options.c:173)");
 	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(c.ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);   // options.c:78-84
 	if (opt.bw_long < opt.bw) opt.bw_long = opt.bw;
@@ -824,6 +911,17 @@ int map_reads_body(const MapCall &c)
 	std::unique_ptr<TraceRange> tr;                       // stage ranges for rocprofv3 --marker-trace / rocprof-sys
 	auto stage = [&](const char *name) { tr.reset(); if (name) tr.reset(new TraceRange(name)); };
 	const bool dev_seed = opt.seeding_on_device > 0;
+	if (opt.flag & (MM2GB_F_NO_DIAG | MM2GB_F_NO_DUAL)) {                                             // (without the bits: no ranks, null pointers as ever)
+		B.q_rank = c.q_rank; B.ref_rank = c.ref_rank;
+		if (!B.q_rank || !B.ref_rank) {
+			name_ranks(c.n_reads, c.names, c.n_ref, c.ref_names, B.own_q_rank, B.own_ref_rank);
+			B.q_rank = B.own_q_rank.data(); B.ref_rank = B.own_ref_rank.data();
+		}
+	}
+	const bool ask_resident = opt.seeding_on_device >= MM2GB_SEEDING_RESIDENT;
+	const bool want_resident = ask_resident && !c.aln && !(opt.flag & MM2GB_F_RMQ) && ((opt.flag & MM2GB_F_NO_LJOIN) || opt.bw_long <= opt.bw);
+	B.resident = want_resident;                           // (seed_on_device takes it back for a batch beyond one chaining micro-batch, or one without a hit)
+	const bool verbose = getenv("MM2GB_DEBUG_PHASES") != nullptr;
 
 	stage("mm2gb:map_seed");
 	if (dev_seed ? seed_on_device(B) : seed_on_host(B)) return -1;                                    // 1
@@ -832,16 +930,37 @@ int map_reads_body(const MapCall &c)
 	if (collect_anchors(B, dev_seed)) return -1;                                                      // 2
 	B.st.n_anchors = B.a_off[B.R];
 	lap(B.st.s_anchors);
-	stage("mm2gb:map_chain");
-	if (chain(B) || ((opt.flag & MM2GB_F_RMQ) && first_chain(B))) return -1;                          // 3
-	lap(B.st.s_chain);
-	stage("mm2gb:map_rechain");
-	if (c.spl) B.st.n_chains = B.u_off[B.R];                                                          // 4 (map.c:698: not under MM_F_SPLICE)
-	else if (rechain(B)) return -1;
-	lap(B.st.s_rechain);
-	stage("mm2gb:map_hit_records");
-	if (hit_records(B)) return -1;                                                                    // 5
-	lap(B.st.s_regs);
+	if (B.resident) {
+		stage("mm2gb:map_chain");
+		if (chain_resident(B)) return -1;                                                             // 3 (no stage 4: that is what lets the chains stay)
+		lap(B.st.s_chain);
+		stage("mm2gb:map_hit_records");
+		if (hit_records_resident(B)) return -1;                                                       // 5, and the divergence walk of 6
+		lap(B.st.s_regs);
+	} else {
+		stage("mm2gb:map_chain");
+		if (chain(B) || ((opt.flag & MM2GB_F_RMQ) && first_chain(B))) return -1;                      // 3
+		lap(B.st.s_chain);
+		stage("mm2gb:map_rechain");
+		if (c.spl) B.st.n_chains = B.u_off[B.R];                                                      // 4 (map.c:698: not under MM_F_SPLICE)
+		else if (rechain(B)) return -1;
+		lap(B.st.s_rechain);
+		stage("mm2gb:map_hit_records");
+		if (hit_records(B)) return -1;                                                                // 5
+		lap(B.st.s_regs);
+		if (verbose && dev_seed && !(opt.flag & MM2GB_F_RMQ)) {       // what the staged stages copied, from their arrays' sizes (re-chaining on the device not counted)
+			const int64_t R8 = (int64_t)(B.R + 1) * 8, n = B.st.n_anchors, n_u = B.u_off[B.R], n_c = B.c_off[B.R];
+			B.link[1] += R8 + n * 16;                                                                 // 2: offsets and anchors down
+			B.link[0] += R8 + n * 16;                                                                 // 3: and up again
+			B.link[1] += n >= 200000000 ? 2 * R8 + n_u * 8 + n_c * 16 : n * 8;                        //    chains down (mm2gb_chain_gpu), or scores and predecessors (mm2gb_chain_host)
+			B.link[0] += 2 * R8 + n_u * 8 + n_c * 16 + (int64_t)B.R * 8;                              // 5: chains up
+			B.link[1] += n_u * (int64_t)sizeof(mm2gb_reg_t);                                          //    hit records down
+		}
+	}
+	if (verbose && dev_seed)
+		fprintf(stderr, "[mm2gb] map path: %s%s; %lld anchors, %lld chains; copied to the device %lld B, back %lld B\n", B.resident ? "resident" : "staged",
+		        ask_resident && !B.resident ? (want_resident ? " (resident asked for: the batch's anchors exceed one chaining micro-batch, or it has none)" : " (resident asked for: the options do not allow it)") : "",
+		        (long long)B.st.n_anchors, (long long)B.st.n_chains, (long long)B.link[0], (long long)B.link[1]);
 	stage("mm2gb:map_hits_to_paf");
 	if (!B.aln) finish_reads(B);                                                                      // 6
 	else {
@@ -929,6 +1048,8 @@ int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bas
 	if (const char *v = getenv("MM2GB_STREAM_THREADS_PCT")) oversub_pct = std::max(25, atoi(v));
 	opt.host_threads = std::max(1, workers == 1 ? all_threads : (all_threads * oversub_pct / 100 + workers - 1) / workers);
 	if (opt.mid_occ <= 0) opt.mid_occ = mm2gb_index_mid_occ(c.ix, opt.mid_occ_frac, opt.min_mid_occ, opt.max_mid_occ);     // once, not per chunk
+	std::vector<int32_t> q_rank, ref_rank;                // the names' ranks too
+	if ((opt.flag & (MM2GB_F_NO_DIAG | MM2GB_F_NO_DUAL)) && n_reads > 0 && c.n_ref > 0) name_ranks(n_reads, c.names, c.n_ref, c.ref_names, q_rank, ref_rank);
 	std::vector<char*> part(n_chunks, nullptr);
 	std::vector<int64_t> part_len(n_chunks, 0);
 	std::vector<mm2gb_map_stats_t> st(n_chunks);
@@ -945,6 +1066,7 @@ int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bas
 			MapCall one = c;
 			one.eng = engines[e]; one.opt = &opt; one.n_reads = cut[k + 1] - cut[k]; one.names += cut[k]; one.seqs += cut[k]; one.lens += cut[k];
 			one.paf_out = &part[k]; one.paf_len = &part_len[k]; one.stats = &st[k]; one.s_extra = &extra[k * 3];
+			if (!q_rank.empty()) { one.q_rank = q_rank.data() + cut[k]; one.ref_rank = ref_rank.data(); }
 			if (map_reads_try(one)) {
 				std::lock_guard<std::mutex> g(why_lock);
 				if (!failed.exchange(1)) why = "chunk " + std::to_string(k) + " on engine " + std::to_string(e) + ": " + mm2gb_last_error();
@@ -995,6 +1117,19 @@ int mm2gb_map_opt_init_preset(mm2gb_map_opt_t *o, const char *preset)       // o
 	mm2gb_map_opt_init(o);
 	o->bw = p->bw; o->bw_long = p->bw_long; o->max_gap = p->max_gap; o->flag |= p->map_flag;
 	o->min_mid_occ = p->min_mid_occ; o->max_mid_occ = p->max_mid_occ; o->best_n = p->best_n;
+	return 0;
+}
+
+int mm2gb_map_opt_init_ava(mm2gb_map_opt_t *o, const char *preset)          // options.c:96-109
+{
+	if (!o || !preset) return fail("mm2gb_map_opt_init_ava: null argument");
+	const bool ont = !strcmp(preset, "ava-ont"), pb = !strcmp(preset, "ava-pb");
+	if (!ont && !pb) return fail(std::string("mm2gb_map_opt_init_ava: preset ") + preset + " is not supported (ava-ont, ava-pb)");
+	mm2gb_map_opt_init(o);
+	o->flag |= MM2GB_F_ALL_CHAINS | MM2GB_F_NO_DIAG | MM2GB_F_NO_DUAL | MM2GB_F_NO_LJOIN;
+	o->min_chain_score = 100; o->pri_ratio = 0.0f; o->occ_dist = 0;
+	if (ont) o->bw = o->bw_long = 2000;
+	else o->bw_long = o->bw;
 	return 0;
 }
 

@@ -157,4 +157,25 @@ struct RegBatch {
 };
 void launch_gen_regs(const RegBatch &b, hipStream_t s);
 
+// mm_est_err's walk (esterr.c:30-61) for every hit record of a batch (est_err_kernels.hip; est_err.cpp is the definition): how many of a
+// chain's anchors the walk over the read's minimizer positions meets and how many minimizers it passes, the two end increments included.
+// The pow of esterr.c:62 is the caller's, on the host.
+struct EstErrBatch {
+	const int64_t *reg_off;            // n_reads + 1: read r owns regs[reg_off[r] .. reg_off[r+1])
+	const RegRecord *regs;             // looked at: as (within the read's anchors), cnt, rid, qs, rs, re, the rev bit
+	const int64_t *a_off;              // n_reads + 1
+	const uint4   *a;                  // the kept anchors, read by read
+	const int32_t *qlen;               // per read
+	const int64_t *mini_off;           // n_reads + 1
+	const unsigned long long *mini_pos;// q_span << 32 | position, read by read (seed.c:125)
+	const int32_t *ref_len;            // per reference sequence
+	int64_t        n_reads, n_regs;
+	int32_t       *reg_read;           // scratch, n_regs: read of every record
+	int32_t       *read_literal;       // scratch, n_reads: the read's positions are not strictly ascending -- its hits are walked as esterr.c does
+	int2          *out;                // out, n_regs: (n_match, n_tot); n_tot = -1: esterr.c:45-51, div stays -1
+	unsigned long long *sum_k;         // out, n_reads: esterr.c:37-38
+	int            grid_waves;
+};
+void launch_est_err(const EstErrBatch &b, hipStream_t s);
+
 } // namespace mm2gb
