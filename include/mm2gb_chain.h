@@ -110,6 +110,8 @@ int  mm2gb_engine_band_shape(const mm2gb_engine_t *eng, int *out6);
  * anchors, [5] the walk's span from the first chunk's start to the last chunk's end; times in ticks of the 100 MHz s_memrealtime clock */
 int  mm2gb_engine_skip_stats(mm2gb_engine_t *eng, int64_t *out6);
 int  mm2gb_engine_device(const mm2gb_engine_t *eng);
+/* compute units of the engine's device, as the launches that size their grids by it count them (-1: null engine) */
+int  mm2gb_engine_cu_count(const mm2gb_engine_t *eng);
 /* of the engine's last completed call: chunks that a GANG of workgroups scored -- a chunk whose share of the micro-batch's pairs is worth two
  * workgroups or more is cut into strips that several workgroups take in turn (what plscore.cu's long-segment kernel does with one block per
  * segment, plscore.cu:187-290, cannot: a segment there is one block's) -- and the workgroups that started in a gang.  MM2GB_GANG_MAX (default 8,

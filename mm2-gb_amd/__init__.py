@@ -76,7 +76,7 @@ _lib = None
 
 # every symbol include/mm2gb_chain.h and include/mm2gb_plutils.h declare
 CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "mm2gb_config_parse", "mm2gb_config_load",
-                "mm2gb_device_count", "mm2gb_device_numa_node", "mm2gb_pin_thread_to_device", "mm2gb_numa_cpus_for_bdf", "mm2gb_engine_create", "mm2gb_engine_destroy", "mm2gb_engine_set_misc", "mm2gb_engine_device", "mm2gb_engine_gang_counts", "mm2gb_has_gang_build",
+                "mm2gb_device_count", "mm2gb_device_numa_node", "mm2gb_pin_thread_to_device", "mm2gb_numa_cpus_for_bdf", "mm2gb_engine_create", "mm2gb_engine_destroy", "mm2gb_engine_set_misc", "mm2gb_engine_device", "mm2gb_engine_cu_count", "mm2gb_engine_gang_counts", "mm2gb_has_gang_build",
                 "mm2gb_engine_reserve", "mm2gb_score_host", "mm2gb_score_device", "mm2gb_engine_sync", "mm2gb_engine_stats",
                 "mm2gb_engine_stream", "mm2gb_engine_last_kernel_ms", "mm2gb_chain_host", "mm2gb_chain_gpu", "mm2gb_post_device", "mm2gb_post_device_enqueue", "mm2gb_post_device_totals", "mm2gb_post_device_digest", "mm2gb_chains_free", "mm2gb_backtrack_host",
                 "mm2gb_free", "mm2gb_lchain_dp", "mm2gb_synth_count", "mm2gb_synth_fill",
@@ -328,6 +328,12 @@ class Engine:
         out = (C.c_int * 6)()
         _check(L.mm2gb_engine_band_shape(self._h, out))
         return dict(zip(("slab", "lag_wave", "lag_team4", "lag_team8", "lag_wg", "min_window"), (int(v) for v in out)))
+
+    def cu_count(self):
+        """Compute units of the engine's device (mm2gb_engine_cu_count): what the kernels that cap their grids by it use."""
+        L = lib()
+        L.mm2gb_engine_cu_count.argtypes = [C.c_void_p]
+        return int(L.mm2gb_engine_cu_count(self._h))
 
     def skip_stats(self):
         """Counters of the skip-limited walk's last micro-batch (engine made with MM2GB_SKIP_STATS=1): rounds of 64 candidates, max_ii search

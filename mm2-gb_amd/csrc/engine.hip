@@ -1531,6 +1531,7 @@ void mm2gb_engine_gang_counts(const mm2gb_engine_t *eng, int64_t *chunks, int64_
 	if (chunks) *chunks = eng ? eng->e.last_gang_chunks : 0;
 	if (workgroups) *workgroups = eng ? eng->e.last_gang_wgs : 0;
 }
+int mm2gb_engine_cu_count(const mm2gb_engine_t *eng) { return eng ? eng->e.n_cu : -1; }
 const char *mm2gb_version(void) { return MM2GB_VERSION; }
 int mm2gb_has_gang_build(void) { return 1; }
 

@@ -158,29 +158,40 @@ def hit(as_, cnt, qs, rs, re, rid=0, rev=False):
 
 
 def est_err_literal(rd, ref_len):
-    """esterr.c:30-62 in plain Python on one read of est_err_host's input: [(n_match, n_tot)] with n_tot = -1 where the walk does not start, and sum_k."""
+    """esterr.c:16-62 in plain Python on one read of est_err_host's input: [(n_match, n_tot)] with n_tot = -1 where the walk does not start, and sum_k."""
     mp = [int(v) for v in rd["mini_pos"]]
     n, qlen = len(mp), rd["qlen"]
     a = np.asarray(rd["anchors"], dtype=np.uint64).reshape(-1, 2)
     sum_k = sum(v >> 32 & 0xff for v in mp)
+    pos = [v & 0xffffffff for v in mp]
     out = []
 
     def qpos(row):
         x, y = int(row[0]), int(row[1])
         p, span = y & 0xffffffff, y >> 32 & 0xff
         return qlen - 1 - (p + 1 - span) if x >> 63 else p
+
+    def find(x):                                                # esterr.c:16-28: the binary search, whatever the order of mini_pos
+        lo, hi = 0, n - 1
+        while lo <= hi:
+            m = (lo + hi) >> 1
+            if pos[m] < x:
+                lo = m + 1
+            elif pos[m] > x:
+                hi = m - 1
+            else:
+                return m
+        return -1
     for h in rd["hits"]:
         if n == 0 or h["cnt"] == 0:
             out.append((0, -1))
             continue
         avg_k = np.float32(sum_k) / np.float32(n)
         at = lambda k: a[h["as"] + h["cnt"] - 1 - k] if h.get("rev") else a[h["as"] + k]
-        pos = [v & 0xffffffff for v in mp]
-        x0 = qpos(at(0))
-        if x0 not in pos:
+        st = en = find(qpos(at(0)))
+        if st < 0:
             out.append((0, -1))
             continue
-        st = en = pos.index(x0)
         k, n_match, j = 1, 1, st + 1
         while j < n and k < h["cnt"]:
             if qpos(at(k)) == pos[j]:
@@ -257,3 +268,205 @@ def synthetic_read(rng, n_mini, chain_lens, gap_hi=4, qlen=None, absent_every=0)
         n_a += len(p)
     anchors = np.concatenate(parts) if parts else np.zeros((0, 2), np.uint64)
     return dict(qlen=qlen, mini_pos=mini([int(v) for v in pos]), anchors=anchors, hits=hits)
+
+
+# ---------------------------------------------------------------- the walk at the shapes of the wave instantiation (hits of 64 anchors or more)
+LONG_CNTS = (64, 65, 128, 129, 200)
+DEFECTS = ("swap", "same", "off")
+
+
+def read_layout(n_mini, seed=0):
+    """(positions, spans) of a read of n_mini minimizers: positions ascend by 3..11, spans vary as in crafted_reads' "varying spans" case."""
+    rng = np.random.default_rng(1000 + seed)
+    pos = (np.cumsum(rng.integers(3, 12, n_mini)) + 40).astype(np.int64)
+    spans = (15 + (np.arange(n_mini) * 7) % 23).astype(np.int64)
+    return pos, spans
+
+
+def mini_of(pos, spans):
+    return (np.asarray(spans, dtype=np.uint64) << np.uint64(32)) | np.asarray(pos, dtype=np.uint64)
+
+
+def chain_on(qlen, pos, spans, rev=False, r0=1000):
+    """The anchors ((n, 2) uint64, in the chain's order) of a chain over the forward query positions pos (in query order) with the spans given; a reverse
+    chain's own order is the query order backwards."""
+    p, s = np.asarray(pos, dtype=np.int64), np.asarray(spans, dtype=np.int64)
+    if rev:
+        p, s = p[::-1], s[::-1]
+        x = (r0 + np.arange(len(p)) * 16).astype(np.uint64) | np.uint64(1 << 63)
+        y = qlen - 1 - (p + 1 - s)
+    else:
+        x, y = (r0 + np.arange(len(p)) * 16).astype(np.uint64), p
+    assert (y >= 0).all() and (y < 2**31).all()
+    return np.stack([x, ((s << 32) | y).astype(np.uint64)], axis=1)
+
+
+def with_defect(pos, spans, kind, k):
+    """The chain's forward positions (query order) with one defect at k >= 1, so that the walk counts k anchors: "swap" anchors k - 1 and k change places, "same"
+    anchor k sits at anchor k - 1's position, "off" anchor k is one base off its minimizer."""
+    p, s = np.array(pos, dtype=np.int64), np.array(spans, dtype=np.int64)
+    if kind == "swap":
+        p[[k - 1, k]], s[[k - 1, k]] = p[[k, k - 1]], s[[k, k - 1]]
+    elif kind == "same":
+        p[k], s[k] = p[k - 1], s[k - 1]
+    elif kind == "off":
+        p[k] += 1
+    else:
+        raise ValueError(kind)
+    return p, s
+
+
+class ReadBuilder:
+    """One read of est_err_host's input, its hits added one by one."""
+
+    def __init__(self, qlen, mini_pos):
+        self.qlen, self.mini_pos, self.parts, self.hits, self.n_a = int(qlen), np.asarray(mini_pos, dtype=np.uint64), [], [], 0
+
+    def add(self, pos, spans, rev=False, qs=200, rs=200, re=2000, rid=0):
+        a = chain_on(self.qlen, pos, spans, rev, r0=1000 + 7 * len(self.hits))
+        self.hits.append(hit(self.n_a, len(a), qs, rs, re, rid=rid, rev=rev))
+        self.parts.append(a)
+        self.n_a += len(a)
+        return self
+
+    def read(self):
+        return dict(qlen=self.qlen, mini_pos=self.mini_pos, anchors=np.concatenate(self.parts) if self.parts else np.zeros((0, 2), np.uint64), hits=self.hits)
+
+
+LONG_REF_LEN = [5_000, 1_200]
+
+
+def crafted_long():
+    """(reads, ref_len, what each read is): the walk's cases at the sizes of k_est_err<64> (and their 16-lane twins where the case has one).  Every read is small
+    enough for est_err_literal; big_read() is the one that is not."""
+    reads, what = [], []
+
+    def done(b, name):
+        reads.append(b.read())
+        what.append(name)
+    n = 460
+    pos, spans = read_layout(n)
+    qlen = int(pos[-1]) + 600                                                                  # (the read goes on past its last minimizer: room for anchors beyond it)
+    # one defect at k in {1, 63, 64, 65, cnt - 1} of a chain of cnt anchors over every minimizer, or every first to third, from a start inside the read
+    for cnt in LONG_CNTS:
+        for rev in (False, True):
+            b = ReadBuilder(qlen, mini_of(pos, spans))
+            for gaps in (1, 3):
+                idx = 7 + np.concatenate([[0], np.cumsum(1 + (np.arange(cnt - 1) * 5) % gaps)])
+                assert idx[-1] < n
+                b.add(pos[idx], spans[idx], rev)                                               # no defect: cnt anchors counted
+                for kind in DEFECTS:
+                    for k in sorted({1, 63, 64, 65, cnt - 1}):
+                        if k < cnt:
+                            b.add(*with_defect(pos[idx], spans[idx], kind, k), rev=rev)
+            done(b, f"cnt {cnt} {'reverse' if rev else 'forward'}")
+    # two failures of different kinds in different rounds of a hit: the earlier one ends the walk, valid anchors after it do not count
+    b = ReadBuilder(qlen, mini_of(pos, spans))
+    idx = 20 + 2 * np.arange(128)
+    for rev in (False, True):
+        for first, second in (("off", "swap"), ("swap", "off"), ("same", "off"), ("off", "same")):
+            p, s = with_defect(pos[idx], spans[idx], second, 100)
+            b.add(*with_defect(p, s, first, 70), rev=rev)
+    done(b, "two defects, 70 and 100")
+    # the chain goes on beyond the read's last minimizer: cnt > n - st, positions past the last one; and hits whose first anchor is the last minimizer
+    b = ReadBuilder(qlen, mini_of(pos, spans))
+    beyond = lambda m: int(pos[-1]) + 5 * (1 + np.arange(m))
+    for tail, more in ((70, 10), (5, 3), (64, 1), (1, 4), (1, 70), (130, 80)):
+        for rev in (False, True):
+            b.add(np.concatenate([pos[n - tail:], beyond(more)]), np.concatenate([spans[n - tail:], np.full(more, 15)]), rev)
+    done(b, "beyond the last minimizer")
+    # mini_pos not strictly ascending: the literal walk, in both instantiations (hits of 5, 64 and 200 anchors from minimizer 100 on)
+    for name, change in (("twice before st", ("dup", 50)), ("twice inside", ("dup", 102)), ("twice after en", ("dup", 420)), ("a descending pair", ("swap", 102)),
+                         ("the first anchor's twice", ("dup", 100)), ("a descending pair before st", ("swap", 30))):
+        mp = mini_of(pos, spans)
+        mp = np.insert(mp, change[1], mp[change[1]]) if change[0] == "dup" else np.concatenate([mp[:change[1]], mp[change[1] + 1:change[1] + 2], mp[change[1]:change[1] + 1], mp[change[1] + 2:]])
+        b = ReadBuilder(qlen, mp)
+        for cnt in (5, 64, 200):
+            idx = 100 + np.arange(cnt)
+            for rev in (False, True):
+                b.add(pos[idx], spans[idx], rev)
+                b.add(*with_defect(pos[idx], spans[idx], "off", cnt - 2), rev=rev)
+                b.add(pos[idx[::2]], spans[idx[::2]], rev)                                     # every second minimizer: the walk passes the changed place without asking for it
+        done(b, "mini_pos: " + name)
+    # coordinates near 2^31
+    big_q = 2**31 - 2
+    bp = (2**30 + np.arange(96) * ((2**30 - 40) // 96)).astype(np.int64)
+    bs = (15 + (np.arange(96) * 5) % 11).astype(np.int64)
+    assert bp[-1] <= 2**31 - 20
+    b = ReadBuilder(big_q, mini_of(bp, bs))
+    for cnt, start in ((8, 3), (70, 20), (96, 0)):
+        for rev in (False, True):
+            b.add(bp[start:start + cnt], bs[start:start + cnt], rev, qs=int(bp[start]) - 14, re=4_000)
+            b.add(*with_defect(bp[start:start + cnt], bs[start:start + cnt], "off", cnt - 3), rev=rev, qs=big_q - 10)
+    done(b, "coordinates near 2^31")
+    # the comparisons against avg_k at equality: qs, rs, qlen - qs and ref_len - re at floor(avg_k) and floor(avg_k) + 1, one at a time, the partner well above
+    for name, sp in (("avg_k exactly 16", np.full(52, 16)), ("avg_k 17.288...", np.asarray([15] * 35 + [22] * 17))):
+        p = 20 + 23 * np.arange(52)
+        b = ReadBuilder(2_000, mini_of(p, sp))
+        lo = int(sp.sum() // 52)
+        for cnt in (6, 52):                                                                    # (52 minimizers: the 16-lane form; the wave's turn is below)
+            for v in (lo, lo + 1):
+                for rev in (False, True):
+                    b.add(p[:cnt], sp[:cnt], rev, qs=v, rs=300, re=2_000)
+                    b.add(p[:cnt], sp[:cnt], rev, qs=300, rs=v, re=2_000)
+                    b.add(p[:cnt], sp[:cnt], rev, qs=2_000 - v, rs=300, re=2_000)
+                    b.add(p[:cnt], sp[:cnt], rev, qs=300, rs=300, re=LONG_REF_LEN[0] - v)
+                    b.add(p[:cnt], sp[:cnt], rev, qs=v, rs=v, re=LONG_REF_LEN[0] - v)
+        done(b, name)
+        p2 = 20 + 23 * np.arange(208)
+        sp2 = np.tile(sp, 4)
+        b = ReadBuilder(8_000, mini_of(p2, sp2))
+        for v in (lo, lo + 1):
+            for rev in (False, True):
+                b.add(p2[:130], sp2[:130], rev, qs=v, rs=300, re=2_000)
+                b.add(p2[:130], sp2[:130], rev, qs=300, rs=v, re=2_000)
+                b.add(p2[:130], sp2[:130], rev, qs=8_000 - v, rs=300, re=2_000)
+                b.add(p2[:130], sp2[:130], rev, qs=300, rs=300, re=LONG_REF_LEN[0] - v)
+        done(b, name + ", hits of 130")
+    return reads, LONG_REF_LEN, what
+
+
+BIG_N = 1_300_001
+
+
+def big_read():
+    """One read of 1 300 001 minimizers with spans 15 and 21 in turn, two of them 16: sum_k = 18 n - 1 = 23 400 017, odd and above 2^24, so (float)sum_k is
+    23 400 016 and avg_k the float below 18 -- computed exactly it would be 18.  Three hits; the first has qs = rs = 18."""
+    n = BIG_N
+    spans = np.where(np.arange(n) % 2 == 0, 15, 21).astype(np.int64)
+    spans[[0, 2]] = 16
+    assert int(spans.sum()) == 18 * n - 1
+    pos = np.cumsum(3 + (np.arange(n) * 7) % 9, dtype=np.int64) + 40
+    qlen = int(pos[-1]) + 60
+    assert qlen < 2**31
+    b = ReadBuilder(qlen, mini_of(pos, spans))
+    i0 = 1_000 + np.arange(40)
+    b.add(pos[i0], spans[i0], False, qs=18, rs=18, re=2_000)
+    i1 = 700_000 + 3 * np.arange(200)
+    b.add(pos[i1], spans[i1], True, qs=18, rs=17, re=2_000)
+    i2 = 1_200_000 + 2 * np.arange(50_000)
+    b.add(*with_defect(pos[i2], spans[i2], "off", 33_333), rev=False, qs=500, rs=500, re=LONG_REF_LEN[0] - 18)
+    return b.read()
+
+
+def stride_batch(cu, seed=13):
+    """One batch that makes each of launch_est_err's three grids stride (it caps a launch at ceil(32 cu / 4) blocks: 32 cu reads, 32 cu hits of a wave, 128 cu
+    hits of 16 lanes per pass): 40 cu small reads of 5-40 minimizers and 0-8 short hits, 300 larger reads that carry more than 32 cu hits of 64-80 anchors
+    among them, and a read without minimizers followed by one without hits at each end and from index 32 cu on.  Returns (reads, ref_len, counts)."""
+    rng = np.random.default_rng(seed)
+    n_small, n_large = 40 * cu, 300
+    per_large = -(-(32 * cu) * 11 // (10 * n_large))                                # (a tenth more than needed: a chain that meets the read's end is cut short)
+    no_mini = lambda: dict(qlen=500, mini_pos=mini([]), anchors=np.asarray(fwd_chain([50, 80, 120]), dtype=np.uint64), hits=[hit(0, 3, 36, 1000, 1071)])
+    no_hits = lambda: dict(qlen=1000, mini_pos=mini(list(range(20, 900, 17))), anchors=np.zeros((0, 2), np.uint64), hits=[])
+    body = []
+    every = max(1, n_small // n_large)
+    for i in range(n_small):
+        n_mini = int(rng.integers(5, 41))
+        body.append(synthetic_read(rng, n_mini, [int(v) for v in rng.integers(1, min(n_mini, 30) + 1, int(rng.integers(0, 9)))], gap_hi=2, absent_every=5))
+        if i % every == every - 1 and i // every < n_large:
+            body.append(synthetic_read(rng, 1_200, [int(v) for v in rng.integers(64, 81, per_large)], gap_hi=2, absent_every=6))
+    at = 32 * cu - 2                                                              # (two reads lead the batch)
+    reads = [no_mini(), no_hits()] + body[:at] + [no_mini(), no_hits()] + body[at:] + [no_mini(), no_hits()]
+    cnts = [h["cnt"] for rd in reads for h in rd["hits"]]
+    counts = dict(reads=len(reads), short_hits=sum(c < 64 for c in cnts), long_hits=sum(c >= 64 for c in cnts))
+    return reads, [100_000], counts

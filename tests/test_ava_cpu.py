@@ -137,3 +137,74 @@ def test_est_err_host_refuses_records_outside_their_read():
         mm.est_err_host(bad, ref_len)
     with pytest.raises(mm.Mm2gbError, match=">= n_ref"):
         mm.est_err_host([dict(reads[0], hits=[av.hit(0, 13, 0, 0, 10, rid=2)])], ref_len)
+
+
+# ---------------------------------------------------------------- the walk at the sizes of the wave instantiation
+def test_est_err_host_crafted_long():
+    reads, ref_len, what = av.crafted_long()
+    got = mm.est_err_host(reads, ref_len, threads=3)
+    check_against_literal(got, reads, ref_len)
+    by = dict(zip(what, zip(reads, got)))
+    assert len(by) == len(what)
+    # a defect at k: k anchors counted, whatever the kind, the strand and the chain's spacing
+    for cnt in av.LONG_CNTS:
+        ks = sorted(k for k in {1, 63, 64, 65, cnt - 1} if k < cnt)
+        for strand in ("forward", "reverse"):
+            rd, g = by[f"cnt {cnt} {strand}"]
+            assert all(h["cnt"] == cnt for h in rd["hits"]) and g["n_match"].tolist() == ([cnt] + ks * len(av.DEFECTS)) * 2
+    assert by["two defects, 70 and 100"][1]["n_match"].tolist() == [70] * 8                      # the earlier defect ends the walk
+    rd, g = by["beyond the last minimizer"]
+    n = len(rd["mini_pos"])
+    assert g["n_match"].tolist() == [70, 70, 5, 5, 64, 64, 1, 1, 1, 1, 130, 130] and all(h["cnt"] > m for h, m in zip(rd["hits"], g["n_match"]))
+    assert [h["cnt"] for h in rd["hits"][8:10]] == [71, 71] and g["n_tot"][8] == 1 + 2                 # the first anchor is the last minimizer, cnt > 1
+    assert max(h["cnt"] for h in rd["hits"]) == 210 > n - (n - 130)
+    # mini_pos not strictly ascending: where the changed place lies outside [st, en] the counts are those of the read without it
+    clean = by["mini_pos: twice before st"][1]["n_match"].tolist()
+    assert clean == [5, 3, 3, 5, 3, 3, 64, 62, 32, 64, 62, 32, 200, 198, 100, 200, 198, 100]
+    for name in ("twice after en", "a descending pair before st", "twice inside", "the first anchor's twice"):
+        assert by["mini_pos: " + name][1]["n_match"].tolist() == clean, name
+    assert by["mini_pos: twice inside"][1]["n_tot"].tolist() != by["mini_pos: twice before st"][1]["n_tot"].tolist()       # (one more place between st and en)
+    assert by["mini_pos: a descending pair"][1]["n_match"].tolist() == [3, 3, 3, 3, 3, 3, 3, 3, 32, 3, 3, 32, 3, 3, 100, 3, 3, 100]
+    # near 2^31
+    rd, g = by["coordinates near 2^31"]
+    assert rd["qlen"] == 2**31 - 2 and int(rd["mini_pos"][-1] & 0xffffffff) > 2**31 - 2**24 and g["n_match"].tolist() == [8, 5, 8, 5, 70, 67, 70, 67, 96, 93, 96, 93]
+    # at equality nothing is added: 16 > 16.0 is false, 17 > 16.0 true; 17 > 17.288 false, 18 true
+    for name, lo in (("avg_k exactly 16", 16), ("avg_k 17.288...", 17)):
+        for suffix, per, base in (("", 5, None), (", hits of 130", 4, 130)):
+            rd, g = by[name + suffix]
+            tot = g["n_tot"].tolist()
+            for j, h in enumerate(rd["hits"]):
+                walked = h["cnt"] if base is None else base
+                v_at = (j // (2 * per)) % 2                                                         # the hits come as (cnt,) v, strand, quantity
+                which = j % per
+                if which < 2:                                                                       # qs or rs at v, the other end of the hit far from its ends
+                    assert tot[j] == walked + v_at + 1, (name, suffix, j)
+                elif which < 4:
+                    assert tot[j] == walked + 1 + v_at, (name, suffix, j)
+                else:                                                                               # qs, rs and ref_len - re at v: both tests turn on v alone
+                    assert tot[j] == walked + 2 * v_at, (name, suffix, j)
+
+
+def test_est_err_host_sum_k_above_2_to_24():
+    """1 300 001 minimizers: sum_k is odd and above 2^24, so its float is not its value, and avg_k falls just below 18 where the exact quotient rounds to 18."""
+    rd = av.big_read()
+    n = len(rd["mini_pos"])
+    got = mm.est_err_host([rd], av.LONG_REF_LEN, threads=2)[0]
+    sum_k = int((rd["mini_pos"] >> np.uint64(32) & np.uint64(0xff)).sum())
+    assert got["sum_k"] == sum_k == 18 * n - 1 and sum_k > 2**24 and sum_k % 2 == 1
+    avg_k = np.float32(sum_k) / np.float32(n)                                                       # esterr.c:39: (float)sum_k / n
+    assert float(np.float32(sum_k)) == sum_k - 1 and avg_k < np.float32(18.0) == np.float32(sum_k / n)
+    h = rd["hits"][0]
+    by_hand = (40 - 1) + 1 + int(np.float32(h["qs"]) > avg_k and np.float32(h["rs"]) > avg_k) + int(np.float32(rd["qlen"] - h["qs"]) > avg_k and np.float32(av.LONG_REF_LEN[0] - h["re"]) > avg_k)
+    assert (h["qs"], h["rs"]) == (18, 18) and by_hand == 42 and got["n_tot"][0] == by_hand and got["n_match"][0] == 40
+    assert got["n_match"].tolist() == [40, 200, 33_333]
+    assert got["n_tot"].tolist() == [42, 3 * 199 + 1 + 1, 2 * 33_332 + 1 + 2]                        # (rs = 17 is not above avg_k; ref_len - re = 18 is)
+
+
+def test_stride_batch_at_a_small_cu_count():
+    """The batch tests/test_gpu_ava.py builds for the device's CU count, at 4 CUs: its counts, its special reads, and the host form against the literal walk."""
+    reads, ref_len, c = av.stride_batch(4)
+    assert c["reads"] == len(reads) > 32 * 4 and c["short_hits"] > 128 * 4 and c["long_hits"] > 32 * 4
+    for at in (0, 32 * 4, len(reads) - 2):
+        assert len(reads[at]["mini_pos"]) == 0 and len(reads[at]["hits"]) == 1 and len(reads[at + 1]["hits"]) == 0 and len(reads[at + 1]["mini_pos"]) > 0
+    check_against_literal(mm.est_err_host(reads, ref_len, threads=4), reads, ref_len)

@@ -104,3 +104,34 @@ def test_est_err_many_reads(engine):
     reads = [av.synthetic_read(rng, int(rng.integers(1, 3000)), [int(v) for v in rng.integers(1, 150, int(rng.integers(0, 201)))], gap_hi=5, absent_every=7) for _ in range(300)]
     want = same_est(engine, reads, [100_000])
     assert sum(len(w["div"]) for w in want) > 20_000 and any((w["n_tot"] < 0).any() for w in want)
+
+
+def test_est_err_crafted_long(engine):
+    """The walk's cases at the sizes of k_est_err<64>: a defect of each kind at k = 1, 63, 64, 65 and cnt - 1 of hits of 64 to 200 anchors, two defects in different
+    rounds, chains that go on beyond the read's last minimizer, reads whose mini_pos is not strictly ascending (the literal walk in both instantiations),
+    coordinates near 2^31 and the comparisons against avg_k at equality."""
+    reads, ref_len, what = av.crafted_long()
+    want = same_est(engine, reads, ref_len)
+    by = dict(zip(what, want))
+    assert by["two defects, 70 and 100"]["n_match"].tolist() == [70] * 8 and by["cnt 200 reverse"]["n_match"].tolist()[:5] == [200, 1, 63, 64, 65]
+    one_at_a_time = [same_est(engine, [rd], ref_len)[0] for rd in reads]                            # a read alone: its place in the batch plays no part
+    assert all(np.array_equal(a["n_tot"], b["n_tot"]) and np.array_equal(a["n_match"], b["n_match"]) for a, b in zip(one_at_a_time, want))
+
+
+def test_est_err_sum_k_above_2_to_24(engine):
+    want = same_est(engine, [av.big_read()], av.LONG_REF_LEN)
+    assert want[0]["sum_k"] == 18 * av.BIG_N - 1 and want[0]["n_tot"].tolist() == [42, 599, 66_667] and want[0]["n_match"].tolist() == [40, 200, 33_333]
+
+
+def test_est_err_every_grid_strides(engine):
+    """launch_est_err caps each launch at ceil(32 CU / 4) blocks: a batch with more than 32 CU reads, more than 32 CU hits of a wave and more than 128 CU hits of
+    16 lanes makes each of the three kernels take a second step through its grid, with a read without minimizers and one without hits at the seams."""
+    cu = engine.cu_count()
+    assert cu >= 1
+    reads, ref_len, c = av.stride_batch(cu)
+    print(f"CUs {cu}: {c['reads']} reads (one pass: {32 * cu}), {c['long_hits']} hits of 64 anchors or more (one pass: {32 * cu}), {c['short_hits']} shorter hits (one pass: {128 * cu})")
+    assert c["reads"] == len(reads) > 32 * cu and c["long_hits"] > 32 * cu and c["short_hits"] > 128 * cu
+    for at in (0, 32 * cu, len(reads) - 2):
+        assert len(reads[at]["mini_pos"]) == 0 and len(reads[at]["hits"]) == 1 and len(reads[at + 1]["hits"]) == 0
+    want = same_est(engine, reads, ref_len)
+    assert want[32 * cu]["n_tot"].tolist() == [-1] and any((w["n_tot"] < 0).any() for w in want[32 * cu + 2:]) and any((w["n_match"] >= 64).any() for w in want[32 * cu + 2:])
