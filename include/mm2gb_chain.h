@@ -394,6 +394,29 @@ int  mm2gb_map_opt_init_preset(mm2gb_map_opt_t *opt, const char *preset);
 #define MM2GB_F_NO_LJOIN   0x400LL
 #define MM2GB_F_ALL_CHAINS 0x800000LL
 int  mm2gb_map_opt_init_ava(mm2gb_map_opt_t *opt, const char *preset);
+/* Short single-end reads (minimap2 -x sr).  mm2gb_map_opt_init_sr: mm2gb_map_opt_init, then the mapping fields of
+ * options.c:133-150 that mm2gb_map_opt_t has room for -- flag |= MM_F_SR | MM_F_FRAG_MODE | MM_F_NO_PRINT_2ND | MM_F_HEAP_SORT, max_gap = 100, bw = bw_long = 100,
+ * pri_ratio = 0.5, min_cnt = 2, min_chain_score = 25, best_n = 20, mid_occ = 1000 (fixed: not recomputed from the index); max_chain_skip stays what mm2gb_map_opt_init
+ * sets, which is what main.c:316-318 forces under MM_F_SR.  The index is the caller's: k = 21, w = 11, no HPC.  max_occ = 5000 and max_frag_len = 800 have no field here.
+ * They go to mm2gb_map_reads_sr (below); mm2gb_map_reads* and the alignment calls refuse the four bits as they always have.
+ *   MM2GB_F_HEAP_SORT   anchors in the order collect_seed_hits_heap leaves them (map.c:229-293): mm2gb_collect_seeds_heap_host / _gpu below
+ * mm2gb_collect_seeds_heap_host / _gpu: the arguments of mm2gb_collect_seeds_host / _gpu, and the anchors not sorted by x but as the reference's heap merge of the
+ * seeds' hit lists leaves them: the forward-strand anchors in ascending cr (the hit as the index holds it), then the reverse-strand ones in ascending cr.  Among EQUAL cr
+ * -- one minimizer value at two places of a read: both seeds carry the same list -- the order is the heap's own (ks_heapdown, ksort.h:43-53, moves a child with an equal
+ * key up: not seed order).  The host form restates the heap and is the definition.  The device form (csrc/seed_heap_kernels.hip) sorts a read's hits by (cr, seed, k) --
+ * one wave in LDS up to 1024 hits, rocprim's segmented radix sort beyond --, which is the heap's order for every read without two equal cr; a read with two is flagged
+ * and done again by the host form inside the call, so both forms return the same anchors element for element.  *n_tied_reads (may be NULL): the reads with two equal cr,
+ * the same number from both forms.  MM_F_QSTRAND is refused by name (the reference's heap form has no such branch). */
+#define MM2GB_F_FRAG_MODE    0x2000LL
+#define MM2GB_F_NO_PRINT_2ND 0x4000LL
+#define MM2GB_F_HEAP_SORT    0x400000LL
+void mm2gb_map_opt_init_sr(mm2gb_map_opt_t *opt);
+int  mm2gb_collect_seeds_heap_host(int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off,
+                                   const uint64_t *hits, const int32_t *qlen, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len,
+                                   const int32_t *ref_rank, int n_threads, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads);
+int  mm2gb_collect_seeds_heap_gpu(mm2gb_engine_t *eng, int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds,
+                                  const int64_t *hit_off, const uint64_t *hits, const int32_t *qlen, const int32_t *q_rank,
+                                  int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads);
 /* mm_est_err's walk (esterr.c:30-61) for every hit record of a batch, on host threads (the definition) and on the device (est_err_kernels.hip; equal results):
  * read r owns regs[reg_off[r] .. reg_off[r+1]) -- looked at: as (an index into the read's anchors, which begin at anchor_off[r]), cnt, rid, qs, rs, re and the rev bit --
  * and the minimizer positions mini_pos[mini_off[r] .. mini_off[r+1]) (mm2gb_matches_t::mini_pos).  out[j]: n_match and n_tot after both end increments (esterr.c:60-61), or
@@ -736,6 +759,67 @@ int  mm2gb_map_reads_splice(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k,
 int  mm2gb_map_reads_stream_splice(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
                                    int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs,
                                    const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra /* 3, optional; summed over chunks */);
+
+/* ---- alignment of hits under MM_F_SR, batched: mm_align_skeleton with mm_align1's is_sr branches.  A third set of calls on the records of
+ *      mm2gb_align_regs_*, which keep refusing MM_F_SR.  Per chain: mm_max_stretch (align.c:498-524) picks the best run of anchors on one diagonal, no end filter and
+ *      no bad-seed filters, qs0 = 0 and qe0 = qlen, rs0 / re0 from align.c:625-630, the two extensions ordinary ksw_extd2 jobs with end_bonus, and ONE gap fill over the
+ *      whole stretch whose first pass is not a DP (align.c:744-751): one M word of qe - qs columns, score = sum of a / -b per column and + e2 where either base is
+ *      ambiguous (as the reference writes it; not sc_ambi).  mm_test_zdrop walks that word with the real matrix and makes no inversion trial; a fill that drops by more
+ *      than zdrop runs again as a ksw_extd2 job (band bw_long * 1.5 + 1, exact maximum), may split the chain, and the tail is planned in the same form next round.
+ *      mm_update_extra leaves out its log-gap term (a gap costs q + e), mm_update_dp_max is not run.  mm2gb_align_sr_opt_init: options.c:133-150.
+ *      Refused by name, nothing run and *out zeroed: a flag word without MM_F_SR, MM_F_SPLICE, MM_F_QSTRAND, MM_F_EQX, an index with MM2GB_I_HPC (align.c:583),
+ *      q == q2 && e == e2, a stretch whose two sides differ in length (anchors that are not the chainer's), and what mm2gb_align_regs_* refuse about max_sw_mat, records,
+ *      anchors and segments.  sr_counts (may be NULL): see MM2GB_SR_N_*.  In *out, fill_one_pass counts the fills left ungapped and fill_two_pass those run again.
+ *      The host form is the definition; the device form equals it: k_al_ungapped (csrc/align_kernels.hip) takes a wave per first-pass fill over the gathered bytes --
+ *      score by reduction, mm_test_zdrop's walk as a scan -- and no DP launch is made for them. ---- */
+enum { MM2GB_SR_N_FILL_UNGAPPED,     /* fills whose ungapped first pass stood */
+       MM2GB_SR_N_FILL_RERUN,        /* fills that dropped and ran again as a DP */
+       MM2GB_SR_N_STRETCH_SHORT,     /* chains whose best stretch holds fewer anchors than the chain */
+       MM2GB_SR_N_COUNTS };
+void mm2gb_align_sr_opt_init(mm2gb_align_opt_t *opt);
+int  mm2gb_align_regs_sr_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                              int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *sr_counts);
+int  mm2gb_align_regs_sr_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                             int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                             const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_align_out_t *out, int64_t *sr_counts);
+
+/* mm2gb_map_reads_sr / mm2gb_map_reads_stream_sr: minimap2 -x sr [-c | -c --cs | --cs=long --MD -c] on single-end reads, to the PAF (the arguments of mm2gb_map_reads /
+ * mm2gb_map_reads_stream and a mm2gb_map_sr_t): anchors in heap order (under MM_F_HEAP_SORT), the chaining DP with the gaps of map.c:678-686 -- max_dist_y = max(qlen,
+ * max_gap), max_dist_x = max(max_frag_len - qlen, max_gap) or max_gap_ref where set: one chaining call per distinct max_dist_x among a batch's reads (reads of one length
+ * share it, and so do all reads of max_frag_len - max_gap bases or more) --, the rescue of map.c:708-731 (max_occ > mid_occ: reads with rep_len > 0 and no chain are
+ * seeded, collected and chained again with max_occ in mid_occ's place, as one more batch; that round's rep_len stands in the line), no re-chaining stage, mm_gen_regs,
+ * mm_set_parent, mm_select_sub, no mm_est_err (without an alignment no dv:f), then with align != 0 mm2gb_align_regs_sr_* and the steps after it in their forms with an
+ * alignment, mm_set_mapq with is_sr = 1, the text calls for `what`, and under MM_F_NO_PRINT_2ND no line for a secondary hit.
+ * seeding_on_device: 0 seeds on host threads; 1 on the device, the matches left resident for the heap-order collection (mm2gb_collect_seeds_heap_gpu's kernels read them
+ * where they lie) and copied back once for the rescue's test and the lines' rl:i; 2 is treated as 1: the resident path skips nothing that the rescue needs.
+ * sr_out (optional): the call's own counts and the seconds of the alignment call, the steps after it and the text; stats->s_chain holds stages 2 and 3 together, and
+ * n_rechained / n_rmq_tied stay 0 (there is no re-chaining stage and no RMQ here).  The stream form sums them over chunks.
+ * Refused by name: an HPC index (align.c:583), MM_F_RMQ (options.c:173), MM_F_QSTRAND, MM_F_EQX, MM_F_SPLICE, the read-overlap bits, options without MM_F_SR, align != 0
+ * without ref_seqs, what != 0 with align == 0; more than one segment and SAM output do not exist.  mm2gb_map_sr_init: max_occ = 5000, max_frag_len = 800, align = 0 and
+ * mm2gb_align_sr_opt_init's values in opt. */
+typedef struct {
+	const char *const *ref_seqs;      /* the reference sequences as text, in the index's order (not read while align is 0; may then be NULL) */
+	mm2gb_align_opt_t opt;            /* the alignment's option set (not read while align is 0) */
+	int32_t align;                    /* 0: no base-level alignment, PAF from the chains; 1: minimap2 -c */
+	int32_t what;                     /* MM2GB_TEXT_*; 0 while align is 0 */
+	int32_t align_on_device, text_on_device;      /* as in mm2gb_map_aln_t */
+	int32_t max_occ, max_frag_len;    /* mm_mapopt_t::max_occ, max_frag_len: the two fields mm2gb_map_opt_t has no room for */
+} mm2gb_map_sr_t;
+typedef struct {
+	int64_t n_chain_calls;            /* chaining calls made (one per distinct max_dist_x, both rounds) */
+	int64_t n_rescued;                /* reads that went through the max_occ round */
+	int64_t n_tied_reads;             /* reads whose anchors the host's heap ordered (two equal index entries) */
+	int64_t sr_counts[MM2GB_SR_N_COUNTS];
+	double  s_extra[3];               /* seconds: the alignment call, the steps after it, the text */
+} mm2gb_map_sr_out_t;
+void mm2gb_map_sr_init(mm2gb_map_sr_t *sr);
+int  mm2gb_map_reads_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref, const mm2gb_map_opt_t *opt,
+                        const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
+                        mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out);
+int  mm2gb_map_reads_stream_sr(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                               int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
+                               const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out);
 
 #ifdef __cplusplus
 }

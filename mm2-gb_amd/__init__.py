@@ -92,7 +92,8 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_align_opt_init", "mm2gb_align_regs_host", "mm2gb_align_regs_gpu", "mm2gb_align_out_free",
                 "mm2gb_align_splice_opt_init", "mm2gb_align_regs_splice_host", "mm2gb_align_regs_splice_gpu", "mm2gb_aln_text_splice_host", "mm2gb_aln_text_splice_gpu",
                 "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice", "mm2gb_map_opt_init_preset",
-                "mm2gb_ksw_extz2_host", "mm2gb_ksw_extz2_gpu", "mm2gb_align_regs_extz_host", "mm2gb_align_regs_extz_gpu"]
+                "mm2gb_ksw_extz2_host", "mm2gb_ksw_extz2_gpu", "mm2gb_align_regs_extz_host", "mm2gb_align_regs_extz_gpu",
+                "mm2gb_map_opt_init_sr", "mm2gb_collect_seeds_heap_host", "mm2gb_collect_seeds_heap_gpu", "mm2gb_map_sr_init", "mm2gb_map_reads_sr"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -548,6 +549,55 @@ def collect_seeds_host(flag, reads, ref_len=None, ref_rank=None, threads=4):
 Engine.gen_regs = _engine_gen_regs
 
 
+def _seed_arrays(reads, ref_len, ref_rank):
+    """The arrays the seed collection calls take, from reads as Engine.collect_seeds takes them."""
+    R = len(reads)
+    seed_off = np.zeros(R + 1, np.int64)
+    seed_off[1:] = np.cumsum([len(r["seeds"]) for r in reads])
+    seeds = np.ascontiguousarray(np.concatenate([np.asarray(r["seeds"], np.uint32).reshape(-1, 4) for r in reads]) if R else np.zeros((0, 4), np.uint32), dtype=np.uint32)
+    hit_off = np.zeros(len(seeds) + 1, np.int64)
+    np.cumsum(seeds[:, 0], out=hit_off[1:])
+    hits = np.ascontiguousarray(np.concatenate([np.asarray(r["hits"], np.uint64) for r in reads]) if R else np.zeros(0, np.uint64), dtype=np.uint64)
+    qlen = np.ascontiguousarray([r["qlen"] for r in reads], dtype=np.int32)
+    q_rank = np.ascontiguousarray([r.get("q_rank", 0) for r in reads], dtype=np.int32) if any("q_rank" in r for r in reads) else None
+    rl = np.ascontiguousarray(ref_len, dtype=np.int32) if ref_len is not None else None
+    rr = np.ascontiguousarray(ref_rank, dtype=np.int32) if ref_rank is not None else None
+    n_ref = len(rl) if rl is not None else (len(rr) if rr is not None else 0)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    return R, seed_off, seeds, hit_off, hits, qlen, q_rank, rl, rr, n_ref, ptr
+
+
+def _engine_collect_seeds_heap(self, flag, reads, ref_len=None, ref_rank=None):
+    """mm2gb_collect_seeds_heap_gpu: Engine.collect_seeds with the anchors in the order collect_seed_hits_heap leaves them (minimap2 -x sr: MM_F_HEAP_SORT) -- forward
+    strand first, each strand in ascending index position, equal positions in the reference heap's own order.  Returns (one (m,2) uint64 array per read, n_tied_reads):
+    the reads with two equal positions, which the call does again with the host form."""
+    R, seed_off, seeds, hit_off, hits, qlen, q_rank, rl, rr, n_ref, ptr = _seed_arrays(reads, ref_len, ref_rank)
+    fn = lib().mm2gb_collect_seeds_heap_gpu
+    fn.argtypes = [C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(C.c_int64)]
+    a_off = np.zeros(R + 1, np.int64)
+    out = np.zeros((max(len(hits), 1), 2), np.uint64)
+    n_tied = C.c_int64(0)
+    _check(fn(self._h, int(flag), R, seed_off.ctypes.data, seeds.ctypes.data, hit_off.ctypes.data, hits.ctypes.data, qlen.ctypes.data, ptr(q_rank), n_ref, ptr(rl), ptr(rr),
+              a_off.ctypes.data, out.ctypes.data, C.byref(n_tied)))
+    return [out[a_off[r]:a_off[r + 1]].copy() for r in range(R)], int(n_tied.value)
+
+
+Engine.collect_seeds_heap = _engine_collect_seeds_heap
+
+
+def collect_seeds_heap_host(flag, reads, ref_len=None, ref_rank=None, threads=4):
+    """mm2gb_collect_seeds_heap_host: the definition of Engine.collect_seeds_heap (map.c:229-293 with ksort.h's heap), on host threads; same arguments and results."""
+    R, seed_off, seeds, hit_off, hits, qlen, q_rank, rl, rr, n_ref, ptr = _seed_arrays(reads, ref_len, ref_rank)
+    fn = lib().mm2gb_collect_seeds_heap_host
+    fn.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    a_off = np.zeros(R + 1, np.int64)
+    out = np.zeros((max(len(hits), 1), 2), np.uint64)
+    n_tied = C.c_int64(0)
+    _check(fn(int(flag), R, seed_off.ctypes.data, seeds.ctypes.data, hit_off.ctypes.data, hits.ctypes.data, qlen.ctypes.data, ptr(q_rank), n_ref, ptr(rl), ptr(rr), int(threads),
+              a_off.ctypes.data, out.ctypes.data, C.byref(n_tied)))
+    return [out[a_off[r]:a_off[r + 1]].copy() for r in range(R)], int(n_tied.value)
+
+
 # ---- base-level DP (mm2gb_ksw_extd2_host / _gpu): the dual-affine extension alignment of ksw2, batched ----
 KSW_SCORE_ONLY, KSW_RIGHT, KSW_GENERIC_SC, KSW_APPROX_MAX, KSW_APPROX_DROP, KSW_EXTZ_ONLY, KSW_REV_CIGAR = 0x01, 0x02, 0x04, 0x08, 0x10, 0x40, 0x80
 KSW_NEG_INF = -0x40000000
@@ -891,6 +941,44 @@ def _engine_align_regs_splice(self, opt, k, hpc, refs, reads, regs, anchors):
 
 
 Engine.align_regs_splice = _engine_align_regs_splice
+
+
+# ---- alignment of hits under MM_F_SR (mm2gb_align_regs_sr_host / _gpu): mm_align1's is_sr branches; the calls above keep refusing MM_F_SR ----
+SR_COUNTS = ("fill_ungapped", "fill_rerun", "stretch_short")
+
+
+def align_sr_opt(**kw):
+    """mm2gb_align_sr_opt_init (options.c:133-150: a 2, b 8, q 12, e 2, q2 24, e2 1, zdrop = zdrop_inv = 100, end_bonus 10, min_dp_max 40, ...), then keyword overrides."""
+    o = AlignOpt()
+    fn = lib().mm2gb_align_sr_opt_init
+    fn.argtypes = [C.POINTER(AlignOpt)]
+    fn.restype = None
+    fn(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise Mm2gbError(f"mm2gb_align_opt_t has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def _align_sr_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail):
+    sc = (C.c_int64 * len(SR_COUNTS))()
+    res, info = _align_call(fn, head, opt, k, hpc, refs, reads, regs, anchors, tail, after=(sc,))
+    info["sr_counts"] = dict(zip(SR_COUNTS, (int(x) for x in sc)))
+    return res, info
+
+
+def align_regs_sr_host(opt, k, hpc, refs, reads, regs, anchors, threads=4):
+    """mm2gb_align_regs_sr_host: align_regs_host's arguments and results for short reads (opt: align_sr_opt()), with info["sr_counts"] -- the definition."""
+    return _align_sr_call(lib().mm2gb_align_regs_sr_host, (), opt, k, hpc, refs, reads, regs, anchors, (int(threads),))
+
+
+def _engine_align_regs_sr(self, opt, k, hpc, refs, reads, regs, anchors):
+    """mm2gb_align_regs_sr_gpu: align_regs_sr_host's arguments and results; the ungapped first pass of every fill in k_al_ungapped, the DPs on the device."""
+    return _align_sr_call(lib().mm2gb_align_regs_sr_gpu, (self._h,), opt, k, hpc, refs, reads, regs, anchors, ())
+
+
+Engine.align_regs_sr = _engine_align_regs_sr
 
 
 # ---- the text of a PAF line's alignment tags (mm2gb_aln_text_host / _gpu): cg:Z, cs:Z, MD:Z for a batch of records ----
@@ -1436,6 +1524,31 @@ def preset_ava(name):
     raise Mm2gbError(f"preset_ava: {name!r} is not supported (ava-ont, ava-pb)")
 
 
+# short single-end reads (minimap2 -x sr): MM2GB_F_SR, _FRAG_MODE, _NO_PRINT_2ND, _HEAP_SORT
+F_SR, F_FRAG_MODE, F_NO_PRINT_2ND, F_HEAP_SORT = 0x1000, 0x2000, 0x4000, 0x400000
+
+
+def map_opt_sr(**kw):
+    """mm2gb_map_opt_init_sr: the mapping fields of "sr" / "short" (options.c:133-150: the four bits above, max_gap = bw = bw_long = 100, pri_ratio = 0.5, min_cnt = 2,
+    min_chain_score = 25, best_n = 20, mid_occ = 1000), then keyword overrides.  For map_reads(..., opt=map_opt_sr(), k=21, align=map_sr()); without align=map_sr()
+    map_reads refuses these flags as before.  The index: **preset_sr()."""
+    o = MapOpt()
+    fn = lib().mm2gb_map_opt_init_sr
+    fn.argtypes = [C.POINTER(MapOpt)]
+    fn.restype = None
+    fn(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise Mm2gbError(f"mm2gb_map_opt_t has no field {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def preset_sr():
+    """The index parameters of the short-read preset, as keywords for SeedIndex: -k21 -w11, no HPC (options.c:134)."""
+    return dict(k=21, w=11, hpc=False)
+
+
 class EstErr(C.Structure):
     _fields_ = [("n_match", C.c_int32), ("n_tot", C.c_int32)]
 
@@ -1563,15 +1676,65 @@ def _stats_with_extra(st, extra):
     return dict(st.as_dict(), s_align=round(extra[0], 4), s_post_align=round(extra[1], 4), s_text=round(extra[2], 4))
 
 
+class MapSr(C.Structure):
+    """mm2gb_map_sr_t: what mm2gb_map_reads_sr needs beside the mapping options (make one with map_sr)."""
+    _fields_ = [("ref_seqs", C.POINTER(C.c_char_p)), ("opt", AlignOpt), ("align", C.c_int32), ("what", C.c_int32), ("align_on_device", C.c_int32), ("text_on_device", C.c_int32),
+                ("max_occ", C.c_int32), ("max_frag_len", C.c_int32)]
+
+
+class MapSrOut(C.Structure):
+    """mm2gb_map_sr_out_t: the short-read calls' own counts and seconds."""
+    _fields_ = [("n_chain_calls", C.c_int64), ("n_rescued", C.c_int64), ("n_tied_reads", C.c_int64), ("sr_counts", C.c_int64 * len(SR_COUNTS)), ("s_extra", C.c_double * 3)]
+
+
+def map_sr(refs=None, align=False, cs=None, md=False, align_on_device=0, text_on_device=0, **fields):
+    """Short single-end reads for map_reads / map_reads_stream (their align= argument; minimap2 -x sr): mm2gb_map_sr_init's values (max_occ = 5000, max_frag_len = 800,
+    align_sr_opt()'s alignment values), then keyword overrides of max_occ / max_frag_len or of a field of the alignment's option set.  align=True: base-level alignment
+    (minimap2 -c; refs: the reference sequences as bytes, in the index's order) with cg:Z; cs: None, "short" or "long"; md: MD:Z.  align_on_device / text_on_device as
+    for map_align.  Use opt=map_opt_sr(), k=21 and an index built with **preset_sr()."""
+    if cs not in (None, "short", "long"):
+        raise Mm2gbError('map_sr: cs is None, "short" or "long"')
+    if align and refs is None:
+        raise Mm2gbError("map_sr: align=True needs refs, the reference sequences")
+    a = MapSr()
+    fn = lib().mm2gb_map_sr_init
+    fn.argtypes = [C.POINTER(MapSr)]
+    fn.restype = None
+    fn(C.byref(a))
+    if refs is not None:
+        a._refs = [bytes(s) for s in refs]
+        a._arr = (C.c_char_p * max(len(a._refs), 1))(*a._refs)
+        a.ref_seqs = a._arr
+    a.align = 1 if align else 0
+    a.what = (TEXT_CG if align else 0) | ({None: 0, "short": TEXT_CS, "long": TEXT_CS | TEXT_CS_LONG}[cs]) | (TEXT_MD if md else 0)
+    a.align_on_device, a.text_on_device = int(align_on_device), int(text_on_device)
+    for k, v in fields.items():
+        if k in ("max_occ", "max_frag_len"):
+            setattr(a, k, v)
+        elif hasattr(a.opt, k):
+            setattr(a.opt, k, v)
+        else:
+            raise Mm2gbError(f"map_sr: no field {k!r} (max_occ, max_frag_len, or a field of mm2gb_align_opt_t)")
+    return a
+
+
+def _sr_stats(st, so):
+    return dict(st.as_dict(), n_chain_calls=int(so.n_chain_calls), n_rescued=int(so.n_rescued), n_tied_reads=int(so.n_tied_reads),
+                sr_counts=dict(zip(SR_COUNTS, (int(x) for x in so.sr_counts))), s_align=round(so.s_extra[0], 4), s_post_align=round(so.s_extra[1], 4), s_text=round(so.s_extra[2], 4))
+
+
 def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
     """mm2gb_map_reads: reads = list of (name, sequence bytes); returns (PAF text, stats dict).  index: a SeedIndex of the references.
-    align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln) or a map_splice(...) for spliced reads (mm2gb_map_reads_splice); the stats then hold s_align, s_post_align and s_text as well."""
+    align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln) or a map_splice(...) for spliced reads (mm2gb_map_reads_splice); the stats then hold s_align, s_post_align and s_text as well.
+    A map_sr(...) with opt=map_opt_sr(): short single-end reads (mm2gb_map_reads_sr; minimap2 -x sr [-c]); the stats then hold the call's own counts as well (n_chain_calls,
+    n_rescued, n_tied_reads, sr_counts) and the three alignment seconds."""
     L = lib()
     head = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
     tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
     L.mm2gb_map_reads.argtypes = head + tail
     L.mm2gb_map_reads_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
     L.mm2gb_map_reads_splice.argtypes = head + [C.POINTER(MapSplice)] + tail + [C.c_void_p]
+    L.mm2gb_map_reads_sr.argtypes = head + [C.POINTER(MapSr)] + tail + [C.POINTER(MapSrOut)]
     opt = opt or map_opt()
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
     names = (C.c_char_p * len(reads))(*[n.encode() for n, _ in reads])
@@ -1581,6 +1744,14 @@ def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
     out, n, st, extra = C.c_void_p(), C.c_int64(), MapStats(), (C.c_double * 3)()
     first = (engine._h, index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt))
     rest = (len(reads), names, seqs, lens.ctypes.data, C.byref(out), C.byref(n), C.byref(st))
+    if isinstance(align, MapSr):
+        if align.align:
+            _check_align_refs(align, ref_names)
+        so = MapSrOut()
+        _check(L.mm2gb_map_reads_sr(*first, C.byref(align), *rest, C.byref(so)))
+        text = C.string_at(out, n.value).decode()
+        L.mm2gb_free(out)
+        return text, _sr_stats(st, so)
     if align is None:
         _check(L.mm2gb_map_reads(*first, *rest))
     else:
@@ -1624,13 +1795,14 @@ Engine.release_host_scratch = _engine_release_host_scratch
 def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0, align=None):
     """mm2gb_map_reads_stream: a run of any size as a stream of chunks of about chunk_bases bases; every engine (several per device overlap
     host stages with kernels, engines on several devices shard the reads) takes the next chunk.  Returns (PAF text in read order, stats:
-    counts summed, s_* summed over chunks).  align: as for map_reads (mm2gb_map_reads_stream_aln)."""
+    counts summed, s_* summed over chunks).  align: as for map_reads (mm2gb_map_reads_stream_aln / _splice / _sr)."""
     L = lib()
     head = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
     tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
     L.mm2gb_map_reads_stream.argtypes = head + tail
     L.mm2gb_map_reads_stream_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
     L.mm2gb_map_reads_stream_splice.argtypes = head + [C.POINTER(MapSplice)] + tail + [C.c_void_p]
+    L.mm2gb_map_reads_stream_sr.argtypes = head + [C.POINTER(MapSr)] + tail + [C.POINTER(MapSrOut)]
     opt = opt or map_opt()
     hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
@@ -1641,6 +1813,14 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
     out, n, st, extra = C.c_void_p(), C.c_int64(), MapStats(), (C.c_double * 3)()
     first = (hs, len(engines), index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt))
     rest = (len(reads), names, seqs, lens.ctypes.data, int(chunk_bases), C.byref(out), C.byref(n), C.byref(st))
+    if isinstance(align, MapSr):
+        if align.align:
+            _check_align_refs(align, ref_names)
+        so = MapSrOut()
+        _check(L.mm2gb_map_reads_stream_sr(*first, C.byref(align), *rest, C.byref(so)))
+        text = C.string_at(out, n.value).decode()
+        L.mm2gb_free(out)
+        return text, _sr_stats(st, so)
     if align is None:
         _check(L.mm2gb_map_reads_stream(*first, *rest))
     else:

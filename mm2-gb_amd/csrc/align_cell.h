@@ -31,6 +31,9 @@ __host__ __device__ inline uint8_t al_target(const uint8_t *refs, const AlJob &j
 // ksw_gen_simple_mat's entry for a target and a query residue (align.c:9-22) with a, b, sc_ambi already made positive
 __host__ __device__ inline int al_score(int a, int b, int ambi, int t, int q) { return t >= 4 || q >= 4 ? -ambi : t == q ? a : -b; }
 
+// a column of the short-read form's ungapped first pass (align.c:748-749): + e2 where either base is ambiguous, as the reference writes it (not -sc_ambi)
+__host__ __device__ inline int al_ungapped_score(int a, int b, int e2, int t, int q) { return t >= 4 || q >= 4 ? e2 : t == q ? a : -b; }
+
 // what the walk along a CIGAR leaves: the largest drop and where it lies (pos[0]: target from / to, pos[1]: query from / to)
 struct AlDrop { int32_t max_zdrop, t_from, t_to, q_from, q_to, pad_; };
 

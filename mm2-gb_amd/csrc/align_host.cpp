@@ -53,6 +53,7 @@ struct Read {
 	int64_t first_run = 0;
 	int64_t cnt[MM2GB_ALN_N_COUNTS] = {};
 	int64_t scnt[MM2GB_SPL_N_COUNTS] = {};      // the spliced form's
+	int64_t srcnt[MM2GB_SR_N_COUNTS] = {};      // the short-read form's
 };
 
 inline uint8_t read_base(const AlCtx &c, int64_t read, int strand, int p)
@@ -406,6 +407,78 @@ bool plan_chain(const AlCtx &c, Read &R, const Reg &g, Plan &P, std::vector<int>
 	return true;
 }
 
+// ---- mm_max_stretch (align.c:498-524): the run of anchors on one diagonal with the largest sum of matching bases ----
+void max_stretch(const mm2gb_reg_t &r, const mm2gb_anchor_t *a, int32_t *as, int32_t *cnt)
+{
+	*as = r.as; *cnt = r.cnt;
+	if (r.cnt < 2) return;
+	int32_t i, max_score = -1, max_i = -1, max_len = 0, score = aspan(a[r.as]), len = 1;
+	for (i = r.as + 1; i < r.as + r.cnt; ++i) {
+		const int32_t q_span = aspan(a[i]), lr = ax(a[i]) - ax(a[i - 1]), lq = ay(a[i]) - ay(a[i - 1]);
+		if (lq == lr) { score += lq < q_span ? lq : q_span; ++len; }
+		else {
+			if (score > max_score) { max_score = score; max_len = len; max_i = i - len; }
+			score = q_span; len = 1;
+		}
+	}
+	if (score > max_score) { max_len = len; max_i = i - len; }
+	*as = max_i; *cnt = max_len;
+}
+
+// ---- plan_chain under MM_F_SR (the is_sr branches of align.c:592-597, 623-630, 724-731): the stretch, the whole read as the query's bounds, the target's from what
+//      end_bonus lets an extension pay for, and ONE fill over the stretch, marked ungapped: its first pass is not a DP (the backends) ----
+bool plan_chain_sr(const AlCtx &c, Read &R, const Reg &g, Plan &P)
+{
+	const mm2gb_align_opt_t &o = c.opt;
+	const mm2gb_reg_t &r = g.r;
+	if (r.cnt == 0) return false;
+	const mm2gb_anchor_t *a = R.a.data();
+	const int32_t rid = (int32_t)(a[r.as].x << 1 >> 33), rev = (int32_t)(a[r.as].x >> 63), ref_len = (int32_t)(c.ref_at[(size_t)rid + 1] - c.ref_at[(size_t)rid]), qlen = R.qlen;
+	int32_t as1, cnt1, l;
+	max_stretch(r, a, &as1, &cnt1);
+	if (cnt1 < r.cnt) ++R.srcnt[MM2GB_SR_N_STRETCH_SHORT];
+	const int32_t rs = ax(a[as1]) + 1 - aspan(a[as1]), qs = ay(a[as1]) + 1 - aspan(a[as1]), re = ax(a[as1 + cnt1 - 1]) + 1, qe = ay(a[as1 + cnt1 - 1]) + 1;
+	int32_t rs0, re0, qs0 = 0, qe0 = qlen;
+	l = qs;
+	l += l * o.a + o.end_bonus > o.q ? (l * o.a + o.end_bonus - o.q) / o.e : 0;
+	rs0 = rs - l > 0 ? rs - l : 0;
+	l = qlen - qe;
+	l += l * o.a + o.end_bonus > o.q ? (l * o.a + o.end_bonus - o.q) / o.e : 0;
+	re0 = re + l < ref_len ? re + l : ref_len;
+	if (a[r.as].y & SEED_SELF) {
+		int max_ext = r.qs > r.rs ? r.qs - r.rs : r.rs - r.qs;
+		if (r.rs - rs0 > max_ext) rs0 = r.rs - max_ext;
+		if (r.qs - qs0 > max_ext) qs0 = r.qs - max_ext;
+		max_ext = r.qe > r.re ? r.qe - r.re : r.re - r.qe;
+		if (re0 - r.re > max_ext) re0 = r.re + max_ext;
+		if (qe0 - r.qe > max_ext) qe0 = r.qe + max_ext;
+	}
+	P.as1 = as1; P.cnt1 = cnt1; P.rid = rid; P.rev = rev; P.rs = rs; P.qs = qs; P.re = re; P.qe = qe; P.rs0 = rs0; P.qs0 = qs0; P.re0 = re0; P.qe0 = qe0;
+	P.left = P.right = -1;
+	P.fills.clear();
+	if (rev) ++R.cnt[MM2GB_ALN_N_REV_CHAIN];
+	const int first = (int)R.runs.size();
+	if (qs > 0 && rs > 0) {
+		P.left = (int)R.runs.size();
+		if (rs0 == 0) ++R.cnt[MM2GB_ALN_N_LEFT_AT_0];
+		R.runs.push_back(make_run(c, R, rid, rev, qs0, qs - qs0, rs0, rs - rs0, 1, 0, c.bw, (g.r.flags & RF_SPLIT_INV) ? o.zdrop_inv : o.zdrop, o.end_bonus,
+		                          MM2GB_KSW_EXTZ_ONLY | MM2GB_KSW_RIGHT | MM2GB_KSW_REV_CIGAR));
+	}
+	{
+		int bw1 = c.bw_long;
+		if (a[as1 + cnt1 - 1].y & SEED_LONG_JOIN) bw1 = qe - qs > re - rs ? qe - qs : re - rs;
+		P.fills.push_back({ rs, qs, re, qe, cnt1 - 1, (int)R.runs.size() });
+		R.runs.push_back(make_run(c, R, rid, rev, qs, qe - qs, rs, re - rs, 0, 1, bw1, o.zdrop, -1, MM2GB_KSW_APPROX_MAX));      // (the flag is the second pass's, less al_second_flag's bit)
+		R.runs.back().ungapped = 1;
+	}
+	if (qe < qe0 && re < re0) {
+		P.right = (int)R.runs.size();
+		R.runs.push_back(make_run(c, R, rid, rev, qe, qe0 - qe, re, re0 - re, 0, 2, c.bw, o.zdrop, o.end_bonus, MM2GB_KSW_EXTZ_ONLY));
+	}
+	P.n_runs = (int)R.runs.size() - first; P.trials = 1;
+	return true;
+}
+
 // ---- mg_log2 (mmpriv.h:118-126) ----
 inline float mg_log2(float x)
 {
@@ -482,7 +555,7 @@ void fix_cigar(Read &R, Reg &g, FQ Q, FT T, int *qshift, int *tshift)
 	cg.resize(n_cigar);
 }
 
-// ---- mm_update_extra (align.c:240-289), log_gap on, no =/X ----
+// ---- mm_update_extra (align.c:240-289), no =/X; log_gap off under MM_F_SR (align.c:819) ----
 template <class FQ, class FT>
 void update_extra(const AlCtx &c, Read &R, Reg &g, FQ Q0, FT T0)
 {
@@ -515,7 +588,8 @@ void update_extra(const AlCtx &c, Read &R, Reg &g, FQ Q0, FT T0)
 			for (int l = 0; l < len; ++l)
 				if ((op == 1 ? Q(qoff + l) : T(toff + l)) > 3) ++n_ambi;
 			r.blen += len - n_ambi; g.n_ambi += n_ambi;
-			s -= q + (double)e * mg_log2((float)(1.0 + len));
+			if (c.sr) s -= q + e;
+			else s -= q + (double)e * mg_log2((float)(1.0 + len));
 			if (s < 0) s = 0;
 			if (op == 1) qoff += len; else toff += len;
 		} else if (op == 3) toff += len;
@@ -673,8 +747,9 @@ bool stitch_chain(const AlCtx &c, Read &R, Reg &g, const Plan &P, const AlRun *r
 		++used;
 		re1 = f.re; qe1 = f.qe;
 		++R.cnt[x.code ? MM2GB_ALN_N_FILL_TWO_PASS : MM2GB_ALN_N_FILL_ONE_PASS];
+		if (x.ungapped) ++R.srcnt[x.code ? MM2GB_SR_N_FILL_RERUN : MM2GB_SR_N_FILL_UNGAPPED];
 		if (x.code == 2) ++R.cnt[MM2GB_ALN_N_INV_PROBE_HIT];
-		if (al_too_big(c, x.j)) { ++R.cnt[MM2GB_ALN_N_OVER_SW_MAT]; ++R.scnt[MM2GB_SPL_N_OVER_SW_MAT]; }
+		if (al_too_big(c, x.j) && (!x.ungapped || x.code)) { ++R.cnt[MM2GB_ALN_N_OVER_SW_MAT]; ++R.scnt[MM2GB_SPL_N_OVER_SW_MAT]; }
 		if (c.splice) { if (x.code) ++R.scnt[MM2GB_SPL_N_FILL_TWO_PASS]; if (has_intron(x, pool)) ++R.scnt[MM2GB_SPL_N_FILL_INTRON]; }
 		append_cigar(R, g, x, pool);
 		if (x.res.zdropped) {
@@ -877,7 +952,7 @@ int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, int nt, doub
 			for (Reg &g : R.regs) {
 				if (g.state == ST_FRESH) {
 					Plan P;
-					if (plan_chain(c, R, g, P, K)) { g.plan = (int)R.plans.size(); R.plans.push_back(std::move(P)); g.state = ST_PENDING; }
+					if (c.sr ? plan_chain_sr(c, R, g, P) : plan_chain(c, R, g, P, K)) { g.plan = (int)R.plans.size(); R.plans.push_back(std::move(P)); g.state = ST_PENDING; }
 					else g.state = ST_DONE;
 				} else if (g.state == ST_INV_FRESH) { g.plan = (int)R.runs.size(); R.runs.push_back(g.inv); g.state = ST_INV_PENDING; }
 			}
@@ -889,6 +964,8 @@ int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, int nt, doub
 		for (const AlRun &x : runs)           // nothing is read outside a sequence, on either side of the link
 			if ((x.j.qlen > 0 && (x.j.q0 < 0 || x.j.q0 + x.j.qlen > x.j.qn)) || (x.j.tlen > 0 && (x.j.t0 < 0 || x.j.t0 + x.j.tlen > x.j.tn)))
 				return fail("mm2gb_align_regs: a stretch leaves its sequence (anchors and sequences do not belong together)");
+		for (const AlRun &x : runs)           // align.c:745 asserts it
+			if (x.ungapped && (x.j.qlen != x.j.tlen || x.j.qlen < 0)) return fail("mm2gb_align_regs_sr: a stretch's two sides differ in length (anchors that do not lie on one diagonal in ascending order)");
 		pool.clear();
 		if (be.run(c, runs, pool)) return -1;
 		t0 = clk::now();
@@ -921,7 +998,7 @@ int drive(const AlCtx &c, std::vector<Read*> &reads, AlBackend &be, int nt, doub
 	for_each_on_threads(reads.size(), nt, 1, [&](size_t k) {
 		Read &R = *reads[k];
 		filter_regs(c, R);
-		if (R.qlen >= c.opt.rank_min_len) { update_dp_max(c, R); filter_regs(c, R); }
+		if (!c.sr && R.qlen >= c.opt.rank_min_len) { update_dp_max(c, R); filter_regs(c, R); }          // align.c:1014
 		hit_sort(R);
 		if (R.rounds >= 3) ++R.cnt[MM2GB_ALN_N_READS_3_ROUNDS];
 	});
@@ -939,12 +1016,26 @@ struct HostBackend : AlBackend {
 		for (AlRun &x : runs) {
 			const int qlen = std::max(x.j.qlen, 0), tlen = std::max(x.j.tlen, 0);
 			x.code = 0;
-			if (al_too_big(c, x.j)) { ksw_store(reset, 0, &x.res); x.res.zdropped = 1; continue; }
+			if (al_too_big(c, x.j) && !x.ungapped) { ksw_store(reset, 0, &x.res); x.res.zdropped = 1; continue; }
 			q.resize((size_t)qlen); t.resize((size_t)tlen);
 			for (int k = 0; k < qlen; ++k) q[(size_t)k] = al_query(c.reads.data(), x.j, k);
 			for (int k = 0; k < tlen; ++k) t[(size_t)k] = al_target(c.refs.data(), x.j, k);
 			mm2gb_ksw_job_t job = { 0, 0, qlen, tlen, x.w, x.zdrop, x.end_bonus, x.flag };
 			size_t at = pool.size();
+			if (x.ungapped) {             // align.c:744-757: the one-word first pass, the walk, and the DP only where it drops
+				KswEz z = reset;
+				z.score = 0;
+				for (int k = 0; k < qlen; ++k) z.score += al_ungapped_score(c.opt.a, c.opt.b, c.opt.e2, t[(size_t)k], q[(size_t)k]);
+				const uint32_t word = (uint32_t)qlen << 4;
+				const AlDrop d = al_drop_walk(1, [&](int) { return word; }, [&](int k) { return (int)q[(size_t)k]; }, [&](int k) { return (int)t[(size_t)k]; }, c.a, c.b, c.ambi, c.opt.q, c.opt.e);
+				x.code = al_zdrop_code(c, x.j, d);
+				if (!x.code) { ksw_store(z, 1, &x.res); pool.push_back(word); x.res.cigar_off = (int64_t)at; continue; }
+				if (al_too_big(c, x.j)) { ksw_store(reset, 0, &x.res); x.res.zdropped = 1; continue; }
+				job.flag = al_second_flag(x.flag);
+				ksw_one_host(c.kc, job, q.data(), t.data(), &x.res, pool);
+				x.res.cigar_off = (int64_t)at;
+				continue;
+			}
 			ksw_one_host(c.kc, job, q.data(), t.data(), &x.res, pool);
 			x.res.cigar_off = (int64_t)at;
 			if (x.j.kind != 1) continue;
@@ -968,7 +1059,7 @@ int al_zdrop_code(const AlCtx &c, const AlJob &j, const AlDrop &d)
 {
 	const mm2gb_align_opt_t &o = c.opt;
 	const int q_len = d.q_to - d.q_from, t_len = d.t_to - d.t_from;
-	if (!(o.flag & (MM2GB_F_SPLICE | MM2GB_F_FOR_ONLY | MM2GB_F_REV_ONLY)) && d.max_zdrop > o.zdrop_inv && q_len < o.max_gap && t_len < o.max_gap) {
+	if (!(o.flag & (MM2GB_F_SPLICE | MM2GB_F_SR | MM2GB_F_FOR_ONLY | MM2GB_F_REV_ONLY)) && d.max_zdrop > o.zdrop_inv && q_len < o.max_gap && t_len < o.max_gap) {
 		std::vector<uint8_t> q2((size_t)std::max(q_len, 0)), ts((size_t)std::max(t_len, 0));
 		for (int i = 0; i < q_len; ++i) { const uint8_t x = al_query(c.reads.data(), j, d.q_to - i - 1); q2[(size_t)i] = x >= 4 ? 4 : 3 - x; }
 		for (int i = 0; i < t_len; ++i) ts[(size_t)i] = al_target(c.refs.data(), j, d.t_from + i);
@@ -992,12 +1083,13 @@ void pack_residues(int32_t n_ref, const char *const *ref_seqs, const int32_t *re
 
 int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                   int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts, bool single)
+                  const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts, bool single, int64_t *sr_counts, bool sr)
 {
 	const std::string who = who_;
 	if (!out) return fail(who + ": null argument");
 	memset(out, 0, sizeof *out);
 	if (splice_counts) memset(splice_counts, 0, MM2GB_SPL_N_COUNTS * 8);
+	if (sr_counts) memset(sr_counts, 0, MM2GB_SR_N_COUNTS * 8);
 	mm2gb_align_opt_t opt_own;
 	const mm2gb_align_opt_t *opt = opt_;
 	if (spl && opt_) {            // options.c:70-71: either strand flag implies MM_F_SPLICE
@@ -1007,7 +1099,11 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_a
 	}
 	if (!opt || n_reads < 0 || n_ref < 0 || (n_ref > 0 && (!ref_seqs || !ref_lens)) || (n_reads > 0 && (!read_seqs || !read_lens || !reg_off || !anchor_off))) return fail(who + ": null argument");
 	static const struct { int64_t bit; const char *name; } refused[] = { { MM2GB_F_SPLICE, "MM_F_SPLICE" }, { MM2GB_F_SR, "MM_F_SR" }, { MM2GB_F_QSTRAND, "MM_F_QSTRAND" }, { MM2GB_F_EQX, "MM_F_EQX" } };
-	for (const auto &x : refused) if ((opt->flag & x.bit) && !(spl && x.bit == MM2GB_F_SPLICE)) return fail(who + ": " + x.name + " is not supported");
+	for (const auto &x : refused) if ((opt->flag & x.bit) && !(spl && x.bit == MM2GB_F_SPLICE) && !(sr && x.bit == MM2GB_F_SR)) return fail(who + ": " + x.name + " is not supported");
+	if (sr) {
+		if (!(opt->flag & MM2GB_F_SR)) return fail(who + ": the flag word lacks MM_F_SR (the calls without _sr align other reads)");
+		if (idx_flag & MM2GB_I_HPC) return fail(who + ": an index with MM2GB_I_HPC is not supported (align.c:583)");
+	}
 	mm2gb_ksw_splice_param_t sp;
 	if (spl) {
 		if (!(opt->flag & MM2GB_F_SPLICE)) return fail(who + ": the flag word lacks MM_F_SPLICE (the calls without _splice align unspliced reads)");
@@ -1054,6 +1150,7 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_a
 		kp.m = 5; memcpy(kp.mat, c.mat, 25); kp.q = (int8_t)opt->q; kp.e = (int8_t)opt->e; kp.q2 = (int8_t)opt->q2; kp.e2 = (int8_t)opt->e2;
 		c.kc = single ? ksw_derive_single(kp) : ksw_derive(kp);          // align.c:331; nothing else of the call reads q2 or e2
 	}
+	c.sr = sr;
 	c.n_ref = n_ref; c.n_reads = n_reads;
 	const int nt = std::min(n_threads, 256);
 	pack_residues(n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, nt, c.ref_at, c.read_at, c.refs, c.reads);
@@ -1108,6 +1205,7 @@ int al_align_regs(const char *who_, const mm2gb_align_opt_t *opt_, const mm2gb_a
 			else out->counts[k2] += R[(size_t)r].cnt[k2];
 		}
 		if (splice_counts) for (int k2 = 0; k2 < MM2GB_SPL_N_COUNTS; ++k2) splice_counts[k2] += R[(size_t)r].scnt[k2];
+		if (sr_counts) for (int k2 = 0; k2 < MM2GB_SR_N_COUNTS; ++k2) sr_counts[k2] += R[(size_t)r].srcnt[k2];
 	}
 	out->reg_off[n_reads] = nr;
 	out->n_regs = n_regs; out->n_cigar = n_cigar;
@@ -1177,16 +1275,16 @@ int mm2gb_align_splice_opt_init(mm2gb_align_splice_opt_t *opt, const char *prese
 
 int mm2gb::al_align_regs_host(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
                               const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts, bool single)
+                              const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts, bool single, int64_t *sr_counts, bool sr)
 {
 	// MM2GB_ALIGN_ROUNDS=batch (read at every call): the device form's schedule -- every read in one sequence of rounds, planning and stitching on
 	// n_threads threads -- with the host DP behind it; the same bytes come out.  For checking that schedule where there is no device.
 	const char *mode = getenv("MM2GB_ALIGN_ROUNDS");
 	if (mode && !strcmp(mode, "batch")) {
 		HostBackend be;
-		return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, &be, out, splice_counts, single);
+		return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, &be, out, splice_counts, single, sr_counts, sr);
 	}
-	return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, nullptr, out, splice_counts, single);
+	return al_align_regs(who, opt, spl, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, nullptr, out, splice_counts, single, sr_counts, sr);
 }
 
 int mm2gb_align_regs_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
@@ -1209,6 +1307,22 @@ int mm2gb_align_regs_extz_host(const mm2gb_align_opt_t *opt, int k, int idx_flag
                                const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out)
 {
 	return al_align_regs_host("mm2gb_align_regs_extz_host", opt, nullptr, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, out, nullptr, true);
+}
+
+void mm2gb_align_sr_opt_init(mm2gb_align_opt_t *o)          // options.c:14-66, then 133-150
+{
+	memset(o, 0, sizeof *o);
+	o->flag = MM2GB_F_SR | MM2GB_F_FRAG_MODE | MM2GB_F_NO_PRINT_2ND | MM2GB_F_HEAP_SORT;
+	o->min_cnt = 2; o->min_chain_score = 25; o->bw = o->bw_long = 100; o->max_gap = 100;
+	o->a = 2; o->b = 8; o->q = 12; o->e = 2; o->q2 = 24; o->e2 = 1; o->sc_ambi = 1; o->zdrop = o->zdrop_inv = 100; o->end_bonus = 10; o->min_dp_max = 40; o->min_ksw_len = 200;
+	o->max_clip_ratio = 1.0f; o->max_sw_mat = 100000000; o->rank_min_len = 500; o->rank_frac = 0.9f;
+}
+
+int mm2gb_align_regs_sr_host(const mm2gb_align_opt_t *opt, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
+                             int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                             const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *sr_counts)
+{
+	return al_align_regs_host("mm2gb_align_regs_sr_host", opt, nullptr, k, idx_flag, n_ref, ref_seqs, ref_lens, n_reads, read_seqs, read_lens, reg_off, regs, anchor_off, anchors, n_threads, out, nullptr, false, sr_counts, true);
 }
 
 void mm2gb_align_out_free(mm2gb_align_out_t *out)

@@ -12,6 +12,7 @@ struct AlCtx {
 	int k = 0, idx_flag = 0, a = 0, b = 0, ambi = 0, bw = 0, bw_long = 0;      // a, b, ambi: positive; bw, bw_long: mm_align1's (align.c:588-590)
 	int8_t mat[25];
 	KswConst kc;
+	bool sr = false;                           // the short-read form: plan_chain_sr, ungapped first-pass fills, no log-gap term, no update_dp_max
 	bool splice = false;                       // the spliced form: kc is ksw_exts2's, and the four numbers below are read
 	int noncan = 0, junc_bonus = 0, anchor_ext_len = 0, anchor_ext_shift = 0;
 	int32_t n_ref = 0;
@@ -49,6 +50,7 @@ struct AlRun {
 	int32_t twin;                      // above 0: the job `twin` places before this one IN THE ROUND'S ARRAY has the same two stretches (a chain's second trial) and the
 	                                   // device backend uses its bytes.  Holds because a read's jobs enter the round's array contiguous and in plan_chain's order (drive());
 	                                   // whoever reorders a round's jobs (a sort by size, say) must carry the link along or the second trial reads another job's bytes
+	int32_t ungapped;                  // the short-read form's fill: the first pass is the one-word ungapped alignment (align.c:744-751), not a DP; w, zdrop and flag are the second pass's
 	int32_t code;                      // gap fills: mm_test_zdrop's answer for the first pass (0, 1, 2); a second pass ran when it is not 0
 	mm2gb_ksw_res_t res;               // of the pass that counts; res.cigar_off: where its words lie in the round's pool
 };
@@ -73,10 +75,12 @@ int  al_zdrop_code(const AlCtx &ctx, const AlJob &j, const AlDrop &d);
 // single: the _extz calls, which take q == q2 && e == e2 and nothing else, and run the single-affine DP
 int  al_align_regs(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens,
                    int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                   const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts, bool single = false);
+                   const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, AlBackend *whole_batch, mm2gb_align_out_t *out, int64_t *splice_counts, bool single = false,
+                   int64_t *sr_counts = nullptr, bool sr = false);          // sr: the _sr calls (MM_F_SR), with their counts
 // MM2GB_ALIGN_ROUNDS=batch (read at every call): the host forms run the device form's schedule with the host DP behind it
 int  al_align_regs_host(const char *who, const mm2gb_align_opt_t *opt, const mm2gb_align_splice_opt_t *spl, int k, int idx_flag, int32_t n_ref, const char *const *ref_seqs,
                         const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens, const int64_t *reg_off, const mm2gb_reg_t *regs,
-                        const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts, bool single = false);
+                        const int64_t *anchor_off, const mm2gb_anchor_t *anchors, int n_threads, mm2gb_align_out_t *out, int64_t *splice_counts, bool single = false,
+                        int64_t *sr_counts = nullptr, bool sr = false);
 
 } // namespace mm2gb

@@ -97,6 +97,7 @@ struct Engine {
 	int64_t cap_post_n = 0, cap_post_reads = 0;
 	DevBuf post_dbg_tasks, post_dbg_stasks, rmq_dbg_reads, rmq_skey_in, rmq_skey, rmq_sa, rmq_srange, rmq_sort_tmp, post_z, post_fp, post_picked, post_utmp, post_heads, post_nu, post_nkept, post_misc, post_bins, post_order, post_up4, post_up16, post_sort_s, post_sort_perm, post_sort_tmp, post_cls, post_cls_cnt, post_cls_nz, post_read_nz, post_uloc, post_wtask, post_stask, rmq_tied, rmq_sum, rmq_by_y, rmq_ord, rmq_meta, rmq_win, rmq_tree, reg_out;
 	DevBuf sd_seeds, sd_seed_off, sd_hit_off, sd_hits, sd_qlen, sd_q_rank, sd_ref_len, sd_ref_rank, sd_seed_read, sd_tmp, sd_n_kept, sd_a_off, sd_out;   // mm2gb_collect_seeds_gpu
+	DevBuf sh_ord, sh_keys, sh_long, sh_sort_tmp, sh_tied;   // mm2gb_collect_seeds_heap_gpu (seed_heap_kernels.hip): the sorted order, the long reads' keys, ranges and sort space, the tie flags
 	// sequence bytes -> matches on the device (seed_kernels.hip; mm2gb_sketch_gpu, mm2gb_collect_matches_gpu): the sequences, their offsets and
 	// ids, the minimizers with their reads and offsets, one arena for the work arrays of either stage, what the host's mapq / divergence code wants
 	DevBuf sk_seqs, sk_seq_off, sk_rid, sk_mini, sk_mini_read, sk_mini_off, sk_work, sd_src_first, sd_mini_pos, sd_rep_len;
@@ -196,8 +197,16 @@ struct Engine {
 	int  chain_gpu_sliced(int64_t n_reads, const int64_t *offsets, const mm2gb_anchor_t *anchors, mm2gb_chains_t *out, int64_t slice);
 	int  collect_seeds(int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off, const uint64_t *hits,
 	                   const int32_t *qlen, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors);
+	// collect_seed_hits_heap (seed_heap_kernels.hip): as collect_seeds in the heap's order; reads with two equal cr are done again by the host form
+	int  collect_seeds_heap(int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off, const uint64_t *hits,
+	                        const int32_t *qlen, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads);
 	// the minimizers of sequences laid end to end, left in sk_mini / sk_mini_read / sk_mini_off (arguments checked by the callers)
 	int  sketch_device(int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini);
+	// collect_seeds_heap on the matches collect_matches_device left resident (the short-read mapper seeded on the device)
+	int  heap_order_on_device(const char *who, int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off,
+	                          const uint64_t *hits, const int32_t *qlen, bool names, const int32_t *q_rank, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off,
+	                          mm2gb_anchor_t *anchors, int64_t *n_tied_reads);      // what the two share, on matches that lie on the device
+	int  collect_seeds_heap_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads);
 	// mm_collect_matches for a batch, left in sd_seeds / sd_seed_off / sd_hit_off / sd_hits (+ sd_qlen, sd_mini_pos, sd_rep_len)
 	int  collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits);
 	// launch_collect_seeds on what collect_matches_device left; q_rank / ref_rank / ref_len as for collect_seeds (null: no name tests).  anchors null: the anchors

@@ -16,6 +16,7 @@
 #include "engine.h"
 #include "est_err.h"
 #include "host_chain.h"
+#include "seed_heap.h"
 
 namespace mm2gb {
 
@@ -516,6 +517,7 @@ void Engine::shutdown()
 	slice_in.clear();
 	for (DevBuf *b : { &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
+	                   &sh_ord, &sh_keys, &sh_long, &sh_sort_tmp, &sh_tied,
 	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
 	                   &ee_reg_off, &ee_a_off, &ee_a, &ee_qlen, &ee_mini_off, &ee_mini, &ee_ref_len, &ee_hash, &ee_reg_read, &ee_literal, &ee_out, &ee_sum_k,
 	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack, &kw_junc,
@@ -1137,6 +1139,136 @@ int Engine::collect_seeds(int64_t opt_flag, int64_t n_reads, const int64_t *seed
 	return 0;
 }
 
+// collect_seed_hits_heap (map.c:229-293) for every read of a batch: matches in, anchors in the heap's order out.  The kernels order a read's hits by (cr, seed, k),
+// which is the heap's order wherever a read's cr are distinct; a read with two equal cr comes back flagged and is done again here by the host form.
+int Engine::collect_seeds_heap(int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off, const uint64_t *hits,
+                               const int32_t *qlen, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors,
+                               int64_t *n_tied_reads)
+{
+	constexpr int64_t F_NO_DIAG = 0x001, F_NO_DUAL = 0x002, F_QSTRAND = 0x100000000LL;
+	if (n_tied_reads) *n_tied_reads = 0;
+	if (opt_flag & F_QSTRAND) return fail("mm2gb_collect_seeds_heap_gpu: MM_F_QSTRAND is not supported (collect_seed_hits_heap has no such branch)");
+	if (n_reads < 0 || !seed_off || !anchor_off || seed_off[0] != 0) return fail("mm2gb_collect_seeds_heap_gpu: seed_off[0] must be 0");
+	anchor_off[0] = 0;
+	if (n_reads == 0) return 0;
+	for (int64_t r = 0; r < n_reads; ++r) if (seed_off[r + 1] < seed_off[r]) return fail("mm2gb_collect_seeds_heap_gpu: seed_off must be non-decreasing");
+	const int64_t n_seeds = seed_off[n_reads];
+	if (!qlen || !hit_off || (n_seeds > 0 && !seeds) || hit_off[0] != 0) return fail("mm2gb_collect_seeds_heap_gpu: null argument, or hit_off[0] is not 0");
+	for (int64_t k = 0; k < n_seeds; ++k) if (hit_off[k + 1] - hit_off[k] != (int64_t)seeds[k].n) return fail("mm2gb_collect_seeds_heap_gpu: hit_off does not match the seeds' hit counts");
+	const int64_t n_hits = hit_off[n_seeds];
+	if (n_hits >= ((int64_t)1 << 31)) return fail("mm2gb_collect_seeds_heap_gpu: a batch is limited to 2^31 hits");
+	const bool names = (opt_flag & (F_NO_DIAG | F_NO_DUAL)) != 0 && q_rank != nullptr;
+	if (names && (!ref_rank || n_ref <= 0)) return fail("mm2gb_collect_seeds_heap_gpu: NO_DIAG / NO_DUAL need ref_rank");
+	if (names && (opt_flag & F_NO_DIAG) && !ref_len) return fail("mm2gb_collect_seeds_heap_gpu: NO_DIAG needs ref_len");
+	if (n_hits == 0) { for (int64_t r = 0; r < n_reads; ++r) anchor_off[r + 1] = 0; return 0; }
+	if (!hits || !anchors) return fail("mm2gb_collect_seeds_heap_gpu: null buffer");
+	if (names)
+		for (int64_t h = 0; h < n_hits; ++h) if ((int64_t)(hits[h] >> 32) >= n_ref) return fail("mm2gb_collect_seeds_heap_gpu: a hit names a reference sequence >= n_ref");
+	MM2GB_HIP(hipSetDevice(device));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	const size_t nr = (size_t)n_reads, ns = (size_t)std::max<int64_t>(n_seeds, 1), nh = (size_t)n_hits, nf = (size_t)std::max<int32_t>(n_ref, 1);
+	if (sd_seeds.ensure(ns * 16) || sd_seed_off.ensure((nr + 1) * 8) || sd_hit_off.ensure((ns + 1) * 8) || sd_hits.ensure(nh * 8) || sd_qlen.ensure(nr * 4) ||
+	    sd_q_rank.ensure(nr * 4) || sd_ref_len.ensure(nf * 4) || sd_ref_rank.ensure(nf * 4)) return -1;
+	MM2GB_HIP(hipMemcpyAsync(sd_seeds.ptr, seeds, (size_t)n_seeds * 16, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(sd_seed_off.ptr, seed_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(sd_hit_off.ptr, hit_off, (size_t)(n_seeds + 1) * 8, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(sd_hits.ptr, hits, nh * 8, hipMemcpyHostToDevice, stream));
+	MM2GB_HIP(hipMemcpyAsync(sd_qlen.ptr, qlen, nr * 4, hipMemcpyHostToDevice, stream));
+	if (names) MM2GB_HIP(hipMemcpyAsync(sd_q_rank.ptr, q_rank, nr * 4, hipMemcpyHostToDevice, stream));
+	if (names && ref_len) MM2GB_HIP(hipMemcpyAsync(sd_ref_len.ptr, ref_len, (size_t)n_ref * 4, hipMemcpyHostToDevice, stream));
+	if (names) MM2GB_HIP(hipMemcpyAsync(sd_ref_rank.ptr, ref_rank, (size_t)n_ref * 4, hipMemcpyHostToDevice, stream));
+	return heap_order_on_device("mm2gb_collect_seeds_heap_gpu", opt_flag, n_reads, n_seeds, n_hits, seed_off, seeds, hit_off, hits, qlen, names, q_rank, ref_len, ref_rank, anchor_off, anchors, n_tied_reads);
+}
+
+// What both forms of the heap-order collection share, on matches that lie in sd_seeds / sd_seed_off / sd_hit_off / sd_hits / sd_qlen (and, with names, the three rank
+// arrays): the long reads' ranges, the kernels, offsets and anchors back, and the flagged reads again by the host form.  seed_off, seeds, hit_off, qlen: the host's
+// copies of the device arrays; hits: the host's copy, or null -- then the hits are fetched once, and only where a read is flagged.
+int Engine::heap_order_on_device(const char *who_, int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, const int64_t *seed_off, const mm2gb_seed_t *seeds, const int64_t *hit_off,
+                                 const uint64_t *hits, const int32_t *qlen, bool names, const int32_t *q_rank, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off,
+                                 mm2gb_anchor_t *anchors, int64_t *n_tied_reads)
+{
+	const std::string who = who_;
+	std::vector<int64_t> long_range;                     // the long reads' begins, then their ends
+	for (int pass = 0; pass < 2; ++pass)
+		for (int64_t r = 0; r < n_reads; ++r) {
+			const int64_t h0 = hit_off[seed_off[r]], h1 = hit_off[seed_off[r + 1]];
+			if (h1 - h0 > HEAP_WAVE_HITS) long_range.push_back(pass ? h1 : h0);
+		}
+	const int64_t n_long = (int64_t)long_range.size() / 2;
+	const size_t nr = (size_t)n_reads, nh = (size_t)n_hits;
+	const size_t sort_bytes = heap_sort_tmp_bytes(n_hits, n_long, n_reads);
+	if (sd_tmp.ensure(nh * 16) || sd_n_kept.ensure(nr * 4) || sd_a_off.ensure((nr + 1) * 8) || sd_out.ensure(nh * 16) || sh_ord.ensure(nh * 4) || sh_keys.ensure(n_long ? nh * 8 : 8) ||
+	    sh_long.ensure(std::max<size_t>((size_t)n_long * 16, 16)) || sh_sort_tmp.ensure(std::max<size_t>(sort_bytes, 16)) || sh_tied.ensure(nr * 4)) return -1;
+	if (n_long) MM2GB_HIP(hipMemcpyAsync(sh_long.ptr, long_range.data(), (size_t)n_long * 16, hipMemcpyHostToDevice, stream));
+	HeapBatch hb;
+	hb.seeds = (const SeedRecord*)sd_seeds.ptr; hb.seed_off = (const int64_t*)sd_seed_off.ptr; hb.hit_off = (const int64_t*)sd_hit_off.ptr;
+	hb.hits = (const unsigned long long*)sd_hits.ptr; hb.qlen = (const int32_t*)sd_qlen.ptr; hb.q_rank = names ? (const int32_t*)sd_q_rank.ptr : nullptr;
+	hb.ref_len = names && ref_len ? (const int32_t*)sd_ref_len.ptr : nullptr; hb.ref_rank = names ? (const int32_t*)sd_ref_rank.ptr : nullptr;
+	hb.n_reads = n_reads; hb.n_seeds = n_seeds; hb.n_hits = n_hits; hb.flag = (long long)opt_flag;
+	hb.ord = (uint32_t*)sh_ord.ptr; hb.keys = (unsigned long long*)sh_keys.ptr;
+	hb.long_begin = (const int64_t*)sh_long.ptr; hb.long_end = (const int64_t*)sh_long.ptr + n_long; hb.n_long = n_long;
+	hb.sort_tmp = sh_sort_tmp.ptr; hb.sort_tmp_bytes = sort_bytes;
+	hb.tmp = (ulonglong2*)sd_tmp.ptr; hb.n_kept = (int32_t*)sd_n_kept.ptr; hb.tied = (int32_t*)sh_tied.ptr;
+	hb.anchor_off = (int64_t*)sd_a_off.ptr; hb.out = (ulonglong2*)sd_out.ptr; hb.grid_waves = n_cu * 32;
+	if (launch_collect_seeds_heap(hb, stream)) return fail(who + ": a library sort or scan refused to run");
+	MM2GB_HIP(hipGetLastError());
+	std::vector<int32_t> tied(nr);
+	MM2GB_HIP(hipMemcpyAsync(anchor_off, sd_a_off.ptr, (nr + 1) * 8, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipMemcpyAsync(tied.data(), sh_tied.ptr, nr * 4, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (anchor_off[n_reads] < 0 || anchor_off[n_reads] > n_hits) return fail(who + ": the device's offsets do not add up");
+	if (anchor_off[n_reads] > 0) { MM2GB_HIP(hipMemcpyAsync(anchors, sd_out.ptr, (size_t)anchor_off[n_reads] * 16, hipMemcpyDeviceToHost, s_out)); MM2GB_HIP(hipStreamSynchronize(s_out)); }
+	// the tied reads again, by the definition: what is skipped does not depend on the order, so a read's anchors keep their place and number
+	int64_t n_tied = 0;
+	for (int32_t f : tied) if (f) ++n_tied;
+	std::vector<uint64_t> fetched;
+	if (n_tied && !hits) {
+		fetched.resize(nh);
+		MM2GB_HIP(hipMemcpyAsync(fetched.data(), sd_hits.ptr, nh * 8, hipMemcpyDeviceToHost, stream));
+		MM2GB_HIP(hipStreamSynchronize(stream));
+		hits = fetched.data();
+	}
+	std::vector<mm2gb_anchor_t> redo;
+	for (int64_t r = 0; n_tied && r < n_reads; ++r) {
+		if (!tied[(size_t)r]) continue;
+		redo.resize((size_t)(hit_off[seed_off[r + 1]] - hit_off[seed_off[r]]));
+		const int64_t n = collect_seeds_heap_read(opt_flag, seed_off[r + 1] - seed_off[r], seeds + seed_off[r], hit_off + seed_off[r], hits, qlen[r], names, names ? q_rank[r] : 0, ref_len, ref_rank,
+		                                          redo.data(), nullptr);
+		if (n != anchor_off[r + 1] - anchor_off[r]) return fail(who + ": host and device kept different numbers of a tied read's hits");
+		if (n > 0) memcpy(anchors + anchor_off[r], redo.data(), (size_t)n * sizeof(mm2gb_anchor_t));
+	}
+	if (n_tied_reads) *n_tied_reads = n_tied;
+	return 0;
+}
+
+// The same on the matches collect_matches_device left resident (the mapper's short-read path with seeding_on_device = 1): the kernels read seeds, offsets and hits where
+// they lie.  What comes down beside the anchors: the seed records and the two offset arrays (16 + 8 bytes per seed: the long reads' ranges come from them), and -- only
+// where a read is flagged -- the hits, once, for the host form's second go at the tied reads.  No names' ranks: read overlap does not come this way.
+int Engine::collect_seeds_heap_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads)
+{
+	if (n_tied_reads) *n_tied_reads = 0;
+	anchor_off[0] = 0;
+	if (n_reads == 0) return 0;
+	if (n_hits == 0) { for (int64_t r = 0; r < n_reads; ++r) anchor_off[r + 1] = 0; return 0; }
+	if (n_hits >= ((int64_t)1 << 31)) return fail("mm2gb_map_reads_sr: a batch seeded on the device is limited to 2^31 hits");
+	if (!anchors) return fail("mm2gb_map_reads_sr: null buffer");
+	MM2GB_HIP(hipSetDevice(device));
+	const size_t nr = (size_t)n_reads, ns = (size_t)std::max<int64_t>(n_seeds, 1);
+	std::vector<int64_t> seed_off(nr + 1), hit_off(ns + 1, 0);
+	std::vector<mm2gb_seed_t> seeds(ns);
+	std::vector<int32_t> qlen(nr);
+	MM2GB_HIP(hipMemcpyAsync(seed_off.data(), sd_seed_off.ptr, (nr + 1) * 8, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipMemcpyAsync(hit_off.data(), sd_hit_off.ptr, (size_t)(n_seeds + 1) * 8, hipMemcpyDeviceToHost, stream));
+	if (n_seeds > 0) MM2GB_HIP(hipMemcpyAsync(seeds.data(), sd_seeds.ptr, (size_t)n_seeds * 16, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipMemcpyAsync(qlen.data(), sd_qlen.ptr, nr * 4, hipMemcpyDeviceToHost, stream));
+	MM2GB_HIP(hipStreamSynchronize(stream));
+	if (seed_off[0] != 0 || seed_off[nr] != n_seeds || hit_off[0] != 0 || hit_off[(size_t)n_seeds] != n_hits) return fail("mm2gb_map_reads_sr: the device's matches do not add up");
+	for (int64_t r = 0; r < n_reads; ++r) if (seed_off[(size_t)r + 1] < seed_off[(size_t)r]) return fail("mm2gb_map_reads_sr: the device's matches do not add up");
+	for (int64_t k = 0; k < n_seeds; ++k) if (hit_off[(size_t)k + 1] - hit_off[(size_t)k] != (int64_t)seeds[(size_t)k].n) return fail("mm2gb_map_reads_sr: the device's matches do not add up");
+	return heap_order_on_device("mm2gb_map_reads_sr", opt_flag, n_reads, n_seeds, n_hits, seed_off.data(), seeds.data(), hit_off.data(), nullptr, qlen.data(), false, nullptr, nullptr, nullptr,
+	                            anchor_off, anchors, n_tied_reads);
+}
+
 // The minimizer sketch of a batch of sequences (seed_kernels.hip).  Two waits: for the number of pairs (the output is sized by it).
 int Engine::sketch_device(int w, int k, int flag, int64_t n_seqs, const int64_t *seq_off, const char *seqs, const uint32_t *rid, int64_t *n_mini)
 {
@@ -1715,6 +1847,13 @@ int mm2gb_rmq_chain_gpu(mm2gb_engine_t *eng, const mm2gb_rmq_param_t *prm, int64
 int mm2gb_sort_seeds_gpu(mm2gb_engine_t *eng, int64_t n_reads, const int64_t *offsets, mm2gb_anchor_t *anchors)
 {
 	return eng ? eng->e.sort_seeds(n_reads, offsets, anchors) : fail("mm2gb: null engine");
+}
+
+int mm2gb_collect_seeds_heap_gpu(mm2gb_engine_t *eng, int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds,
+                                 const int64_t *hit_off, const uint64_t *hits, const int32_t *qlen, const int32_t *q_rank,
+                                 int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads)
+{
+	return eng ? eng->e.collect_seeds_heap(opt_flag, n_reads, seed_off, seeds, hit_off, hits, qlen, q_rank, n_ref, ref_len, ref_rank, anchor_off, anchors, n_tied_reads) : fail("mm2gb: null engine");
 }
 
 int mm2gb_collect_seeds_gpu(mm2gb_engine_t *eng, int64_t opt_flag, int64_t n_reads, const int64_t *seed_off, const mm2gb_seed_t *seeds,

@@ -26,8 +26,13 @@
 //   The resident path (seeding_on_device = 2, no re-chaining stage, no MM_F_RMQ, no alignment; chain_resident, hit_records_resident): steps 2, 3 and 5 run on
 //   device pointers and mm_est_err's walk runs there too (est_err_kernels.hip), so no anchor crosses the link in either direction: what comes down is the
 //   offsets, the hit records, the walk's counts, sum_k and rep_len.
-// Not reproduced: more than one query segment, spliced mapping without base-level alignment, short-read alignment (sr), read overlap with base-level
-// alignment, junction annotation, --eqx, SAM output, ALT contigs, the heap variant of seed collection, --qstrand, multi-part indexes.
+//   Short single-end reads (mm2gb_map_reads_sr / _stream_sr with the options of mm2gb_map_opt_init_sr; minimap2 -x sr [-c]): stage 2 in the heap's order
+//   (collect_seed_hits_heap, map.c:229-293: seed_heap_host.cpp / seed_heap_kernels.hip; seeded on the device, from the matches resident there), stage 3 as one chaining
+//   call per distinct max_dist_x of the batch (the gaps depend on the read's length, map.c:678-686), the max_occ rescue of map.c:708-731 as one more batch, no stage 4,
+//   and in stage 6 no mm_est_err, the alignment call in its MM_F_SR form (mm2gb_align_regs_sr_*: ungapped fills), mm_set_mapq with is_sr = 1, no line
+//   for a secondary hit under MM_F_NO_PRINT_2ND (anchors_and_chains_sr, finish_reads_sr).
+// Not reproduced: more than one query segment (paired ends), spliced mapping without base-level alignment, read overlap with base-level alignment, junction
+// annotation, --eqx, SAM output, ALT contigs, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -199,8 +204,8 @@ void filter_strand_retained(std::vector<Hit> &r)
 	r.resize(k);
 }
 
-// hit.c:420-466 for long reads (is_sr = 0); match_sc: the alignment's match score, looked at only where a hit carries an alignment
-void set_mapq(std::vector<Hit> &r, int min_chain_sc, int rep_len, int match_sc = 1)
+// hit.c:420-466 (is_sr: hit.c:446-449 left out); match_sc: the alignment's match score, looked at only where a hit carries an alignment
+void set_mapq(std::vector<Hit> &r, int min_chain_sc, int rep_len, int match_sc = 1, bool is_sr = false)
 {
 	if (r.empty()) return;
 	int64_t sum_sc = 0;
@@ -219,8 +224,10 @@ void set_mapq(std::vector<Hit> &r, int min_chain_sc, int rep_len, int match_sc =
 			const float identity = (float)h.mlen / h.blen;
 			const float x = (float)h.dp_max2 * subsc / h.dp_max / h.score0;
 			mapq = (int)(identity * pen_cm * 40.0f * (1.0f - x * x) * logf((float)h.dp_max / match_sc));
-			const int mapq_alt = (int)(6.02f * identity * identity * (h.dp_max - h.dp_max2) / match_sc + .499f);      // "BWA-MEM like", in case the long-read heuristic fails
-			mapq = mapq < mapq_alt ? mapq : mapq_alt;
+			if (!is_sr) {
+				const int mapq_alt = (int)(6.02f * identity * identity * (h.dp_max - h.dp_max2) / match_sc + .499f);  // "BWA-MEM like", in case the long-read heuristic fails
+				mapq = mapq < mapq_alt ? mapq : mapq_alt;
+			}
 		} else {
 			const float x = (float)subsc / h.score0;
 			if (h.has_p) {
@@ -324,6 +331,8 @@ struct MapCall {
 	char **paf_out; int64_t *paf_len; mm2gb_map_stats_t *stats; const mm2gb_map_aln_t *aln; double *s_extra;
 	const mm2gb_align_splice_opt_t *spl = nullptr;       // the spliced calls: their alignment options (aln then holds the rest of the mm2gb_map_splice_t)
 	const int32_t *q_rank = nullptr, *ref_rank = nullptr; // MM_F_NO_DIAG / MM_F_NO_DUAL: the names' ranks where the caller has them already (the stream: once for all chunks)
+	const mm2gb_map_sr_t *sr = nullptr;                  // mm2gb_map_reads_sr: short single-end reads (MM_F_SR); aln then holds its alignment's share, or is null
+	mm2gb_map_sr_out_t *sr_out = nullptr;                // ... and where its own counts go
 };
 
 // what the stages of one batch share
@@ -357,6 +366,7 @@ struct Batch {
 	int64_t link[2] = { 0, 0 };                          // seeded on the device: bytes the stages copied to the device / back (the MM2GB_DEBUG_PHASES line; profiles/ava_rate.py)
 	std::vector<std::string> lines;
 	mm2gb_map_stats_t st = {};
+	mm2gb_map_sr_out_t sro = {};                         // the short-read path's own counts
 	double *const s_extra;
 
 	Batch(const MapCall &call, const mm2gb_map_opt_t &o)
@@ -720,6 +730,194 @@ int hit_records_resident(Batch &B)
 	return 0;
 }
 
+// ---- short single-end reads (mm2gb_map_reads_sr; minimap2 -x sr without base-level alignment): stages 2 and 3 in their MM_F_SR forms ----
+
+// 2 for a list of reads (ascending), from the host's matches: anchors in the heap's order under MM_F_HEAP_SORT (map.c:229-293), sorted otherwise; on the device or
+// on host threads as seeds_on_device says.  a_off: the list's offsets (one more than reads); out: its anchors
+int collect_anchors_sr(Batch &B, const std::vector<int32_t> &reads, std::vector<int64_t> &a_off, BigBuf<mm2gb_anchor_t> &out, int64_t *n_tied)
+{
+	const size_t n = reads.size();
+	const std::vector<mm2gb_matches_t> &mt = B.mt;
+	std::vector<int64_t> seed_off(n + 1, 0);
+	std::vector<int32_t> qlen(n);
+	for (size_t q = 0; q < n; ++q) { seed_off[q + 1] = seed_off[q] + mt[(size_t)reads[q]].n_seeds; qlen[q] = B.qlen[(size_t)reads[q]]; }
+	std::vector<mm2gb_seed_t> seeds((size_t)seed_off[n]);
+	std::vector<int64_t> hit_off((size_t)seed_off[n] + 1, 0);
+	for (size_t q = 0; q < n; ++q) {
+		const mm2gb_matches_t &m = mt[(size_t)reads[q]];
+		if (m.n_seeds) memcpy(seeds.data() + seed_off[q], m.seeds, (size_t)m.n_seeds * sizeof(mm2gb_seed_t));
+		for (int s = 0; s < m.n_seeds; ++s) hit_off[(size_t)(seed_off[q] + s) + 1] = hit_off[(size_t)(seed_off[q] + s)] + m.seeds[s].n;
+	}
+	const int64_t n_hits = hit_off[(size_t)seed_off[n]];
+	BigBuf<uint64_t> &hits = host_scratch(B.c.eng).hits;
+	hits.resize((size_t)std::max<int64_t>(n_hits, 1));
+	uint64_t *const hits_ptr = hits.data();
+	for_each_on_threads(n, B.nt, 64, [&](size_t q) {
+		const size_t r = (size_t)reads[q];
+		for (int32_t s = 0; s < mt[r].n_seeds; ++s) memcpy(hits_ptr + hit_off[(size_t)seed_off[q] + (size_t)s], B.occ[r][(size_t)s], (size_t)mt[r].seeds[s].n * 8);
+	});
+	out.resize((size_t)std::max<int64_t>(n_hits, 1));
+	a_off.assign(n + 1, 0);
+	const bool on_device = B.opt.seeds_on_device > 0 || (B.opt.seeds_on_device == 0 && n_hits >= 400000000);
+	const int64_t flag = seed_flag(B);
+	*n_tied = 0;
+	if (B.opt.flag & MM2GB_F_HEAP_SORT)
+		return on_device ? mm2gb_collect_seeds_heap_gpu(B.c.eng, flag, (int64_t)n, seed_off.data(), seeds.data(), hit_off.data(), hits_ptr, qlen.data(), nullptr, 0, nullptr, nullptr, a_off.data(), out.data(), n_tied)
+		                 : mm2gb_collect_seeds_heap_host(flag, (int64_t)n, seed_off.data(), seeds.data(), hit_off.data(), hits_ptr, qlen.data(), nullptr, 0, nullptr, nullptr, B.nt, a_off.data(), out.data(), n_tied);
+	return on_device ? mm2gb_collect_seeds_gpu(B.c.eng, flag, (int64_t)n, seed_off.data(), seeds.data(), hit_off.data(), hits_ptr, qlen.data(), nullptr, 0, nullptr, nullptr, a_off.data(), out.data())
+	                 : mm2gb_collect_seeds_host(flag, (int64_t)n, seed_off.data(), seeds.data(), hit_off.data(), hits_ptr, qlen.data(), nullptr, 0, nullptr, nullptr, B.nt, a_off.data(), out.data());
+}
+
+// the chains of a batch whose reads were chained in several calls: the calls' results, and per read which one holds it and where
+struct SrChains {
+	std::vector<std::unique_ptr<ChainsOwner>> parts;
+	std::vector<int32_t> part;
+	std::vector<int64_t> slot;
+	int64_t n_calls = 0;
+	explicit SrChains(size_t R) : part(R, -1), slot(R, 0) {}
+};
+
+// 3 for a list of reads with their anchors: under MM_F_SR the gaps depend on the read's length (map.c:678-686) -- max_dist_y = max(qlen, max_gap),
+// max_dist_x = max(max_frag_len - qlen, max_gap), or max_gap_ref where it is set -- and the engine takes both per call.  dq <= qlen always holds, so any
+// max_dist_y >= the longest read gives lchain.c:118-120 the same answers: one value for the batch.  max_dist_x moves the window and max_ii (lchain.c:172-173,
+// 190) and must be exact: one chaining call per distinct value among the list's reads that have anchors, each over those reads' anchors gathered end to
+// end (a list with one value goes as it lies).  Reads of one length share a value, and so do all reads of max_frag_len - max_gap bases or more.
+int chain_groups_sr(Batch &B, const std::vector<int32_t> &reads, const std::vector<int64_t> &a_off, const mm2gb_anchor_t *anchors, SrChains &S)
+{
+	const mm2gb_map_opt_t &opt = B.opt;
+	std::vector<std::pair<int32_t, int32_t>> key;            // (max_dist_x, place in the list) of the reads that have anchors
+	int32_t longest = 0;
+	for (size_t q = 0; q < reads.size(); ++q) {
+		const int32_t len = B.qlen[(size_t)reads[q]];
+		longest = std::max(longest, len);
+		if (a_off[q + 1] > a_off[q]) key.emplace_back(opt.max_gap_ref > 0 ? opt.max_gap_ref : std::max(B.c.sr->max_frag_len > 0 ? B.c.sr->max_frag_len - len : opt.max_gap, opt.max_gap), (int32_t)q);
+	}
+	std::sort(key.begin(), key.end());
+	mm2gb_misc_t &misc = B.misc;
+	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = std::max(longest, opt.max_gap);
+	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
+	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * B.c.k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * B.c.k);
+	struct ChainSkipMode {
+		bool &mode; const bool before;
+		ChainSkipMode(bool &m, bool keep) : mode(m), before(m) { mode = keep; }
+		~ChainSkipMode() { mode = before; }
+	} guard(B.c.eng->e.chain_skip, opt.max_chain_skip != INT32_MAX);
+	std::vector<int64_t> go;
+	std::vector<mm2gb_anchor_t> ga;
+	for (size_t i = 0; i < key.size();) {
+		size_t j = i;
+		while (j < key.size() && key[j].first == key[i].first) ++j;
+		misc.max_dist_x = key[i].first;
+		if (mm2gb_engine_set_misc(B.c.eng, &misc)) return -1;
+		const bool whole = i == 0 && j == key.size();        // one value: the list's anchors as they lie (the reads without anchors are empty reads of the call)
+		const int64_t n = whole ? (int64_t)reads.size() : (int64_t)(j - i);
+		if (!whole) {
+			go.assign((size_t)n + 1, 0);
+			for (size_t t = i; t < j; ++t) go[t - i + 1] = go[t - i] + (a_off[(size_t)key[t].second + 1] - a_off[(size_t)key[t].second]);
+			ga.resize((size_t)go.back());
+			for (size_t t = i; t < j; ++t) memcpy(ga.data() + go[t - i], anchors + a_off[(size_t)key[t].second], (size_t)(go[t - i + 1] - go[t - i]) * sizeof(mm2gb_anchor_t));
+		}
+		S.parts.emplace_back(new ChainsOwner);
+		if (mm2gb_chain_host(B.c.eng, n, whole ? a_off.data() : go.data(), whole ? anchors : ga.data(), B.nt, &S.parts.back()->c, nullptr)) return -1;
+		++S.n_calls;
+		for (size_t t = i; t < j; ++t) { const size_t r = (size_t)reads[(size_t)key[t].second]; S.part[r] = (int32_t)S.parts.size() - 1; S.slot[r] = whole ? key[t].second : (int64_t)(t - i); }
+		i = j;
+	}
+	return 0;
+}
+
+// 2 and 3 under MM_F_SR, with the rescue of map.c:708-731: if max_occ > mid_occ, the reads with rep_len > 0 that are left without a chain (for one segment that is
+// all n_chained_segs < n_segs can mean) get their matches again with max_occ in mid_occ's place -- that round's rep_len and mini_pos replace the first's --, their
+// anchors again and are chained again, as one more batch.  Then every read's chains end to end in the batch's own arrays, where stage 5 reads them
+//      dev_seed: the first round's matches lie on the device and its anchors come from them there (Engine::collect_seeds_heap_resident); the rescue's few reads are
+//      seeded on host threads as ever
+int anchors_and_chains_sr(Batch &B, bool dev_seed)
+{
+	const size_t R = B.R;
+	std::vector<int32_t> all(R);
+	for (size_t r = 0; r < R; ++r) all[r] = (int32_t)r;
+	int64_t tied = 0, tied2 = 0;
+	if (dev_seed) {
+		B.anchors.resize((size_t)std::max<int64_t>(B.dev_hits, 1));
+		Engine &e = B.c.eng->e;
+		if ((B.opt.flag & MM2GB_F_HEAP_SORT) ? e.collect_seeds_heap_resident(seed_flag(B), B.c.n_reads, B.dev_seeds, B.dev_hits, B.a_off.data(), B.anchors.data(), &tied)
+		                                     : e.collect_seeds_resident(seed_flag(B), B.c.n_reads, B.dev_seeds, B.dev_hits, nullptr, B.c.n_ref, B.ref_len.data(), nullptr, B.a_off.data(), B.anchors.data())) return -1;
+	} else
+	if (collect_anchors_sr(B, all, B.a_off, B.anchors, &tied)) return -1;
+	B.st.n_anchors = B.a_off[R];
+	SrChains S(R);
+	if (chain_groups_sr(B, all, B.a_off, B.anchors.data(), S)) return -1;
+	auto n_chains = [&](size_t r) { return S.part[r] < 0 ? (int64_t)0 : S.parts[(size_t)S.part[r]]->c.u_off[S.slot[r] + 1] - S.parts[(size_t)S.part[r]]->c.u_off[S.slot[r]]; };
+	std::vector<int32_t> redo;
+	if (B.c.sr->max_occ > B.opt.mid_occ)
+		for (size_t r = 0; r < R; ++r) if (B.mt[r].rep_len > 0 && n_chains(r) == 0) redo.push_back((int32_t)r);
+	std::vector<int64_t> a_off2;
+	BigBuf<mm2gb_anchor_t> anchors2;
+	if (!redo.empty()) {
+		mm2gb_seed_opt_t so = B.so;
+		so.mid_occ = B.c.sr->max_occ;
+		std::atomic<int> bad(0);
+		std::string why;
+		std::mutex why_lock;
+		for_each_on_threads(redo.size(), B.nt, 1, [&](size_t q) {
+			const size_t r = (size_t)redo[q];
+			mm2gb_matches_free(&B.mt[r]);
+			if (collect_matches_refs(B.c.ix, B.c.seqs[r], B.c.lens[r], &so, &B.mt[r], &B.occ[r])) {
+				std::lock_guard<std::mutex> g(why_lock);
+				if (!bad.exchange(1)) why = mm2gb_last_error();
+			}
+		});
+		if (bad) return fail(why);
+		if (collect_anchors_sr(B, redo, a_off2, anchors2, &tied2)) return -1;
+		B.st.n_anchors += a_off2.back();
+		for (int32_t r : redo) S.part[(size_t)r] = -1;
+		if (chain_groups_sr(B, redo, a_off2, anchors2.data(), S)) return -1;
+	}
+	B.sro.n_rescued = (int64_t)redo.size();
+	B.u_off.assign(R + 1, 0); B.c_off.assign(R + 1, 0);
+	for (size_t r = 0; r < R; ++r) {
+		B.u_off[r + 1] = B.u_off[r] + n_chains(r);
+		if (S.part[r] >= 0) { const mm2gb_chains_t &c = S.parts[(size_t)S.part[r]]->c; B.c_off[r + 1] = c.a_off[S.slot[r] + 1] - c.a_off[S.slot[r]]; }
+		B.c_off[r + 1] += B.c_off[r];
+	}
+	B.first_u.resize((size_t)std::max<int64_t>(B.u_off[R], 1)); B.first_a.resize((size_t)std::max<int64_t>(B.c_off[R], 1));
+	uint64_t *const nu = B.first_u.data();
+	mm2gb_anchor_t *const nc = B.first_a.data();
+	for_each_on_threads(R, B.nt, 256, [&](size_t r) {
+		if (S.part[r] < 0) return;
+		const mm2gb_chains_t &c = S.parts[(size_t)S.part[r]]->c;
+		const int64_t q = S.slot[r];
+		if (B.u_off[r + 1] > B.u_off[r]) memcpy(nu + B.u_off[r], c.u + c.u_off[q], (size_t)(B.u_off[r + 1] - B.u_off[r]) * 8);
+		if (B.c_off[r + 1] > B.c_off[r]) memcpy(nc + B.c_off[r], c.a + c.a_off[q], (size_t)(B.c_off[r + 1] - B.c_off[r]) * sizeof(mm2gb_anchor_t));
+	});
+	B.u = nu; B.ca = nc;
+	B.st.n_chains = B.u_off[R];
+	B.sro.n_tied_reads = tied + tied2; B.sro.n_chain_calls = S.n_calls;
+	if (getenv("MM2GB_DEBUG_PHASES"))
+		fprintf(stderr, "[mm2gb] sr: %lld chaining calls, %lld reads through the max_occ rescue, %lld reads with equal index entries\n", (long long)S.n_calls, (long long)redo.size(), (long long)(tied + tied2));
+	return 0;
+}
+
+// 6 under MM_F_SR without an alignment: mm_set_parent and mm_select_sub as ever, no mm_est_err and no mm_filter_strand_retained (map.c:750: div stays -1, no dv:f),
+// mm_set_mapq, and under MM_F_NO_PRINT_2ND no line for a hit that is not its own parent (map.c:1359)
+void finish_reads_sr(Batch &B)
+{
+	const mm2gb_map_opt_t &opt = B.opt;
+	for_each_on_threads(B.R, B.nt, 64, [&](size_t r) {
+		std::vector<Hit> hs;
+		for (int64_t j = B.u_off[r]; j < B.u_off[r + 1]; ++j) hs.push_back(hit_from(B.regs[(size_t)j]));
+		if (hs.empty()) return;
+		set_parent(opt.mask_level, opt.mask_len, hs, false);
+		select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);
+		set_mapq(hs, opt.min_chain_score, B.mt[r].rep_len, 1, true);
+		for (const Hit &h : hs) {
+			if ((opt.flag & MM2GB_F_NO_PRINT_2ND) && h.id != h.parent) continue;
+			write_paf(B.lines[r], B.c.names[r] ? B.c.names[r] : "*", B.c.lens[r], h, B.c.ref_names[h.rid], B.c.ref_lens[h.rid], B.mt[r].rep_len);
+			B.lines[r] += '\n';
+		}
+	});
+}
+
 // ---- 6. per read on the host ----
 
 // the hits of a read up to mm_filter_strand_retained (map.c:749-752)
@@ -733,6 +931,7 @@ void chain_hits(const Batch &B, size_t r, std::vector<Hit> &hs)
 		set_parent(opt.mask_level, opt.mask_len, hs, false);                                          // map.c:336
 		select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);          // map.c:337
 	}
+	if (B.c.sr) return;                                                                               // map.c:750: neither under MM_F_SR
 	if (B.resident) divergence_from_counts(hs, B.est.data() + B.u_off[r], B.sum_k[r], B.mt[r].n_mini_pos);
 	else estimate_divergence(B.c.lens[r], B.ref_len, hs, B.ca + B.c_off[r], B.mt[r].n_mini_pos, B.mt[r].mini_pos);   // map.c:751
 	filter_strand_retained(hs);                                                                       // map.c:752
@@ -789,6 +988,11 @@ int align_kept(Batch &B, Aligned &A)
 	const MapCall &c = B.c;
 	const int idx_flag = mm2gb_index_flag(c.ix);
 	if (idx_flag < 0) return -1;
+	if (c.sr)
+		return B.aln->align_on_device < 0 ? mm2gb_align_regs_sr_host(&B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(), B.ca,
+		                                                             B.nt, &A.o, B.sro.sr_counts)
+		                                  : mm2gb_align_regs_sr_gpu(c.eng, &B.aln->opt, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(),
+		                                                            B.ca, &A.o, B.sro.sr_counts);
 	if (c.spl)
 		return B.aln->align_on_device < 0 ? mm2gb_align_regs_splice_host(c.spl, c.k, idx_flag, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, A.reg_off.data(), A.rin.data(), B.c_off.data(),
 		                                                                 B.ca, B.nt, &A.o, nullptr)
@@ -812,7 +1016,7 @@ void rank_aligned(Batch &B, Aligned &A)
 		for (int64_t j = A.o.reg_off[r]; j < A.o.reg_off[r + 1]; ++j) { hs.push_back(hit_from(A.o.regs[j], &A.o.aln[j])); hs.back().aln = j; }
 		set_parent(opt.mask_level, opt.mask_len, hs, false, B.aln->opt.a * 2 + B.aln->opt.b);
 		select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, false, (int)(opt.max_gap * 0.8), hs);
-		set_mapq(hs, opt.min_chain_score, B.mt[r].rep_len, B.aln->opt.a);
+		set_mapq(hs, opt.min_chain_score, B.mt[r].rep_len, B.aln->opt.a, B.c.sr != nullptr);
 	});
 }
 
@@ -855,6 +1059,7 @@ void aligned_lines(Batch &B, const Aligned &A)
 		for (size_t i = 0; i < A.kept[r].size(); ++i) {
 			const Hit &h = A.kept[r][i];
 			const size_t j = (size_t)A.line_off[r] + i;
+			if (B.c.sr && (B.opt.flag & MM2GB_F_NO_PRINT_2ND) && h.id != h.parent) continue;          // map.c:1359
 			paf_line(B, r, h, h.has_p ? A.o.cigar + A.o.aln[h.aln].cigar_off : nullptr);
 			if (A.tx_off) B.lines[r].append(A.tx + A.tx_off[j], (size_t)(A.tx_off[j + 1] - A.tx_off[j]));
 			B.lines[r] += '\n';
@@ -875,6 +1080,7 @@ int emit_paf(Batch &B)
 	*B.c.paf_out = buf; *B.c.paf_len = (int64_t)total;
 	B.st.n_reads = B.c.n_reads;
 	if (B.c.stats) *B.c.stats = B.st;
+	if (B.c.sr_out) { *B.c.sr_out = B.sro; for (int i = 0; i < 3; ++i) B.c.sr_out->s_extra[i] = B.s_extra ? B.s_extra[i] : 0.0; }
 	return 0;
 }
 
@@ -884,6 +1090,18 @@ int map_reads_body(const MapCall &c)
 	mm2gb_map_opt_t opt = *c.opt;
 	// (what the options rule out is said before anything else is looked at)
 	constexpr int64_t overlap_bits = MM2GB_F_NO_DIAG | MM2GB_F_NO_DUAL | MM2GB_F_ALL_CHAINS;
+	if (c.sr) {
+		constexpr int64_t sr_bits = MM2GB_F_SR | MM2GB_F_FRAG_MODE | MM2GB_F_NO_PRINT_2ND | MM2GB_F_HEAP_SORT;
+		static const struct { int64_t bit; const char *name; } refused[] = { { MM2GB_F_RMQ, "MM_F_RMQ (options.c:173)" }, { MM2GB_F_QSTRAND, "MM_F_QSTRAND" }, { MM2GB_F_EQX, "MM_F_EQX" }, { MM2GB_F_SPLICE, "MM_F_SPLICE" },
+		                                                                     { MM2GB_F_NO_DIAG, "MM_F_NO_DIAG" }, { MM2GB_F_NO_DUAL, "MM_F_NO_DUAL" }, { MM2GB_F_ALL_CHAINS, "MM_F_ALL_CHAINS" } };
+		for (const auto &x : refused) if (opt.flag & x.bit) return fail(std::string("mm2gb_map_reads_sr: ") + x.name + " is not supported");
+		if (!(opt.flag & MM2GB_F_SR)) return fail("mm2gb_map_reads_sr: the options do not carry MM_F_SR (mm2gb_map_opt_init_sr)");
+		if (opt.flag & ~(int64_t)(0x100000 | 0x200000 | sr_bits)) return fail("mm2gb_map_reads_sr: of mm_mapopt_t::flag only the preset's MM_F_SR, MM_F_FRAG_MODE, MM_F_NO_PRINT_2ND and MM_F_HEAP_SORT are supported, MM_F_FOR_ONLY and MM_F_REV_ONLY beside them");
+		if (c.sr->align == 0 && c.sr->what != 0) return fail("mm2gb_map_reads_sr: what asks for alignment text and align is 0");
+		if (c.sr->align != 0 && !c.aln) return fail("mm2gb_map_reads_sr: null argument");
+		if (opt.seeding_on_device > 1) opt.seeding_on_device = 1;          // (the resident path skips nothing that the rescue needs)
+		if (c.ix && (mm2gb_index_flag(c.ix) & MM2GB_I_HPC)) return fail("mm2gb_map_reads_sr: a homopolymer-compressed index does not work with MM_F_SR (align.c:583)");
+	} else
 	if (opt.flag & ~(int64_t)(0x100000 | 0x200000 | MM2GB_F_RMQ | MM2GB_F_NO_LJOIN | overlap_bits))
 		return fail("mm2gb_map_reads: of mm_mapopt_t::flag only MM_F_FOR_ONLY and MM_F_REV_ONLY are supported, MM_F_RMQ, MM_F_NO_LJOIN and read overlap's MM_F_NO_DIAG, MM_F_NO_DUAL and MM_F_ALL_CHAINS beside them");
 	if ((opt.flag & MM2GB_F_RMQ) && (opt.flag & overlap_bits))         // (read overlap goes through the chaining DP: no fixture has it with mg_lchain_rmq as the first chainer)
@@ -927,6 +1145,31 @@ int map_reads_body(const MapCall &c)
 	if (dev_seed ? seed_on_device(B) : seed_on_host(B)) return -1;                                    // 1
 	lap(B.st.s_seed);
 	stage("mm2gb:map_anchors");
+	if (c.sr) {
+		if (anchors_and_chains_sr(B, dev_seed)) return -1;                                            // 2 and 3 with the rescue (one lap: the rescue runs both again)
+		lap(B.st.s_chain);
+		stage("mm2gb:map_hit_records");
+		if (hit_records(B)) return -1;                                                                // 5
+		lap(B.st.s_regs);
+		stage("mm2gb:map_hits_to_paf");
+		if (!B.aln) finish_reads_sr(B);                                                               // 6
+		else {
+			Aligned A;
+			kept_records(B, A);
+			lap(B.st.s_post);
+			if (align_kept(B, A)) return -1;
+			lap(B.s_extra[0]);
+			rank_aligned(B, A);
+			lap(B.s_extra[1]);
+			if (tag_text(B, A)) return -1;
+			lap(B.s_extra[2]);
+			aligned_lines(B, A);
+		}
+		B.release_matches();
+		lap(B.st.s_post);
+		stage(nullptr);
+		return emit_paf(B);
+	}
 	if (collect_anchors(B, dev_seed)) return -1;                                                      // 2
 	B.st.n_anchors = B.a_off[B.R];
 	lap(B.st.s_anchors);
@@ -1054,6 +1297,7 @@ int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bas
 	std::vector<int64_t> part_len(n_chunks, 0);
 	std::vector<mm2gb_map_stats_t> st(n_chunks);
 	std::vector<double> extra(n_chunks * 3, 0.0);         // with an alignment: seconds for align, the steps after it, text, per chunk
+	std::vector<mm2gb_map_sr_out_t> sro(c.sr_out ? n_chunks : 0);
 	std::atomic<size_t> next(0);
 	std::atomic<int> failed(0);
 	std::string why;                                      // error text is per thread: carry the first one over
@@ -1066,6 +1310,7 @@ int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bas
 			MapCall one = c;
 			one.eng = engines[e]; one.opt = &opt; one.n_reads = cut[k + 1] - cut[k]; one.names += cut[k]; one.seqs += cut[k]; one.lens += cut[k];
 			one.paf_out = &part[k]; one.paf_len = &part_len[k]; one.stats = &st[k]; one.s_extra = &extra[k * 3];
+			if (c.sr_out) { memset(&sro[k], 0, sizeof sro[k]); one.sr_out = &sro[k]; }
 			if (!q_rank.empty()) { one.q_rank = q_rank.data() + cut[k]; one.ref_rank = ref_rank.data(); }
 			if (map_reads_try(one)) {
 				std::lock_guard<std::mutex> g(why_lock);
@@ -1076,6 +1321,14 @@ int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bas
 	if (failed.load()) { for (char *p : part) free(p); return fail("mm2gb_map_reads_stream: " + why); }
 	if (join_parts("mm2gb_map_reads_stream", part, part_len, st, true, c.paf_out, c.paf_len, c.stats)) return -1;
 	if (c.s_extra) for (size_t i = 0; i < extra.size(); ++i) c.s_extra[i % 3] += extra[i];
+	if (c.sr_out) {
+		memset(c.sr_out, 0, sizeof *c.sr_out);
+		for (const mm2gb_map_sr_out_t &q : sro) {
+			c.sr_out->n_chain_calls += q.n_chain_calls; c.sr_out->n_rescued += q.n_rescued; c.sr_out->n_tied_reads += q.n_tied_reads;
+			for (int i = 0; i < MM2GB_SR_N_COUNTS; ++i) c.sr_out->sr_counts[i] += q.sr_counts[i];
+			for (int i = 0; i < 3; ++i) c.sr_out->s_extra[i] += q.s_extra[i];
+		}
+	}
 	return 0;
 }
 
@@ -1131,6 +1384,62 @@ int mm2gb_map_opt_init_ava(mm2gb_map_opt_t *o, const char *preset)          // o
 	if (ont) o->bw = o->bw_long = 2000;
 	else o->bw_long = o->bw;
 	return 0;
+}
+
+void mm2gb_map_opt_init_sr(mm2gb_map_opt_t *o)    // options.c:133-150: the mapping fields this record has room for
+{
+	mm2gb_map_opt_init(o);
+	o->flag |= MM2GB_F_SR | MM2GB_F_FRAG_MODE | MM2GB_F_NO_PRINT_2ND | MM2GB_F_HEAP_SORT;
+	o->max_gap = 100; o->bw = o->bw_long = 100; o->pri_ratio = 0.5f; o->min_cnt = 2; o->min_chain_score = 25; o->best_n = 20; o->mid_occ = 1000;
+}
+
+void mm2gb_map_sr_init(mm2gb_map_sr_t *s)          // options.c:133-150: what the mapping options have no room for, and the alignment's values
+{
+	memset(s, 0, sizeof(*s));
+	mm2gb_align_sr_opt_init(&s->opt);
+	s->max_occ = 5000; s->max_frag_len = 800;
+}
+
+namespace {
+// the call's arguments checked and, with an alignment, the mm2gb_map_aln_t the shared stages read; nullptr, or why not
+const char *sr_as_aln(const mm2gb_map_sr_t *sr, mm2gb_map_aln_t &a, bool &aligned)
+{
+	if (!sr) return "null argument";
+	aligned = sr->align != 0;
+	if (!aligned) return nullptr;
+	a.ref_seqs = sr->ref_seqs; a.opt = sr->opt; a.what = sr->what; a.align_on_device = sr->align_on_device; a.text_on_device = sr->text_on_device;
+	return bad_aln(&a);
+}
+}
+
+int mm2gb_map_reads_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref, const mm2gb_map_opt_t *opt,
+                       const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
+                       mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out)
+{
+	if (!eng) return fail("mm2gb: null engine");
+	mm2gb_map_aln_t aln;
+	bool aligned = false;
+	if (const char *why = sr_as_aln(sr, aln, aligned)) return fail(std::string("mm2gb_map_reads_sr: ") + why);
+	double extra[3] = { 0, 0, 0 };
+	if (sr_out) memset(sr_out, 0, sizeof *sr_out);
+	MapCall c = { eng, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
+	c.sr = sr; c.sr_out = sr_out;
+	return map_reads_try(c);
+}
+
+int mm2gb_map_reads_stream_sr(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                              int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
+                              const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out)
+{
+	mm2gb_map_aln_t aln;
+	bool aligned = false;
+	if (const char *why = sr_as_aln(sr, aln, aligned)) return fail(std::string("mm2gb_map_reads_stream_sr: ") + why);
+	double extra[3] = { 0, 0, 0 };
+	mm2gb_map_sr_out_t own;
+	if (sr_out) memset(sr_out, 0, sizeof *sr_out);
+	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
+	c.sr = sr; c.sr_out = sr_out ? sr_out : &own;
+	return stream_body(engines, n_engines, chunk_bases, c);
 }
 
 int mm2gb_engine_release_host_scratch(mm2gb_engine_t *eng)
