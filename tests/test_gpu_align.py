@@ -1,5 +1,6 @@
 """The alignment of hits with the DP and its sequences on the device (mm2gb_align_regs_gpu, csrc/align_kernels.hip) against the host form and the
-committed fixtures (tests/golden/align): every record, field and CIGAR word.  Reads fixtures only."""
+committed fixtures (tests/golden/align): every record, field and CIGAR word.  Reads fixtures only; the chains crafted for k_al_gather's slice cuts,
+the drop walk's thresholds and positions and k_al_zdrop's list are tests/test_gpu_align_crafted.py's."""
 import numpy as np
 import pytest
 
