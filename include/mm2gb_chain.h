@@ -718,6 +718,23 @@ int  mm2gb_aln_text_splice_gpu(mm2gb_engine_t *eng, int what, int32_t n_ref, con
                                const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
                                int64_t **text_off, char **text);
 
+/* ---- = / X CIGARs (minimap2 --eqx), batched: mm_update_cigar_eqx (align.c:169-238) as a call of its own on the records the
+ *      alignment calls return.  Every M word becomes runs of = (operation 7) and X (operation 8): residues compare as seq_nt4_table codes (N
+ *      against N is =), a reverse-strand record reads its query reverse-complemented, a run never crosses a word; I, D and N words are copied.
+ *      Arguments as mm2gb_aln_text_*.  *aln_out (n_regs records; malloc'd, free with mm2gb_free) is aln with cigar_off / n_cigar of the new
+ *      words, which lie in *cigar_out (malloc'd, free with mm2gb_free); a record with cigar_off < 0 stays as it is.  The input is untouched.
+ *      Refused, with the error text set and nothing run: what mm2gb_aln_text_splice_* refuse (an operation other than M, I, D, N; a word of
+ *      length 0; words that do not sum to the record's spans; a record outside its sequences), and a = or X word: the rewrite has been done.
+ *      The host form is the definition; the device form (csrc/eqx_kernels.hip) equals it word for word.  mm2gb_cigar_eqx_gpu_info: as
+ *      mm2gb_aln_text_gpu_info (columns per slice, threads of a workgroup; the last call's seconds). ---- */
+int  mm2gb_cigar_eqx_host(int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs, const int32_t *read_lens,
+                          int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar, int n_threads,
+                          mm2gb_aln_t **aln_out, uint32_t **cigar_out);
+int  mm2gb_cigar_eqx_gpu(mm2gb_engine_t *eng, int32_t n_ref, const char *const *ref_seqs, const int32_t *ref_lens, int64_t n_reads, const char *const *read_seqs,
+                         const int32_t *read_lens, int64_t n_regs, const mm2gb_reg_t *regs, const int32_t *read_of_reg, const mm2gb_aln_t *aln, const uint32_t *cigar,
+                         mm2gb_aln_t **aln_out, uint32_t **cigar_out);
+int  mm2gb_cigar_eqx_gpu_info(mm2gb_engine_t *eng, int64_t *consts2, double *s4);
+
 /* ---- the mapper with base-level alignment (minimap2 -c, --cs, --MD; csrc/mapper.cpp): mm2gb_map_reads / mm2gb_map_reads_stream with a
  *      mm2gb_map_aln_t.  After mm_filter_strand_retained the batch's surviving records go through mm2gb_align_regs_* in one call (map.c:342-352;
  *      k and the HPC flag are the index's; what that call refuses fails the mapping call with the same text; with opt.q == opt.q2 &&
@@ -820,6 +837,51 @@ int  mm2gb_map_reads_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, con
 int  mm2gb_map_reads_stream_sr(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
                                int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
                                const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out);
+
+/* ---- SAM output and = / X CIGARs from the mapper (minimap2 -a, --eqx, -Y, --sam-hit-only): the calls above that align, with a mm2gb_map_out_t as their
+ *      last argument.  NULL, or a zeroed record: the bytes of the call without it.
+ *      format 1: every line is mm_write_sam3's at n_seg = 1 (format.c:389-546): FLAG 0x10 on the reverse strand, 0x100 for a hit that is not its own
+ *      parent, 0x800 for every primary hit of a read but its first (mm_set_sam_pri, hit.c:220-229); RNAME, POS + 1, MAPQ; the CIGAR with clips (H on 0x800
+ *      lines, S elsewhere and everywhere under MM2GB_F_SOFTCLIP; swapped on the reverse strand); "*\t0\t0"; SEQ: the whole read on the first line and
+ *      under MM2GB_F_SOFTCLIP, qs .. qe on 0x800 lines, "*" on 0x100 lines, reverse-complemented on the reverse strand with IUPAC codes and case kept;
+ *      QUAL "*"; the PAF line's tags; SA:Z on a primary line of a read with other aligned primaries; cs:Z / MD:Z as `what` asks (MM2GB_TEXT_CG means
+ *      nothing here); rl:i.  A read without a hit gets "name 4 * 0 0 * * 0 0 SEQ * rl:i" unless MM2GB_F_SAM_HIT_ONLY; stats->n_mapped counts reads with a
+ *      hit, not lines.  mm2gb_sam_header gives the @SQ lines and a @PG line of this project (malloc'd, free with mm2gb_free); paf_out holds no header.
+ *      MM2GB_F_EQX in flag, either format: the CIGAR column / cg:Z show mm2gb_cigar_eqx_*'s words, made in one call per batch after the text call, which
+ *      reads the M words (format.c prints the same cs:Z / MD:Z for either).  eqx_on_device: 1 the device form -- on the residues the alignment call left
+ *      on the device where they are this batch's, uploaded otherwise --, -1 host threads, 0 the default: host threads (profiles/eqx_rate.json).
+ *      Refused by name: a format other than 0 / 1, a flag bit other than the three, SAM or MM2GB_F_EQX on a call that does not align
+ *      (mm2gb_map_reads_sr_out with align = 0: -a implies -c); the read-overlap bits are refused with any alignment as before.  Every refusal of the
+ *      calls above stays, MM_F_EQX in the mapping options' and the alignment options' flag included: the bit belongs to mm2gb_map_out_t alone.
+ *      Not taken: -L (the CIGAR in CG:B:I), qualities (reads are as from FASTA), -R, -y, --paf-no-hit, --secondary-seq, paired ends. ---- */
+#define MM2GB_F_SOFTCLIP     0x80000LL
+#define MM2GB_F_SAM_HIT_ONLY 0x40000000LL
+typedef struct {
+	int32_t format;                   /* 0 PAF, 1 SAM */
+	int32_t eqx_on_device;            /* 1 the device form of the = / X rewrite; -1 host threads; 0 (default): host threads */
+	int64_t flag;                     /* MM2GB_F_EQX, MM2GB_F_SOFTCLIP, MM2GB_F_SAM_HIT_ONLY: the reference's values */
+} mm2gb_map_out_t;
+void mm2gb_map_out_init(mm2gb_map_out_t *out);
+int  mm2gb_sam_header(int32_t n_ref, const char *const *ref_names, const int32_t *ref_lens, char **out, int64_t *len);
+int  mm2gb_map_reads_aln_out(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                             const mm2gb_map_opt_t *opt, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                             char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out);
+int  mm2gb_map_reads_stream_aln_out(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                    int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                    const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out);
+int  mm2gb_map_reads_splice_out(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                                const mm2gb_map_opt_t *opt, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                                char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out);
+int  mm2gb_map_reads_stream_splice_out(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                       int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                       const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out);
+int  mm2gb_map_reads_sr_out(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref, const mm2gb_map_opt_t *opt,
+                            const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
+                            mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out, const mm2gb_map_out_t *out);
+int  mm2gb_map_reads_stream_sr_out(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                   int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                   const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out,
+                                   const mm2gb_map_out_t *out);
 
 #ifdef __cplusplus
 }

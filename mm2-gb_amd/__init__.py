@@ -93,7 +93,10 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_align_splice_opt_init", "mm2gb_align_regs_splice_host", "mm2gb_align_regs_splice_gpu", "mm2gb_aln_text_splice_host", "mm2gb_aln_text_splice_gpu",
                 "mm2gb_map_opt_init_splice", "mm2gb_map_reads_splice", "mm2gb_map_reads_stream_splice", "mm2gb_map_opt_init_preset",
                 "mm2gb_ksw_extz2_host", "mm2gb_ksw_extz2_gpu", "mm2gb_align_regs_extz_host", "mm2gb_align_regs_extz_gpu",
-                "mm2gb_map_opt_init_sr", "mm2gb_collect_seeds_heap_host", "mm2gb_collect_seeds_heap_gpu", "mm2gb_map_sr_init", "mm2gb_map_reads_sr"]
+                "mm2gb_map_opt_init_sr", "mm2gb_collect_seeds_heap_host", "mm2gb_collect_seeds_heap_gpu", "mm2gb_map_sr_init", "mm2gb_map_reads_sr",
+                "mm2gb_cigar_eqx_host", "mm2gb_cigar_eqx_gpu", "mm2gb_cigar_eqx_gpu_info", "mm2gb_map_out_init", "mm2gb_sam_header",
+                "mm2gb_map_reads_aln_out", "mm2gb_map_reads_stream_aln_out", "mm2gb_map_reads_splice_out", "mm2gb_map_reads_stream_splice_out",
+                "mm2gb_map_reads_sr_out", "mm2gb_map_reads_stream_sr_out"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -1058,6 +1061,57 @@ Engine.aln_text_splice = _engine_aln_text_splice
 Engine.aln_text_info = _engine_aln_text_info
 
 
+# ---- = / X CIGARs (mm2gb_cigar_eqx_host / _gpu; minimap2 --eqx): mm_update_cigar_eqx for a batch of records ----
+def _cigar_eqx_call(fn, head, refs, reads, regs, read_of_reg, aln, cigar, tail):
+    refs = [bytes(s) for s in refs]; reads = [bytes(s) for s in reads]
+    ref_arr = (C.c_char_p * max(len(refs), 1))(*refs); read_arr = (C.c_char_p * max(len(reads), 1))(*reads)
+    ref_len = np.ascontiguousarray([len(s) for s in refs], dtype=np.int32); read_len = np.ascontiguousarray([len(s) for s in reads], dtype=np.int32)
+    regs = np.ascontiguousarray(regs, dtype=REG_DTYPE); aln = np.ascontiguousarray(aln, dtype=ALN_DTYPE)
+    read_of_reg = np.ascontiguousarray(read_of_reg, dtype=np.int32); cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+    if not len(regs) == len(aln) == len(read_of_reg):
+        raise Mm2gbError("cigar_eqx: regs, read_of_reg and aln must have one entry per record")
+    have = aln["cigar_off"] >= 0
+    if have.any() and (int((aln["cigar_off"] + aln["n_cigar"])[have].max()) > len(cigar) or int(aln["n_cigar"][have].min()) < 0):
+        raise Mm2gbError("cigar_eqx: a record's CIGAR words lie outside cigar")
+    a_out, w_out = C.c_void_p(0), C.c_void_p(0)
+    fn.argtypes = [C.c_void_p] * len(head) + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p] + [C.c_int] * len(tail) + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    _check(fn(*head, len(refs), ref_arr, ref_len.ctypes.data, len(reads), read_arr, read_len.ctypes.data, len(regs), regs.ctypes.data, read_of_reg.ctypes.data,
+              aln.ctypes.data, cigar.ctypes.data, *tail, C.byref(a_out), C.byref(w_out)))
+    try:
+        a = _take(a_out.value, len(regs), ALN_DTYPE)
+        have = a["cigar_off"] >= 0
+        n = int((a["cigar_off"] + a["n_cigar"])[have].max()) if have.any() else 0
+        return a, _take(w_out.value, n, np.uint32)
+    finally:
+        lib().mm2gb_free(a_out); lib().mm2gb_free(w_out)
+
+
+def cigar_eqx_host(refs, reads, regs, read_of_reg, aln, cigar, threads=4):
+    """mm2gb_cigar_eqx_host: mm_update_cigar_eqx (minimap2 --eqx) on finished records -- every M word as runs of = (7) and X (8); I, D and N words
+    copied -- the definition.  Arguments as aln_text_host's.  Returns (aln, cigar): aln with cigar_off / n_cigar of the new words, and the words;
+    the input is untouched."""
+    return _cigar_eqx_call(lib().mm2gb_cigar_eqx_host, (), refs, reads, regs, read_of_reg, aln, cigar, (int(threads),))
+
+
+def _engine_cigar_eqx(self, refs, reads, regs, read_of_reg, aln, cigar):
+    """mm2gb_cigar_eqx_gpu: cigar_eqx_host's arguments and results, every column on the device (csrc/eqx_kernels.hip)."""
+    return _cigar_eqx_call(lib().mm2gb_cigar_eqx_gpu, (self._h,), refs, reads, regs, read_of_reg, aln, cigar, ())
+
+
+def _engine_cigar_eqx_info(self):
+    """As aln_text_info, for the last Engine.cigar_eqx call."""
+    c = (C.c_int64 * 2)(); s = (C.c_double * 4)()
+    fn = lib().mm2gb_cigar_eqx_gpu_info
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(fn(self._h, c, s))
+    return dict(slice=int(c[0]), wg=int(c[1]), s_upload=s[0], s_prepare=s[1], s_kernels=s[2], s_back=s[3])
+
+
+Engine.cigar_eqx = _engine_cigar_eqx
+Engine.cigar_eqx_info = _engine_cigar_eqx_info
+
+
 def _take_chains(out, R):
     """Copy a mm2gb_chains_t into per-read (u, a_out) arrays and release it."""
     try:
@@ -1723,11 +1777,55 @@ def _sr_stats(st, so):
                 sr_counts=dict(zip(SR_COUNTS, (int(x) for x in so.sr_counts))), s_align=round(so.s_extra[0], 4), s_post_align=round(so.s_extra[1], 4), s_text=round(so.s_extra[2], 4))
 
 
-def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
+class MapOut(C.Structure):
+    """mm2gb_map_out_t: SAM output and = / X CIGARs from the mapping calls that align (make one with map_out)."""
+    _fields_ = [("format", C.c_int32), ("eqx_on_device", C.c_int32), ("flag", C.c_int64)]
+
+
+F_SOFTCLIP, F_SAM_HIT_ONLY = 0x80000, 0x40000000
+
+
+def map_out(sam=False, eqx=False, softclip=False, hit_only=False, eqx_on_device=0):
+    """The out= argument of map_reads / map_reads_stream (with an align= that aligns): sam: SAM lines (minimap2 -a; sam_header gives the header);
+    eqx: = / X in the CIGAR column or cg:Z (--eqx); softclip: S clips and the whole SEQ on supplementary lines (-Y); hit_only: no line for a read
+    without a hit (--sam-hit-only).  eqx_on_device: 1 the device form of the rewrite, -1 host threads, 0 the default (host threads)."""
+    o = MapOut()
+    lib().mm2gb_map_out_init.argtypes = [C.POINTER(MapOut)]
+    lib().mm2gb_map_out_init.restype = None
+    lib().mm2gb_map_out_init(C.byref(o))
+    o.format = 1 if sam else 0
+    o.flag = (F_EQX if eqx else 0) | (F_SOFTCLIP if softclip else 0) | (F_SAM_HIT_ONLY if hit_only else 0)
+    o.eqx_on_device = int(eqx_on_device)
+    return o
+
+
+def sam_header(ref_names, ref_lens):
+    """mm2gb_sam_header: the @SQ line of every reference and this project's @PG line, as text."""
+    L = lib()
+    L.mm2gb_sam_header.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    rn = (C.c_char_p * max(len(ref_names), 1))(*[n.encode() for n in ref_names])
+    lens = np.ascontiguousarray(ref_lens, dtype=np.int32)
+    if len(lens) != len(ref_names):
+        raise Mm2gbError("sam_header: one length per name")
+    out, n = C.c_void_p(), C.c_int64()
+    _check(L.mm2gb_sam_header(len(ref_names), rn, lens.ctypes.data, C.byref(out), C.byref(n)))
+    text = C.string_at(out, n.value).decode()
+    L.mm2gb_free(out)
+    return text
+
+
+def _out_needs_align(out, align):
+    if out is not None and align is None and (out.format or out.flag & F_EQX):
+        raise Mm2gbError("map_reads: SAM output and eqx need base-level alignment, an align= argument (minimap2 -a implies -c)")
+
+
+def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None, out=None):
     """mm2gb_map_reads: reads = list of (name, sequence bytes); returns (PAF text, stats dict).  index: a SeedIndex of the references.
     align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln) or a map_splice(...) for spliced reads (mm2gb_map_reads_splice); the stats then hold s_align, s_post_align and s_text as well.
     A map_sr(...) with opt=map_opt_sr(): short single-end reads (mm2gb_map_reads_sr; minimap2 -x sr [-c]); the stats then hold the call's own counts as well (n_chain_calls,
-    n_rescued, n_tied_reads, sr_counts) and the three alignment seconds."""
+    n_rescued, n_tied_reads, sr_counts) and the three alignment seconds.
+    out: a map_out(...) with any align= that aligns: SAM lines instead of PAF, = / X CIGARs (the calls named _out); None: the bytes of before."""
+    _out_needs_align(out, align)
     L = lib()
     head = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
     tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
@@ -1735,6 +1833,10 @@ def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
     L.mm2gb_map_reads_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
     L.mm2gb_map_reads_splice.argtypes = head + [C.POINTER(MapSplice)] + tail + [C.c_void_p]
     L.mm2gb_map_reads_sr.argtypes = head + [C.POINTER(MapSr)] + tail + [C.POINTER(MapSrOut)]
+    L.mm2gb_map_reads_aln_out.argtypes = L.mm2gb_map_reads_aln.argtypes + [C.POINTER(MapOut)]
+    L.mm2gb_map_reads_splice_out.argtypes = L.mm2gb_map_reads_splice.argtypes + [C.POINTER(MapOut)]
+    L.mm2gb_map_reads_sr_out.argtypes = L.mm2gb_map_reads_sr.argtypes + [C.POINTER(MapOut)]
+    last = () if out is None else (C.byref(out),)          # (`out` names the result pointer below)
     opt = opt or map_opt()
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
     names = (C.c_char_p * len(reads))(*[n.encode() for n, _ in reads])
@@ -1748,7 +1850,7 @@ def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
         if align.align:
             _check_align_refs(align, ref_names)
         so = MapSrOut()
-        _check(L.mm2gb_map_reads_sr(*first, C.byref(align), *rest, C.byref(so)))
+        _check((L.mm2gb_map_reads_sr_out if last else L.mm2gb_map_reads_sr)(*first, C.byref(align), *rest, C.byref(so), *last))
         text = C.string_at(out, n.value).decode()
         L.mm2gb_free(out)
         return text, _sr_stats(st, so)
@@ -1756,7 +1858,11 @@ def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None):
         _check(L.mm2gb_map_reads(*first, *rest))
     else:
         _check_align_refs(align, ref_names)
-        _check((L.mm2gb_map_reads_splice if isinstance(align, MapSplice) else L.mm2gb_map_reads_aln)(*first, C.byref(align), *rest, extra))
+        if not last:
+            fn = L.mm2gb_map_reads_splice if isinstance(align, MapSplice) else L.mm2gb_map_reads_aln
+        else:
+            fn = L.mm2gb_map_reads_splice_out if isinstance(align, MapSplice) else L.mm2gb_map_reads_aln_out
+        _check(fn(*first, C.byref(align), *rest, extra, *last))
     text = C.string_at(out, n.value).decode()
     L.mm2gb_free(out)
     return text, st.as_dict() if align is None else _stats_with_extra(st, extra)
@@ -1792,10 +1898,11 @@ def _engine_release_host_scratch(self):
 Engine.release_host_scratch = _engine_release_host_scratch
 
 
-def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0, align=None):
+def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0, align=None, out=None):
     """mm2gb_map_reads_stream: a run of any size as a stream of chunks of about chunk_bases bases; every engine (several per device overlap
     host stages with kernels, engines on several devices shard the reads) takes the next chunk.  Returns (PAF text in read order, stats:
-    counts summed, s_* summed over chunks).  align: as for map_reads (mm2gb_map_reads_stream_aln / _splice / _sr)."""
+    counts summed, s_* summed over chunks).  align, out: as for map_reads (mm2gb_map_reads_stream_aln / _splice / _sr, and their _out forms)."""
+    _out_needs_align(out, align)
     L = lib()
     head = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
     tail = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
@@ -1803,6 +1910,10 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
     L.mm2gb_map_reads_stream_aln.argtypes = head + [C.POINTER(MapAln)] + tail + [C.c_void_p]
     L.mm2gb_map_reads_stream_splice.argtypes = head + [C.POINTER(MapSplice)] + tail + [C.c_void_p]
     L.mm2gb_map_reads_stream_sr.argtypes = head + [C.POINTER(MapSr)] + tail + [C.POINTER(MapSrOut)]
+    L.mm2gb_map_reads_stream_aln_out.argtypes = L.mm2gb_map_reads_stream_aln.argtypes + [C.POINTER(MapOut)]
+    L.mm2gb_map_reads_stream_splice_out.argtypes = L.mm2gb_map_reads_stream_splice.argtypes + [C.POINTER(MapOut)]
+    L.mm2gb_map_reads_stream_sr_out.argtypes = L.mm2gb_map_reads_stream_sr.argtypes + [C.POINTER(MapOut)]
+    last = () if out is None else (C.byref(out),)          # (`out` names the result pointer below)
     opt = opt or map_opt()
     hs = (C.c_void_p * len(engines))(*[e._h for e in engines])
     rn = (C.c_char_p * len(ref_names))(*[n.encode() for n in ref_names])
@@ -1817,7 +1928,7 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
         if align.align:
             _check_align_refs(align, ref_names)
         so = MapSrOut()
-        _check(L.mm2gb_map_reads_stream_sr(*first, C.byref(align), *rest, C.byref(so)))
+        _check((L.mm2gb_map_reads_stream_sr_out if last else L.mm2gb_map_reads_stream_sr)(*first, C.byref(align), *rest, C.byref(so), *last))
         text = C.string_at(out, n.value).decode()
         L.mm2gb_free(out)
         return text, _sr_stats(st, so)
@@ -1825,7 +1936,11 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
         _check(L.mm2gb_map_reads_stream(*first, *rest))
     else:
         _check_align_refs(align, ref_names)
-        _check((L.mm2gb_map_reads_stream_splice if isinstance(align, MapSplice) else L.mm2gb_map_reads_stream_aln)(*first, C.byref(align), *rest, extra))
+        if not last:
+            fn = L.mm2gb_map_reads_stream_splice if isinstance(align, MapSplice) else L.mm2gb_map_reads_stream_aln
+        else:
+            fn = L.mm2gb_map_reads_stream_splice_out if isinstance(align, MapSplice) else L.mm2gb_map_reads_stream_aln_out
+        _check(fn(*first, C.byref(align), *rest, extra, *last))
     text = C.string_at(out, n.value).decode()
     L.mm2gb_free(out)
     return text, st.as_dict() if align is None else _stats_with_extra(st, extra)

@@ -31,8 +31,13 @@
 //   call per distinct max_dist_x of the batch (the gaps depend on the read's length, map.c:678-686), the max_occ rescue of map.c:708-731 as one more batch, no stage 4,
 //   and in stage 6 no mm_est_err, the alignment call in its MM_F_SR form (mm2gb_align_regs_sr_*: ungapped fills), mm_set_mapq with is_sr = 1, no line
 //   for a secondary hit under MM_F_NO_PRINT_2ND (anchors_and_chains_sr, finish_reads_sr).
-// Not reproduced: more than one query segment (paired ends), spliced mapping without base-level alignment, read overlap with base-level alignment, junction
-// annotation, --eqx, SAM output, ALT contigs, --qstrand, multi-part indexes.
+//   With a mm2gb_map_out_t (the calls named _out, on the three families that align; minimap2 -a, --eqx, -Y, --sam-hit-only): after 6c the kept records' M words go
+//   through mm2gb_cigar_eqx_* in one call under MM_F_EQX (eqx_words; mm_update_cigar_eqx is the last statement of mm_update_extra and nothing after it tells M from = / X,
+//   DESIGN 6g), and a line is mm_write_sam3's at n_seg = 1 (write_sam, format.c:389-546) with mm_set_sam_pri's choice of the primary line, or the PAF line with cg:Z from
+//   the new words.  cs:Z / MD:Z are always asked of the text calls with the M words (format.c treats 0, 7 and 8 alike).  Left out of SAM: -L (CG:B:I), qualities (QUAL is
+//   *), -R read groups, -y comments, --secondary-seq; of PAF: --paf-no-hit.
+// Not reproduced: more than one query segment (paired ends; none of mm_write_sam3's n_seg > 1 branches), spliced mapping without base-level alignment, read overlap with
+// base-level alignment, junction annotation, ALT contigs, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -49,6 +54,7 @@
 #include "host_chain.h"
 #include "align_host.h"
 #include "aln_text_host.h"
+#include "eqx.h"
 #include "est_err.h"
 #include "trace.h"
 
@@ -62,7 +68,7 @@ struct Hit {                                   // mm_reg1_t without the alignmen
 	uint32_t hash;
 	float div;
 	// with an alignment (mm_extra_t, minimap.h:94-102; the record's split and inv bits): none of it is set or looked at without one
-	bool has_p = false, inv = false;
+	bool has_p = false, inv = false, sam_pri = false;   // sam_pri: mm_set_sam_pri's (hit.c:220-229), the read's one line without 0x100 / 0x800
 	int split = 0, dp_score = 0, dp_max = 0, dp_max2 = 0, n_ambi = 0, trans_strand = 0, n_cigar = 0;
 	uint32_t flags = 0;                        // mm_reg1_t's bit-field word as the record carries it between the calls
 	int64_t aln = -1;                          // its place in the alignment call's result
@@ -253,13 +259,9 @@ void set_mapq(std::vector<Hit> &r, int min_chain_sc, int rep_len, int match_sc =
 
 void append_int(std::string &s, long long v) { char buf[24]; snprintf(buf, sizeof buf, "%lld", v); s += buf; }
 
-// format.c:274-321; words: the hit's CIGAR words where it carries an alignment (mm_event_identity, align.c:895-915, counts its gaps);
-// the line ends after rl:i -- what follows it (cg:Z, cs:Z, MD:Z) and the line's end are the caller's
-void write_paf(std::string &out, const char *qname, int qlen, const Hit &h, const char *rname, int rlen, int rep_len, const uint32_t *words = nullptr)
+// write_tags (format.c:274-300), what a PAF and a SAM line share; words: the hit's CIGAR words where it carries an alignment (mm_event_identity, align.c:895-915, counts its gaps)
+void write_tags(std::string &out, const Hit &h, const uint32_t *words)
 {
-	out += qname; out += '\t'; append_int(out, qlen); out += '\t'; append_int(out, h.qs); out += '\t'; append_int(out, h.qe); out += '\t';
-	out += h.rev ? '-' : '+'; out += '\t'; out += rname; out += '\t'; append_int(out, rlen); out += '\t'; append_int(out, h.rs); out += '\t';
-	append_int(out, h.re); out += '\t'; append_int(out, h.mlen); out += '\t'; append_int(out, h.blen); out += '\t'; append_int(out, h.mapq);
 	if (h.has_p) {
 		out += "\tNM:i:"; append_int(out, h.blen - h.mlen + h.n_ambi); out += "\tms:i:"; append_int(out, h.dp_max); out += "\tAS:i:"; append_int(out, h.dp_score);
 		out += "\tnn:i:"; append_int(out, h.n_ambi);
@@ -282,7 +284,87 @@ void write_paf(std::string &out, const char *qname, int qlen, const Hit &h, cons
 		else { char buf[16]; snprintf(buf, sizeof buf, "%.4f", h.div); out += buf; }
 	}
 	if (h.split) { out += "\tzd:i:"; append_int(out, h.split); }
+}
+
+// format.c:302-321; the line ends after rl:i -- what follows it (cg:Z, cs:Z, MD:Z) and the line's end are the caller's
+void write_paf(std::string &out, const char *qname, int qlen, const Hit &h, const char *rname, int rlen, int rep_len, const uint32_t *words = nullptr)
+{
+	out += qname; out += '\t'; append_int(out, qlen); out += '\t'; append_int(out, h.qs); out += '\t'; append_int(out, h.qe); out += '\t';
+	out += h.rev ? '-' : '+'; out += '\t'; out += rname; out += '\t'; append_int(out, rlen); out += '\t'; append_int(out, h.rs); out += '\t';
+	append_int(out, h.re); out += '\t'; append_int(out, h.mlen); out += '\t'; append_int(out, h.blen); out += '\t'; append_int(out, h.mapq);
+	write_tags(out, h, words);
 	out += "\trl:i:"; append_int(out, rep_len);
+}
+
+// CIGAR words as "%d%c" each (format.c:326, 383)
+void append_cigar(std::string &out, const uint32_t *words, int32_t n)
+{
+	for (int32_t k = 0; k < n; ++k) { append_int(out, words[k] >> 4); out += "MIDNSHP=XB??????"[words[k] & 0xf]; }
+}
+
+// sam_write_sq (format.c:339-351) for SEQ: on the reverse strand the bases backwards, each letter's complement in the sense of bseq.c's table, restated: the IUPAC
+// pairs A/T, C/G, B/V, D/H, K/M, R/Y swap, U gives A, every other byte (N, S, W, the letters that are no code, whatever is no letter) stays; case is kept
+char sam_complement(char ch)
+{
+	static const char *pairs = "ATCGBVDHKMRY";
+	const bool lower = ch >= 'a' && ch <= 'z';
+	const char up = lower ? (char)(ch - 32) : ch;
+	char to = up == 'U' ? 'A' : up;
+	for (int i = 0; i < 12; ++i) if (pairs[i] == up) { to = pairs[i ^ 1]; break; }
+	return lower && to >= 'A' && to <= 'Z' ? (char)(to + 32) : to;
+}
+void append_seq(std::string &out, const char *seq, int len, bool rev)
+{
+	if (!rev) { out.append(seq, (size_t)len); return; }
+	const size_t at = out.size();
+	out.resize(at + (size_t)len);
+	for (int i = 0; i < len; ++i) out[at + (size_t)i] = sam_complement(seq[len - 1 - i]);
+}
+
+// mm_write_sam3 at n_seg = 1 (format.c:389-546) for hit h of hs, the read's hits; out_flag: MM2GB_F_SOFTCLIP is looked at; cigar / n_cigar: the words the CIGAR column
+// shows (the M words, or their = / X form); words: the M words for write_tags.  The line ends after the tags and SA:Z -- cs:Z / MD:Z, rl:i and the line's end are the caller's
+void write_sam(std::string &out, const char *qname, int qlen, const char *seq, const Hit &h, const std::vector<Hit> &hs, const char *const *ref_names, int64_t out_flag,
+               const uint32_t *cigar, int32_t n_cigar, const uint32_t *words)
+{
+	const int flag = (h.rev ? 0x10 : 0) | (h.parent != h.id ? 0x100 : !h.sam_pri ? 0x800 : 0);
+	const bool soft = (out_flag & MM2GB_F_SOFTCLIP) != 0, whole = (flag & 0x900) == 0 || soft;
+	out += qname; out += '\t'; append_int(out, flag); out += '\t'; out += ref_names[h.rid]; out += '\t'; append_int(out, h.rs + 1); out += '\t'; append_int(out, h.mapq); out += '\t';
+	if (!h.has_p) out += '*';
+	else {
+		const int clip[2] = { h.rev ? qlen - h.qe : h.qs, h.rev ? h.qs : qlen - h.qe };
+		const char clip_char = (flag & 0x800) && !soft ? 'H' : 'S';
+		if (clip[0]) { append_int(out, clip[0]); out += clip_char; }
+		append_cigar(out, cigar, n_cigar);
+		if (clip[1]) { append_int(out, clip[1]); out += clip_char; }
+	}
+	out += "\t*\t0\t0\t";
+	if (whole) append_seq(out, seq, qlen, h.rev);
+	else if (flag & 0x100) out += '*';
+	else append_seq(out, seq + h.qs, h.qe - h.qs, h.rev);
+	out += "\t*";
+	write_tags(out, h, words);
+	if (h.parent == h.id && h.has_p && hs.size() > 1) {                                 // supplementary alignments may exist (format.c:510-533)
+		bool any = false;
+		for (const Hit &q : hs) {
+			if (&q == &h || q.parent != q.id || !q.has_p) continue;
+			if (!any) { out += "\tSA:Z:"; any = true; }
+			const int ql = q.qe - q.qs, tl = q.re - q.rs, l_m = std::min(ql, tl), l_i = ql > tl ? ql - tl : 0, l_d = tl > ql ? tl - ql : 0;
+			const int clip5 = q.rev ? qlen - q.qe : q.qs, clip3 = q.rev ? q.qs : qlen - q.qe;
+			out += ref_names[q.rid]; out += ','; append_int(out, q.rs + 1); out += ','; out += q.rev ? '-' : '+'; out += ',';
+			if (clip5) { append_int(out, clip5); out += 'S'; }
+			if (l_m) { append_int(out, l_m); out += 'M'; }
+			if (l_i) { append_int(out, l_i); out += 'I'; }
+			if (l_d) { append_int(out, l_d); out += 'D'; }
+			if (clip3) { append_int(out, clip3); out += 'S'; }
+			out += ','; append_int(out, q.mapq); out += ','; append_int(out, q.blen - q.mlen + q.n_ambi); out += ';';
+		}
+	}
+}
+
+// the line of a read without a hit (format.c:419, 440, 481-488)
+void write_sam_unmapped(std::string &out, const char *qname, int qlen, const char *seq, int rep_len)
+{
+	out += qname; out += "\t4\t*\t0\t0\t*\t*\t0\t0\t"; out.append(seq, (size_t)qlen); out += "\t*\trl:i:"; append_int(out, rep_len); out += '\n';
 }
 
 // a hit record as a Hit; x: its alignment, where the record has been through the alignment call
@@ -333,6 +415,7 @@ struct MapCall {
 	const int32_t *q_rank = nullptr, *ref_rank = nullptr; // MM_F_NO_DIAG / MM_F_NO_DUAL: the names' ranks where the caller has them already (the stream: once for all chunks)
 	const mm2gb_map_sr_t *sr = nullptr;                  // mm2gb_map_reads_sr: short single-end reads (MM_F_SR); aln then holds its alignment's share, or is null
 	mm2gb_map_sr_out_t *sr_out = nullptr;                // ... and where its own counts go
+	const mm2gb_map_out_t *out = nullptr;                // the _out calls: SAM, = / X words (null, or zeroed: the PAF of the calls without it)
 };
 
 // what the stages of one batch share
@@ -360,18 +443,23 @@ struct Batch {
 	std::vector<mm2gb_reg_t> regs;
 	std::vector<int32_t> own_q_rank, own_ref_rank;       // MM_F_NO_DIAG / MM_F_NO_DUAL: the names' ranks, where the call did not bring them
 	const int32_t *q_rank = nullptr, *ref_rank = nullptr;
+	bool out_sam = false, out_eqx = false;               // the _out calls: SAM lines; = / X words
 	bool resident = false;                               // the resident path runs: no anchor, chain or kept anchor on the host (u, ca, a_off's anchors stay unset)
 	std::vector<mm2gb_est_err_t> est;                    // ... the walk's counts per hit record and sum_k per read instead
 	std::vector<uint64_t> sum_k;
 	int64_t link[2] = { 0, 0 };                          // seeded on the device: bytes the stages copied to the device / back (the MM2GB_DEBUG_PHASES line; profiles/ava_rate.py)
 	std::vector<std::string> lines;
+	std::vector<uint8_t> no_hit;                         // SAM: the read's line is the one of a read without a hit (not counted in n_mapped)
 	mm2gb_map_stats_t st = {};
 	mm2gb_map_sr_out_t sro = {};                         // the short-read path's own counts
 	double *const s_extra;
 
 	Batch(const MapCall &call, const mm2gb_map_opt_t &o)
 		: c(call), opt(o), aln(call.aln), R((size_t)call.n_reads), nt(std::max(1, o.host_threads)), so{ o.mid_occ, o.max_max_occ, o.occ_dist, o.q_occ_frac }, mt(R), occ(R),
-		  qlen(call.lens, call.lens + R), ref_len(call.ref_lens, call.ref_lens + call.n_ref), a_off(R + 1, 0), anchors(host_scratch(call.eng).anchors), lines(R), s_extra(call.s_extra) {}
+		  qlen(call.lens, call.lens + R), ref_len(call.ref_lens, call.ref_lens + call.n_ref), a_off(R + 1, 0), anchors(host_scratch(call.eng).anchors), lines(R), no_hit(R, 0), s_extra(call.s_extra)
+	{
+		out_sam = call.out && call.out->format == 1; out_eqx = call.out && (call.out->flag & MM2GB_F_EQX);
+	}
 	~Batch() { release_matches(); }
 	void release_matches() { for (auto &m : mt) mm2gb_matches_free(&m); }
 };
@@ -962,11 +1050,16 @@ struct Aligned {
 	std::vector<int64_t> reg_off, line_off;
 	std::vector<mm2gb_reg_t> rin;
 	mm2gb_align_out_t o;
+	std::vector<mm2gb_reg_t> treg;                       // the records that get a line, as the text and = / X calls take them
+	std::vector<mm2gb_aln_t> taln;
+	std::vector<int32_t> tread;
 	int64_t *tx_off = nullptr;
 	char *tx = nullptr;
+	mm2gb_aln_t *eq_aln = nullptr;                       // under MM_F_EQX: where the = / X words of every such record lie in eq_cigar
+	uint32_t *eq_cigar = nullptr;
 	Aligned() { memset(&o, 0, sizeof o); }
 	Aligned(const Aligned&) = delete;
-	~Aligned() { mm2gb_align_out_free(&o); free(tx_off); free(tx); }       // (freed on every way out)
+	~Aligned() { mm2gb_align_out_free(&o); free(tx_off); free(tx); free(eq_aln); free(eq_cigar); }       // (freed on every way out)
 };
 
 // 6a. the surviving records of every read, as map.c has them when it calls align_regs (map.c:756) ...
@@ -1017,6 +1110,8 @@ void rank_aligned(Batch &B, Aligned &A)
 		set_parent(opt.mask_level, opt.mask_len, hs, false, B.aln->opt.a * 2 + B.aln->opt.b);
 		select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, false, (int)(opt.max_gap * 0.8), hs);
 		set_mapq(hs, opt.min_chain_score, B.mt[r].rep_len, B.aln->opt.a, B.c.sr != nullptr);
+		bool first = true;                                                                            // mm_set_sam_pri (map.c:349)
+		for (Hit &h : hs) { h.sam_pri = h.id == h.parent && first; if (h.sam_pri) first = false; }
 	});
 }
 
@@ -1029,17 +1124,20 @@ int tag_text(Batch &B, Aligned &A)
 	A.line_off.assign(R + 1, 0);
 	for (size_t r = 0; r < R; ++r) A.line_off[r + 1] = A.line_off[r] + (int64_t)A.kept[r].size();
 	const int64_t n_out = A.line_off[R];
-	if (!aln->what || n_out == 0) return 0;
-	std::vector<mm2gb_reg_t> treg((size_t)n_out);
-	std::vector<mm2gb_aln_t> taln((size_t)n_out);
-	std::vector<int32_t> tread((size_t)n_out);
+	// SAM shows the words in its CIGAR column and MM_F_EQX wants other words than the text call reads: cg:Z is then left to the lines (append_cigar)
+	const int what = B.out_sam || B.out_eqx ? aln->what & ~MM2GB_TEXT_CG : aln->what;
+	std::vector<mm2gb_reg_t> &treg = A.treg;
+	std::vector<mm2gb_aln_t> &taln = A.taln;
+	std::vector<int32_t> &tread = A.tread;
+	treg.resize((size_t)n_out); taln.resize((size_t)n_out); tread.resize((size_t)n_out);
 	for (size_t r = 0; r < R; ++r)
 		for (size_t i = 0; i < A.kept[r].size(); ++i) {
 			const size_t j = (size_t)A.line_off[r] + i;
 			treg[j] = A.o.regs[A.kept[r][i].aln]; taln[j] = A.o.aln[A.kept[r][i].aln]; tread[j] = (int32_t)r;
 		}
+	if (!what || n_out == 0) return 0;
 	if (aln->text_on_device <= 0)                         // text_on_device 0: the host form (profiles/aln_text_rate.json)
-		return (c.spl ? mm2gb_aln_text_splice_host : mm2gb_aln_text_host)(aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar,
+		return (c.spl ? mm2gb_aln_text_splice_host : mm2gb_aln_text_host)(what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar,
 		                                                                  B.nt, &A.tx_off, &A.tx);
 	std::vector<int64_t> ref_at((size_t)c.n_ref + 1, 0), read_at(R + 1, 0);
 	for (int32_t i = 0; i < c.n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + c.ref_lens[i];
@@ -1047,21 +1145,54 @@ int tag_text(Batch &B, Aligned &A)
 	// the alignment call's device backend says what it left resident (engine.h: al_resident): this batch's residues, or nothing
 	Engine &e = c.eng->e;
 	if (aln->align_on_device >= 0 && e.al_resident[0] == ref_at.back() && e.al_resident[1] == read_at.back())
-		return aln_text_resident(e, c.spl != nullptr, c.spl ? "mm2gb_map_reads_splice" : "mm2gb_map_reads_aln", aln->what, c.n_ref, c.ref_lens, ref_at.data(), c.n_reads, c.lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
+		return aln_text_resident(e, c.spl != nullptr, c.spl ? "mm2gb_map_reads_splice" : "mm2gb_map_reads_aln", what, c.n_ref, c.ref_lens, ref_at.data(), c.n_reads, c.lens, read_at.data(), n_out, treg.data(), tread.data(), taln.data(),
 		                         A.o.cigar, &A.tx_off, &A.tx);
-	return (c.spl ? mm2gb_aln_text_splice_gpu : mm2gb_aln_text_gpu)(c.eng, aln->what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, &A.tx_off, &A.tx);
+	return (c.spl ? mm2gb_aln_text_splice_gpu : mm2gb_aln_text_gpu)(c.eng, what, c.n_ref, aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, treg.data(), tread.data(), taln.data(), A.o.cigar, &A.tx_off, &A.tx);
+}
+
+// 6d. under MM_F_EQX: the = / X words of the same records, in one call (mm_update_cigar_eqx, align.c:169-238, as a pass after everything that reads the M words)
+int eqx_words(Batch &B, Aligned &A)
+{
+	const MapCall &c = B.c;
+	const int64_t n_out = (int64_t)A.treg.size();
+	if (!B.out_eqx || n_out == 0) return 0;
+	if (c.out->eqx_on_device <= 0)                         // eqx_on_device 0: the host form (profiles/eqx_rate.json)
+		return mm2gb_cigar_eqx_host(c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, A.treg.data(), A.tread.data(), A.taln.data(), A.o.cigar, B.nt, &A.eq_aln, &A.eq_cigar);
+	std::vector<int64_t> ref_at((size_t)c.n_ref + 1, 0), read_at(B.R + 1, 0);
+	for (int32_t i = 0; i < c.n_ref; ++i) ref_at[(size_t)i + 1] = ref_at[(size_t)i] + c.ref_lens[i];
+	for (size_t i = 0; i < B.R; ++i) read_at[i + 1] = read_at[i] + c.lens[i];
+	Engine &e = c.eng->e;                                 // (as tag_text: the batch's residues where the alignment or the text call left them)
+	if (B.aln->align_on_device >= 0 && e.al_resident[0] == ref_at.back() && e.al_resident[1] == read_at.back())
+		return cigar_eqx_resident(e, "mm2gb_map_reads", c.n_ref, c.ref_lens, ref_at.data(), c.n_reads, c.lens, read_at.data(), n_out, A.treg.data(), A.tread.data(), A.taln.data(), A.o.cigar,
+		                          &A.eq_aln, &A.eq_cigar);
+	return mm2gb_cigar_eqx_gpu(c.eng, c.n_ref, B.aln->ref_seqs, c.ref_lens, c.n_reads, c.seqs, c.lens, n_out, A.treg.data(), A.tread.data(), A.taln.data(), A.o.cigar, &A.eq_aln, &A.eq_cigar);
 }
 
 // ... then the lines
 void aligned_lines(Batch &B, const Aligned &A)
 {
+	const int64_t out_flag = B.c.out ? B.c.out->flag : 0;
 	for_each_on_threads(B.R, B.nt, 1, [&](size_t r) {
+		const char *qname = B.c.names[r] ? B.c.names[r] : "*";
+		if (B.out_sam && A.kept[r].empty() && !(out_flag & MM2GB_F_SAM_HIT_ONLY)) {                   // map.c:1367
+			write_sam_unmapped(B.lines[r], qname, B.c.lens[r], B.c.seqs[r], B.mt[r].rep_len);
+			B.no_hit[r] = 1;
+		}
 		for (size_t i = 0; i < A.kept[r].size(); ++i) {
 			const Hit &h = A.kept[r][i];
 			const size_t j = (size_t)A.line_off[r] + i;
 			if (B.c.sr && (B.opt.flag & MM2GB_F_NO_PRINT_2ND) && h.id != h.parent) continue;          // map.c:1359
-			paf_line(B, r, h, h.has_p ? A.o.cigar + A.o.aln[h.aln].cigar_off : nullptr);
+			const uint32_t *words = h.has_p ? A.o.cigar + A.o.aln[h.aln].cigar_off : nullptr;
+			const bool eq = h.has_p && A.eq_aln;
+			const uint32_t *shown = eq ? A.eq_cigar + A.eq_aln[j].cigar_off : words;
+			const int32_t n_shown = eq ? A.eq_aln[j].n_cigar : h.n_cigar;
+			if (B.out_sam) write_sam(B.lines[r], qname, B.c.lens[r], B.c.seqs[r], h, A.kept[r], B.c.ref_names, out_flag, shown, n_shown, words);
+			else {
+				paf_line(B, r, h, words);
+				if (B.out_eqx && h.has_p && (B.aln->what & MM2GB_TEXT_CG)) { B.lines[r] += "\tcg:Z:"; append_cigar(B.lines[r], shown, n_shown); }
+			}
 			if (A.tx_off) B.lines[r].append(A.tx + A.tx_off[j], (size_t)(A.tx_off[j + 1] - A.tx_off[j]));
+			if (B.out_sam) { B.lines[r] += "\trl:i:"; append_int(B.lines[r], B.mt[r].rep_len); }     // format.c:540: after cs:Z / MD:Z in SAM
 			B.lines[r] += '\n';
 		}
 	});
@@ -1075,7 +1206,7 @@ int emit_paf(Batch &B)
 	char *buf = (char*)malloc(total + 1);
 	if (!buf) return fail("mm2gb_map_reads: out of memory");
 	size_t at = 0;
-	for (const auto &l : B.lines) { memcpy(buf + at, l.data(), l.size()); at += l.size(); if (!l.empty()) ++B.st.n_mapped; }
+	for (const auto &l : B.lines) { memcpy(buf + at, l.data(), l.size()); at += l.size(); if (!l.empty() && !B.no_hit[(size_t)(&l - B.lines.data())]) ++B.st.n_mapped; }
 	buf[total] = 0;
 	*B.c.paf_out = buf; *B.c.paf_len = (int64_t)total;
 	B.st.n_reads = B.c.n_reads;
@@ -1109,6 +1240,13 @@ int map_reads_body(const MapCall &c)
 	if (c.aln && (opt.flag & overlap_bits)) {
 		const char *bit = opt.flag & MM2GB_F_ALL_CHAINS ? "MM_F_ALL_CHAINS" : opt.flag & MM2GB_F_NO_DIAG ? "MM_F_NO_DIAG" : "MM_F_NO_DUAL";
 		return fail(std::string(c.spl ? "mm2gb_map_reads_splice: " : "mm2gb_map_reads_aln: ") + bit + " is not supported with base-level alignment (read overlap runs without it)");
+	}
+	if (c.out) {
+		const std::string who = c.sr ? "mm2gb_map_reads_sr_out: " : c.spl ? "mm2gb_map_reads_splice_out: " : "mm2gb_map_reads_aln_out: ";
+		if (c.out->format != 0 && c.out->format != 1) return fail(who + "format is 0 (PAF) or 1 (SAM)");
+		if (c.out->flag & ~(int64_t)(MM2GB_F_EQX | MM2GB_F_SOFTCLIP | MM2GB_F_SAM_HIT_ONLY)) return fail(who + "of mm_mapopt_t::flag the output options take only MM_F_EQX, MM_F_SOFTCLIP and MM_F_SAM_HIT_ONLY");
+		if (c.out->format == 1 && !c.aln) return fail(who + "SAM output needs base-level alignment (minimap2 -a implies -c)");
+		if ((c.out->flag & MM2GB_F_EQX) && !c.aln) return fail(who + "MM_F_EQX needs base-level alignment (there is no CIGAR to rewrite)");
 	}
 	if (!c.eng || !c.ix || !c.paf_out || !c.paf_len || c.n_reads < 0 || c.n_ref <= 0 || !c.ref_names || !c.ref_lens || (c.n_reads > 0 && (!c.names || !c.seqs || !c.lens)))
 		return fail("mm2gb_map_reads: null argument");
@@ -1161,7 +1299,7 @@ int map_reads_body(const MapCall &c)
 			lap(B.s_extra[0]);
 			rank_aligned(B, A);
 			lap(B.s_extra[1]);
-			if (tag_text(B, A)) return -1;
+			if (tag_text(B, A) || eqx_words(B, A)) return -1;
 			lap(B.s_extra[2]);
 			aligned_lines(B, A);
 		}
@@ -1214,7 +1352,7 @@ int map_reads_body(const MapCall &c)
 		lap(B.s_extra[0]);
 		rank_aligned(B, A);                                                                           // 6b
 		lap(B.s_extra[1]);
-		if (tag_text(B, A)) return -1;                                                                // 6c
+		if (tag_text(B, A) || eqx_words(B, A)) return -1;                                             // 6c, 6d
 		lap(B.s_extra[2]);
 		aligned_lines(B, A);
 	}
@@ -1416,6 +1554,16 @@ int mm2gb_map_reads_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, cons
                        const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
                        mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out)
 {
+	return mm2gb_map_reads_sr_out(eng, ix, k, ref_names, ref_lens, n_ref, opt, sr, n_reads, names, seqs, lens, paf_out, paf_len, stats, sr_out, nullptr);
+}
+
+int mm2gb_map_reads_sr_out(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref, const mm2gb_map_opt_t *opt,
+                           const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
+                           mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out, const mm2gb_map_out_t *out)
+{
+	// (what the output options rule out is said before anything else is looked at, the engine included)
+	if (out && sr && !sr->align && (out->format == 1 || (out->flag & MM2GB_F_EQX)))
+		return fail(std::string("mm2gb_map_reads_sr_out: ") + (out->format == 1 ? "SAM output needs base-level alignment (minimap2 -a implies -c)" : "MM_F_EQX needs base-level alignment (there is no CIGAR to rewrite)"));
 	if (!eng) return fail("mm2gb: null engine");
 	mm2gb_map_aln_t aln;
 	bool aligned = false;
@@ -1423,13 +1571,21 @@ int mm2gb_map_reads_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, cons
 	double extra[3] = { 0, 0, 0 };
 	if (sr_out) memset(sr_out, 0, sizeof *sr_out);
 	MapCall c = { eng, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
-	c.sr = sr; c.sr_out = sr_out;
+	c.sr = sr; c.sr_out = sr_out; c.out = out;
 	return map_reads_try(c);
 }
 
 int mm2gb_map_reads_stream_sr(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
                               int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
                               const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out)
+{
+	return mm2gb_map_reads_stream_sr_out(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt, sr, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, sr_out, nullptr);
+}
+
+int mm2gb_map_reads_stream_sr_out(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                  int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                  const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out,
+                                  const mm2gb_map_out_t *out)
 {
 	mm2gb_map_aln_t aln;
 	bool aligned = false;
@@ -1438,7 +1594,7 @@ int mm2gb_map_reads_stream_sr(mm2gb_engine_t *const *engines, int n_engines, con
 	mm2gb_map_sr_out_t own;
 	if (sr_out) memset(sr_out, 0, sizeof *sr_out);
 	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
-	c.sr = sr; c.sr_out = sr_out ? sr_out : &own;
+	c.sr = sr; c.sr_out = sr_out ? sr_out : &own; c.out = out;
 	return stream_body(engines, n_engines, chunk_bases, c);
 }
 
@@ -1453,9 +1609,18 @@ int mm2gb_map_reads_aln(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, con
                         const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                         char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
 {
+	return mm2gb_map_reads_aln_out(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, aln, n_reads, names, seqs, lens, paf_out, paf_len, stats, s_extra, nullptr);
+}
+
+int mm2gb_map_reads_aln_out(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                            const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                            char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out)
+{
 	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_aln: ") + why);
 	double s3[3] = { 0, 0, 0 };
-	const int rc = map_reads_try({ eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 });
+	MapCall c = { eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 };
+	c.out = out;
+	const int rc = map_reads_try(c);
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
 }
@@ -1511,9 +1676,18 @@ int mm2gb_map_reads_stream_aln(mm2gb_engine_t *const *engines, int n_engines, co
                                int32_t n_ref, const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs,
                                const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
 {
+	return mm2gb_map_reads_stream_aln_out(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt_in, aln, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, s_extra, nullptr);
+}
+
+int mm2gb_map_reads_stream_aln_out(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                   int32_t n_ref, const mm2gb_map_opt_t *opt_in, const mm2gb_map_aln_t *aln, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                   const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out)
+{
 	if (const char *why = bad_aln(aln)) return fail(std::string("mm2gb_map_reads_stream_aln: ") + why);
 	double s3[3] = { 0, 0, 0 };
-	const int rc = stream_body(engines, n_engines, chunk_bases, { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 });
+	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, aln, s3 };
+	c.out = out;
+	const int rc = stream_body(engines, n_engines, chunk_bases, c);
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
 }
@@ -1539,11 +1713,18 @@ int mm2gb_map_reads_splice(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, 
                            const mm2gb_map_opt_t *opt_in, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
                            char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
 {
+	return mm2gb_map_reads_splice_out(eng, ix, k, ref_names, ref_lens, n_ref, opt_in, spl, n_reads, names, seqs, lens, paf_out, paf_len, stats, s_extra, nullptr);
+}
+
+int mm2gb_map_reads_splice_out(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref,
+                               const mm2gb_map_opt_t *opt_in, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens,
+                               char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out)
+{
 	mm2gb_map_aln_t aln;
 	if (const char *why = splice_as_aln(spl, aln)) return fail(std::string("mm2gb_map_reads_splice: ") + why);
 	double s3[3] = { 0, 0, 0 };
 	MapCall c = { eng, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, &aln, s3 };
-	c.spl = &spl->opt;
+	c.spl = &spl->opt; c.out = out;
 	const int rc = map_reads_try(c);
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
@@ -1553,14 +1734,41 @@ int mm2gb_map_reads_stream_splice(mm2gb_engine_t *const *engines, int n_engines,
                                   int32_t n_ref, const mm2gb_map_opt_t *opt_in, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs,
                                   const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra)
 {
+	return mm2gb_map_reads_stream_splice_out(engines, n_engines, ix, k, ref_names, ref_lens, n_ref, opt_in, spl, n_reads, names, seqs, lens, chunk_bases, paf_out, paf_len, stats, s_extra, nullptr);
+}
+
+int mm2gb_map_reads_stream_splice_out(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                                      int32_t n_ref, const mm2gb_map_opt_t *opt_in, const mm2gb_map_splice_t *spl, int32_t n_reads, const char *const *names, const char *const *seqs,
+                                      const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, double *s_extra, const mm2gb_map_out_t *out)
+{
 	mm2gb_map_aln_t aln;
 	if (const char *why = splice_as_aln(spl, aln)) return fail(std::string("mm2gb_map_reads_stream_splice: ") + why);
 	double s3[3] = { 0, 0, 0 };
 	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt_in, n_reads, names, seqs, lens, paf_out, paf_len, stats, &aln, s3 };
-	c.spl = &spl->opt;
+	c.spl = &spl->opt; c.out = out;
 	const int rc = stream_body(engines, n_engines, chunk_bases, c);
 	if (s_extra) for (int i = 0; i < 3; ++i) s_extra[i] = s3[i];
 	return rc;
+}
+
+void mm2gb_map_out_init(mm2gb_map_out_t *o) { if (o) memset(o, 0, sizeof *o); }
+
+// mm_write_sam_hdr (format.c:118-139) without a read group: an @SQ line per reference, then this project's @PG line
+int mm2gb_sam_header(int32_t n_ref, const char *const *ref_names, const int32_t *ref_lens, char **out, int64_t *len)
+{
+	if (!out || !len || n_ref < 0 || (n_ref > 0 && (!ref_names || !ref_lens))) return fail("mm2gb_sam_header: null argument");
+	*out = nullptr; *len = 0;
+	std::string s;
+	for (int32_t i = 0; i < n_ref; ++i) {
+		if (!ref_names[i]) return fail("mm2gb_sam_header: a reference without a name");
+		s += "@SQ\tSN:"; s += ref_names[i]; s += "\tLN:"; append_int(s, ref_lens[i]); s += '\n';
+	}
+	s += "@PG\tID:mm2-gb_amd\tPN:mm2-gb_amd\n";
+	char *buf = (char*)malloc(s.size() + 1);
+	if (!buf) return fail("mm2gb_sam_header: out of memory");
+	memcpy(buf, s.c_str(), s.size() + 1);
+	*out = buf; *len = (int64_t)s.size();
+	return 0;
 }
 
 } // extern "C"
