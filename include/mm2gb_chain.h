@@ -288,6 +288,10 @@ int  mm2gb_collect_seeds_host(int64_t opt_flag, int64_t n_reads, const int64_t *
                               const uint64_t *hits, const int32_t *qlen, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len,
                               const int32_t *ref_rank, int n_threads, int64_t *anchor_off, mm2gb_anchor_t *anchors);   /* = mm2gb_collect_seeds_gpu, on host threads */
 int  mm2gb_collect_matches(const mm2gb_index_t *ix, const char *seq, int32_t len, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out);
+/* mm2gb_collect_matches_frag: the same for a fragment of one or two segments seeded as ONE list (map.c:186-200, 663-666; paired ends): every segment sketched by itself,
+ * the second one's minimizers moved behind the first's (position + lens[0]) with segment id 1 (mm2gb_seed_t::seg_tandem), and the q-occurrence filter, the tandem
+ * test, the streaks of mm_seed_select, rep_len and mini_pos on the joint list of lens[0] + lens[1] bases.  n_segs = 1 is mm2gb_collect_matches. */
+int  mm2gb_collect_matches_frag(const mm2gb_index_t *ix, int32_t n_segs, const char *const *seqs, const int32_t *lens, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out);
 void mm2gb_matches_free(mm2gb_matches_t *m);
 
 /* ---- the same stages on the device (csrc/seed_kernels.hip), byte-identical to the host functions above, for a batch of sequences laid
@@ -315,6 +319,11 @@ typedef struct {
 } mm2gb_match_batch_t;
 int  mm2gb_collect_matches_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_reads,
                                const int64_t *seq_off, const char *seqs, mm2gb_match_batch_t *out);
+/* mm2gb_collect_matches_frag_gpu: the sequences frag_off[f] .. frag_off[f + 1] (one or two; frag_off has n_frag + 1 entries, from 0 to n_seqs) are fragment f, and the
+ * result is per FRAGMENT (seed_off and rep_len have n_frag entries): what mm2gb_collect_matches_frag returns for it, record for record.  After the sketch one kernel
+ * moves the second mates' minimizers and re-labels every minimizer with its fragment; the match kernels then run on per-fragment offsets. */
+int  mm2gb_collect_matches_frag_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_seqs, const int64_t *seq_off, const char *seqs,
+                                    int64_t n_frag, const int64_t *frag_off, mm2gb_match_batch_t *out);
 void mm2gb_match_batch_free(mm2gb_match_batch_t *m);
 
 /* ---- the index built on the device (csrc/index_kernels.hip): the sequences are sketched there in chunks of whole sequences (at most
@@ -813,7 +822,7 @@ int  mm2gb_align_regs_sr_gpu(mm2gb_engine_t *eng, const mm2gb_align_opt_t *opt, 
  * sr_out (optional): the call's own counts and the seconds of the alignment call, the steps after it and the text; stats->s_chain holds stages 2 and 3 together, and
  * n_rechained / n_rmq_tied stay 0 (there is no re-chaining stage and no RMQ here).  The stream form sums them over chunks.
  * Refused by name: an HPC index (align.c:583), MM_F_RMQ (options.c:173), MM_F_QSTRAND, MM_F_EQX, MM_F_SPLICE, the read-overlap bits, options without MM_F_SR, align != 0
- * without ref_seqs, what != 0 with align == 0; more than one segment and SAM output do not exist.  mm2gb_map_sr_init: max_occ = 5000, max_frag_len = 800, align = 0 and
+ * without ref_seqs, what != 0 with align == 0; mates of a pair come through mm2gb_map_frags_sr (below).  mm2gb_map_sr_init: max_occ = 5000, max_frag_len = 800, align = 0 and
  * mm2gb_align_sr_opt_init's values in opt. */
 typedef struct {
 	const char *const *ref_seqs;      /* the reference sequences as text, in the index's order (not read while align is 0; may then be NULL) */
@@ -824,8 +833,8 @@ typedef struct {
 	int32_t max_occ, max_frag_len;    /* mm_mapopt_t::max_occ, max_frag_len: the two fields mm2gb_map_opt_t has no room for */
 } mm2gb_map_sr_t;
 typedef struct {
-	int64_t n_chain_calls;            /* chaining calls made (one per distinct max_dist_x, both rounds) */
-	int64_t n_rescued;                /* reads that went through the max_occ round */
+	int64_t n_chain_calls;            /* chaining calls made (one per distinct max_dist_x -- with fragments: per distinct (n_seg, max_dist_x, max_dist_y) --, both rounds) */
+	int64_t n_rescued;                /* reads (fragments) that went through the max_occ round */
 	int64_t n_tied_reads;             /* reads whose anchors the host's heap ordered (two equal index entries) */
 	int64_t sr_counts[MM2GB_SR_N_COUNTS];
 	double  s_extra[3];               /* seconds: the alignment call, the steps after it, the text */
@@ -853,7 +862,8 @@ int  mm2gb_map_reads_stream_sr(mm2gb_engine_t *const *engines, int n_engines, co
  *      Refused by name: a format other than 0 / 1, a flag bit other than the three, SAM or MM2GB_F_EQX on a call that does not align
  *      (mm2gb_map_reads_sr_out with align = 0: -a implies -c); the read-overlap bits are refused with any alignment as before.  Every refusal of the
  *      calls above stays, MM_F_EQX in the mapping options' and the alignment options' flag included: the bit belongs to mm2gb_map_out_t alone.
- *      Not taken: -L (the CIGAR in CG:B:I), qualities (reads are as from FASTA), -R, -y, --paf-no-hit, --secondary-seq, paired ends. ---- */
+ *      Not taken: -L (the CIGAR in CG:B:I), qualities (reads are as from FASTA), -R, -y, --paf-no-hit, --secondary-seq, SAM for paired ends (the pair fields of
+ *      mm_write_sam3's n_seg > 1 branches). ---- */
 #define MM2GB_F_SOFTCLIP     0x80000LL
 #define MM2GB_F_SAM_HIT_ONLY 0x40000000LL
 typedef struct {
@@ -882,6 +892,48 @@ int  mm2gb_map_reads_stream_sr_out(mm2gb_engine_t *const *engines, int n_engines
                                    int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
                                    const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out,
                                    const mm2gb_map_out_t *out);
+
+/* ---- paired-end short reads (minimap2 -x sr r1.fq r2.fq, without -c), to the PAF: fragments of two mates seeded and chained as one query.
+ *      mm2gb_frag_offsets: fragments as map.c:1297-1304 forms them under MM_F_FRAG_MODE -- a run of consecutive reads with the same name, a trailing "/" + one digit
+ *      not being part of the name (mm_qname_same, bseq.h:31-44).  frag_off: room for n_reads + 1 entries; *n_frag fragments, frag_off[*n_frag] = n_reads.  Two input
+ *      files are the same thing interleaved.
+ *      mm2gb_map_frags_sr / mm2gb_map_frags_stream_sr: the arguments of mm2gb_map_reads_sr / _stream_sr plus the fragments, pe_ori (mm_mapopt_t::pe_ori, 0..3; -x sr: 1) and
+ *      an optional mm2gb_map_out_t.  A fragment of one read goes the single-end way, with the bytes of mm2gb_map_reads_sr.  For a fragment of two: mate j is
+ *      reverse-complemented before mapping when (j == 0 && pe_ori >> 1 & 1) || (j == 1 && pe_ori & 1) and its hits' qs / qe / strand are flipped back afterwards
+ *      (map.c:1169-1199); the mates are seeded as one list (mm2gb_collect_matches_frag, or its device form with seeding_on_device = 1, the matches left resident for
+ *      the heap-order collection), anchors collected with qlen = qlen_sum, one chaining DP at n_seg = 2 with max_dist_x = max(max_frag_len - qlen_sum, max_gap) (or
+ *      max_gap_ref) and max_dist_y = max(qlen_sum, max_gap) -- at n_seg > 1 max_dist_y also bounds the reference gap between anchors of different mates, so a chaining
+ *      call is made per distinct (n_seg, max_dist_x, max_dist_y) of the batch: n_chain_calls --; the rescue of map.c:708-731 for a fragment with rep_len > 0 that has no
+ *      chain or whose best-scoring chain lacks a mate; mm_gen_regs with qlen_sum and the hash of the FIRST mate's name, mm_set_parent, mm_select_sub_multi (pe.c:6-43),
+ *      mm_seg_gen (hit.c:331-385) into per-mate hits, per mate mm_set_parent and mm_set_mapq with the fragment's rep_len, and the PAF lines of mate 0, then mate 1,
+ *      each under its own name and length.  The stream form cuts chunks only between fragments.  stats->n_mapped counts fragments with a line.
+ *      Refused by name: sr->align != 0 with a two-mate fragment in the batch ("paired ends with base-level alignment": -c, mm_pair and mm_set_pe_thru are not built), a
+ *      mm2gb_map_out_t with SAM or MM_F_EQX, a fragment of more than two reads (MM_MAX_SEG > 2), pe_ori outside 0..3, and everything mm2gb_map_reads_sr refuses.
+ *      Not built: MM_F_INDEPEND_SEG.
+ *      mm2gb_select_sub_multi_host / mm2gb_seg_gen_host: the two steps by themselves, batched over fragments on the host (there is no device form: at that stage the
+ *      records and kept anchors lie on the host).  qlens: two entries per fragment (the second ignored where n_segs[f] is 1).
+ *      select_sub_multi: fragment f's records regs[reg_off[f] .. reg_off[f + 1]) (after mm_set_parent) are squeezed in place to their first n_kept[f], ids and parents
+ *      re-synchronised (mm_sync_regs).  seg_gen: unit 2 f + s of *out is fragment f's segment s: its records (seg_split and seg_id set in flags: bits 15, 16-23) and its
+ *      anchors with y in the mate's own coordinates; records' `as` count from the unit's first anchor.  Free with mm2gb_seg_out_free. ---- */
+int  mm2gb_frag_offsets(int32_t n_reads, const char *const *names, int32_t *frag_off, int32_t *n_frag);
+int  mm2gb_map_frags_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref, const mm2gb_map_opt_t *opt,
+                        const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
+                        mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out, int32_t n_frag, const int32_t *frag_off, int32_t pe_ori, const mm2gb_map_out_t *out);
+int  mm2gb_map_frags_stream_sr(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                               int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
+                               const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out,
+                               int32_t n_frag, const int32_t *frag_off, int32_t pe_ori, const mm2gb_map_out_t *out);
+typedef struct {
+	int64_t *reg_off;                 /* 2 * n_frag + 1 */
+	mm2gb_reg_t *regs;
+	int64_t *anchor_off;              /* 2 * n_frag + 1 */
+	mm2gb_anchor_t *anchors;
+} mm2gb_seg_out_t;
+int  mm2gb_select_sub_multi_host(float pri_ratio, float pri1, float pri2, int32_t min_diff, int32_t best_n, int64_t n_frag, const int32_t *n_segs, const int32_t *qlens,
+                                 const int32_t *max_gap_ref, const int64_t *reg_off, mm2gb_reg_t *regs, int32_t *n_kept);
+int  mm2gb_seg_gen_host(int64_t n_frag, const int32_t *n_segs, const int32_t *qlens, const uint32_t *hash, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                        const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_seg_out_t *out);
+void mm2gb_seg_out_free(mm2gb_seg_out_t *out);
 
 #ifdef __cplusplus
 }

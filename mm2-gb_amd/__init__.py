@@ -96,7 +96,9 @@ CORE_SYMBOLS = ["mm2gb_last_error", "mm2gb_version", "mm2gb_config_defaults", "m
                 "mm2gb_map_opt_init_sr", "mm2gb_collect_seeds_heap_host", "mm2gb_collect_seeds_heap_gpu", "mm2gb_map_sr_init", "mm2gb_map_reads_sr",
                 "mm2gb_cigar_eqx_host", "mm2gb_cigar_eqx_gpu", "mm2gb_cigar_eqx_gpu_info", "mm2gb_map_out_init", "mm2gb_sam_header",
                 "mm2gb_map_reads_aln_out", "mm2gb_map_reads_stream_aln_out", "mm2gb_map_reads_splice_out", "mm2gb_map_reads_stream_splice_out",
-                "mm2gb_map_reads_sr_out", "mm2gb_map_reads_stream_sr_out"]
+                "mm2gb_map_reads_sr_out", "mm2gb_map_reads_stream_sr_out",
+                "mm2gb_collect_matches_frag", "mm2gb_collect_matches_frag_gpu", "mm2gb_frag_offsets", "mm2gb_map_frags_sr", "mm2gb_map_frags_stream_sr",
+                "mm2gb_select_sub_multi_host", "mm2gb_seg_gen_host", "mm2gb_seg_out_free"]
 BOUNDARY_SYMBOLS = ["init_stream_gpu", "chain_stream_gpu", "finish_stream_gpu", "free_stream_gpu"]
 
 
@@ -1448,6 +1450,22 @@ class SeedIndex:
         lib().mm2gb_matches_free(C.byref(m))
         return out
 
+    def matches_frag(self, mates, mid_occ, max_max_occ=4095, occ_dist=500, q_occ_frac=0.01):
+        """mm2gb_collect_matches_frag for one fragment: mates = one or two sequences (bytes; a mate that pe_ori turns is given turned), seeded as one list of their summed
+        length (the second mate's seeds carry segment id 1 in seeds[:, 3] and positions past the first mate).  The dict matches() returns, qlen the summed length."""
+        mates = [bytes(s) for s in mates]
+        opt = SeedOpt(int(mid_occ), int(max_max_occ), int(occ_dist), float(q_occ_frac))
+        m = Matches()
+        arr = (C.c_char_p * max(len(mates), 1))(*mates)
+        lens = np.ascontiguousarray([len(s) for s in mates], dtype=np.int32)
+        fn = lib().mm2gb_collect_matches_frag
+        fn.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(SeedOpt), C.POINTER(Matches)]
+        _check(fn(self._h, len(mates), arr, lens.ctypes.data, C.byref(opt), C.byref(m)))
+        out = dict(seeds=_take(m.seeds, m.n_seeds * 4, np.uint32).reshape(-1, 4), hits=_take(m.hits, m.n_hits, np.uint64), qlen=int(lens.sum()),
+                   rep_len=int(m.rep_len), mini_pos=_take(m.mini_pos, m.n_mini_pos, np.uint64))
+        lib().mm2gb_matches_free(C.byref(m))
+        return out
+
 
 class MatchBatch(C.Structure):
     _fields_ = [("n_seeds", C.c_int64), ("n_hits", C.c_int64), ("seed_off", C.c_void_p), ("seeds", C.c_void_p), ("hit_off", C.c_void_p),
@@ -1503,8 +1521,33 @@ def _engine_collect_matches(self, index, seqs, mid_occ, max_max_occ=4095, occ_di
                  rep_len=int(rep_len[r]), mini_pos=mini_pos[seed_off[r]:seed_off[r + 1]]) for r in range(R)]
 
 
+def _engine_collect_matches_frag(self, index, frags, mid_occ, max_max_occ=4095, occ_dist=500, q_occ_frac=0.01):
+    """mm2gb_collect_matches_frag_gpu: frags = a list of fragments, each a list of one or two sequences (bytes); for every fragment the dict SeedIndex.matches_frag
+    returns, computed on the device in one call."""
+    frags = [[bytes(s) for s in f] for f in frags]
+    seqs, off, flat = _lay_end_to_end([s for f in frags for s in f])
+    frag_off = np.zeros(len(frags) + 1, np.int64)
+    frag_off[1:] = np.cumsum([len(f) for f in frags])
+    opt = SeedOpt(int(mid_occ), int(max_max_occ), int(occ_dist), float(q_occ_frac))
+    m = MatchBatch()
+    fn = lib().mm2gb_collect_matches_frag_gpu
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SeedOpt), C.c_int64, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p, C.POINTER(MatchBatch)]
+    _check(fn(self._h, index._h if index is not None else None, C.byref(opt), len(seqs), off.ctypes.data, flat, len(frags), frag_off.ctypes.data, C.byref(m)))
+    R = len(frags)
+    seed_off = _take(m.seed_off, R + 1, np.int64)
+    seeds = _take(m.seeds, m.n_seeds * 4, np.uint32).reshape(-1, 4)
+    hit_off = _take(m.hit_off, m.n_seeds + 1, np.int64)
+    hits = _take(m.hits, m.n_hits, np.uint64)
+    mini_pos = _take(m.mini_pos, m.n_seeds, np.uint64)
+    rep_len = _take(m.rep_len, R, np.int32)
+    lib().mm2gb_match_batch_free(C.byref(m))
+    return [dict(seeds=seeds[seed_off[r]:seed_off[r + 1]], hits=hits[hit_off[seed_off[r]]:hit_off[seed_off[r + 1]]], qlen=sum(len(s) for s in frags[r]),
+                 rep_len=int(rep_len[r]), mini_pos=mini_pos[seed_off[r]:seed_off[r + 1]]) for r in range(R)]
+
+
 Engine.sketch = _engine_sketch
 Engine.collect_matches = _engine_collect_matches
+Engine.collect_matches_frag = _engine_collect_matches_frag
 
 
 class MapOpt(C.Structure):
@@ -1819,8 +1862,87 @@ def _out_needs_align(out, align):
         raise Mm2gbError("map_reads: SAM output and eqx need base-level alignment, an align= argument (minimap2 -a implies -c)")
 
 
-def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None, out=None):
+def frag_offsets(names):
+    """mm2gb_frag_offsets: where the fragments of a list of read names begin (one more entry than fragments, the last one len(names)): a run of consecutive reads with
+    the same name is a fragment, a trailing "/" + digit not being part of the name (the reference's mm_qname_same)."""
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
+    off = np.zeros(len(names) + 1, np.int32)
+    n = C.c_int32()
+    fn = lib().mm2gb_frag_offsets
+    fn.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.POINTER(C.c_int32)]
+    _check(fn(len(names), arr, off.ctypes.data, C.byref(n)))
+    return off[:n.value + 1].copy()
+
+
+def interleave(reads1, reads2):
+    """Two files of mates as the one list the mapping calls take: reads1[0], reads2[0], reads1[1], ...; both lists of (name, sequence), equally long."""
+    if len(reads1) != len(reads2):
+        raise Mm2gbError("interleave: the two lists differ in length")
+    return [r for pair in zip(reads1, reads2) for r in pair]
+
+
+class SegOut(C.Structure):
+    _fields_ = [("reg_off", C.c_void_p), ("regs", C.c_void_p), ("anchor_off", C.c_void_p), ("anchors", C.c_void_p)]
+
+
+def _frag_arrays(n_segs, qlens):
+    ns = np.ascontiguousarray(n_segs, dtype=np.int32)
+    ql = np.zeros((len(ns), 2), np.int32)
+    for f, q in enumerate(qlens):
+        ql[f, :min(len(q), 2)] = q[:2]                     # (a fragment of three: n_segs says so, and the call refuses it)
+    return ns, ql
+
+
+def select_sub_multi_host(regs, qlens, max_gap_ref, pri_ratio=0.5, pri1=0.2, pri2=0.7, min_diff=42, best_n=20):
+    """mm2gb_select_sub_multi_host (mm_select_sub_multi, pe.c:6-43): regs = per fragment a REG_DTYPE array after mm_set_parent, qlens = per fragment its one or two
+    mate lengths, max_gap_ref = per fragment the chaining call's max_dist_x.  Returns per fragment the records that stay, ids and parents re-synchronised."""
+    ns, ql = _frag_arrays([len(q) for q in qlens], qlens)
+    off = np.concatenate([[0], np.cumsum([len(r) for r in regs])]).astype(np.int64)
+    flat = np.concatenate([np.asarray(r, REG_DTYPE) for r in regs]) if len(regs) and off[-1] else np.zeros(0, REG_DTYPE)
+    flat = np.ascontiguousarray(flat)
+    gap = np.ascontiguousarray(max_gap_ref, dtype=np.int32)
+    kept = np.zeros(max(len(ns), 1), np.int32)
+    fn = lib().mm2gb_select_sub_multi_host
+    fn.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(fn(pri_ratio, pri1, pri2, int(min_diff), int(best_n), len(ns), ns.ctypes.data, ql.ctypes.data, gap.ctypes.data, off.ctypes.data, flat.ctypes.data, kept.ctypes.data))
+    return [flat[off[f]:off[f] + kept[f]].copy() for f in range(len(ns))]
+
+
+def seg_gen_host(regs, anchors, qlens, hashes):
+    """mm2gb_seg_gen_host (mm_seg_gen, hit.c:331-385): regs / anchors = per fragment its kept records (REG_DTYPE) and kept anchors ((m,2) uint64), qlens = per fragment
+    its mate lengths, hashes = per fragment the hash mm_gen_regs gets.  Returns per fragment a list of (records, anchors) per mate."""
+    ns, ql = _frag_arrays([len(q) for q in qlens], qlens)
+    off = np.concatenate([[0], np.cumsum([len(r) for r in regs])]).astype(np.int64)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(r, REG_DTYPE) for r in regs]) if len(regs) and off[-1] else np.zeros(0, REG_DTYPE))
+    a_off = np.concatenate([[0], np.cumsum([len(a) for a in anchors])]).astype(np.int64)
+    a = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint64).reshape(-1, 2) for x in anchors]) if len(anchors) and a_off[-1] else np.zeros((0, 2), np.uint64))
+    hs = np.ascontiguousarray(hashes, dtype=np.uint32)
+    o = SegOut()
+    fn = lib().mm2gb_seg_gen_host
+    fn.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SegOut)]
+    _check(fn(len(ns), ns.ctypes.data, ql.ctypes.data, hs.ctypes.data, off.ctypes.data, flat.ctypes.data, a_off.ctypes.data, a.ctypes.data, C.byref(o)))
+    U = 2 * len(ns)
+    r_off, x_off = _take(o.reg_off, U + 1, np.int64), _take(o.anchor_off, U + 1, np.int64)
+    r = _take(o.regs, int(r_off[-1]), REG_DTYPE) if U else np.zeros(0, REG_DTYPE)
+    x = _take(o.anchors, int(x_off[-1]) * 2, np.uint64).reshape(-1, 2) if U else np.zeros((0, 2), np.uint64)
+    lib().mm2gb_seg_out_free.argtypes = [C.POINTER(SegOut)]
+    lib().mm2gb_seg_out_free.restype = None
+    lib().mm2gb_seg_out_free(C.byref(o))
+    return [[(r[r_off[2 * f + s]:r_off[2 * f + s + 1]], x[x_off[2 * f + s]:x_off[2 * f + s + 1]]) for s in range(int(ns[f]))] for f in range(len(ns))]
+
+
+def _frags_args(frags, pe_ori):
+    """The fragments' offsets as the C calls take them (the array is returned too: it must outlive the call)."""
+    fo = np.ascontiguousarray(frags, dtype=np.int32)
+    if len(fo) < 1:
+        raise Mm2gbError("frags: frag_offsets(names), one more entry than fragments")
+    return fo, (len(fo) - 1, fo.ctypes.data, int(pe_ori))
+
+
+def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None, out=None, frags=None, pe_ori=1):
     """mm2gb_map_reads: reads = list of (name, sequence bytes); returns (PAF text, stats dict).  index: a SeedIndex of the references.
+    frags (with align=map_sr(), opt=map_opt_sr()): frag_offsets(names) -- paired ends: mm2gb_map_frags_sr maps every run of two reads as one fragment (minimap2 -x sr
+    r1.fq r2.fq without -c; interleave() makes the list from two files); pe_ori: mm_mapopt_t::pe_ori (1: the second mate is turned, the preset's).  None: single reads.
     align: a map_align(...) for base-level alignment (mm2gb_map_reads_aln) or a map_splice(...) for spliced reads (mm2gb_map_reads_splice); the stats then hold s_align, s_post_align and s_text as well.
     A map_sr(...) with opt=map_opt_sr(): short single-end reads (mm2gb_map_reads_sr; minimap2 -x sr [-c]); the stats then hold the call's own counts as well (n_chain_calls,
     n_rescued, n_tied_reads, sr_counts) and the three alignment seconds.
@@ -1846,11 +1968,18 @@ def map_reads(engine, index, ref_names, reads, opt=None, k=15, align=None, out=N
     out, n, st, extra = C.c_void_p(), C.c_int64(), MapStats(), (C.c_double * 3)()
     first = (engine._h, index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt))
     rest = (len(reads), names, seqs, lens.ctypes.data, C.byref(out), C.byref(n), C.byref(st))
+    if frags is not None and not isinstance(align, MapSr):
+        raise Mm2gbError("map_reads: frags= goes with align=map_sr() and opt=map_opt_sr() (paired ends are short reads)")
     if isinstance(align, MapSr):
         if align.align:
             _check_align_refs(align, ref_names)
         so = MapSrOut()
-        _check((L.mm2gb_map_reads_sr_out if last else L.mm2gb_map_reads_sr)(*first, C.byref(align), *rest, C.byref(so), *last))
+        if frags is not None:
+            L.mm2gb_map_frags_sr.argtypes = L.mm2gb_map_reads_sr.argtypes + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+            keep, more = _frags_args(frags, pe_ori)          # (keep: the offsets' array lives until the call returns)
+            _check(L.mm2gb_map_frags_sr(*first, C.byref(align), *rest, C.byref(so), *more, last[0] if last else None))
+        else:
+            _check((L.mm2gb_map_reads_sr_out if last else L.mm2gb_map_reads_sr)(*first, C.byref(align), *rest, C.byref(so), *last))
         text = C.string_at(out, n.value).decode()
         L.mm2gb_free(out)
         return text, _sr_stats(st, so)
@@ -1898,10 +2027,11 @@ def _engine_release_host_scratch(self):
 Engine.release_host_scratch = _engine_release_host_scratch
 
 
-def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0, align=None, out=None):
+def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bases=0, align=None, out=None, frags=None, pe_ori=1):
     """mm2gb_map_reads_stream: a run of any size as a stream of chunks of about chunk_bases bases; every engine (several per device overlap
     host stages with kernels, engines on several devices shard the reads) takes the next chunk.  Returns (PAF text in read order, stats:
-    counts summed, s_* summed over chunks).  align, out: as for map_reads (mm2gb_map_reads_stream_aln / _splice / _sr, and their _out forms)."""
+    counts summed, s_* summed over chunks).  align, out: as for map_reads (mm2gb_map_reads_stream_aln / _splice / _sr, and their _out forms).
+    frags, pe_ori: as for map_reads (mm2gb_map_frags_stream_sr; a chunk ends between fragments)."""
     _out_needs_align(out, align)
     L = lib()
     head = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.c_void_p, C.c_int32, C.c_void_p]
@@ -1924,11 +2054,18 @@ def map_reads_stream(engines, index, ref_names, reads, opt=None, k=15, chunk_bas
     out, n, st, extra = C.c_void_p(), C.c_int64(), MapStats(), (C.c_double * 3)()
     first = (hs, len(engines), index._h, k, rn, index.lens.ctypes.data, len(ref_names), C.byref(opt))
     rest = (len(reads), names, seqs, lens.ctypes.data, int(chunk_bases), C.byref(out), C.byref(n), C.byref(st))
+    if frags is not None and not isinstance(align, MapSr):
+        raise Mm2gbError("map_reads_stream: frags= goes with align=map_sr() and opt=map_opt_sr() (paired ends are short reads)")
     if isinstance(align, MapSr):
         if align.align:
             _check_align_refs(align, ref_names)
         so = MapSrOut()
-        _check((L.mm2gb_map_reads_stream_sr_out if last else L.mm2gb_map_reads_stream_sr)(*first, C.byref(align), *rest, C.byref(so), *last))
+        if frags is not None:
+            L.mm2gb_map_frags_stream_sr.argtypes = L.mm2gb_map_reads_stream_sr.argtypes + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+            keep, more = _frags_args(frags, pe_ori)          # (keep: the offsets' array lives until the call returns)
+            _check(L.mm2gb_map_frags_stream_sr(*first, C.byref(align), *rest, C.byref(so), *more, last[0] if last else None))
+        else:
+            _check((L.mm2gb_map_reads_stream_sr_out if last else L.mm2gb_map_reads_stream_sr)(*first, C.byref(align), *rest, C.byref(so), *last))
         text = C.string_at(out, n.value).decode()
         L.mm2gb_free(out)
         return text, _sr_stats(st, so)

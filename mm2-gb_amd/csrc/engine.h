@@ -100,7 +100,7 @@ struct Engine {
 	DevBuf sh_ord, sh_keys, sh_long, sh_sort_tmp, sh_tied;   // mm2gb_collect_seeds_heap_gpu (seed_heap_kernels.hip): the sorted order, the long reads' keys, ranges and sort space, the tie flags
 	// sequence bytes -> matches on the device (seed_kernels.hip; mm2gb_sketch_gpu, mm2gb_collect_matches_gpu): the sequences, their offsets and
 	// ids, the minimizers with their reads and offsets, one arena for the work arrays of either stage, what the host's mapq / divergence code wants
-	DevBuf sk_seqs, sk_seq_off, sk_rid, sk_mini, sk_mini_read, sk_mini_off, sk_work, sd_src_first, sd_mini_pos, sd_rep_len;
+	DevBuf sk_seqs, sk_seq_off, sk_rid, sk_mini, sk_mini_read, sk_mini_off, sk_work, sd_src_first, sd_mini_pos, sd_rep_len, sk_frag;   // sk_frag: fragments' first sequences, their offsets, first mates' lengths
 	// mm_est_err's walk (est_err_kernels.hip; mm2gb_est_err_gpu and the mapper's resident path): the call's arrays as the host gives them (the resident path reads
 	// the engine's own instead: reg_out, post_out[0], sd_qlen, sd_seed_off, sd_mini_pos), the reads' hashes of the resident path's hit records, scratch, results
 	DevBuf ee_reg_off, ee_a_off, ee_a, ee_qlen, ee_mini_off, ee_mini, ee_ref_len, ee_hash, ee_reg_read, ee_literal, ee_out, ee_sum_k;
@@ -208,7 +208,10 @@ struct Engine {
 	                          mm2gb_anchor_t *anchors, int64_t *n_tied_reads);      // what the two share, on matches that lie on the device
 	int  collect_seeds_heap_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, int64_t *anchor_off, mm2gb_anchor_t *anchors, int64_t *n_tied_reads);
 	// mm_collect_matches for a batch, left in sd_seeds / sd_seed_off / sd_hit_off / sd_hits (+ sd_qlen, sd_mini_pos, sd_rep_len)
-	int  collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits);
+	// frag_off (n_frag + 1, host; null: every sequence a read of its own): the sequences frag_off[f] .. frag_off[f + 1], one or two, are the mates of fragment f, seeded as
+	// one list (launch_frag_view); everything left behind is then per fragment -- sd_seed_off, sd_rep_len and sd_qlen have n_frag entries, sd_qlen the mates' summed length
+	int  collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits,
+	                            int64_t n_frag = 0, const int64_t *frag_off = nullptr);
 	// launch_collect_seeds on what collect_matches_device left; q_rank / ref_rank / ref_len as for collect_seeds (null: no name tests).  anchors null: the anchors
 	// stay in sd_out / sd_a_off and only the offsets come down (the mapper's resident path)
 	int  collect_seeds_resident(int64_t opt_flag, int64_t n_reads, int64_t n_seeds, int64_t n_hits, const int32_t *q_rank, int32_t n_ref, const int32_t *ref_len, const int32_t *ref_rank,

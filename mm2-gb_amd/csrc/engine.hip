@@ -518,7 +518,7 @@ void Engine::shutdown()
 	for (DevBuf *b : { &post_dbg_tasks, &post_dbg_stasks, &rmq_dbg_reads, &rmq_skey_in, &rmq_skey, &rmq_sa, &rmq_srange, &rmq_sort_tmp, &post_z, &post_fp, &post_picked, &post_utmp, &post_heads, &post_nu, &post_nkept, &post_misc, &post_bins, &post_order, &post_up4, &post_up16, &post_sort_s, &post_sort_perm, &post_sort_tmp, &post_cls, &post_cls_cnt, &post_cls_nz, &post_read_nz, &post_uloc, &post_wtask, &post_stask, &rmq_tied, &rmq_sum, &rmq_by_y, &rmq_ord, &rmq_meta, &rmq_win, &rmq_tree, &reg_out,
 	                   &sd_seeds, &sd_seed_off, &sd_hit_off, &sd_hits, &sd_qlen, &sd_q_rank, &sd_ref_len, &sd_ref_rank, &sd_seed_read, &sd_tmp, &sd_n_kept, &sd_a_off, &sd_out,
 	                   &sh_ord, &sh_keys, &sh_long, &sh_sort_tmp, &sh_tied,
-	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len,
+	                   &sk_seqs, &sk_seq_off, &sk_rid, &sk_mini, &sk_mini_read, &sk_mini_off, &sk_work, &sd_src_first, &sd_mini_pos, &sd_rep_len, &sk_frag,
 	                   &ee_reg_off, &ee_a_off, &ee_a, &ee_qlen, &ee_mini_off, &ee_mini, &ee_ref_len, &ee_hash, &ee_reg_read, &ee_literal, &ee_out, &ee_sum_k,
 	                   &kw_jobs, &kw_q, &kw_t, &kw_res, &kw_slab, &kw_cig, &kw_img, &kw_cnt, &kw_off, &kw_pack, &kw_junc,
 	                   &al_refs, &al_reads, &al_jobs, &al_slices, &al_list, &al_drop,
@@ -1304,20 +1304,42 @@ int Engine::sketch_device(int w, int k, int flag, int64_t n_seqs, const int64_t 
 }
 
 // mm_collect_matches for a batch of reads: sketch, q-occurrence filter, look-up, streak thinning, repeat length, the kept seeds' hits.
-int Engine::collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits)
+int Engine::collect_matches_device(const DevIndexView &ix, const mm2gb_seed_opt_t &opt, int64_t n_reads, const int64_t *seq_off, const char *seqs, int64_t *n_seeds, int64_t *n_hits,
+                                   int64_t n_frag, const int64_t *frag_off)
 {
 	int64_t n_mini = 0;
 	*n_seeds = *n_hits = 0;
 	if (sketch_device(ix.w, ix.k, ix.flag, n_reads, seq_off, seqs, nullptr, &n_mini)) return -1;
+	// fragments: the mates' minimizers become one list per fragment, and from here on a "read" is a fragment
+	const int64_t *unit_seq_off = (const int64_t*)sk_seq_off.ptr, *unit_mini_off = (const int64_t*)sk_mini_off.ptr;
+	const int32_t *len0 = nullptr;
+	if (frag_off) {
+		if (n_frag < 1 || frag_off[0] != 0 || frag_off[n_frag] != n_reads) return fail("mm2gb: the fragments do not cover the batch's sequences");
+		for (int64_t f = 0; f < n_frag; ++f) if (frag_off[f + 1] - frag_off[f] < 1 || frag_off[f + 1] - frag_off[f] > 2) return fail("mm2gb: a fragment has one or two sequences");
+		const size_t f1 = (size_t)n_frag + 1;
+		if (sk_frag.ensure(3 * (f1 * 8 + 256) + f1 * 4 + 256)) return -1;      // (three arrays of offsets and one of lengths, each on a 256-byte boundary)
+		Carver c(sk_frag.ptr);
+		FragView v;
+		int64_t *d_frag_off = c.take<int64_t>(f1);
+		v.n_frag = n_frag; v.n_seqs = n_reads; v.n_mini = n_mini; v.frag_off = d_frag_off; v.seq_off = unit_seq_off; v.mini_off = unit_mini_off;
+		v.mini = (ulonglong2*)sk_mini.ptr; v.mini_read = (int32_t*)sk_mini_read.ptr;
+		v.f_seq_off = c.take<int64_t>(f1); v.f_mini_off = c.take<int64_t>(f1); v.len0 = c.take<int32_t>(f1);
+		if (seq_off[n_reads] == 0) MM2GB_HIP(hipMemcpyAsync(sk_seq_off.ptr, seq_off, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, stream));   // (the sketch returned before its copies)
+		MM2GB_HIP(hipMemcpyAsync(d_frag_off, frag_off, f1 * 8, hipMemcpyHostToDevice, stream));
+		launch_frag_view(v, stream);
+		MM2GB_HIP(hipGetLastError());
+		unit_seq_off = v.f_seq_off; unit_mini_off = v.f_mini_off; len0 = v.len0;
+		n_reads = n_frag;
+	}
 	const size_t nr = (size_t)n_reads, nm = (size_t)n_mini;
 	if (sd_seeds.ensure(std::max<size_t>(nm, 1) * 16) || sd_seed_off.ensure((nr + 1) * 8) || sd_hit_off.ensure((nm + 1) * 8) || sd_qlen.ensure(std::max<size_t>(nr, 1) * 4) ||
 	    sd_src_first.ensure(std::max<size_t>(nm, 1) * 8) || sd_mini_pos.ensure(std::max<size_t>(nm, 1) * 8) || sd_rep_len.ensure(std::max<size_t>(nr, 1) * 4)) return -1;
-	if (seq_off[n_reads] == 0) MM2GB_HIP(hipMemcpyAsync(sk_seq_off.ptr, seq_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));   // (the sketch returned before its copies)
+	if (!frag_off && seq_off[n_reads] == 0) MM2GB_HIP(hipMemcpyAsync(sk_seq_off.ptr, seq_off, (nr + 1) * 8, hipMemcpyHostToDevice, stream));   // (the sketch returned before its copies)
 	MatchBatch b;
 	memset(&b, 0, sizeof b);
 	b.ix = ix; b.mid_occ = opt.mid_occ; b.max_max_occ = opt.max_max_occ; b.occ_dist = opt.occ_dist; b.q_occ_frac = opt.q_occ_frac;
-	b.n_reads = n_reads; b.n_mini = n_mini; b.seq_off = (const int64_t*)sk_seq_off.ptr;
-	b.mini = (const ulonglong2*)sk_mini.ptr; b.mini_read = (const int32_t*)sk_mini_read.ptr; b.mini_off = (const int64_t*)sk_mini_off.ptr;
+	b.n_reads = n_reads; b.n_mini = n_mini; b.seq_off = unit_seq_off;
+	b.mini = (const ulonglong2*)sk_mini.ptr; b.mini_read = (const int32_t*)sk_mini_read.ptr; b.mini_off = unit_mini_off; b.len0 = len0;
 	// (the sketch's work arrays are done with: the matches' arrays take their place in the arena)
 	if (sk_work.ensure(match_layout(b, nullptr))) return -1;
 	match_layout(b, sk_work.ptr);
@@ -1911,16 +1933,29 @@ void mm2gb_match_batch_free(mm2gb_match_batch_t *m)
 int mm2gb_collect_matches_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_reads, const int64_t *seq_off, const char *seqs,
                               mm2gb_match_batch_t *out)
 {
-	if (!eng || !ix || !opt || !out) return fail("mm2gb_collect_matches_gpu: null argument");
-	if (check_seq_off("mm2gb_collect_matches_gpu", n_reads, seq_off, seqs)) return -1;
+	return mm2gb_collect_matches_frag_gpu(eng, ix, opt, n_reads, seq_off, seqs, 0, nullptr, out);
+}
+
+int mm2gb_collect_matches_frag_gpu(mm2gb_engine_t *eng, const mm2gb_index_t *ix, const mm2gb_seed_opt_t *opt, int64_t n_seqs, const int64_t *seq_off, const char *seqs,
+                                   int64_t n_frag, const int64_t *frag_off, mm2gb_match_batch_t *out)
+{
+	const char *who = frag_off ? "mm2gb_collect_matches_frag_gpu" : "mm2gb_collect_matches_gpu";
+	if (!eng || !ix || !opt || !out) return fail(std::string(who) + ": null argument");
+	if (check_seq_off(who, n_seqs, seq_off, seqs)) return -1;
+	if (frag_off) {
+		if (n_frag < 0 || frag_off[0] != 0 || frag_off[n_frag] != n_seqs) return fail("mm2gb_collect_matches_frag_gpu: frag_off[0] must be 0 and frag_off[n_frag] the number of sequences");
+		for (int64_t f = 0; f < n_frag; ++f)
+			if (frag_off[f + 1] - frag_off[f] < 1 || frag_off[f + 1] - frag_off[f] > 2) return fail("mm2gb_collect_matches_frag_gpu: a fragment has one or two sequences (MM_MAX_SEG > 2 is not taken)");
+	}
 	memset(out, 0, sizeof(*out));
 	Engine &e = eng->e;
 	int64_t n_seeds = 0, n_hits = 0;
-	if (n_reads > 0) {
+	if (n_seqs > 0) {
 		DevIndexView view;
 		if (index_on_device(ix, e.device, &view)) return -1;
-		if (e.collect_matches_device(view, *opt, n_reads, seq_off, seqs, &n_seeds, &n_hits)) return -1;
+		if (e.collect_matches_device(view, *opt, n_seqs, seq_off, seqs, &n_seeds, &n_hits, n_frag, frag_off)) return -1;
 	}
+	const int64_t n_reads = frag_off ? n_frag : n_seqs;           // the units of the result
 	out->n_seeds = n_seeds; out->n_hits = n_hits;
 	out->seed_off = (int64_t*)calloc((size_t)n_reads + 1, 8);
 	out->seeds = (mm2gb_seed_t*)malloc(((size_t)n_seeds + 1) * sizeof(mm2gb_seed_t));

@@ -86,6 +86,9 @@ template <class T> struct BigBuf {
 
 // mm2gb_collect_matches (seeding.cpp) without the copy of the occurrences: refs[s] points at kept seed s's occurrences in the index, out->hits stays null
 int collect_matches_refs(const mm2gb_index_t *ix, const char *seq, int32_t len, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out, std::vector<const uint64_t*> *refs);
+// ... and for a fragment of n_segs segments seeded as one list (mm2gb_collect_matches_frag); flt_mid_occ: the q-occurrence filter's threshold (map.c:664: mid_occ in either round)
+int collect_matches_frag_refs(const mm2gb_index_t *ix, int n_segs, const char *const *seqs, const int32_t *lens, const mm2gb_seed_opt_t *opt, int32_t flt_mid_occ, mm2gb_matches_t *out,
+                              std::vector<const uint64_t*> *refs);
 
 // The large host arrays of an engine's mapping and re-chaining calls, kept from call to call (first touch of a gigabyte of fresh pages costs
 // more than filling it) and owned by the engine: matches, anchors, the re-chained reads' anchors, the spliced chains (mapper.cpp); the gathers of

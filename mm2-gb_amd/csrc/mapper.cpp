@@ -36,8 +36,13 @@
 //   DESIGN 6g), and a line is mm_write_sam3's at n_seg = 1 (write_sam, format.c:389-546) with mm_set_sam_pri's choice of the primary line, or the PAF line with cg:Z from
 //   the new words.  cs:Z / MD:Z are always asked of the text calls with the M words (format.c treats 0, 7 and 8 alike).  Left out of SAM: -L (CG:B:I), qualities (QUAL is
 //   *), -R read groups, -y comments, --secondary-seq; of PAF: --paf-no-hit.
-// Not reproduced: more than one query segment (paired ends; none of mm_write_sam3's n_seg > 1 branches), spliced mapping without base-level alignment, read overlap with
-// base-level alignment, junction annotation, ALT contigs, --qstrand, multi-part indexes.
+//   Paired-end short reads (mm2gb_map_frags_sr / _stream_sr; minimap2 -x sr r1.fq r2.fq without -c): the batch's units are FRAGMENTS of one or two mates (MapCall::frag,
+//   frag_units).  Stage 1 seeds a fragment's mates as one list of qlen_sum bases (collect_matches_frag_refs, or seed_kernels.hip's k_f_view before the match kernels), stage 2 is
+//   the single-end one at qlen = qlen_sum, stage 3 one chaining call per distinct (n_seg, max_dist_x, max_dist_y) with n_seg = 2 for two mates (chain_groups_sr), the rescue
+//   also where the best chain lacks a mate, stage 5 as ever with the first mate's name in the hash, and stage 6 (finish_frags_sr) mm_set_parent, mm_select_sub_multi (pe.c:6-43),
+//   mm_seg_gen (hit.c:331-385) into per-mate hits, per mate mm_set_parent and mm_set_mapq, the pe_ori flip (map.c:1188-1199) and mate 0's lines, then mate 1's.
+// Not reproduced: base-level alignment of mate pairs (-c with mm_pair, mm_set_pe_thru), SAM for pairs (none of mm_write_sam3's n_seg > 1 branches), more than two query segments,
+// MM_F_INDEPEND_SEG, spliced mapping without base-level alignment, read overlap with base-level alignment, junction annotation, ALT contigs, --qstrand, multi-part indexes.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -416,7 +421,14 @@ struct MapCall {
 	const mm2gb_map_sr_t *sr = nullptr;                  // mm2gb_map_reads_sr: short single-end reads (MM_F_SR); aln then holds its alignment's share, or is null
 	mm2gb_map_sr_out_t *sr_out = nullptr;                // ... and where its own counts go
 	const mm2gb_map_out_t *out = nullptr;                // the _out calls: SAM, = / X words (null, or zeroed: the PAF of the calls without it)
+	// mm2gb_map_frags_sr: the call's units (n_reads, names, seqs, lens above) are FRAGMENTS -- the first mate's name, the mates' summed length -- and unit u's reads are
+	// frag_off[u] .. frag_off[u + 1] (one or two) of frag's arrays, which hold all the call's reads whatever part of the units a chunk takes
+	const struct FragReads *frag = nullptr;
+	const int32_t *frag_off = nullptr;
+	int n_segs(size_t u) const { return frag ? frag_off[u + 1] - frag_off[u] : 1; }
 };
+
+struct FragReads { const char *const *names; const char *const *seqs; const int32_t *lens; int32_t pe_ori; };   // seqs: a mate that pe_ori turns is turned already (map.c:1169-1171)
 
 // what the stages of one batch share
 struct Batch {
@@ -471,7 +483,10 @@ int seed_on_host(Batch &B)
 	std::string why;                                      // error text is per thread: carry the first one over
 	std::mutex why_lock;
 	for_each_on_threads(B.R, B.nt, 1, [&](size_t r) {
-		if (B.c.lens[r] > 0 && collect_matches_refs(B.c.ix, B.c.seqs[r], B.c.lens[r], &B.so, &B.mt[r], &B.occ[r])) {
+		if (B.c.lens[r] <= 0) return;
+		const int32_t r0 = B.c.frag ? B.c.frag_off[r] : 0;
+		if (B.c.frag ? collect_matches_frag_refs(B.c.ix, B.c.n_segs(r), B.c.frag->seqs + r0, B.c.frag->lens + r0, &B.so, B.so.mid_occ, &B.mt[r], &B.occ[r])
+		             : collect_matches_refs(B.c.ix, B.c.seqs[r], B.c.lens[r], &B.so, &B.mt[r], &B.occ[r])) {
 			std::lock_guard<std::mutex> g(why_lock);
 			if (!bad.exchange(1)) why = mm2gb_last_error();
 		}
@@ -492,18 +507,24 @@ int64_t resident_max_anchors()
 int seed_on_device(Batch &B)
 {
 	const size_t R = B.R;
-	const int32_t *lens = B.c.lens;
 	Engine &e = B.c.eng->e;
-	std::vector<int64_t> seq_off(R + 1, 0);
-	for (size_t r = 0; r < R; ++r) seq_off[r + 1] = seq_off[r] + lens[r];
-	if (seq_off[R] >= ((int64_t)1 << 31) - 1) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 bases");
+	// the sequences that go up: the batch's reads, or with fragments every unit's mates (the device then joins them into units again: Engine::collect_matches_device)
+	const bool frags = B.c.frag != nullptr;
+	const int32_t first = frags ? B.c.frag_off[0] : 0;
+	const size_t S = frags ? (size_t)(B.c.frag_off[R] - first) : R;
+	const int32_t *lens = frags ? B.c.frag->lens + first : B.c.lens;
+	const char *const *seqs = frags ? B.c.frag->seqs + first : B.c.seqs;
+	std::vector<int64_t> seq_off(S + 1, 0), frag_off(frags ? R + 1 : 0);
+	for (size_t r = 0; r < S; ++r) seq_off[r + 1] = seq_off[r] + lens[r];
+	for (size_t u = 0; u < frag_off.size(); ++u) frag_off[u] = B.c.frag_off[u] - first;
+	if (seq_off[S] >= ((int64_t)1 << 31) - 1) return fail("mm2gb_map_reads: a batch seeded on the device is limited to 2^31 bases");
 	BigBuf<uint64_t> &flat = host_scratch(B.c.eng).hits;      // (no host array of hits in this form: its memory holds the reads end to end)
-	flat.resize((size_t)seq_off[R] / 8 + 1);
+	flat.resize((size_t)seq_off[S] / 8 + 1);
 	char *const bases = (char*)flat.data();
-	for_each_on_threads(R, B.nt, 1, [&](size_t r) { if (lens[r] > 0) memcpy(bases + seq_off[r], B.c.seqs[r], (size_t)lens[r]); });
+	for_each_on_threads(S, B.nt, 1, [&](size_t r) { if (lens[r] > 0) memcpy(bases + seq_off[r], seqs[r], (size_t)lens[r]); });
 	DevIndexView view;
 	if (index_on_device(B.c.ix, e.device, &view)) return -1;
-	if (e.collect_matches_device(view, B.so, B.c.n_reads, seq_off.data(), bases, &B.dev_seeds, &B.dev_hits)) return -1;
+	if (e.collect_matches_device(view, B.so, (int64_t)S, seq_off.data(), bases, &B.dev_seeds, &B.dev_hits, frags ? (int64_t)R : 0, frags ? frag_off.data() : nullptr)) return -1;
 	std::vector<int64_t> seed_off(R + 1, 0);
 	std::vector<int32_t> rep(R, 0);
 	// (the resident path walks the minimizer positions where they are: only their number per read comes down)
@@ -512,7 +533,7 @@ int seed_on_device(Batch &B)
 	if (hipMemcpy(seed_off.data(), e.sd_seed_off.ptr, (R + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(rep.data(), e.sd_rep_len.ptr, R * 4, hipMemcpyDeviceToHost) != hipSuccess ||
 	    (!B.resident && B.dev_seeds > 0 && hipMemcpy(mini_pos.data(), e.sd_mini_pos.ptr, (size_t)B.dev_seeds * 8, hipMemcpyDeviceToHost) != hipSuccess))
 		return fail("mm2gb_map_reads: the device's matches could not be copied back");
-	B.link[0] += seq_off[R] + (int64_t)(R + 1) * 8;
+	B.link[0] += seq_off[S] + (int64_t)(S + 1) * 8;
 	B.link[1] += (int64_t)((R + 1) * 8 + R * 4) + (B.resident ? 0 : B.dev_seeds * 8);
 	for (size_t r = 0; r < R; ++r) {
 		const int64_t n = seed_off[r + 1] - seed_off[r];
@@ -872,17 +893,22 @@ struct SrChains {
 // end (a list with one value goes as it lies).  Reads of one length share a value, and so do all reads of max_frag_len - max_gap bases or more.
 int chain_groups_sr(Batch &B, const std::vector<int32_t> &reads, const std::vector<int64_t> &a_off, const mm2gb_anchor_t *anchors, SrChains &S)
 {
+	// With fragments (mm2gb_map_frags_sr) a unit of two mates is chained at n_seg = 2, where max_dist_y also bounds the reference gap between anchors of different
+	// mates (lchain.c:121: same segment or not, dr > max_dist_y is out) and must be exact as well: max(qlen_sum, max_gap).  So the key of a call is (n_seg, max_dist_x,
+	// max_dist_y); the units of one read share one max_dist_y as ever and are grouped as ever.
 	const mm2gb_map_opt_t &opt = B.opt;
-	std::vector<std::pair<int32_t, int32_t>> key;            // (max_dist_x, place in the list) of the reads that have anchors
+	struct Key { int32_t n_seg, max_x, max_y, second; bool same(const Key &o) const { return n_seg == o.n_seg && max_x == o.max_x && max_y == o.max_y; } };
+	std::vector<Key> key;                                    // (the call's parameters, place in the list) of the reads that have anchors
 	int32_t longest = 0;
+	for (size_t q = 0; q < reads.size(); ++q) if (B.c.n_segs((size_t)reads[q]) == 1) longest = std::max(longest, B.qlen[(size_t)reads[q]]);
 	for (size_t q = 0; q < reads.size(); ++q) {
-		const int32_t len = B.qlen[(size_t)reads[q]];
-		longest = std::max(longest, len);
-		if (a_off[q + 1] > a_off[q]) key.emplace_back(opt.max_gap_ref > 0 ? opt.max_gap_ref : std::max(B.c.sr->max_frag_len > 0 ? B.c.sr->max_frag_len - len : opt.max_gap, opt.max_gap), (int32_t)q);
+		const int32_t len = B.qlen[(size_t)reads[q]], n_seg = B.c.n_segs((size_t)reads[q]);
+		if (a_off[q + 1] > a_off[q]) key.push_back({ n_seg, opt.max_gap_ref > 0 ? opt.max_gap_ref : std::max(B.c.sr->max_frag_len > 0 ? B.c.sr->max_frag_len - len : opt.max_gap, opt.max_gap),
+		                                             std::max(n_seg == 1 ? longest : len, opt.max_gap), (int32_t)q });
 	}
-	std::sort(key.begin(), key.end());
+	std::sort(key.begin(), key.end(), [](const Key &u, const Key &v) { return u.n_seg != v.n_seg ? u.n_seg < v.n_seg : u.max_x != v.max_x ? u.max_x < v.max_x : u.max_y != v.max_y ? u.max_y < v.max_y : u.second < v.second; });
 	mm2gb_misc_t &misc = B.misc;
-	misc.max_iter = opt.max_chain_iter; misc.max_dist_y = std::max(longest, opt.max_gap);
+	misc.max_iter = opt.max_chain_iter;
 	misc.max_skip = opt.max_chain_skip; misc.bw = opt.bw; misc.min_cnt = opt.min_cnt; misc.min_score = opt.min_chain_score; misc.is_cdna = 0; misc.n_seg = 1;
 	misc.chn_pen_gap = (float)(opt.chain_gap_scale * 0.01 * B.c.k); misc.chn_pen_skip = (float)(opt.chain_skip_scale * 0.01 * B.c.k);
 	struct ChainSkipMode {
@@ -894,8 +920,8 @@ int chain_groups_sr(Batch &B, const std::vector<int32_t> &reads, const std::vect
 	std::vector<mm2gb_anchor_t> ga;
 	for (size_t i = 0; i < key.size();) {
 		size_t j = i;
-		while (j < key.size() && key[j].first == key[i].first) ++j;
-		misc.max_dist_x = key[i].first;
+		while (j < key.size() && key[j].same(key[i])) ++j;
+		misc.max_dist_x = key[i].max_x; misc.max_dist_y = key[i].max_y; misc.n_seg = key[i].n_seg;
 		if (mm2gb_engine_set_misc(B.c.eng, &misc)) return -1;
 		const bool whole = i == 0 && j == key.size();        // one value: the list's anchors as they lie (the reads without anchors are empty reads of the call)
 		const int64_t n = whole ? (int64_t)reads.size() : (int64_t)(j - i);
@@ -936,9 +962,24 @@ int anchors_and_chains_sr(Batch &B, bool dev_seed)
 	SrChains S(R);
 	if (chain_groups_sr(B, all, B.a_off, B.anchors.data(), S)) return -1;
 	auto n_chains = [&](size_t r) { return S.part[r] < 0 ? (int64_t)0 : S.parts[(size_t)S.part[r]]->c.u_off[S.slot[r] + 1] - S.parts[(size_t)S.part[r]]->c.u_off[S.slot[r]]; };
+	// a fragment of two mates also goes again when its best-scoring chain -- the first with the strictly largest score -- holds anchors of one mate only (map.c:710-720)
+	auto lacks_mate = [&](size_t r) {
+		const mm2gb_chains_t &c = S.parts[(size_t)S.part[r]]->c;
+		const uint64_t *u = c.u + c.u_off[S.slot[r]];
+		const mm2gb_anchor_t *a = c.a + c.a_off[S.slot[r]];
+		int64_t best = 0, best_i = -1, best_off = -1, off = 0;
+		for (int64_t i = 0; i < n_chains(r); ++i) {
+			if (best < (int64_t)(u[i] >> 32)) { best = (int64_t)(u[i] >> 32); best_i = i; best_off = off; }
+			off += (uint32_t)u[i];
+		}
+		if (best_i < 0) return false;
+		int n_chained = 1;
+		for (int64_t i = 1; i < (int64_t)(uint32_t)u[best_i]; ++i) if ((a[best_off + i].y >> 48 & 0xff) != (a[best_off + i - 1].y >> 48 & 0xff)) ++n_chained;
+		return n_chained < B.c.n_segs(r);
+	};
 	std::vector<int32_t> redo;
 	if (B.c.sr->max_occ > B.opt.mid_occ)
-		for (size_t r = 0; r < R; ++r) if (B.mt[r].rep_len > 0 && n_chains(r) == 0) redo.push_back((int32_t)r);
+		for (size_t r = 0; r < R; ++r) if (B.mt[r].rep_len > 0 && (n_chains(r) == 0 || (B.c.n_segs(r) > 1 && lacks_mate(r)))) redo.push_back((int32_t)r);
 	std::vector<int64_t> a_off2;
 	BigBuf<mm2gb_anchor_t> anchors2;
 	if (!redo.empty()) {
@@ -950,7 +991,9 @@ int anchors_and_chains_sr(Batch &B, bool dev_seed)
 		for_each_on_threads(redo.size(), B.nt, 1, [&](size_t q) {
 			const size_t r = (size_t)redo[q];
 			mm2gb_matches_free(&B.mt[r]);
-			if (collect_matches_refs(B.c.ix, B.c.seqs[r], B.c.lens[r], &so, &B.mt[r], &B.occ[r])) {
+			const int32_t r0 = B.c.frag ? B.c.frag_off[r] : 0;      // (two mates: the q-occurrence filter keeps mid_occ -- map.c:664 runs it once, before either round)
+			if (B.c.n_segs(r) > 1 ? collect_matches_frag_refs(B.c.ix, 2, B.c.frag->seqs + r0, B.c.frag->lens + r0, &so, B.so.mid_occ, &B.mt[r], &B.occ[r])
+			                      : collect_matches_refs(B.c.ix, B.c.seqs[r], B.c.lens[r], &so, &B.mt[r], &B.occ[r])) {
 				std::lock_guard<std::mutex> g(why_lock);
 				if (!bad.exchange(1)) why = mm2gb_last_error();
 			}
@@ -1002,6 +1045,149 @@ void finish_reads_sr(Batch &B)
 			if ((opt.flag & MM2GB_F_NO_PRINT_2ND) && h.id != h.parent) continue;
 			write_paf(B.lines[r], B.c.names[r] ? B.c.names[r] : "*", B.c.lens[r], h, B.c.ref_names[h.rid], B.c.ref_lens[h.rid], B.mt[r].rep_len);
 			B.lines[r] += '\n';
+		}
+	});
+}
+
+// ---- fragments of two mates (mm2gb_map_frags_sr; minimap2 -x sr on paired ends without base-level alignment): stage 6 ----
+
+// pe.c:6-43: mm_select_sub for a fragment.  A secondary stays if it is within min_diff of its parent; else, where it lies close to its parent on the reference (same
+// strand and sequence, within the mates' lengths + max_gap_ref), if it has pri1 of the parent's score; else pri_ratio of it -- but pri2 where the parent spans the mates'
+// boundary and the secondary does not; at most best_n of them.  (In place like the reference: r[parent] is read from the array as squeezed so far.)
+void select_sub_multi(float pri_ratio, float pri1, float pri2, int max_gap_ref, int min_diff, int best_n, int n_segs, const int32_t *qlens, std::vector<Hit> &r)
+{
+	if (!(pri_ratio > 0.0f) || r.empty()) return;
+	const size_t n = r.size();
+	const int max_dist = n_segs == 2 ? qlens[0] + qlens[1] + max_gap_ref : 0;
+	size_t k = 0;
+	int n_2nd = 0;
+	for (size_t i = 0; i < n; ++i) {
+		bool keep = false;
+		if (r[i].parent == (int)i) keep = true;
+		else if (r[i].score + min_diff >= r[(size_t)r[i].parent].score) keep = true;
+		else {
+			const Hit &p = r[(size_t)r[i].parent], &q = r[i];
+			if (p.rev == q.rev && p.rid == q.rid && q.re - p.rs < max_dist && p.re - q.rs < max_dist) keep = q.score >= p.score * pri1;
+			else {
+				const bool par_both = n_segs == 2 && p.qs < qlens[0] && p.qe > qlens[0], chi_both = n_segs == 2 && q.qs < qlens[0] && q.qe > qlens[0];
+				keep = q.score >= p.score * (chi_both || chi_both == par_both ? pri_ratio : pri2);
+			}
+		}
+		if (keep && r[i].parent != (int)i && n_2nd++ >= best_n) keep = false;
+		if (keep) r[k++] = r[i];
+	}
+	if (k == n) return;
+	r.resize(k); sync_hits(r);
+	bool first = true;                                     // mm_set_sam_pri at the end of mm_sync_regs (hit.c:220-229, 252): the record's bit 12, which no PAF line shows
+	for (Hit &h : r) { h.sam_pri = h.id == h.parent && first; if (h.sam_pri) first = false; h.flags = (h.flags & ~(1u << 12)) | (h.sam_pri ? 1u << 12 : 0u); }
+}
+
+uint64_t hit_hash64(uint64_t key)                          // hit.c:40-50
+{
+	key = (~key + (key << 21)); key = key ^ key >> 24; key = ((key + (key << 3)) + (key << 8)); key = key ^ key >> 14;
+	key = ((key + (key << 2)) + (key << 4)); key = key ^ key >> 28; key = (key + (key << 31));
+	return key;
+}
+
+// mm_gen_regs (hit.c:52-88) on the host, for the few chains of one mate (the batch's fragment chains go through the device form, stage 5): best score first, ties by the
+// hash of the chain's first anchor; as: where the chain's anchors begin in a
+void gen_regs_host(uint32_t hash, int qlen, const std::vector<uint64_t> &u, const mm2gb_anchor_t *a, std::vector<Hit> &out)
+{
+	out.clear();
+	std::vector<mm2gb_anchor_t> z(u.size());               // (a pair of words sorted by the first, like an anchor)
+	int64_t k = 0;
+	for (size_t i = 0; i < u.size(); ++i) {
+		const uint32_t h = (uint32_t)hit_hash64((hit_hash64(a[k].x) + hit_hash64(a[k].y)) ^ hash);
+		z[i].x = u[i] ^ h; z[i].y = (uint64_t)k << 32 | (uint32_t)u[i];
+		k += (uint32_t)u[i];
+	}
+	sort_by_x_like_host(z.data(), z.data() + z.size());
+	for (size_t i = 0; i < z.size(); ++i) {
+		const mm2gb_anchor_t &zi = z[z.size() - 1 - i];
+		Hit h = {};
+		h.id = (int)i; h.parent = PARENT_UNSET; h.score = h.score0 = (int)(zi.x >> 32); h.hash = (uint32_t)zi.x; h.cnt = (int)(uint32_t)zi.y; h.as = (int)(zi.y >> 32); h.div = -1.0f;
+		const mm2gb_anchor_t *f = a + h.as, *l = f + h.cnt - 1;
+		const int q_span = (int)(f->y >> 32 & 0xff);
+		h.rev = f->x >> 63; h.rid = (int)(f->x << 1 >> 33);
+		h.rs = (int32_t)f->x + 1 > q_span ? (int32_t)f->x + 1 - q_span : 0; h.re = (int32_t)l->x + 1;
+		if (!h.rev) { h.qs = (int32_t)f->y + 1 - q_span; h.qe = (int32_t)l->y + 1; }
+		else { h.qs = qlen - ((int32_t)l->y + 1); h.qe = qlen - ((int32_t)f->y + 1 - q_span); }
+		h.mlen = h.blen = q_span;                           // mm_cal_fuzzy_len (hit.c:8-20)
+		for (int j = 1; j < h.cnt; ++j) {
+			const int span = (int)(f[j].y >> 32 & 0xff), tl = (int32_t)f[j].x - (int32_t)f[j - 1].x, ql = (int32_t)f[j].y - (int32_t)f[j - 1].y;
+			h.blen += tl > ql ? tl : ql;
+			h.mlen += tl > span && ql > span ? span : tl < ql ? tl : ql;
+		}
+		h.flags = h.rev ? 1u << 10 : 0u;
+		out.push_back(h);
+	}
+}
+
+// mm_seg_gen (hit.c:331-385): a fragment's kept records split into per-mate hits.  Every anchor goes to its mate's list (y >> 48: the segment id) with its query
+// position in the mate's own coordinates -- lowered by the lengths of the mates before it, on the reverse strand by those of the mates after it --; a per-mate chain is
+// the fragment record's score over the mate's share of its anchors, the empty ones squeezed out; then mm_gen_regs per mate with the mate's length and the fragment's hash,
+// seg_split and seg_id set (mm_reg1_t's bits 15 and 16-23).  a: the fragment's kept anchors, where the records' `as` count from.
+void seg_gen(uint32_t hash, int n_segs, const int32_t *qlens, const std::vector<Hit> &r0, const mm2gb_anchor_t *a, std::vector<Hit> *regs, std::vector<mm2gb_anchor_t> *seg_a)
+{
+	int acc[3] = { 0, 0, 0 };
+	for (int s = 1; s <= n_segs; ++s) acc[s] = acc[s - 1] + qlens[s - 1];
+	const int qlen_sum = acc[n_segs];
+	for (int s = 0; s < n_segs; ++s) {
+		std::vector<uint64_t> u;
+		seg_a[s].clear();
+		for (const Hit &h : r0) {
+			uint32_t n = 0;
+			for (int j = 0; j < h.cnt; ++j) {
+				mm2gb_anchor_t a1 = a[h.as + j];
+				if ((int)(a1.y >> 48 & 0xff) != s) continue;
+				a1.y -= a1.x >> 63 ? (uint64_t)(qlen_sum - (qlens[s] + acc[s])) : (uint64_t)acc[s];
+				seg_a[s].push_back(a1); ++n;
+			}
+			if (n) u.push_back((uint64_t)h.score << 32 | n);
+		}
+		gen_regs_host(hash, qlens[s], u, seg_a[s].data(), regs[s]);
+		for (Hit &h : regs[s]) h.flags |= 1u << 15 | (uint32_t)s << 16;
+	}
+}
+
+// 6 for a batch of fragments: a unit of one read as finish_reads_sr has it; a unit of two mates through mm_select_sub_multi and mm_seg_gen, then per mate mm_set_parent and
+// mm_set_mapq with the fragment's rep_len (map.c:749, 761-768), the hits of a mate that pe_ori turned flipped back (map.c:1188-1199), and the lines of mate 0, then mate 1
+void finish_frags_sr(Batch &B)
+{
+	const mm2gb_map_opt_t &opt = B.opt;
+	const FragReads &fr = *B.c.frag;
+	for_each_on_threads(B.R, B.nt, 64, [&](size_t r) {
+		std::vector<Hit> hs;
+		for (int64_t j = B.u_off[r]; j < B.u_off[r + 1]; ++j) hs.push_back(hit_from(B.regs[(size_t)j]));
+		if (hs.empty()) return;
+		const int32_t r0 = B.c.frag_off[r], n_segs = B.c.n_segs(r), rep_len = B.mt[r].rep_len;
+		set_parent(opt.mask_level, opt.mask_len, hs, false);
+		auto lines = [&](const std::vector<Hit> &of, int32_t read) {
+			for (const Hit &h : of) {
+				if ((opt.flag & MM2GB_F_NO_PRINT_2ND) && h.id != h.parent) continue;
+				write_paf(B.lines[r], fr.names[read] ? fr.names[read] : "*", fr.lens[read], h, B.c.ref_names[h.rid], B.c.ref_lens[h.rid], rep_len);
+				B.lines[r] += '\n';
+			}
+		};
+		if (n_segs == 1) {
+			select_sub(opt.pri_ratio, B.c.k * 2, opt.best_n, true, (int)(opt.max_gap * 0.8), hs);
+			set_mapq(hs, opt.min_chain_score, rep_len, 1, true);
+			lines(hs, r0);
+			return;
+		}
+		const int32_t *qlens = fr.lens + r0;
+		const int32_t max_gap_ref = opt.max_gap_ref > 0 ? opt.max_gap_ref : std::max(B.c.sr->max_frag_len > 0 ? B.c.sr->max_frag_len - B.c.lens[r] : opt.max_gap, opt.max_gap);   // (the chaining call's max_dist_x)
+		select_sub_multi(opt.pri_ratio, 0.2f, 0.7f, max_gap_ref, B.c.k * 2, opt.best_n, n_segs, qlens, hs);
+		std::vector<Hit> regs[2];
+		std::vector<mm2gb_anchor_t> seg_a[2];
+		const uint32_t hash = wang((B.c.names[r] ? name_hash(B.c.names[r]) : 0) ^ (wang((uint32_t)B.c.lens[r]) + wang((uint32_t)opt.seed)));    // map.c:659-661, as hit_records has it
+		seg_gen(hash, n_segs, qlens, hs, B.ca + B.c_off[r], regs, seg_a);
+		for (int s = 0; s < n_segs; ++s) {
+			set_parent(opt.mask_level, opt.mask_len, regs[s], false);
+			set_mapq(regs[s], opt.min_chain_score, rep_len, 1, true);
+			if ((s == 0 && (fr.pe_ori >> 1 & 1)) || (s == 1 && (fr.pe_ori & 1)))
+				for (Hit &h : regs[s]) { const int t = h.qs; h.qs = qlens[s] - h.qe; h.qe = qlens[s] - t; h.rev = !h.rev; }
+			lines(regs[s], r0 + s);
 		}
 	});
 }
@@ -1230,6 +1416,7 @@ int map_reads_body(const MapCall &c)
 		if (opt.flag & ~(int64_t)(0x100000 | 0x200000 | sr_bits)) return fail("mm2gb_map_reads_sr: of mm_mapopt_t::flag only the preset's MM_F_SR, MM_F_FRAG_MODE, MM_F_NO_PRINT_2ND and MM_F_HEAP_SORT are supported, MM_F_FOR_ONLY and MM_F_REV_ONLY beside them");
 		if (c.sr->align == 0 && c.sr->what != 0) return fail("mm2gb_map_reads_sr: what asks for alignment text and align is 0");
 		if (c.sr->align != 0 && !c.aln) return fail("mm2gb_map_reads_sr: null argument");
+		if (c.frag && c.aln) return fail("mm2gb_map_frags_sr: paired ends with base-level alignment are not supported (-c on mate pairs needs mm_pair and mm_set_pe_thru)");
 		if (opt.seeding_on_device > 1) opt.seeding_on_device = 1;          // (the resident path skips nothing that the rescue needs)
 		if (c.ix && (mm2gb_index_flag(c.ix) & MM2GB_I_HPC)) return fail("mm2gb_map_reads_sr: a homopolymer-compressed index does not work with MM_F_SR (align.c:583)");
 	} else
@@ -1290,7 +1477,7 @@ int map_reads_body(const MapCall &c)
 		if (hit_records(B)) return -1;                                                                // 5
 		lap(B.st.s_regs);
 		stage("mm2gb:map_hits_to_paf");
-		if (!B.aln) finish_reads_sr(B);                                                               // 6
+		if (!B.aln) { if (c.frag) finish_frags_sr(B); else finish_reads_sr(B); }                      // 6
 		else {
 			Aligned A;
 			kept_records(B, A);
@@ -1447,6 +1634,7 @@ int stream_body(mm2gb_engine_t *const *engines, int n_engines, int64_t chunk_bas
 			memset(&st[k], 0, sizeof(st[k]));
 			MapCall one = c;
 			one.eng = engines[e]; one.opt = &opt; one.n_reads = cut[k + 1] - cut[k]; one.names += cut[k]; one.seqs += cut[k]; one.lens += cut[k];
+			if (c.frag) one.frag_off += cut[k];                // (a chunk is whole units: fragments are never split)
 			one.paf_out = &part[k]; one.paf_len = &part_len[k]; one.stats = &st[k]; one.s_extra = &extra[k * 3];
 			if (c.sr_out) { memset(&sro[k], 0, sizeof sro[k]); one.sr_out = &sro[k]; }
 			if (!q_rank.empty()) { one.q_rank = q_rank.data() + cut[k]; one.ref_rank = ref_rank.data(); }
@@ -1596,6 +1784,171 @@ int mm2gb_map_reads_stream_sr_out(mm2gb_engine_t *const *engines, int n_engines,
 	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
 	c.sr = sr; c.sr_out = sr_out ? sr_out : &own; c.out = out;
 	return stream_body(engines, n_engines, chunk_bases, c);
+}
+
+// ---- fragments (paired ends) ----
+
+int mm2gb_frag_offsets(int32_t n_reads, const char *const *names, int32_t *frag_off, int32_t *n_frag)
+{
+	if (n_reads < 0 || !frag_off || !n_frag || (n_reads > 0 && !names)) return fail("mm2gb_frag_offsets: null argument");
+	auto name_len = [](const char *s) { const size_t l = strlen(s); return l >= 3 && s[l - 1] >= '0' && s[l - 1] <= '9' && s[l - 2] == '/' ? l - 2 : l; };   // bseq.h:31-36
+	int32_t n = 0;
+	frag_off[0] = 0;
+	for (int32_t i = 1; i <= n_reads; ++i) {               // map.c:1299-1304
+		bool same = false;
+		if (i < n_reads && names[i - 1] && names[i]) { const size_t l1 = name_len(names[i - 1]), l2 = name_len(names[i]); same = l1 == l2 && strncmp(names[i - 1], names[i], l1) == 0; }
+		if (!same) frag_off[++n] = i;
+	}
+	*n_frag = n;
+	return 0;
+}
+
+namespace {
+// what the two fragment calls share: the arguments checked, the mates that pe_ori turns reverse-complemented (own), the units' names and summed lengths (u_*), and the call
+// record on units.  A batch in which no fragment has two reads is the plain call's (frag stays null).
+struct FragUnits {
+	std::vector<std::string> own;
+	std::vector<const char*> seqs, u_names, u_seqs;
+	std::vector<int32_t> u_lens;
+	FragReads reads;
+};
+int frag_units(const char *who, MapCall &c, int32_t n_frag, const int32_t *frag_off, int32_t pe_ori, FragUnits &F)
+{
+	const std::string w(who);
+	if (pe_ori < 0 || pe_ori > 3) return fail(w + ": pe_ori is 0..3 (mm_mapopt_t::pe_ori; -x sr: 1)");
+	if (c.out && (c.out->format != 0 || (c.out->flag & MM2GB_F_EQX))) return fail(w + ": SAM output and MM_F_EQX are not supported for fragments (the pair fields of mm_write_sam3 and -c on mate pairs are not built)");
+	if (c.n_reads < 0 || n_frag < 0 || !frag_off || frag_off[0] != 0 || frag_off[n_frag] != c.n_reads || (c.n_reads > 0 && (!c.names || !c.seqs || !c.lens))) return fail(w + ": null argument, or frag_off does not run from 0 to n_reads");
+	bool any_pair = false;
+	for (int32_t f = 0; f < n_frag; ++f) {
+		const int32_t n = frag_off[f + 1] - frag_off[f];
+		if (n < 1) return fail(w + ": a fragment without a read");
+		if (n > 2) return fail(w + ": a fragment of more than two reads is not supported (MM_MAX_SEG > 2 is not taken): " + std::string(c.names[frag_off[f]] ? c.names[frag_off[f]] : "*"));
+		any_pair |= n == 2;
+	}
+	c.out = nullptr;                                       // (PAF, no = / X: nothing of it is left to look at)
+	if (!any_pair) return 0;
+	if (c.sr && c.sr->align != 0) return fail(w + ": paired ends with base-level alignment are not supported (-c on mate pairs needs mm_pair and mm_set_pe_thru)");
+	F.seqs.assign(c.seqs, c.seqs + c.n_reads);
+	F.own.resize((size_t)c.n_reads);
+	F.u_names.resize((size_t)n_frag); F.u_seqs.resize((size_t)n_frag); F.u_lens.resize((size_t)n_frag);
+	for (int32_t f = 0; f < n_frag; ++f) {
+		const int32_t r0 = frag_off[f], n = frag_off[f + 1] - r0;
+		int64_t sum = 0;
+		for (int32_t j = 0; j < n; ++j) {
+			const int32_t r = r0 + j;
+			if (c.lens[r] < 0 || (c.lens[r] > 0 && !c.seqs[r])) return fail(w + ": null argument");
+			sum += c.lens[r];
+			if (n == 2 && ((j == 0 && (pe_ori >> 1 & 1)) || (j == 1 && (pe_ori & 1)))) {                    // map.c:1169-1171
+				append_seq(F.own[(size_t)r], c.seqs[r], c.lens[r], true);
+				F.seqs[(size_t)r] = F.own[(size_t)r].c_str();
+			}
+		}
+		if (sum >= INT32_MAX) return fail(w + ": a fragment of 2^31 bases or more");
+		F.u_names[(size_t)f] = c.names[r0]; F.u_seqs[(size_t)f] = F.seqs[(size_t)r0]; F.u_lens[(size_t)f] = (int32_t)sum;
+	}
+	F.reads = { c.names, F.seqs.data(), c.lens, pe_ori };
+	c.frag = &F.reads; c.frag_off = frag_off;
+	c.n_reads = n_frag; c.names = F.u_names.data(); c.seqs = F.u_seqs.data(); c.lens = F.u_lens.data();
+	return 0;
+}
+}
+
+int mm2gb_map_frags_sr(mm2gb_engine_t *eng, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens, int32_t n_ref, const mm2gb_map_opt_t *opt,
+                       const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs, const int32_t *lens, char **paf_out, int64_t *paf_len,
+                       mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out, int32_t n_frag, const int32_t *frag_off, int32_t pe_ori, const mm2gb_map_out_t *out)
+{
+	if (!eng) return fail("mm2gb: null engine");
+	mm2gb_map_aln_t aln;
+	bool aligned = false;
+	if (const char *why = sr_as_aln(sr, aln, aligned)) return fail(std::string("mm2gb_map_frags_sr: ") + why);
+	double extra[3] = { 0, 0, 0 };
+	if (sr_out) memset(sr_out, 0, sizeof *sr_out);
+	MapCall c = { eng, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
+	c.sr = sr; c.sr_out = sr_out; c.out = out;
+	FragUnits F;
+	if (frag_units("mm2gb_map_frags_sr", c, n_frag, frag_off, pe_ori, F)) return -1;
+	return map_reads_try(c);
+}
+
+int mm2gb_map_frags_stream_sr(mm2gb_engine_t *const *engines, int n_engines, const mm2gb_index_t *ix, int k, const char *const *ref_names, const int32_t *ref_lens,
+                              int32_t n_ref, const mm2gb_map_opt_t *opt, const mm2gb_map_sr_t *sr, int32_t n_reads, const char *const *names, const char *const *seqs,
+                              const int32_t *lens, int64_t chunk_bases, char **paf_out, int64_t *paf_len, mm2gb_map_stats_t *stats, mm2gb_map_sr_out_t *sr_out,
+                              int32_t n_frag, const int32_t *frag_off, int32_t pe_ori, const mm2gb_map_out_t *out)
+{
+	mm2gb_map_aln_t aln;
+	bool aligned = false;
+	if (const char *why = sr_as_aln(sr, aln, aligned)) return fail(std::string("mm2gb_map_frags_stream_sr: ") + why);
+	double extra[3] = { 0, 0, 0 };
+	mm2gb_map_sr_out_t own;
+	if (sr_out) memset(sr_out, 0, sizeof *sr_out);
+	MapCall c = { nullptr, ix, k, ref_names, ref_lens, n_ref, opt, n_reads, names, seqs, lens, paf_out, paf_len, stats, aligned ? &aln : nullptr, extra };
+	c.sr = sr; c.sr_out = sr_out ? sr_out : &own; c.out = out;
+	FragUnits F;
+	if (frag_units("mm2gb_map_frags_stream_sr", c, n_frag, frag_off, pe_ori, F)) return -1;
+	return stream_body(engines, n_engines, chunk_bases, c);
+}
+
+// mm_select_sub_multi / mm_seg_gen by themselves, batched over fragments (the mapper's stage 6 calls the same two functions per fragment)
+int mm2gb_select_sub_multi_host(float pri_ratio, float pri1, float pri2, int32_t min_diff, int32_t best_n, int64_t n_frag, const int32_t *n_segs, const int32_t *qlens,
+                                const int32_t *max_gap_ref, const int64_t *reg_off, mm2gb_reg_t *regs, int32_t *n_kept)
+{
+	if (n_frag < 0 || (n_frag > 0 && (!n_segs || !qlens || !max_gap_ref || !reg_off || !n_kept)) || (n_frag > 0 && reg_off[n_frag] > reg_off[0] && !regs)) return fail("mm2gb_select_sub_multi_host: null argument");
+	for (int64_t f = 0; f < n_frag; ++f) {
+		if (n_segs[f] < 1 || n_segs[f] > 2) return fail("mm2gb_select_sub_multi_host: a fragment has one or two segments (MM_MAX_SEG > 2 is not taken)");
+		const int64_t n = reg_off[f + 1] - reg_off[f];
+		if (n < 0) return fail("mm2gb_select_sub_multi_host: reg_off must not decrease");
+		for (int64_t i = 0; i < n; ++i) { const int p = regs[reg_off[f] + i].parent; if (p < 0 || p > i) return fail("mm2gb_select_sub_multi_host: a record's parent is itself or an earlier record of its fragment (mm_set_parent)"); }
+	}
+	for (int64_t f = 0; f < n_frag; ++f) {
+		std::vector<Hit> hs;
+		for (int64_t j = reg_off[f]; j < reg_off[f + 1]; ++j) hs.push_back(hit_from(regs[j]));
+		select_sub_multi(pri_ratio, pri1, pri2, max_gap_ref[f], min_diff, best_n, n_segs[f], qlens + 2 * f, hs);
+		for (size_t i = 0; i < hs.size(); ++i) reg_from(hs[i], regs[reg_off[f] + (int64_t)i]);
+		n_kept[f] = (int32_t)hs.size();
+	}
+	return 0;
+}
+
+void mm2gb_seg_out_free(mm2gb_seg_out_t *o)
+{
+	if (!o) return;
+	free(o->reg_off); free(o->regs); free(o->anchor_off); free(o->anchors);
+	memset(o, 0, sizeof *o);
+}
+
+int mm2gb_seg_gen_host(int64_t n_frag, const int32_t *n_segs, const int32_t *qlens, const uint32_t *hash, const int64_t *reg_off, const mm2gb_reg_t *regs,
+                       const int64_t *anchor_off, const mm2gb_anchor_t *anchors, mm2gb_seg_out_t *out)
+{
+	if (!out) return fail("mm2gb_seg_gen_host: null argument");
+	memset(out, 0, sizeof *out);
+	if (n_frag < 0 || (n_frag > 0 && (!n_segs || !qlens || !hash || !reg_off || !anchor_off))) return fail("mm2gb_seg_gen_host: null argument");
+	for (int64_t f = 0; f < n_frag; ++f) {
+		if (n_segs[f] < 1 || n_segs[f] > 2) return fail("mm2gb_seg_gen_host: a fragment has one or two segments (MM_MAX_SEG > 2 is not taken)");
+		const int64_t n_a = anchor_off[f + 1] - anchor_off[f];
+		if (reg_off[f + 1] < reg_off[f] || n_a < 0 || ((reg_off[f + 1] > reg_off[f]) && (!regs || !anchors))) return fail("mm2gb_seg_gen_host: offsets must not decrease, and records need anchors");
+		for (int64_t j = reg_off[f]; j < reg_off[f + 1]; ++j) {
+			if (regs[j].cnt < 1 || regs[j].as < 0 || (int64_t)regs[j].as + regs[j].cnt > n_a) return fail("mm2gb_seg_gen_host: a record's anchors lie outside its fragment's");
+			for (int32_t t = 0; t < regs[j].cnt; ++t) if ((int)(anchors[anchor_off[f] + regs[j].as + t].y >> 48 & 0xff) >= n_segs[f]) return fail("mm2gb_seg_gen_host: an anchor's segment id is not below n_segs");
+		}
+	}
+	std::vector<std::vector<Hit>> r((size_t)n_frag * 2);
+	std::vector<std::vector<mm2gb_anchor_t>> a((size_t)n_frag * 2);
+	for (int64_t f = 0; f < n_frag; ++f) {
+		std::vector<Hit> hs;
+		for (int64_t j = reg_off[f]; j < reg_off[f + 1]; ++j) hs.push_back(hit_from(regs[j]));
+		seg_gen(hash[f], n_segs[f], qlens + 2 * f, hs, anchors + anchor_off[f], &r[(size_t)f * 2], &a[(size_t)f * 2]);
+	}
+	const size_t U = (size_t)n_frag * 2;
+	out->reg_off = (int64_t*)calloc(U + 1, 8); out->anchor_off = (int64_t*)calloc(U + 1, 8);
+	if (!out->reg_off || !out->anchor_off) { mm2gb_seg_out_free(out); return fail("mm2gb_seg_gen_host: out of memory"); }
+	for (size_t q = 0; q < U; ++q) { out->reg_off[q + 1] = out->reg_off[q] + (int64_t)r[q].size(); out->anchor_off[q + 1] = out->anchor_off[q] + (int64_t)a[q].size(); }
+	out->regs = (mm2gb_reg_t*)calloc((size_t)out->reg_off[U] + 1, sizeof(mm2gb_reg_t)); out->anchors = (mm2gb_anchor_t*)calloc((size_t)out->anchor_off[U] + 1, sizeof(mm2gb_anchor_t));
+	if (!out->regs || !out->anchors) { mm2gb_seg_out_free(out); return fail("mm2gb_seg_gen_host: out of memory"); }
+	for (size_t q = 0; q < U; ++q) {
+		for (size_t i = 0; i < r[q].size(); ++i) reg_from(r[q][i], out->regs[out->reg_off[q] + (int64_t)i]);
+		if (!a[q].empty()) memcpy(out->anchors + out->anchor_off[q], a[q].data(), a[q].size() * sizeof(mm2gb_anchor_t));
+	}
+	return 0;
 }
 
 int mm2gb_engine_release_host_scratch(mm2gb_engine_t *eng)

@@ -81,6 +81,8 @@ struct MatchBatch {
 	int64_t n_reads, n_mini;
 	const int64_t *seq_off;            // n_reads + 1 (read lengths)
 	const ulonglong2 *mini; const int32_t *mini_read; const int64_t *mini_off;
+	const int32_t *len0;               // fragments (launch_frag_view ran; then "read" means fragment everywhere here): n_reads, the first mate's length -- a seed at or past it
+	                                   // is the second mate's (segment id 1); INT32_MAX for a fragment of one read.  Null: single reads, segment id 0
 	// scratch by minimizer (n_mini + 1 entries unless said)
 	unsigned long long *skey_in, *skey;    // the reads' x, unsorted / sorted within each read (q-occurrence filter)
 	unsigned char *keepq;
@@ -102,6 +104,19 @@ struct MatchBatch {
 	long long *src_first;              // by seed: where its occurrences begin in ix.where
 	unsigned long long *mini_pos; int32_t *rep_len, *qlen;
 };
+// The mates of a fragment as ONE read of the match selection (map.c:186-200): after the sketch of the batch's sequences, a fragment is the run of sequences
+// frag_off[f] .. frag_off[f + 1] (one or two).  A second mate's minimizers get the first mate's length added to their position (y += len0 << 1) and segment id 1
+// in y >> 32, every minimizer's owner becomes its fragment, and the per-fragment offsets the match kernels take (bases, minimizers) are read off the per-sequence ones.
+struct FragView {
+	int64_t n_frag, n_seqs, n_mini;
+	const int64_t *frag_off;           // n_frag + 1: first sequence of each fragment; frag_off[n_frag] = n_seqs
+	const int64_t *seq_off, *mini_off; // n_seqs + 1, the sketch's
+	ulonglong2 *mini; int32_t *mini_read;   // n_mini, rewritten in place
+	int64_t *f_seq_off, *f_mini_off;   // out, n_frag + 1
+	int32_t *len0;                     // out, n_frag (MatchBatch::len0)
+};
+void launch_frag_view(const FragView &v, hipStream_t s);
+
 size_t match_layout(MatchBatch &b, void *base);
 int    launch_matches_select(const MatchBatch &b, hipStream_t s);  // everything but the hits; tot is final when it is through.  -1: a library call refused
 void   launch_matches_gather(const MatchBatch &b, hipStream_t s);  // hits (b.hits sized by tot[3])

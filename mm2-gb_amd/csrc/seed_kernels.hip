@@ -321,6 +321,38 @@ void launch_sketch_write(const SketchBatch &b, hipStream_t s)
 	hipLaunchKernelGGL(k_sk_emit<true>, dim3(blocks(b.n + 1)), dim3(TB), 0, s, b);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- fragments
+namespace {
+
+// a thread per minimizer and per fragment boundary: the minimizer's sequence is found among frag_off by bisection (a fragment holds one or two sequences)
+__global__ __launch_bounds__(TB) void k_f_view(FragView v)
+{
+	const int64_t t = (int64_t)blockIdx.x * TB + threadIdx.x;
+	if (t <= v.n_frag) {
+		const int64_t r0 = v.frag_off[t];
+		v.f_seq_off[t] = v.seq_off[r0]; v.f_mini_off[t] = v.mini_off[r0];
+		if (t < v.n_frag) v.len0[t] = v.frag_off[t + 1] - r0 > 1 ? (int32_t)(v.seq_off[r0 + 1] - v.seq_off[r0]) : INT32_MAX;
+	}
+	if (t >= v.n_mini) return;
+	const int64_t r = v.mini_read[t];
+	int64_t lo = 0, hi = v.n_frag;                                                // frag_off[lo] <= r < frag_off[hi]
+	while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (v.frag_off[mid] <= r) lo = mid; else hi = mid; }
+	const int64_t r0 = v.frag_off[lo];
+	if (r > r0) {
+		ulonglong2 q = v.mini[t];
+		q.y += (unsigned long long)(v.seq_off[r] - v.seq_off[r0]) << 1 | (unsigned long long)(r - r0) << 32;     // (a sequence's own id is 0: sketch_device's rid is null here)
+		v.mini[t] = q;
+	}
+	v.mini_read[t] = (int32_t)lo;
+}
+
+} // namespace
+
+void launch_frag_view(const FragView &v, hipStream_t s)
+{
+	hipLaunchKernelGGL(k_f_view, dim3(blocks(std::max(v.n_mini, v.n_frag + 1))), dim3(TB), 0, s, v);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- matches
 namespace {
 
@@ -527,7 +559,8 @@ __global__ __launch_bounds__(TB) void k_m_seeds(MatchBatch b)
 	if (i >= M || b.flt[i]) return;
 	const uint32_t s = b.spos[i], span = b.m_span[i] & 0xff, q = b.m_q[i];
 	SeedRecord rec;
-	rec.n = b.m_n[i]; rec.q_pos = q; rec.span_flt = span; rec.seg_tandem = b.m_span[i] & (1u << 31);     // one segment: seg_id 0
+	const uint32_t seg = b.len0 && (int32_t)(q >> 1) >= b.len0[b.m_read[i]] ? 1u : 0u;                   // single reads: seg_id 0; a fragment's second mate lies past the first
+	rec.n = b.m_n[i]; rec.q_pos = q; rec.span_flt = span; rec.seg_tandem = (b.m_span[i] & (1u << 31)) | seg;
 	b.seeds[s] = rec;
 	b.mini_pos[s] = (unsigned long long)span << 32 | q >> 1;
 	b.hit_off[s] = b.hpos[i];

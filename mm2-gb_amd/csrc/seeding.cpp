@@ -9,7 +9,7 @@
 //   collect_matches   mm_collect_matches (seed.c:98-131) for one read: query minimizers, the over-represented ones dropped
 //                     (mm_seed_mz_flt, seed.c:5-30), every minimizer the index knows (mm_seed_collect_all, seed.c:32-54), the high-occurrence
 //                     ones thinned out (mm_seed_select, seed.c:58-96), repeat length and minimizer positions
-// The output of collect_matches is the input of mm2gb_collect_seeds_gpu.  One query segment per read (n_segs = 1).
+// The output of collect_matches is the input of mm2gb_collect_seeds_gpu.  One query segment per read, or the two mates of a fragment as one list (collect_matches_frag_refs).
 // Host code: an index look-up per minimizer is a pointer chase through a structure the size of the genome -- not a kernel.
 #include <algorithm>
 #include <cstdlib>
@@ -288,6 +288,12 @@ int mm2gb_collect_matches(const mm2gb_index_t *ix, const char *seq, int32_t len,
 	return collect_matches_refs(ix, seq, len, opt, out, nullptr);
 }
 
+int mm2gb_collect_matches_frag(const mm2gb_index_t *ix, int32_t n_segs, const char *const *seqs, const int32_t *lens, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out)
+{
+	if (n_segs < 1 || n_segs > 2) return fail("mm2gb_collect_matches_frag: a fragment has one or two segments (MM_MAX_SEG > 2 is not taken)");
+	return collect_matches_frag_refs(ix, n_segs, seqs, lens, opt, opt ? opt->mid_occ : 0, out, nullptr);
+}
+
 } // extern "C"
 
 // The index in a device's memory: keys, first, where, bucket copied as they are; the look-up there is SeedIndex::find as written (k_m_lookup).
@@ -329,15 +335,32 @@ int mm2gb::index_on_device(const mm2gb_index_t *ix_, int device, DevIndexView *o
 
 // refs == nullptr: out->hits is a copy of every kept seed's occurrences; otherwise out->hits stays null and refs[s] points at seed s's
 // occurrences in the index (the mapper copies them straight into the batch's array: host_chain.h)
-int mm2gb::collect_matches_refs(const mm2gb_index_t *ix_, const char *seq, int32_t len, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out, std::vector<const uint64_t*> *refs)
+int mm2gb::collect_matches_refs(const mm2gb_index_t *ix, const char *seq, int32_t len, const mm2gb_seed_opt_t *opt, mm2gb_matches_t *out, std::vector<const uint64_t*> *refs)
+{
+	if (len < 0 || (len > 0 && !seq)) return fail("mm2gb_collect_matches: null argument");
+	return collect_matches_frag_refs(ix, 1, &seq, &len, opt, opt ? opt->mid_occ : 0, out, refs);
+}
+
+// The same for a fragment of n_segs segments (map.c:186-200, 663-666): every segment sketched by itself, segment j's minimizers moved behind those of the segments before
+// it (y += (lens[0] + .. + lens[j-1]) << 1) with j in y >> 32, and everything after that on ONE list of length qlen_sum -- the q-occurrence filter, the tandem test across
+// the segments' boundary, the streaks and their length, the repeat length's state machine, mini_pos in concatenated coordinates.  flt_mid_occ: the threshold of the
+// q-occurrence filter, which the reference runs once with mid_occ before either round of seed collection (map.c:664); opt->mid_occ is the round's (max_occ in the rescue)
+int mm2gb::collect_matches_frag_refs(const mm2gb_index_t *ix_, int n_segs, const char *const *seqs, const int32_t *lens, const mm2gb_seed_opt_t *opt, int32_t flt_mid_occ, mm2gb_matches_t *out,
+                                     std::vector<const uint64_t*> *refs)
 {
 	const SeedIndex *ix = reinterpret_cast<const SeedIndex*>(ix_);
-	if (!ix || !opt || !out || len < 0 || (len > 0 && !seq)) return fail("mm2gb_collect_matches: null argument");
+	if (!ix || !opt || !out || n_segs < 1 || !seqs || !lens) return fail("mm2gb_collect_matches: null argument");
+	int32_t len = 0;                                       // qlen_sum
+	for (int j = 0; j < n_segs; ++j) { if (lens[j] < 0 || (lens[j] > 0 && !seqs[j])) return fail("mm2gb_collect_matches: null argument"); len += lens[j]; }
 	memset(out, 0, sizeof(*out));
 	std::vector<Mini> mv;
-	if (len > 0) sketch(seq, len, ix->w, ix->k, 0, (ix->flag & MM2GB_I_HPC) != 0, mv);                   // map.c:186-199, one segment
+	for (int j = 0, sum = 0; j < n_segs; sum += lens[j++]) {
+		const size_t from = mv.size();
+		if (lens[j] > 0) sketch(seqs[j], lens[j], ix->w, ix->k, (uint32_t)j, (ix->flag & MM2GB_I_HPC) != 0, mv);
+		for (size_t i = from; i < mv.size(); ++i) mv[i].y += (uint64_t)sum << 1;
+	}
 	// seed.c:5-30: a minimizer that makes up more than q_occ_frac of the read's minimizers (and more than mid_occ of them) goes
-	if (opt->q_occ_frac > 0.0f && opt->mid_occ > 0 && (int64_t)mv.size() > opt->mid_occ) {
+	if (opt->q_occ_frac > 0.0f && flt_mid_occ > 0 && (int64_t)mv.size() > flt_mid_occ) {
 		// occurrences of every minimizer value in the read, counted in an open-addressed table (the reference sorts a copy, seed.c:12-16; what
 		// is dropped depends on the counts only)
 		size_t cap = 64;
@@ -346,12 +369,12 @@ int mm2gb::collect_matches_refs(const mm2gb_index_t *ix_, const char *seq, int32
 		std::vector<int32_t> cnt(cap, 0);
 		auto slot_of = [&](uint64_t x) { size_t h = (size_t)((x * 0x9E3779B97F4A7C15ull) >> 20) & (cap - 1); while (key[h] != ~0ull && key[h] != x) h = (h + 1) & (cap - 1); return h; };
 		bool any = false;
-		for (const Mini &q : mv) { const size_t h = slot_of(q.x); key[h] = q.x; any |= ++cnt[h] > opt->mid_occ; }
+		for (const Mini &q : mv) { const size_t h = slot_of(q.x); key[h] = q.x; any |= ++cnt[h] > flt_mid_occ; }
 		if (any) {
 			size_t kept = 0;
 			for (size_t i = 0; i < mv.size(); ++i) {
 				const int32_t c = cnt[slot_of(mv[i].x)];
-				if (!(c > opt->mid_occ && c > mv.size() * opt->q_occ_frac)) mv[kept++] = mv[i];
+				if (!(c > flt_mid_occ && c > mv.size() * opt->q_occ_frac)) mv[kept++] = mv[i];
 			}
 			mv.resize(kept);
 		}
