@@ -101,6 +101,9 @@ int  mm2gb_engine_last_score_mode(mm2gb_engine_t *eng);
 /* measurement aid: groups of 64 targets that k_score's band pass (far predecessors by diagonal band; MM2GB_BAND, MM2GB_BAND_SLAB,
  * MM2GB_BAND_LAG when the engine is made) swept in the engine's calls since its stats were last reset: out[0] the wave path, out[1] the teams */
 int  mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out);
+/* measurement aid: chunks of the planner's sparse list (stretches of isolated anchors, no window wider than MM2GB_SPARSE_MAX_WINDOW when the
+ * engine is made; 0: no such list) that the score kernel scored in the engine's calls since its stats were last reset: the length of the list */
+int  mm2gb_engine_sparse_chunks(const mm2gb_engine_t *eng, int64_t *scored);
 /* measurement aid: the band pass's shape as the engine's score kernel is configured now: out[0] the slab (0: the band pass is off), out[1..4] the
  * lag of the wave path, the 4-wave teams, the 8-wave teams and whole-workgroup teams (MM2GB_BAND_LAG_WAVE, _TEAM4, _TEAM8, _WG; MM2GB_BAND_LAG
  * sets all four), out[5] the mean window, in anchors, above which a chunk takes the band pass */

@@ -327,6 +327,14 @@ class Engine:
         _check(lib().mm2gb_engine_band_groups(self._h, out))
         return int(out[0]), int(out[1])
 
+    def sparse_chunks(self):
+        """Chunks of the planner's sparse list (stretches of isolated anchors) that the score kernel scored in the last call."""
+        L = lib()
+        L.mm2gb_engine_sparse_chunks.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        n = C.c_int64()
+        _check(L.mm2gb_engine_sparse_chunks(self._h, C.byref(n)))
+        return int(n.value)
+
     def band_shape(self):
         """The band pass's shape as configured: the slab (0: off), the lag of each path and the mean window above which a chunk takes it."""
         L = lib()

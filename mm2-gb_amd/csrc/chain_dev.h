@@ -26,6 +26,11 @@ struct DevParams {
 // anchors, above which a chunk takes the band pass.
 constexpr int BAND_LAG_WAVE = 0, BAND_LAG_TEAM4 = 256, BAND_LAG_TEAM8 = 512, BAND_LAG_WG = 512;
 constexpr int BAND_MIN_WINDOW = 256;
+// A SPARSE chunk (chain_kernels.hip, plan_finish / sparse_chunk): no window wider than this many anchors, so every window lies in its
+// own tile and the one before it.  The engine's MM2GB_SPARSE_MAX_WINDOW lowers it (0: no chunk is sparse); never above SPARSE_WINDOW_LIMIT.
+constexpr int SPARSE_WINDOW_LIMIT = 63, SPARSE_MAX_WINDOW = 63;
+// a sparse chunk's mean window is below one tile, a band chunk's above band_min_window: no chunk is both (band_chunk)
+static_assert(SPARSE_WINDOW_LIMIT < 64 && SPARSE_WINDOW_LIMIT < BAND_MIN_WINDOW, "a sparse chunk never takes the band pass");
 
 // bits of DevBatch::flags[0]
 enum : unsigned { FLAG_ANY_SEGID = 1u,     // some anchor carries a segment id -> MODE_GENERAL
@@ -103,8 +108,8 @@ struct DevBatch {
 	int64_t  *chunk_pp;        // planner scratch: pairs before the chunk's first block
 	int32_t  *chunk_kk, *chunk_blk; // planner scratch: clamped blocks before it; its first block
 	int64_t  *tile_sums, *tile_base; // planner scratch: 3 values per tile of 1024 planning blocks
-	int32_t  *bins;            // planner scratch: 3 x 256 cost bins
-	int32_t  *order;           // chunk ids, most expensive first
+	int32_t  *bins;            // planner scratch: PLAN_LISTS x PLAN_COST_BINS cost bins
+	int32_t  *order;           // chunk ids scored by one wave, most expensive first: the wave list, and behind it (from counters[CNT_NWAVE]) the sparse list
 	int32_t  *long_list;       // chunk ids scored by a whole workgroup
 	int32_t  *mid_list;        // chunk ids scored by a 4-wave team
 	// scalars
@@ -116,12 +121,18 @@ struct DevBatch {
 	GangSlot *gang_slots;      // GANG_MAX_CHUNKS of them, set up by plan_gangs; null: no gangs
 };
 enum { CNT_NCHUNK = 0, CNT_CURSOR = 1, CNT_NLONG = 2, CNT_LCURSOR = 3, CNT_NTRACK = 4, CNT_NCLAMP = 5, CNT_NMID = 6, CNT_MCURSOR = 7,
+       CNT_NWAVE = 8,           // chunks on the wave list (the sparse list starts there in DevBatch::order)
+       CNT_NSPARSE = 9,         // chunks on the sparse list
+       CNT_SCURSOR = 10,        // its work cursor
+       CNT_SPARSE_DONE = 11,    // sparse chunks scored (k_score, phase 2)
        CNT_NGANG = 12,          // chunks scored by a gang of workgroups
        CNT_GANG_STRIPS = 13,    // strips of such chunks
        CNT_GANG_WGS = 14,       // workgroups that started in a gang
        CNT_BAND_WAVE = 16,      // groups of targets the band pass swept (k_score, band_group) in the wave path ...
        CNT_BAND_TEAM = 17,      // ... and in the team paths
        CNT_WORDS = 18 };
+// work lists of the planner (bits 1-2 of chunk_track; the engine sizes DevBatch::bins by it)
+constexpr int PLAN_LISTS = 4;
 
 struct LaunchCfg {
 	int score_grid;          // persistent 1024-thread workgroups of k_score
@@ -138,6 +149,7 @@ struct LaunchCfg {
 	int64_t long_min_cost;   // chunks at least this expensive ...
 	int     long_min_window; // ... whose mean window is at least this are candidates for the cooperative mode
 	int     wide_window;     // mean window from which a big team pays; narrower heavy chunks get 4-wave teams
+	int     sparse_max_window; // a chunk that is neither heavy nor tracked and has no window wider than this goes to the sparse list; 0: none does
 };
 
 void launch_window(const DevBatch &b, const DevParams &P, hipStream_t s);

@@ -26,6 +26,10 @@ namespace mm2gb {
 #define WAVE 64
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
+// the lane from the execution mask, all 64 lanes on -- for the functions that are called, not inlined (band_slab_part, sparse_chunk): a
+// called function that asked for threadIdx would make every caller keep the launch's packed work-item ids in a register of their
+// own for the whole kernel
+__device__ __forceinline__ int lane_by_count() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ int bcast(int v, int src_lane) { return __builtin_amdgcn_readlane(v, src_lane); }
 __device__ __forceinline__ int first_lane(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // Wave-wide maximum and the previous lane's value without the LDS crossbar: DPP row shifts and row broadcasts (six dependent vector
@@ -334,7 +338,10 @@ constexpr int COST_SUB = MM2GB_COST_BINS_PER_OCTAVE;   // bins per power of two 
 constexpr int COST_SUB_LOG = COST_SUB == 16 ? 4 : COST_SUB == 8 ? 3 : 2;
 constexpr int COST_BINS = 64 * COST_SUB;
 static_assert(COST_BINS <= PLAN_COST_BINS, "the engine allocates PLAN_COST_BINS bins per list");
-enum { LIST_WAVE = 0, LIST_BIG = 1, LIST_TEAM4 = 2, N_LISTS = 3 };
+// LIST_SPARSE: chunks of isolated anchors -- neither heavy nor tracked, no window wider than cfg.sparse_max_window (< one tile) -- which cost
+// memory traffic and next to no arithmetic.  The table build scores them with a function of their own, claimed several at a time (k_score phase 2).
+enum { LIST_WAVE = 0, LIST_BIG = 1, LIST_TEAM4 = 2, LIST_SPARSE = 3, N_LISTS = 4 };
+static_assert(N_LISTS == PLAN_LISTS, "the engine allocates PLAN_LISTS lists of bins");
 
 __device__ __forceinline__ int cost_bin(int64_t c)
 {
@@ -440,13 +447,17 @@ __global__ __launch_bounds__(256) void plan_finish(DevBatch b, LaunchCfg cfg)
 		const long long len = end - start;
 		const bool heavy = cfg.ring_slots > 0 && cost >= cfg.long_min_cost && len * cfg.long_min_window <= cost;
 		int list = LIST_WAVE;
-		if (heavy) {
-			// widest window of the chunk: the part of its first block from the first cut on, then whole (cut-free) blocks,
-			// then the part of the next chunk's block before that block's first cut
+		// widest window of the chunk: the part of its first block from the first cut on, then whole (cut-free) blocks,
+		// then the part of the next chunk's block before that block's first cut
+		auto widest_window = [&]() {
 			const int blk0 = b.chunk_blk[c], blk_end = last ? (int)b.n_blocks : b.chunk_blk[c + 1];
 			int wmax = b.blk_wmax[2 * blk0 + 1];
 			for (int k = blk0 + 1; k < blk_end; ++k) wmax = max(wmax, b.blk_wmax[2 * k]);
 			if (!last) wmax = max(wmax, b.blk_wmax[2 * blk_end]);
+			return wmax;
+		};
+		if (heavy) {
+			const int wmax = widest_window();
 			// a team's share of the LDS ring must hold the tiles its widest window reaches back to, plus the one being written
 			const int need_slots = (wmax + WAVE - 1) / WAVE + 1;
 			const int big_slots = cfg.ring_slots / (16 / cfg.big_team), small_slots = cfg.ring_slots / 4;   // k_score: 16 waves, four small teams
@@ -459,7 +470,7 @@ __global__ __launch_bounds__(256) void plan_finish(DevBatch b, LaunchCfg cfg)
 			                         cost * 100 * cfg.score_grid * N_SMALL_TEAMS_PLAN <= (long long)cfg.team4_share_pct * b.totals[0]));
 			if (len * cfg.wide_window > cost && need_slots <= small_slots) list = LIST_TEAM4;
 			else if (need_slots <= big_slots) list = small_share ? LIST_TEAM4 : LIST_BIG;   // else: window wider than the ring can hold -> one wave
-		}
+		} else if (!track && cfg.sparse_max_window > 0 && widest_window() <= min(cfg.sparse_max_window, SPARSE_WINDOW_LIMIT)) list = LIST_SPARSE;
 		b.chunk_end[c] = end;
 		b.chunk_cost[c] = cost;
 		b.chunk_track[c] = (uint8_t)((track ? 1 : 0) | (list << 1));
@@ -479,14 +490,17 @@ __global__ __launch_bounds__(256) void plan_finish(DevBatch b, LaunchCfg cfg)
 
 __global__ __launch_bounds__(64) void plan_bins(DevBatch b)
 {
+	// (the sparse list lies behind the wave list in DevBatch::order: its bases count from the wave list's end, which plan_scatter adds)
 	if (threadIdx.x < N_LISTS) {
 		int acc = 0;
 		int *bins = b.bins + threadIdx.x * COST_BINS;
 		for (int k = COST_BINS - 1; k >= 0; --k) { const int v = bins[k]; bins[k] = acc; acc += v; }   // count -> base
 		if (threadIdx.x == LIST_BIG) b.counters[CNT_NLONG] = acc;
 		if (threadIdx.x == LIST_TEAM4) b.counters[CNT_NMID] = acc;
+		if (threadIdx.x == LIST_WAVE) b.counters[CNT_NWAVE] = acc;
+		if (threadIdx.x == LIST_SPARSE) b.counters[CNT_NSPARSE] = acc;
 	}
-	if (threadIdx.x == 0) { b.counters[CNT_CURSOR] = 0; b.counters[CNT_LCURSOR] = 0; b.counters[CNT_MCURSOR] = 0; }
+	if (threadIdx.x == 0) { b.counters[CNT_CURSOR] = 0; b.counters[CNT_LCURSOR] = 0; b.counters[CNT_MCURSOR] = 0; b.counters[CNT_SCURSOR] = 0; }
 }
 
 __global__ __launch_bounds__(256) void plan_scatter(DevBatch b)
@@ -508,7 +522,8 @@ __global__ __launch_bounds__(256) void plan_scatter(DevBatch b)
 		for (int k = threadIdx.x; k < N_LISTS * COST_BINS; k += blockDim.x) if (s_cnt[k]) s_base[k] = atomicAdd(&b.bins[k], s_cnt[k]);
 		__syncthreads();
 		if (key >= 0) {
-			int *dst = key >= LIST_TEAM4 * COST_BINS ? b.mid_list : key >= LIST_BIG * COST_BINS ? b.long_list : b.order;
+			const int list = key / COST_BINS;
+			int *dst = list == LIST_TEAM4 ? b.mid_list : list == LIST_BIG ? b.long_list : list == LIST_SPARSE ? b.order + b.counters[CNT_NWAVE] : b.order;
 			dst[s_base[key] + rank] = (int)c;
 		}
 		__syncthreads();
@@ -1254,11 +1269,12 @@ __device__ __forceinline__ bool pair_score_uniform(const DevParams &P, int xi, i
 	return (unsigned)(dq - 1) < (unsigned)P.dq_lim && dr != 0 && dd <= P.bw;
 }
 
-template <bool TRACK, typename FOld>
+// BY_COUNT: the lane comes from lane_by_count (a called function's copy: sparse_chunk)
+template <bool TRACK, typename FOld, bool BY_COUNT = false>
 __device__ __forceinline__ void in_tile_lut(const DevBatch &b, const Target &T, int i0, int n_here, const DevParams &P, int4 *stage,
                                             int &best, int &arg, Keep &keep, FOld f_old, const Progress &prog = Progress())
 {
-	const int lane = lane_id(), i = i0 + lane;
+	const int lane = BY_COUNT ? lane_by_count() : lane_id(), i = i0 + lane;
 	// The in-tile phase is a chain of dependent instructions, and in a team every other wave's next tile waits for it: while it lasts
 	// this wave goes first among the 8 waves of its SIMD (the sweeping ones have independent work to fill the slots it leaves).
 	__builtin_amdgcn_s_setprio(MM2GB_INTILE_PRIO);
@@ -1670,9 +1686,6 @@ typedef const int __attribute__((address_space(1))) *glb_i32_cptr;
 typedef int __attribute__((address_space(1))) *glb_i32_ptr;
 typedef unsigned short __attribute__((address_space(1))) *glb_u16_ptr;
 typedef int4 __attribute__((address_space(3))) *lds_i32x4_ptr;
-// (the lane from the execution mask, all 64 lanes on: a called function that asked for threadIdx would make every caller keep the
-// launch's packed work-item ids in a register of their own for the whole kernel)
-__device__ __forceinline__ int lane_by_count() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 struct BandParams { int bw, dq_lim, lut_base, free_sweep, band_slab; };   // what the band pass needs of DevParams
 template <class T> __device__ __forceinline__ T uniform_glb(T p)
 {
@@ -2056,6 +2069,91 @@ __device__ __forceinline__ void run_chunk_pairs(const DevBatch &b, const DevPara
 	if (band_groups > 0 && lane == 0) atomicAdd(&b.counters[CNT_BAND_WAVE], band_groups);
 }
 
+// ---- sparse chunks (LIST_SPARSE): isolated anchors between the chains, table build ------------------------------------------
+// No window of such a chunk is wider than 63 anchors (plan_finish), so a tile's sources are the tile before it and the tile itself, and
+// most tiles have none at all: the chunk is a pass over memory -- 16 B + 4 B read and 8 B written per anchor -- with next to no
+// arithmetic.  The previous tile stays in registers (position, query position, span, final score: nothing is read twice); it is staged
+// and swept only where a window reaches into it, with the checked sweep of an edge block (sweep_staged_lut), and the in-tile phase
+// (in_tile_lut, plain build: such a chunk is never tracked) runs only where some anchor has a predecessor inside the tile.
+// ONE function per kernel, called, not inlined, by the recipe of band_slab_part: it must not cost the runners beside it registers.
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));      // (a plain vector: HIP's uint4 has no copy from another address space)
+typedef const u32x4_t __attribute__((address_space(1))) *glb_u32x4_cptr;
+struct SparseParams { int bw, dq_lim, lut_base, lut_last, lut_clamp, free_sweep; };   // what it needs of DevParams
+__device__ __noinline__ void sparse_chunk(const glb_u32x4_cptr raw_, const glb_i32_cptr st_, const glb_i32_ptr f_, const glb_i32_ptr p_,
+                                          const SparseParams sp, const lds_i32x4_ptr stage_, const int cs_, const int ce_)
+{
+	const glb_u32x4_cptr raw = uniform_glb(raw_);
+	const glb_i32_cptr st = uniform_glb(st_);
+	const glb_i32_ptr f = uniform_glb(f_), p = uniform_glb(p_);
+	DevParams P = {};                                               // the fields the edge sweep and the plain in-tile steps read
+	P.bw = first_lane(sp.bw); P.dq_lim = first_lane(sp.dq_lim); P.lut_base = first_lane(sp.lut_base); P.lut_last = first_lane(sp.lut_last);
+	P.lut_clamp = first_lane(sp.lut_clamp); P.free_sweep = first_lane(sp.free_sweep);
+	int4 *stage = (int4*)(lds_i32x4_ptr)(uintptr_t)(unsigned)first_lane((int)(unsigned)(uintptr_t)stage_);
+	const int cs = first_lane(cs_), ce = first_lane(ce_);
+	const int lane = lane_by_count();
+	const DevBatch none = {};                                       // (in_tile_lut reads the batch in the rescue build only)
+	Keep keep; keep.idx = -1; keep.x = keep.hi = keep.y = keep.tag = keep.f = 0;
+	int px = 0, py = 0, pq = 0, pf = 0;                             // the previous tile, one anchor per lane
+	for (int i0 = cs; i0 < ce; i0 += WAVE) {
+		const int i = i0 + lane, n_here = min(WAVE, ce - i0);
+		Target T;
+		T.live = i < ce;
+		const int il = T.live ? i : ce - 1;
+		const u32x4_t a = raw[il];                                   // x.lo x.hi y.lo y.hi (a_x, a_y, a_tag)
+		T.x = (int)a.x; T.y = (int)a.z; T.tag = tag_of(a.w); T.hi = 0;
+		T.st = T.live ? st[il] : INT_MAX;                            // dead lanes never activate
+		T.q = T.tag & 0xff; T.seg = T.tag >> 8;
+		int best = T.q + 1, arg = -1;
+		const int tile_lo = first_lane(T.st);                       // lane 0 has the smallest window start
+		if (tile_lo < i0) {
+			// some window reaches into the previous tile (a full one), never beyond it
+			const int jb = i0 - WAVE;
+			stage_block_lut_at(lane, px, py, pf, pq, stage);
+			const TileXY xy = { T.x, T.y, T.st };
+			sweep_staged_lut(xy, jb, max(tile_lo - jb, 0), false, false, stage, P, best, arg);
+			__builtin_amdgcn_wave_barrier();
+		}
+		// (in_tile_lut does nothing to best / arg where no anchor reaches back to a source of its own tile)
+		if ((__ballot(T.live && T.st < i) >> 1) != 0ull)
+			in_tile_lut<false, int (*)(int), true>(none, T, i0, n_here, P, stage, best, arg, keep, nullptr);
+		const int fi = arg < 0 ? T.q : best;
+		if (T.live) {
+			f[i] = fi;
+			p[i] = arg < 0 ? 0 : i - arg;
+		}
+		px = T.x; py = T.y; pq = T.q; pf = fi;
+	}
+}
+// the callers' side, chunk ci of the batch
+__device__ __forceinline__ void sparse_run(const DevBatch &b, const DevParams &P, int4 *stage, const int ci)
+{
+	const SparseParams sp = { P.bw, P.dq_lim, P.lut_base, P.lut_last, P.lut_clamp, P.free_sweep };
+	sparse_chunk((glb_u32x4_cptr)(const u32x4_t*)b.raw, (glb_i32_cptr)b.st, (glb_i32_ptr)b.f, (glb_i32_ptr)b.p, sp, (lds_i32x4_ptr)stage,
+	             first_lane(b.chunk_start[ci]), first_lane(b.chunk_end[ci]));
+}
+// This wave takes chunks from the sparse list until it is empty, SPARSE_CLAIM of them per atomic add.  Several per claim because
+// the cursor is ONE address for 8 k waves and a sparse chunk is a few microseconds of work: claimed one by one, the list is served at
+// the rate the L2 does atomics on one line and no faster (the bench batch: 317 k chunks).
+// Returns how many it scored.  (Nested ifs, no `continue`: DESIGN 10 on loops headed by an atomic.)
+constexpr int SPARSE_CLAIM = 8;
+__device__ __forceinline__ int sparse_take(const DevBatch &b, const DevParams &P, int4 *stage, const int n_sparse)
+{
+	const int32_t *list = b.order + first_lane(b.counters[CNT_NWAVE]);
+	int taken = 0;
+	int seen = 0;
+	while (seen < n_sparse) {
+		int c = 0;
+		if (lane_id() == 0) c = atomicAdd(&b.counters[CNT_SCURSOR], SPARSE_CLAIM);
+		c = first_lane(c);
+		seen = c + SPARSE_CLAIM;
+		if (c < n_sparse) {
+			const int c_end = min(c + SPARSE_CLAIM, n_sparse);
+			for (int k = c; k < c_end; ++k) sparse_run(b, P, stage, first_lane(list[k]));
+			taken += c_end - c;
+		}
+	}
+	return taken;
+}
 // ---- team mode: the waves of a team (4, 8 or 16) pipeline the tiles of ONE heavy chunk ------------------------
 // Wave w takes tiles w, w+16, ...  A tile's sources are swept oldest first, so the only sources that may not be final
 // yet are the most recent tiles': the sweep reaches them last, and by then the waves ahead have normally finished
@@ -2601,13 +2699,22 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 		}
 	}
 	if (b.dbg && lane_id() == 0) atomicMax((unsigned long long*)&b.dbg[blockIdx.x * 4 + 2], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-	// phase 2: one wave per chunk
-	const int n_chunks = b.counters[CNT_NCHUNK] - n_long - n_mid;
+	// phase 2: one wave per chunk -- the wave list, then the sparse list behind it in `order`.  The table build scores a
+	// sparse chunk with sparse_chunk; the per-pair builds have no such function: they run through both lists with run_chunk.
+	// A launch with gangs has no sparse list (Engine::enqueue makes none where it hands out gang slots: gangs are for batches that end
+	// with their largest chunks, not with their cheapest, and the call site cost this kernel's runners 20 spilled registers): its
+	// phase 2 is the wave list alone
+	const bool lean = MODE == MODE_LUT && !GANG;
+	const int n_wave = GANG ? b.counters[CNT_NCHUNK] - n_long - n_mid : first_lane(b.counters[CNT_NWAVE]);
+	const int n_sparse = GANG ? 0 : first_lane(b.counters[CNT_NSPARSE]);
+	const int n_chunks = lean ? n_wave : n_wave + n_sparse;
+	int n_tail = 0;
 	while (true) {
 		int c = 0;
 		if (lane_id() == 0) c = atomicAdd(&b.counters[CNT_CURSOR], 1);
 		c = first_lane(c);
 		if (c >= n_chunks) break;
+		if (!GANG) n_tail += c >= n_wave;
 		const int ci = first_lane(b.order[c]);
 		const int cs = first_lane(b.chunk_start[ci]), ce = first_lane(b.chunk_end[ci]);
 		if (MODE == MODE_LUT) {
@@ -2619,6 +2726,8 @@ __global__ __launch_bounds__(SCORE_THREADS, 8) void k_score(DevBatch b, DevParam
 			else run_chunk<MODE, false>(b, P, lut, stage, cs, ce);
 		}
 	}
+	if (lean && n_sparse > 0) n_tail = sparse_take(b, P, stage, n_sparse);
+	if (n_tail > 0 && lane_id() == 0) atomicAdd(&b.counters[CNT_SPARSE_DONE], n_tail);
 	if (b.dbg && lane_id() == 0) atomicMax((unsigned long long*)&b.dbg[blockIdx.x * 4 + 3], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 }
 

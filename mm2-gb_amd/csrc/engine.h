@@ -145,6 +145,7 @@ struct Engine {
 
 	mm2gb_stats_t last = {};
 	bool misc_valid = false, coop_disabled = false, debug_phases = false, one_compute_stream = false;
+	int64_t sparse_min_n = 0;       // micro-batches from this many anchors on get the planner's sparse list (launch.sparse_max_window)
 	int64_t team4_min_n = 0;        // micro-batches from this many anchors on send wide-window heavy chunks to 4-wave teams (launch.team4_share_pct)
 	int64_t gang_max_n = 0;         // micro-batches up to this many anchors run the instantiation of k_score with the gang phase
 	int64_t last_gang_chunks = 0, last_gang_wgs = 0;        // of the last call: chunks scored by a gang of workgroups, workgroups that started in one
@@ -158,6 +159,7 @@ struct Engine {
 	bool lds_contract_ok = false;   // this device reads 0 beyond a workgroup's LDS and saturates v_sad_u32 ... clamp (probed in init)
 	int64_t dual_stream_max_n = 16 * 1000 * 1000;   // micro-batches up to this many anchors alternate between the two compute streams
 	bool chain_skip = false;        // the DP keeps misc.max_skip (k_skip_fill) where the limit can be reached; false: exhaustive (k_score), the default.  MM2GB_CHAIN_SKIP=keep at creation
+	int64_t last_sparse_chunks = 0;           // chunks of the planner's sparse list that k_score scored, since the last reset of the stats
 	int64_t last_band_groups[2] = { 0, 0 };   // groups of targets k_score's band pass swept in the wave path / the team paths, since the last reset of the stats
 	int  last_score_form = 0;       // form of the DP the last enqueued micro-batch ran: 0 exhaustive (k_score), 1 the skip-limited walk (k_skip_fill)
 	int  last_score_set = 0, last_score_host_mode = 0;   // work set (whose flag word the device combined with it) and launch.host_mode of the last enqueued micro-batch (mm2gb_engine_last_score_mode)

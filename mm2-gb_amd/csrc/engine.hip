@@ -434,6 +434,15 @@ int Engine::init(const mm2gb_config_t *c, const mm2gb_misc_t *m, int dev)
 	if (const char *v = getenv("MM2GB_TEAM4_ALL")) launch.team4_all = atoi(v) != 0;
 	if (const char *v = getenv("MM2GB_TEAM4_SHARE_PCT")) launch.team4_share_pct = std::max(0, atoi(v));
 	if (const char *v = getenv("MM2GB_TEAM4_MIN_ANCHORS")) team4_min_n = std::max<int64_t>(0, atoll(v));
+	// Sparse chunks (chain_kernels.hip, sparse_chunk): stretches of isolated anchors, no window wider than MM2GB_SPARSE_MAX_WINDOW (at most
+	// SPARSE_WINDOW_LIMIT, below a tile and below every band_min_window a chunk of the band pass has; 0: no such list), get a list of their
+	// own, which phase 2 of the score kernel serves after the wave list, several chunks per claim.  It pays where the kernel's end waits for
+	// that list -- 500 M anchors: 36.7 -> 34.8 ms, configs[2] at 500 M: 28.0 -> 26.5 -- and a 100 M batch of 10-30 kb reads lost 4 % to it
+	// (3.35, 3.34 -> 3.49, 3.48 ms: profiles/sparse_fill/full_two_runs.txt, section A), so it is tied to the batch size as the 4-wave rule
+	// above is: MM2GB_SPARSE_MIN_ANCHORS, the smallest micro-batch that gets the list.  A launch with gangs never gets one (enqueue)
+	launch.sparse_max_window = SPARSE_MAX_WINDOW; sparse_min_n = 250000000;
+	if (const char *v = getenv("MM2GB_SPARSE_MIN_ANCHORS")) sparse_min_n = std::max<int64_t>(0, atoll(v));
+	if (const char *v = getenv("MM2GB_SPARSE_MAX_WINDOW")) launch.sparse_max_window = std::max(0, std::min(SPARSE_WINDOW_LIMIT, atoi(v)));
 	if (const char *v = getenv("MM2GB_DEBUG_PHASES")) debug_phases = *v && *v != '0';
 	// the DP's skip limit (mg_lchain_dp's max_skip): kept only on request, so that hosts that cannot call mm2gb_engine_set_chain_skip (the
 	// reference's own host, the engines of pools and batchers) can opt in; read here once, never per call
@@ -558,7 +567,7 @@ int Engine::reserve(int64_t n, int64_t n_reads, int set)
 		if (w.blk_firstcut.ensure(nb * 4) || w.blk_pairs.ensure(nb * 8) || w.blk_clamped.ensure(nb * 4) || w.blk_wmax.ensure(nb * 8) || w.blk_read.ensure(nb * 4)) return -1;
 		if (w.chunk_start.ensure(nb * 4) || w.chunk_end.ensure(nb * 4) || w.chunk_cost.ensure(nb * 8) || w.chunk_track.ensure(nb) ||
 		    w.order.ensure(nb * 4) || w.long_list.ensure(nb * 4) || w.mid_list.ensure(nb * 4) || w.chunk_pp.ensure(nb * 8) || w.chunk_kk.ensure(nb * 4) || w.chunk_blk.ensure(nb * 4) ||
-		    w.tile_sums.ensure((nb / 1024 + 2) * 24) || w.tile_base.ensure((nb / 1024 + 2) * 24) || w.bins.ensure(3 * PLAN_COST_BINS * 4)) return -1;
+		    w.tile_sums.ensure((nb / 1024 + 2) * 24) || w.tile_base.ensure((nb / 1024 + 2) * 24) || w.bins.ensure(PLAN_LISTS * PLAN_COST_BINS * 4)) return -1;
 		w.cap_n = nn; w.cap_blocks = nb; w.cap_reads = std::max(had_reads, n_reads);
 	}
 	return 0;
@@ -571,6 +580,7 @@ int Engine::begin_call()
 	last = mm2gb_stats_t();
 	last_gang_chunks = last_gang_wgs = 0;
 	last_band_groups[0] = last_band_groups[1] = 0;
+	last_sparse_chunks = 0;
 	return 0;
 }
 
@@ -610,6 +620,7 @@ int Engine::enqueue(int64_t n_reads, const int64_t *d_offsets, const mm2gb_ancho
 		if (w.gang_slots.ensure((size_t)GANG_MAX_CHUNKS * sizeof(GangSlot))) return -1;
 		b.gang_slots = (GangSlot*)w.gang_slots.ptr;                  // (filled by plan_gangs; CNT_NGANG says how many)
 	}
+	if (n < sparse_min_n || b.gang_slots) cfg_now.sparse_max_window = 0;   // (the gang kernel's phase 2 knows the wave list only)
 
 	MM2GB_HIP(hipMemsetAsync(counters.ptr, 0, CNT_WORDS * sizeof(int32_t), stream));
 	MM2GB_HIP(hipMemsetAsync(totals.ptr, 0, 4 * sizeof(int64_t), stream));
@@ -1592,6 +1603,7 @@ int Engine::collect_stats()
 		last.n_clamped_blocks += c[CNT_NCLAMP];
 		last_gang_chunks += c[CNT_NGANG]; last_gang_wgs += c[CNT_GANG_WGS];
 		last_band_groups[0] += c[CNT_BAND_WAVE]; last_band_groups[1] += c[CNT_BAND_TEAM];
+		last_sparse_chunks += c[CNT_SPARSE_DONE];
 		float ms = 0;
 		if (hipEventElapsedTime(&ms, slots[k].prep0, slots[k].prep1) == hipSuccess) last.ms_prep += ms;
 		if (hipEventElapsedTime(&ms, slots[k].prep1, slots[k].score1) == hipSuccess) last.ms_score += ms;
@@ -1735,6 +1747,12 @@ int mm2gb_engine_band_groups(const mm2gb_engine_t *eng, int64_t *out)
 {
 	if (!eng || !out) return fail("mm2gb_engine_band_groups: null argument");
 	out[0] = eng->e.last_band_groups[0]; out[1] = eng->e.last_band_groups[1];
+	return 0;
+}
+int mm2gb_engine_sparse_chunks(const mm2gb_engine_t *eng, int64_t *scored)
+{
+	if (!eng || !scored) return fail("mm2gb_engine_sparse_chunks: null argument");
+	*scored = eng->e.last_sparse_chunks;
 	return 0;
 }
 int mm2gb_engine_band_shape(const mm2gb_engine_t *eng, int *out)
