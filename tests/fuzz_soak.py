@@ -3,13 +3,16 @@ Runs tests/synth_cases.fuzz_case batches (--general: fuzz_case_general, the per-
 to gpurun_out/fuzz_fail_<seed>_<iteration>.npz (anchors, offsets, GPU f/p, parameters) and the exit code is 1.
 --teams adds three engines whose planner thresholds send every chunk that fits the LDS ring to the big (8/16-wave) teams and to
 the 4-wave teams (normally reserved for long chunks), and one that sends every chunk of two strips or more to a gang of workgroups, so the cooperative
-paths see the same odd shapes."""
+paths see the same odd shapes.  Two more take the form of the score kernel that batches of 250 M anchors and more get -- the planner's sparse
+list, the 4-wave share rule, no gangs -- at the default thresholds and with heavy chunks beside the sparse ones in small batches; the length of
+their list is checked against the planner's rule (test_gpu_sparse_fill.expected_sparse) batch by batch.  They sit out the --huge batch."""
 import argparse, json, os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE); sys.path.insert(0, os.path.dirname(HERE))
 import numpy as np
 import mm2gb_amd as mm, orc, synth_cases as sc
 from test_gpu_parity import misc_from, rel
+from test_gpu_sparse_fill import LARGE, expected_sparse, heavy_rule
 
 ap = argparse.ArgumentParser()
 ap.add_argument("seeds", type=int, nargs="+")
@@ -50,6 +53,7 @@ def post_differs(eng, a, off, prm, what):
 
 
 engines = [("default", make_engine({}))]
+large_heavy = {}                       # engines of the large-batch form: (least cost, least mean window + 16) of their heavy chunks
 if args.teams:
     engines.append(("team8", make_engine({"MM2GB_LONG_MIN_COST": "1", "MM2GB_LONG_MIN_WINDOW": "1", "MM2GB_WIDE_WINDOW": "1", "MM2GB_WHOLE_WG_PCT": "0"})))
     engines.append(("team16", make_engine({"MM2GB_LONG_MIN_COST": "1", "MM2GB_LONG_MIN_WINDOW": "1", "MM2GB_WIDE_WINDOW": "1", "MM2GB_WHOLE_WG_PCT": "1"})))
@@ -59,8 +63,26 @@ if args.teams:
     # every chunk of two strips or more on a gang of workgroups (round 4): scores and the rescue state across workgroups, quarters handed out early
     engines.append(("gangs", make_engine({"MM2GB_LONG_MIN_COST": "1", "MM2GB_LONG_MIN_WINDOW": "1", "MM2GB_WIDE_WINDOW": "1", "MM2GB_GANG_PCT": "100000", "MM2GB_GANG_MAX": "64",
                                           "MM2GB_GANG_MAX_ANCHORS": "2000000000"})))
+    # the large-batch form; "large-teams": chunks with a mean window of 64 and more are heavy, which no sparse chunk is (test_gpu_sparse_fill.TEAM_ENVS)
+    for name, env in (("large", LARGE), ("large-teams", dict(LARGE, MM2GB_LONG_MIN_COST="1", MM2GB_LONG_MIN_WINDOW="80"))):
+        engines.append((name, make_engine(env)))
+        large_heavy[name] = heavy_rule(env)
 seen = {name: [0, 0] for name, _ in engines}
+sparse_chunks = {name: 0 for name in large_heavy}
 gang_chunks = 0
+
+
+def list_differs(name, eng, a, off, prm, what):
+    """An engine of the large-batch form: the chunks its last call took from the sparse list, against the planner's rule."""
+    global failed
+    got, want = eng.sparse_chunks(), expected_sparse(a, off, prm, heavy=large_heavy[name]) if len(a) else 0
+    sparse_chunks[name] += got
+    if got != want:
+        print("SPARSE LIST differs:", what, "engine", name, "scored", got, "the planner's rule gives", want, "parameters", orc.param_to_dict(prm), flush=True)
+        np.savez(os.path.join(out_dir, f"fuzz_fail_list_{name}.npz"), a=a, off=off, prm=json.dumps(orc.param_to_dict(prm), default=float))
+        failed = True
+    return got != want
+
 for seed in args.seeds:
     rng = np.random.default_rng(seed)
     for it in range(args.iters):
@@ -74,6 +96,8 @@ for seed in args.seeds:
             seen[name][0] += st["n_long_chunks"]; seen[name][1] += st["n_mid_chunks"]
             if name == "gangs":
                 gang_chunks += eng.gang_counts()[0]
+            if name in large_heavy and list_differs(name, eng, a, off, prm, f"seed {seed} iteration {it}"):
+                break
             if args.post and name == "default":
                 post_differs(eng, a, off, prm, f"seed {seed} iteration {it}")
             bad = np.flatnonzero((f != fo) | (p != po_rel))
@@ -109,8 +133,12 @@ for seed in args.seeds:
         fo, po, pairs = orc.chain_fill_many(a, off, prm, threads=16)
         po_rel = np.concatenate([rel(po[off[r]:off[r + 1]]) for r in range(len(off) - 1)])
         for name, eng in engines:
+            if huge and name in large_heavy:
+                continue
             eng.set_misc(misc_from(prm))
             f, p, st = eng.score(a, off)
+            if name in large_heavy and list_differs(name, eng, a, off, prm, f"BIG seed {seed} iteration {it}"):
+                break
             if args.post and name == "default" and not post_differs(eng, a, off, prm, f"BIG seed {seed} iteration {it}"):
                 pass
             bad = np.flatnonzero((f != fo) | (p != po_rel))
@@ -127,7 +155,8 @@ for seed in args.seeds:
             print("seed", seed, "clean over", args.big, "large batches and", args.huge, "of >= 20 M anchors", flush=True)
     if failed:
         break
-print("chunks sent to big / 4-wave teams per engine:", seen, "| chunks scored by gangs (engine 'gangs'):", gang_chunks)
+print("chunks sent to big / 4-wave teams per engine:", seen, "| chunks scored by gangs (engine 'gangs'):", gang_chunks,
+      "| sparse chunks per engine of the large-batch form:", json.dumps(sparse_chunks))
 for _, e in engines:
     e.close()
 sys.exit(1 if failed else 0)

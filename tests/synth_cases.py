@@ -234,13 +234,28 @@ def with_segments(a, n_seg, seed, share=1.0):
     return sort_by_x(np.concatenate([a, dup]))
 
 
+def sparse_stretch(n, seed, gap=10_000, n_runs=4, rid=5):
+    """A stretch of isolated anchors, `gap` apart on the reference and anywhere on the query, with a few runs of 2-7 anchors at 20 / 20:
+    no window holds more than a few anchors, which is what the planner's sparse list is made of (two planning blocks and more of it
+    hold a chunk of nothing else)."""
+    rng = np.random.default_rng(seed)
+    dx = np.full(n, gap, np.int64)
+    y = rng.integers(1000, 50_000, n)
+    for _ in range(n_runs):
+        pos = int(rng.integers(1, n))
+        for k in range(pos, min(n, pos + int(rng.integers(1, 7)))):
+            dx[k] = 20
+            y[k] = y[k - 1] + 20
+    return pack(np.full(n, rid), np.zeros(n, np.int64), 1000 + np.cumsum(dx), y)
+
+
 SPLICE_KW = dict(is_cdna=1, bw=200_000, max_dist_x=200_000, max_dist_y=2_000)
 GENERAL_CLASSES = "abcdefg"
 
 
 def fuzz_case_general(rng, it):
     """Like fuzz_case, for the score builds fuzz_case never reaches.  Reads are drawn from spliced / qins_chain / jump_chain, the older
-    kinds and slices of earlier reads; the parameter class is cycled by the iteration index (GENERAL_CLASSES[it % 7]), so every class
+    kinds, stretches of isolated anchors (sparse_stretch: chunks for the planner's sparse list) and slices of earlier reads; the parameter class is cycled by the iteration index (GENERAL_CLASSES[it % 7]), so every class
     occurs in any 7 consecutive iterations whatever the seed:
       a  the splice preset (is_cdna, bw = max_dist_x = 200 000, max_dist_y = 2 000)      b  is_cdna with bw in {0, 100, 500}
       c  n_seg in {2, 3} with segment ids                                                 d  n_seg > 1 and is_cdna
@@ -250,10 +265,12 @@ def fuzz_case_general(rng, it):
     cls = GENERAL_CLASSES[it % len(GENERAL_CLASSES)]
     reads = []
     for _ in range(int(rng.integers(1, 7))):
-        kind = int(rng.integers(0, 9))
+        kind = int(rng.integers(0, 10))
         seed = int(rng.integers(1, 1 << 30))
         if kind == 0:
             reads.append(np.zeros((0, 2), np.uint64))
+        elif kind == 8:
+            reads.append(sparse_stretch(int(rng.integers(1100, 3000)), seed, rid=int(rng.integers(0, 4))))
         elif kind == 1:
             reads.append(spliced(int(rng.integers(1, 40)), seed, noise_n=int(rng.choice([0, 0, 300, 2000]))))
         elif kind == 2:

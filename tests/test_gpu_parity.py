@@ -427,13 +427,25 @@ def test_fuzz_random_batches_and_parameters(engine):
                 assert np.array_equal(res[r][0], o["u"]) and np.array_equal(res[r][1], o["a_out"]), (it, r, kw)
 
 
-def test_fuzz_soak_six_engine_configurations():
-    """tests/fuzz_soak.py inside the suite: one seed (from the kernel sources' hash) x 100 batches x six
+def soak_sparse_chunks(stdout):
+    """tests/fuzz_soak.py's last line: sparse chunks scored per engine of the large-batch form"""
+    import json
+    import re
+    m = re.search(r"sparse chunks per engine of the large-batch form: (\{.*\})", stdout.strip().splitlines()[-1])
+    assert m, stdout[-500:]
+    return json.loads(m.group(1))
+
+
+def test_fuzz_soak_eight_engine_configurations():
+    """tests/fuzz_soak.py inside the suite: one seed (from the kernel sources' hash) x 100 batches x eight
     engine configurations -- default planner, every chunk on 8-wave teams, on whole-workgroup teams, on 4-wave teams, on 4-wave teams
-    with windows wider than the ring share, on gangs of workgroups -- each batch against the oracle on every anchor, the device post-pass against the host
-    post-pass, 2 larger bench-like batches with random parameters, and one batch of >= 20 M anchors (30-300 kb reads: team modes, gangs and
-    the planner's lists under real load) -- every anchor of it against the oracle under all six configurations.  The bug that mattered in round 2 (the unchecked sweep judging a
-    tile by an anchor of the next read) was found by exactly this tool."""
+    with windows wider than the ring share, on gangs of workgroups, and the form batches of 250 M anchors and more get (sparse list, 4-wave
+    share rule, no gangs) at the default thresholds and with heavy chunks beside the sparse ones -- each batch against the oracle on every
+    anchor, the device post-pass against the host post-pass, 2 larger bench-like batches with random parameters, and one batch of >= 20 M
+    anchors (30-300 kb reads: team modes, gangs and the planner's lists under real load) -- every anchor of it against the oracle under
+    the first six configurations.  Both engines of the large-batch form must have scored sparse chunks, as many per batch as the planner's
+    rule gives (the tool's check).  The bug that mattered in round 2 (the unchecked sweep judging a tile by an anchor of the next read) was
+    found by exactly this tool."""
     import os
     import subprocess
     import sys
@@ -444,6 +456,8 @@ def test_fuzz_soak_six_engine_configurations():
     print(r.stdout[-1500:])
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     assert f"seed {seed} clean over" in r.stdout
+    scored = soak_sparse_chunks(r.stdout)
+    assert set(scored) == {"large", "large-teams"} and min(scored.values()) > 0, scored
 
 
 def test_large_batch_properties_and_mode_agreement(monkeypatch):

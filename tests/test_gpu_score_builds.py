@@ -17,7 +17,7 @@ import pytest
 
 import orc
 import synth_cases as sc
-from test_gpu_parity import fuzz_seed, misc_from, rel
+from test_gpu_parity import fuzz_seed, misc_from, rel, soak_sparse_chunks
 
 pytestmark = pytest.mark.gpu
 
@@ -349,10 +349,12 @@ def test_fuzz_general(engine, tmp_path):
     assert seen == {LUT, FAST, GENERAL}
 
 
-def test_fuzz_soak_general_six_engine_configurations():
-    """tests/fuzz_soak.py --general in a child process: 28 batches of fuzz_case_general under the six engine configurations of --teams
-    (default planner, every chunk on 8-wave, whole-workgroup and 4-wave teams, 4-wave teams with wide windows, gangs), each against the
-    oracle on every anchor, the default engine's device post-pass against the host post-pass."""
+def test_fuzz_soak_general_eight_engine_configurations():
+    """tests/fuzz_soak.py --general in a child process: 28 batches of fuzz_case_general under the eight engine configurations of --teams
+    (default planner, every chunk on 8-wave, whole-workgroup and 4-wave teams, 4-wave teams with wide windows, gangs, the large-batch
+    form at the default thresholds and with heavy chunks), each against the oracle on every anchor, the default engine's device post-pass
+    against the host post-pass.  The per-pair builds run through the sparse list with run_chunk: both engines of the large-batch form
+    must have scored chunks of it."""
     here = os.path.dirname(os.path.abspath(__file__))
     seed = fuzz_seed() ^ 0x6e4
     r = subprocess.run([sys.executable, os.path.join(here, "fuzz_soak.py"), str(seed), "--general", "--teams", "--post", "--iters", "28"],
@@ -360,3 +362,5 @@ def test_fuzz_soak_general_six_engine_configurations():
     print(r.stdout[-1500:])
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     assert f"seed {seed} clean over 28 batches" in r.stdout
+    scored = soak_sparse_chunks(r.stdout)
+    assert set(scored) == {"large", "large-teams"} and min(scored.values()) > 0, scored
