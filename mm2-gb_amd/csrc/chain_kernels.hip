@@ -1730,8 +1730,19 @@ __device__ __forceinline__ void sweep_block_lut_band(int t_st, int tx4, int ty4,
 
 // What the band pass reads and writes of the batch (band_slab_part makes it from its arguments).
 struct BandIO { glb_i32_cptr raw, st, f, diag; glb_i32_ptr res; };
+typedef int i32x4_t __attribute__((ext_vector_type(4)));          // (a plain vector: HIP's int4 has no copy from another address space)
+typedef const i32x4_t __attribute__((address_space(1))) *glb_i32x4_cptr;
+typedef const char __attribute__((address_space(1))) *glb_char_cptr;
+// a when the lane's bit of the scalar mask m is set, else b: the mask goes into the select as it is -- no compare, no bool made of it
+__device__ __forceinline__ int select_by_mask(const unsigned long long m, const int a, const int b)
+{
+	int r;
+	asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+	return r;
+}
 
 // One group of targets (lane: target index, -1 = none; at least one lane holds one) against the sources [smallest window start, jl).
+// Called with all 64 lanes on (select_by_mask and the lane shifts count on it).
 __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, int4 *stage, const int tgt, const int jl)
 {
 	const int lane = lane_by_count();
@@ -1739,8 +1750,8 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 	const int t = tgt >= 0 ? tgt : bcast(tgt, l0);                 // empty lanes repeat a target of the group
 	const int x = r_x(b.raw, t), y = r_y(b.raw, t), st = b.st[t];
 	int best = r_span(b.raw, t) + 1, arg = -1;                     // threshold form, as the dense sweep
-	const int lo = wave_min_i32(st), hi_st = wave_max_i32_dpp(st);
-	if (lo < jl) {
+	const int lo_all = wave_min_i32(st), hi_st = wave_max_i32_dpp(st);
+	if (lo_all < jl) {
 		const int d = x - y;
 		const int dmin = wave_min_i32(d), dmax = wave_max_i32_dpp(d);
 		const int gx_min = wave_min_i32(x), gx_max = wave_max_i32_dpp(x);
@@ -1751,66 +1762,108 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 		const int tx4 = (int)(((unsigned)x - 1u) << 2), ty4 = (int)(((unsigned)y - 1u) << 2);
 		const unsigned free_span = (unsigned)(P.dq_lim - P.bw);
 		// scan: the hits of 64 sources go, in index order, to the lanes after those already staged (ds_permute pushes each hit to its
-		// lane; what does not fit goes round to the first lanes and waits for the next stage); diagonals are read one step ahead,
-		// past the CU's cache (written by other waves of the workgroup, or by this one from other lanes).  Every stage -- the full
-		// ones, and the last, partial one in one more trip after the scan -- goes through the ONE sweep at the loop's end: each of the
-		// four unrolled forms exists once.
-		int sidx = 0, n_st = 0;
-		int jb = lo;
-		int dn = jb + lane < jl ? __hip_atomic_load(b.diag + jb + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-		while (true) {
-			int idx, carry = 0, n_next = 0;
-			if (jb < jl) {
-				const int j = jb + lane;
-				const int dj = dn;
-				dn = j + WAVE < jl ? __hip_atomic_load(b.diag + j + WAVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-				jb += WAVE;
-				const bool hit = j < jl && (unsigned)(dj - band_lo) <= width;
-				const unsigned long long m = __ballot(hit);
-				if (m == 0) continue;
-				const int c = __popcll(m);
-				const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-				// (a lane without a hit writes to the first lane that takes none, so no hit is overwritten)
-				const int dst = (hit ? n_st + rank : n_st + c) & (WAVE - 1);
-				const int recv = __builtin_amdgcn_ds_permute(dst << 2, j);
-				if (n_st + c < WAVE) {
-					sidx = lane >= n_st && lane < n_st + c ? recv : sidx;
-					n_st += c;
-					continue;
+		// lane; what does not fit goes round to the first lanes and waits for the next stage).  The sources are span / 64 whole blocks,
+		// read and scanned with no test of the index, and one last block of span & 63, whose other lanes read nothing
+		// and cannot hit (the step runs for it even when span & 63 is 0: no lane reads, none hits).  Diagonals are read one block ahead, past the CU's cache (written by other waves of the workgroup, or by this one from
+		// other lanes).  What a step keeps between blocks -- the lanes filled, the hit count, the mask of the lanes that take a hit --
+		// is scalar, and a source's index is kept relative to the first source: the byte offset of its record then fits the 32-bit
+		// offset of a load from a scalar base.  That holds for 2^28 sources, so a longer scan goes in parts of that many, each with a
+		// last stage of its own (the best carries over; any cut into stages gives the same result).  Every stage -- the full ones, and
+		// the last, partial one in one more trip after the scan -- goes through the ONE sweep at the loop's end: each of the four
+		// unrolled forms exists once.
+		constexpr int BAND_SCAN_MAX = 1 << 28;
+		int bestv = best << 7;                                         // the best times 128, low bits clear between stages (sweep_block_lut)
+		for (int lo = lo_all, span; lo < jl; lo += span) {
+			span = min(jl - lo, BAND_SCAN_MAX);
+			const glb_char_cptr diag_lo = (glb_char_cptr)(b.diag + lo), raw_lo = (glb_char_cptr)(b.raw + (size_t)lo * 4), f_lo = (glb_char_cptr)(b.f + lo);
+			// source kb + lane, relative to lo, kb the block's first (made where it is used: nothing but the lane is kept for it between
+			// blocks)
+			auto source_of = [&](const int kb) -> int {
+				int j;
+				asm("v_add_u32_e32 %0, %1, %2" : "=v"(j) : "s"(kb), "v"(lane));
+				return j;
+			};
+			// the block from kb on, one diagonal per lane; the lanes of a block past the scan's end read nothing and get a diagonal just
+			// below the band, which no band test lets in (the width is far below 2^32 - 1: bw indexes a table in LDS)
+			auto diag_block = [&](const int kb) -> int {
+				const glb_i32_cptr at = (glb_i32_cptr)(diag_lo + ((unsigned)source_of(kb) << 2));   // (below 2^30 + 256: a 32-bit offset)
+				if (kb + WAVE <= span) return __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				return lane < span - kb ? __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : band_lo - 1;
+			};
+			const int hi_rel = hi_st - lo;
+			int sidx = 0, n_st = 0, kb = 0;
+			int dn = diag_block(0);
+			while (true) {
+				// the scan proper, up to a full stage or the end of the sources: an inner loop with one exit and no state but sidx, n_st, kb
+				// and the block read ahead
+				int recv = 0;
+				while (kb <= span && n_st < WAVE) {
+					const unsigned long long m = __ballot((unsigned)(dn - band_lo) <= width);   // the hit mask straight from the compare
+					const int j = source_of(kb);
+					kb += WAVE;
+					if (kb <= span) dn = diag_block(kb);                // (a whole block: no test of the index)
+					if (m != 0) {
+						const int c = __popcll(m), room = WAVE - n_st;
+						const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+						// (a lane without a hit writes to the first lane that takes none, so no hit is overwritten; ds_permute takes the
+						// lane modulo 64)
+						recv = __builtin_amdgcn_ds_permute(select_by_mask(m, (n_st + rank) << 2, (n_st + c) << 2), j);
+						// lanes [n_st, n_st + c) of the stage take theirs; past lane 63 the stage is full, and the hits that did not fit
+						// wait in the first n_st - 64 lanes of recv
+						sidx = select_by_mask((c < room ? (1ull << c) - 1 : ~0ull) << n_st, recv, sidx);
+						n_st += c;
+					}
 				}
-				idx = lane >= n_st ? recv : sidx;
-				n_next = n_st + c - WAVE;
-				carry = recv;                                       // lanes below n_next: the hits that did not fit
-			} else {
-				if (n_st == 0) break;
-				// the last stage, filled up with copies of its last source (same score, same index: nothing changes)
-				idx = lane < n_st ? sidx : bcast(sidx, n_st - 1);
+				int idx = sidx;
+				if (n_st >= WAVE) { sidx = recv; n_st -= WAVE; }
+				else {
+					if (n_st == 0) break;
+					// the last stage, filled up with copies of its last source (same score, same index: nothing changes)
+					idx = lane < n_st ? sidx : bcast(sidx, n_st - 1);
+					n_st = 0;
+				}
+				// lane k: the k-th staged source, indices ascending (the tie rule: a later source wins an equal score); its record in one
+				// load, at a 32-bit offset from the part's first
+				unsigned at_f = (unsigned)idx << 2, at_rec = (unsigned)idx << 4;
+				asm("" : "+v"(at_f), "+v"(at_rec));                 // (both offsets made before either load: neither waits for the other's registers)
+				const int sf = *(glb_i32_cptr)(f_lo + at_f);
+				const i32x4_t rec = *(glb_i32x4_cptr)(raw_lo + at_rec);
+				const int xs = rec.x, ys = rec.z, sq = (int)((unsigned)rec.w & 0xffu);
+				// the block's x extent: its ends, when x does not fall from a lane to the next (sources in index order, all of the one
+				// stretch of a read that the group's oldest window starts in, x sorted within it); a block whose x does fall takes the
+				// reductions.  The smaller end is wanted by the free form only.
+				const bool rising = __ballot(prev_lane(xs) > xs) == 0;
+				int sx_max;
+				if (rising) sx_max = bcast(xs, WAVE - 1); else sx_max = wave_max_i32_dpp(xs);
+				// every source inside every target's window (hence of its read) and left of every target: no test; then the dense
+				// sweep's free and FAR forms on the block's own extent (sweep_block_lut2_free)
+				const bool no_check = first_lane(idx) >= hi_rel && gx_min > sx_max;
+				bool free_block = false;
+				if (no_check && P.free_sweep) {
+					int sx_min;
+					if (rising) sx_min = first_lane(xs); else sx_min = wave_min_i32(xs);
+					free_block = (unsigned)(gx_max - sx_min) <= free_span;
+				}
+				const bool far_block = free_block && __ballot(sq + P.bw > gx_min - xs) == 0;
+				const int d0 = (first_lane(xs) - first_lane(ys)) * 4;
+				stage_block_lut_at(lane, xs, ys, sf, sq, stage, far_block, d0);
+				if (far_block) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
+				else if (free_block) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
+				else if (no_check) sweep_block_lut<false, false>(st, tx4, ty4, 0, 0, stage, P, bestv);
+				else sweep_block_lut_band(st - lo, tx4, ty4, idx, stage, P, bestv);
+				// a best that changed holds k+1 of the staged source that won in its low 7 bits: the index comes from lane k (ds_bpermute
+				// takes the lane modulo 64, so the bits above are left in the address), and the low bits go before the next stage
+				const int wj = __builtin_amdgcn_ds_bpermute((bestv << 2) - 4, idx);
+				const int cleared = bestv & ~127;
+				arg = cleared != bestv ? lo + wj : arg;
+				bestv = cleared;
+				__builtin_amdgcn_wave_barrier();
 			}
-			// lane k: the k-th staged source, indices ascending (the tie rule: a later source wins an equal score)
-			const int xs = r_x(b.raw, idx), ys = r_y(b.raw, idx), sq = r_span(b.raw, idx), sf = b.f[idx];
-			const int sx_min = wave_min_i32(xs), sx_max = wave_max_i32_dpp(xs);
-			// every source inside every target's window (hence of its read) and left of every target: no test; then the dense
-			// sweep's free and FAR forms on the block's own extent (sweep_block_lut2_free)
-			const bool no_check = first_lane(idx) >= hi_st && gx_min > sx_max;
-			const bool free_block = no_check && P.free_sweep && (unsigned)(gx_max - sx_min) <= free_span;
-			const bool far_block = free_block && __ballot(sq + P.bw > gx_min - xs) == 0;
-			const int d0 = (first_lane(xs) - first_lane(ys)) * 4;
-			stage_block_lut_at(lane, xs, ys, sf, sq, stage, far_block, d0);
-			int bestv = best << 7;
-			if (far_block) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
-			else if (free_block) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
-			else if (no_check) sweep_block_lut<false, false>(st, tx4, ty4, 0, 0, stage, P, bestv);
-			else sweep_block_lut_band(st, tx4, ty4, idx, stage, P, bestv);
-			const int won = bestv & 127;                            // k+1 of the staged source that holds the best
-			const int wj = __shfl(idx, (won - 1) & (WAVE - 1));
-			arg = (unsigned)(won - 1) < (unsigned)WAVE ? wj : arg;
-			best = bestv >> 7;
-			__builtin_amdgcn_wave_barrier();
-			sidx = carry; n_st = n_next;
 		}
+		best = bestv >> 7;
 	}
 	if (tgt >= 0) { b.res[2 * tgt] = best; b.res[2 * tgt + 1] = arg; }
-	return lo < jl;
+	return lo_all < jl;
 }
 
 // The order of a slab's targets [s0, s0 + n) (n <= 512): sorted by (diagonal, index) -- a bitonic sort of one key per target, eight per
@@ -1943,7 +1996,10 @@ __device__ __noinline__ int band_slab_part(const glb_i32_cptr raw_, const glb_i3
 		for (int r = 0; r < R; ++r) key[r] = 0;
 	} else state = band_slab_order(b.raw, b.st, P.bw, s0, n, jl, lane, key);
 	if (state == BAND_SLAB_SKIP) return 0;                          // (a team's part has loaded nothing but the header)
-	int swept = 0;                                                  // groups that had sources before jl (MM2GB counters CNT_BAND_*)
+	// The callers are allocated against the registers this function touches.  With two fewer than before (v42, v43) the runners of
+	// the batches that never come here were laid out anew and lost 4 %: the two are named as touched, nothing is done to them.
+	asm volatile("" ::: "v42", "v43");
+	int swept = 0;                                                 // groups that had sources before jl (MM2GB counters CNT_BAND_*)
 	for (int g = g_from; g < g_to; ++g) {
 		int tgt;
 		if (ord) {
