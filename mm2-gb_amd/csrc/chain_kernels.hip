@@ -751,9 +751,9 @@ __device__ __forceinline__ SrcGroup load_group(const DevBatch &b, int j0)
 // blocks of a sweep: sources of interior blocks lie inside every target's window and strictly left of every target's x.
 // Exact while 128*(f+16) < 2^30 and coordinate differences fit 30 bits: k_window raises FLAG_NO_LUT for query positions
 // >= 2^22 (f <= y + q_span always) and the batch then runs the MODE_FAST build.
-template <bool CHECK, bool CLAMP>
+template <bool CHECK, bool CLAMP, bool UPTO = false>
 __device__ __forceinline__ void sweep_block_lut(int t_st, int tx4, int ty4, int jb, int k_from, const int4 *stage,
-                                                const DevParams &P, int &bestv)
+                                                const DevParams &P, int &bestv, const int k_to = WAVE)
 {
 	const unsigned base = (unsigned)P.lut_base, last_at = base + ((unsigned)P.lut_last << 2), lim4 = (unsigned)P.dq_lim << 2;
 	constexpr int G = SWEEP_GROUP;                          // sources per unrolled group: G broadcasts + G gathers in flight
@@ -761,7 +761,7 @@ __device__ __forceinline__ void sweep_block_lut(int t_st, int tx4, int ty4, int 
 	// statement owns), so they are correct under whatever mask the caller runs with and the compiler never sees exec change.  (An
 	// earlier build restored -1, which is only right while every caller is wave-uniform; a copy read in a SEPARATE statement has no
 	// data dependence that keeps it in place, and the compiler runs wave-uniform code under whatever mask is at hand.)
-	for (int kg = k_from & ~(G - 1); kg < WAVE; kg += G) {
+	for (int kg = k_from & ~(G - 1); kg < (UPTO ? k_to : WAVE); kg += G) {   // (UPTO: the band pass's stages, the last one short; k_to a multiple of 4: with G above 4 the last group sweeps copies of the last source)
 		const int j0 = jb + kg;
 		int dqm[G], drm[G], pen[G];
 		int4 s4[G];
@@ -841,39 +841,67 @@ __device__ __forceinline__ void stage_block_lut(const DevBatch &b, int jb, int s
 // ... and are swept against one tile ...
 struct TileXY { int x, y, st; };          // what a sweep needs of a tile: position, query position, window start (INT_MAX: dead lane)
 // one tile, a whole block, no test at all: sweep_block_lut2_free (below) explains when and why, and what FAR is
-template <bool FAR>
-__device__ __forceinline__ void sweep_block_lut_free(int tx4, int ty4, const int4 *stage, const unsigned base, const int d0, int &bestv)
+// WIN (the band pass's head stages): the block meets every condition of the form but "inside every target's window" -- some targets'
+// windows start after some of its sources.  One test per source is left, "source index (lane k of idx) >= this target's window start",
+// straight into the execution mask around a lone v_max (saved and put back inside the statement: sweep_block_lut); a lane that fails
+// keeps its best.  Whatever a source outside a target's window gathers and scores is never looked at.
+// UPTO: sources [0, k_to) only, k_to a wave-uniform multiple of G -- the band pass's last stage, whose sources from k_to on are copies
+// of an earlier one.  A loop of its own, not unrolled; the form of the full blocks keeps its constant trip count.
+template <bool FAR, bool WIN>
+__device__ __forceinline__ void sweep_group_lut_free(const int kg, const int tx4, const int ty4, const int td, const int4 *stage, const unsigned base, int &bestv,
+                                                     const int t_st, const int idx)
+{
+	constexpr int G = 4;
+	int4 s4[G];
+	int dqm[G], drm[G], pen[G], v[G];
+#pragma unroll
+	for (int u = 0; u < G; ++u) {
+		if (FAR) { const int2 h = *(const int2*)&stage[kg + u]; s4[u].x = h.x; s4[u].y = h.y; }
+		else s4[u] = stage[kg + u];
+	}
+#pragma unroll
+	for (int u = 0; u < G; ++u) {
+		if (FAR) pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(td, s4[u].y, base);
+		else {
+			dqm[u] = ty4 - s4[u].w; drm[u] = tx4 - s4[u].z;
+			pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(drm[u], dqm[u], base);
+		}
+	}
+#pragma unroll
+	for (int u = 0; u < G; ++u) {
+		if (FAR) v[u] = s4[u].x + pen[u];
+		else {
+			const int dg = drm[u] < dqm[u] ? drm[u] : dqm[u];
+			v[u] = ((s4[u].y < dg ? s4[u].y : dg) << 5) + s4[u].x;
+			asm("" : "+v"(v[u]));
+			v[u] += pen[u];
+		}
+	}
+	if (WIN) {
+#pragma unroll
+		for (int u = 0; u < G; ++u) {
+			const int j = __builtin_amdgcn_readlane(idx, kg + u);
+			unsigned long long saved;
+			asm volatile("s_mov_b64 %[sv], exec\n\tv_cmpx_ge_i32_e32 vcc, %[j], %[st]\n\tv_max_i32_e32 %[b], %[v], %[b]\n\ts_mov_b64 exec, %[sv]"
+			             : [b] "+v"(bestv), [sv] "=&s"(saved) : [st] "v"(t_st), [j] "s"(j), [v] "v"(v[u]) : "vcc");
+		}
+	} else {
+		asm("v_max3_i32 %0, %1, %2, %0" : "+v"(bestv) : "v"(v[0]), "v"(v[1]));
+		asm("v_max3_i32 %0, %1, %2, %0" : "+v"(bestv) : "v"(v[2]), "v"(v[3]));
+	}
+}
+template <bool FAR, bool WIN = false, bool UPTO = false>
+__device__ __forceinline__ void sweep_block_lut_free(int tx4, int ty4, const int4 *stage, const unsigned base, const int d0, int &bestv,
+                                                     const int k_to = WAVE, const int t_st = 0, const int idx = 0)
 {
 	constexpr int G = 4;
 	const int td = (int)((unsigned)(tx4 - ty4 - d0) ^ 0x80000000u);   // FAR: the target's diagonal, like the staged ones
-	for (int kg = 0; kg < WAVE; kg += G) {
-		int4 s4[G];
-		int dqm[G], drm[G], pen[G], v[G];
+	if (UPTO) {
+#pragma clang loop unroll(disable)
+		for (int kg = 0; kg < k_to; kg += G) sweep_group_lut_free<FAR, WIN>(kg, tx4, ty4, td, stage, base, bestv, t_st, idx);
+	} else {
 #pragma unroll
-		for (int u = 0; u < G; ++u) {
-			if (FAR) { const int2 h = *(const int2*)&stage[kg + u]; s4[u].x = h.x; s4[u].y = h.y; }
-			else s4[u] = stage[kg + u];
-		}
-#pragma unroll
-		for (int u = 0; u < G; ++u) {
-			if (FAR) pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(td, s4[u].y, base);
-			else {
-				dqm[u] = ty4 - s4[u].w; drm[u] = tx4 - s4[u].z;
-				pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(drm[u], dqm[u], base);
-			}
-		}
-#pragma unroll
-		for (int u = 0; u < G; ++u) {
-			if (FAR) v[u] = s4[u].x + pen[u];
-			else {
-				const int dg = drm[u] < dqm[u] ? drm[u] : dqm[u];
-				v[u] = ((s4[u].y < dg ? s4[u].y : dg) << 5) + s4[u].x;
-				asm("" : "+v"(v[u]));
-				v[u] += pen[u];
-			}
-		}
-		asm("v_max3_i32 %0, %1, %2, %0" : "+v"(bestv) : "v"(v[0]), "v"(v[1]));
-		asm("v_max3_i32 %0, %1, %2, %0" : "+v"(bestv) : "v"(v[2]), "v"(v[3]));
+		for (int kg = 0; kg < WAVE; kg += G) sweep_group_lut_free<FAR, WIN>(kg, tx4, ty4, td, stage, base, bestv, t_st, idx);
 	}
 }
 // An EDGE block -- some target windows start inside it, or it reaches into the run of anchors that share the tile's first position.
@@ -1698,33 +1726,45 @@ __device__ __forceinline__ int r_span(glb_i32_cptr raw, int i) { return (int)((u
 
 // A staged block whose sources are not consecutive, some target's window starting inside it: sweep_block_lut_edge with the source's
 // index taken from lane k of `idx`.
-__device__ __forceinline__ void sweep_block_lut_band(int t_st, int tx4, int ty4, int idx, const int4 *stage, const DevParams &P, int &bestv)
+__device__ __forceinline__ void sweep_group_lut_band(const int kg, const int t_st, const int tx4, const int ty4, const int idx, const int pos, const int4 *stage,
+                                                     const unsigned base, const unsigned lim4, int &bestv)
+{
+	constexpr int G = 4;
+	int4 s4[G];
+	int dqm[G], drm[G], pen[G];
+#pragma unroll
+	for (int u = 0; u < G; ++u) s4[u] = stage[kg + u];
+#pragma unroll
+	for (int u = 0; u < G; ++u) {
+		dqm[u] = ty4 - s4[u].w; drm[u] = tx4 - s4[u].z;
+		pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(drm[u], dqm[u] & pos, base);
+	}
+#pragma unroll
+	for (int u = 0; u < G; ++u) {
+		const int dg = drm[u] < dqm[u] ? drm[u] : dqm[u];
+		int v = ((s4[u].y < dg ? s4[u].y : dg) << 5) + s4[u].x;
+		asm("" : "+v"(v));
+		v += pen[u];
+		const int j = __builtin_amdgcn_readlane(idx, kg + u);
+		unsigned long long saved;                               // (the mask on entry is saved and put back inside the statement: sweep_block_lut)
+		asm volatile("s_mov_b64 %[sv], exec\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[dq]\n\tv_cmpx_ge_i32_e32 vcc, %[j], %[st]\n\tv_max_i32_e32 %[b], %[v], %[b]\n\ts_mov_b64 exec, %[sv]"
+		             : [b] "+v"(bestv), [sv] "=&s"(saved) : [lim] "s"(lim4), [dq] "v"(dqm[u]), [st] "v"(t_st), [j] "s"(j), [v] "v"(v) : "vcc");
+	}
+}
+// UPTO: as in sweep_block_lut_free.
+template <bool UPTO>
+__device__ __forceinline__ void sweep_block_lut_band(int t_st, int tx4, int ty4, int idx, const int4 *stage, const DevParams &P, int &bestv, const int k_to = WAVE)
 {
 	constexpr int G = 4;
 	const unsigned base = (unsigned)P.lut_base, lim4 = (unsigned)P.dq_lim << 2;
 	int pos = 0x7fffffff;
 	asm volatile("" : "+v"(pos));
-	for (int kg = 0; kg < WAVE; kg += G) {
-		int4 s4[G];
-		int dqm[G], drm[G], pen[G];
+	if (UPTO) {
+#pragma clang loop unroll(disable)
+		for (int kg = 0; kg < k_to; kg += G) sweep_group_lut_band(kg, t_st, tx4, ty4, idx, pos, stage, base, lim4, bestv);
+	} else {
 #pragma unroll
-		for (int u = 0; u < G; ++u) s4[u] = stage[kg + u];
-#pragma unroll
-		for (int u = 0; u < G; ++u) {
-			dqm[u] = ty4 - s4[u].w; drm[u] = tx4 - s4[u].z;
-			pen[u] = *(lds_i32_ptr)(uintptr_t)lut_address(drm[u], dqm[u] & pos, base);
-		}
-#pragma unroll
-		for (int u = 0; u < G; ++u) {
-			const int dg = drm[u] < dqm[u] ? drm[u] : dqm[u];
-			int v = ((s4[u].y < dg ? s4[u].y : dg) << 5) + s4[u].x;
-			asm("" : "+v"(v));
-			v += pen[u];
-			const int j = __builtin_amdgcn_readlane(idx, kg + u);
-			unsigned long long saved;                               // (the mask on entry is saved and put back inside the statement: sweep_block_lut)
-			asm volatile("s_mov_b64 %[sv], exec\n\tv_cmpx_gt_u32_e32 vcc, %[lim], %[dq]\n\tv_cmpx_ge_i32_e32 vcc, %[j], %[st]\n\tv_max_i32_e32 %[b], %[v], %[b]\n\ts_mov_b64 exec, %[sv]"
-			             : [b] "+v"(bestv), [sv] "=&s"(saved) : [lim] "s"(lim4), [dq] "v"(dqm[u]), [st] "v"(t_st), [j] "s"(j), [v] "v"(v) : "vcc");
-		}
+		for (int kg = 0; kg < WAVE; kg += G) sweep_group_lut_band(kg, t_st, tx4, ty4, idx, pos, stage, base, lim4, bestv);
 	}
 }
 
@@ -1770,7 +1810,7 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 		// offset of a load from a scalar base.  That holds for 2^28 sources, so a longer scan goes in parts of that many, each with a
 		// last stage of its own (the best carries over; any cut into stages gives the same result).  Every stage -- the full ones, and
 		// the last, partial one in one more trip after the scan -- goes through the ONE sweep at the loop's end: each of the four
-		// unrolled forms exists once.
+		// unrolled forms exists once (and each loop form of the head stages and of the short last stage).
 		constexpr int BAND_SCAN_MAX = 1 << 28;
 		int bestv = best << 7;                                         // the best times 128, low bits clear between stages (sweep_block_lut)
 		for (int lo = lo_all, span; lo < jl; lo += span) {
@@ -1814,12 +1854,14 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 						n_st += c;
 					}
 				}
-				int idx = sidx;
+				int idx = sidx, k_to = WAVE;
 				if (n_st >= WAVE) { sidx = recv; n_st -= WAVE; }
 				else {
 					if (n_st == 0) break;
-					// the last stage, filled up with copies of its last source (same score, same index: nothing changes)
+					// the last stage, filled up with copies of its last source (same score, same index: nothing changes) and swept as far
+					// as its own sources go, to the sweeps' group of four
 					idx = lane < n_st ? sidx : bcast(sidx, n_st - 1);
+					k_to = (n_st + 3) & ~3;
 					n_st = 0;
 				}
 				// lane k: the k-th staged source, indices ascending (the tie rule: a later source wins an equal score); its record in one
@@ -1837,9 +1879,13 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 				if (rising) sx_max = bcast(xs, WAVE - 1); else sx_max = wave_max_i32_dpp(xs);
 				// every source inside every target's window (hence of its read) and left of every target: no test; then the dense
 				// sweep's free and FAR forms on the block's own extent (sweep_block_lut2_free)
-				const bool no_check = first_lane(idx) >= hi_rel && gx_min > sx_max;
+				// A HEAD stage -- its first source lies before the group's last window start, so some targets' windows may start inside
+				// or after it -- that is left of every target takes the free and FAR forms on the same conditions, with the window
+				// test per source (sweep_block_lut_free<., true>): a pair inside its target's window is then all the forms take it for.
+				const bool inside = first_lane(idx) >= hi_rel, left = gx_min > sx_max;
+				const bool no_check = inside && left;
 				bool free_block = false;
-				if (no_check && P.free_sweep) {
+				if (left && P.free_sweep) {
 					int sx_min;
 					if (rising) sx_min = first_lane(xs); else sx_min = wave_min_i32(xs);
 					free_block = (unsigned)(gx_max - sx_min) <= free_span;
@@ -1847,10 +1893,20 @@ __device__ __forceinline__ int band_group(const BandIO &b, const DevParams &P, i
 				const bool far_block = free_block && __ballot(sq + P.bw > gx_min - xs) == 0;
 				const int d0 = (first_lane(xs) - first_lane(ys)) * 4;
 				stage_block_lut_at(lane, xs, ys, sf, sq, stage, far_block, d0);
-				if (far_block) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
-				else if (free_block) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
-				else if (no_check) sweep_block_lut<false, false>(st, tx4, ty4, 0, 0, stage, P, bestv);
-				else sweep_block_lut_band(st - lo, tx4, ty4, idx, stage, P, bestv);
+				// (the full stages' forms are the unrolled ones; a head stage and a short last stage take a loop up to k_to -- and so do
+				// all stages of the range-test-only form, which was a loop before: its bound is k_to now, 64 for a full stage)
+				const bool full = k_to == WAVE, head = !inside;
+				if (far_block) {
+					if (head) sweep_block_lut_free<true, true, true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv, k_to, st - lo, idx);
+					else if (full) sweep_block_lut_free<true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv);
+					else sweep_block_lut_free<true, false, true>(tx4, ty4, stage, (unsigned)P.lut_base, d0, bestv, k_to);
+				} else if (free_block) {
+					if (head) sweep_block_lut_free<false, true, true>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv, k_to, st - lo, idx);
+					else if (full) sweep_block_lut_free<false>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv);
+					else sweep_block_lut_free<false, false, true>(tx4, ty4, stage, (unsigned)P.lut_base, 0, bestv, k_to);
+				} else if (no_check) sweep_block_lut<false, false, true>(st, tx4, ty4, 0, 0, stage, P, bestv, k_to);
+				else if (full) sweep_block_lut_band<false>(st - lo, tx4, ty4, idx, stage, P, bestv);
+				else sweep_block_lut_band<true>(st - lo, tx4, ty4, idx, stage, P, bestv, k_to);
 				// a best that changed holds k+1 of the staged source that won in its low 7 bits: the index comes from lane k (ds_bpermute
 				// takes the lane modulo 64, so the bits above are left in the address), and the low bits go before the next stage
 				const int wj = __builtin_amdgcn_ds_bpermute((bestv << 2) - 4, idx);
